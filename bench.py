@@ -31,16 +31,23 @@ gloo, only carries the 128-byte id, the barriers and the max over ranks); if tha
 back to --transport torch (the collectives of torch.distributed on tensors that alias the library's memory) and
 says so in config.transport.  --single-process runs all N ranks from ONE process, one context per GPU behind
 lumen_group_create -- the topology of the reference's server (one Go process, cmd/server/main.go:187-266); with
---share-gpu its N contexts sit on device 0 (copy transport: the one-GPU rehearsal).  For N > 1 the line carries
+--share-gpu its N contexts sit on device 0 (copy transport: the one-GPU rehearsal).  For N > 1 the --full line carries
 rccl_ranks_seen, per-collective times and GB/s, per-rank stage times and roofline, and `check`: root, encoded
 columns and inner products of an N-rank run at 2048x1024 against a single-rank recompute.
 
-Rank 0 prints ONE JSON line (see the keys at the bottom of main()).  At N = 1 the default run also carries
-  * marshal_s / io_inclusive_s: the proof as wire-format bytes in page-locked host memory
+Rank 0 prints ONE JSON line (see the keys at the bottom of main()).  A plain run sets up, warms up, times the
+--steps steps and prints the line (`value` and `ms_per_step`: one timed step).  --dump-outputs DIR (one GPU) also
+writes what the last timed step returned -- a seeded sample of MatR, MatZ and the queried columns, the Merkle tree
+and its root -- as DIR/<name>.npy (bench_lib/dump.py).  Everything else is measured only with --full:
+  * box: clocks / power / temperatures of the device idle, under load and after, and its identity;
+  * roofline / kernels / ntt_kernel: a profiled step with HIP events around every launch, and the plain transform;
+  * marshal_s / io_inclusive_s (N = 1): the proof as wire-format bytes in page-locked host memory
     (EncryptedProof.WriteTo, fhe/ligero.go:659-705) and a step that starts with the input ciphertexts in
     host memory and ends there (never `value`);
-  * other_configs: short passes over the other BASELINE.json configurations (2048x1024, 4096x2048,
-    8192x4096, and 16384x4096 with the ring switch to LogN = 10), so that the driver's one command attests them.
+  * other_configs (N = 1): short passes over the other BASELINE.json configurations (2048x1024, 4096x2048,
+    8192x4096, and 16384x4096 with the ring switch to LogN = 10), so that one command attests them;
+  * cpu_baseline (N = 1): the CPU oracle on a sample of the same step, extrapolated;
+  * N > 1: the per-rank stage times, collectives and the check against a single-rank recompute.
 """
 import argparse
 import json
@@ -52,6 +59,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 # the parts (bench_lib/); re-exported here because tools/ and tests/ say bench.Job, bench.join_ranks, ...
+from bench_lib.dump import dump_outputs  # noqa: E402
 from bench_lib.job import CONFIGS, PUBLISHED_SECONDS, RHO_INV, SECURITY_BITS, Job, owned_queries  # noqa: E402,F401
 from bench_lib.legs import (cpu_baseline, hashlib_sha, io_leg, other_configs, plain_ntt_rates,  # noqa: E402,F401
                             plain_prover_seconds, stage_seconds, timed_steps)
@@ -87,7 +95,7 @@ def main():
     ap.add_argument("--allow-replicated", action="store_true",
                     help="N>1 worlds the lane-sharded path cannot serve: run the round-1 replicated-input path "
                          "instead of refusing (named in config.parallelism)")
-    ap.add_argument("--include-io", action="store_true", help="kept for old command lines: the io leg is on by default")
+    ap.add_argument("--include-io", action="store_true", help="kept for old command lines: the io leg is on by default with --full")
     ap.add_argument("--no-io", action="store_true",
                     help="skip marshal_s / io_inclusive_s (upload of the inputs from and the proof's wire bytes into "
                          "page-locked host memory; reported beside `value`, never as `value`)")
@@ -96,7 +104,18 @@ def main():
     ap.add_argument("--other-steps", type=int, default=3)
     ap.add_argument("--ring-switch-logn", type=int, default=0,
                     help="BASELINE config 5: ring-switch MatR/MatZ to this ring degree (fhe/ring_switch.go)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps, measure and check everything else the line can carry (box, kernel "
+                         "profile, io legs, other configurations, CPU baseline; N > 1: per-rank report and check); the "
+                         "--no-* options above drop parts of it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (seeded samples of MatR, MatZ and the "
+                         "queried columns, the Merkle tree and root) as DIR/<name>.npy; one GPU only")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs is not None and args.gpus != 1:
+        ap.error("--dump-outputs needs --gpus 1")
     # the host driver of this pool only does dmabuf IPC: RCCL (the library's own group and torch's) needs this before
     # the HIP runtime starts in this process
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
@@ -151,35 +170,45 @@ def main():
         for c in job.ctxs:
             c.sync()
 
-    probe = BoxProbe(local_rank) if rank == 0 else None  # (clocks / power / temperatures: idle now, once under load, right after)
+    # (clocks / power / temperatures: idle now, once under load, right after)
+    probe = BoxProbe(local_rank) if rank == 0 and args.full else None
     for _ in range(args.warmup):
         job.step(dist)
     barrier()
     if probe:
         probe.start_timed_region()
-    step_s = []
+    step_s, outs = [], None
     t0 = t_prev = time.perf_counter()
-    for _ in range(args.steps):
-        job.step(dist)
+    for i in range(args.steps):
+        # --dump-outputs: the last step hands back its outputs instead of freeing them
+        keep = args.dump_outputs is not None and i == args.steps - 1
+        r = job.step(dist, keep=keep)
+        if keep:
+            outs = r
         t_now = time.perf_counter()  # (a step ends drained: its own stream synchronisation -- nothing is added here)
         step_s.append(t_now - t_prev)
         t_prev = t_now
     barrier()
     elapsed = time.perf_counter() - t0
     box = probe.end_timed_region() if probe else None
+    if outs is not None:
+        dump_outputs(args.dump_outputs, job, outs)
+        for s in outs[:3]:
+            s.free()
     if dist is not None:
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda" if dist.get_backend() == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     sec_per_step = elapsed / args.steps
 
-    roofline, stages, executed, per_rank_prof = ((None, None, None, None) if args.no_kernel_profile
+    full = args.full
+    roofline, stages, executed, per_rank_prof = ((None, None, None, None) if args.no_kernel_profile or not full
                                                  else profile_kernels(job, dist, args.config))
-    multi = multi_rank_report(job, args, dist, per_rank_prof, sec_per_step) if world > 1 else None
-    ntt_kernel = plain_ntt_rates(job) if world == 1 and not args.no_kernel_profile else None
-    io = io_leg(job, args.config) if world == 1 and not args.no_io else None
+    multi = multi_rank_report(job, args, dist, per_rank_prof, sec_per_step) if world > 1 and full else None
+    ntt_kernel = plain_ntt_rates(job) if full and world == 1 and not args.no_kernel_profile else None
+    io = io_leg(job, args.config) if full and world == 1 and not args.no_io else None
     others = None
-    if world == 1 and not args.no_other_configs and not args.ring_switch_logn:
+    if full and world == 1 and not args.no_other_configs and not args.ring_switch_logn:
         others = other_configs(job, args, sec_per_step, local_rank, barrier)
     if rank == 0:
         census = limb_ntt_census(job.rows, job.cols, job.L, job.K, job.log_n)
@@ -236,7 +265,7 @@ def main():
             out.update(io)
         if others:
             out["other_configs"] = others
-        if world == 1 and not args.no_cpu_baseline:
+        if full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.config)
         print(json.dumps(out), flush=True)
     # orderly teardown: every rank is past its last collective (the report's gather above) before any communicator

@@ -9,7 +9,7 @@ cd "$GRAFT_REPO_ROOT"
 for r in $(seq 1 $rounds); do
   for v in "$@"; do
     if [ "$v" = product ]; then unset LUMEN_HIP_LIB; else export LUMEN_HIP_LIB=$GRAFT_REPO_ROOT/lumenos_amd/csrc/variants/$v/liblumenos_hip.so; fi
-    python3 bench.py --steps 8 --warmup 2 --no-cpu-baseline --no-io --no-other-configs > "$out/bench_${v}_$r.json" 2> "$out/bench_${v}_$r.err"
+    python3 bench.py --full --steps 8 --warmup 2 --no-cpu-baseline --no-io --no-other-configs > "$out/bench_${v}_$r.json" 2> "$out/bench_${v}_$r.err"
     python3 - "$out/bench_${v}_$r.json" "$v" "$r" <<'PY'
 import json, sys
 j = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

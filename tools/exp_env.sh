@@ -4,7 +4,7 @@
 #   bash tools/exp_env.sh "" "LUMEN_KS_LANES=2" "LUMEN_KS_BATCH=32"
 cd "$GRAFT_REPO_ROOT"
 for e in "$@"; do
-  out=$(env $e python3 bench.py --no-cpu-baseline --steps 2 --warmup 1 ${BENCH_ARGS} 2>/dev/null | tail -1)
+  out=$(env $e python3 bench.py --full --no-cpu-baseline --steps 2 --warmup 1 ${BENCH_ARGS} 2>/dev/null | tail -1)
   python3 - "$e" "$out" <<'PY'
 import json, sys
 e, line = sys.argv[1], sys.argv[2]

@@ -4,10 +4,11 @@
 #   usage (GPU box, repo root): bash tools/exp_moddown.sh gpurun_out/moddown product tg2 tg6 tg12 ...
 # "product" = lumenos_amd/csrc/liblumenos_hip.so, NAME = lumenos_amd/csrc/variants/NAME/liblumenos_hip.so
 set -e
+root=$(cd "$(dirname "$0")/.." && pwd)
 out=$GRAFT_REPO_ROOT/$1; shift
 mkdir -p "$out"
 cd /tmp && export TMPDIR=/tmp
-B="$GRAFT_REPO_ROOT/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-io --no-other-configs"
+B="$root/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-io --no-other-configs"
 B1="$GRAFT_REPO_ROOT/bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-kernel-profile --no-io --no-other-configs"
 for v in "$@"; do
   if [ "$v" = product ]; then unset LUMEN_HIP_LIB; else export LUMEN_HIP_LIB=$GRAFT_REPO_ROOT/lumenos_amd/csrc/variants/$v/liblumenos_hip.so; fi

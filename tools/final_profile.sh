@@ -7,10 +7,10 @@ cd "$GRAFT_REPO_ROOT"
 bash tools/profile_bench.sh "$out/prof" 16384x4096 > "$out/profile.log" 2>&1
 cp "$out/prof/pmc_traffic_16384x4096.json" profiles/pmc_traffic_16384x4096.json   # so that the runs below quote it
 for cfg in 2048x1024 4096x2048 8192x4096; do
-  python3 bench.py --config $cfg --steps 3 --no-cpu-baseline 2>/dev/null | tail -1 > "$out/bench_$cfg.json"
+  python3 bench.py --full --config $cfg --steps 3 --no-cpu-baseline 2>/dev/null | tail -1 > "$out/bench_$cfg.json"
 done
-python3 bench.py --config 16384x4096 --steps 3 --ring-switch-logn 10 --no-cpu-baseline 2>/dev/null | tail -1 > "$out/bench_16384x4096_ringswitch.json"
-python3 bench.py --include-io --steps 3 2>/dev/null | tail -1 > "$out/bench_16384x4096.json"
+python3 bench.py --full --config 16384x4096 --steps 3 --ring-switch-logn 10 --no-cpu-baseline 2>/dev/null | tail -1 > "$out/bench_16384x4096_ringswitch.json"
+python3 bench.py --full --include-io --steps 3 2>/dev/null | tail -1 > "$out/bench_16384x4096.json"
 python3 tools/ntt_only.py 14 512 1500 > "$out/ntt_only_n14.txt" 2>&1
 ./tools/ubench_bfly > "$out/ubench_bfly.txt" 2>&1
 for f in "$out"/bench_*.json; do python3 -c "

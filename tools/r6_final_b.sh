@@ -1,7 +1,7 @@
 #!/bin/bash
 out=$GRAFT_REPO_ROOT/gpurun_out/final_r06; mkdir -p "$out"; cd "$GRAFT_REPO_ROOT"
 bash tools/final_profile.sh gpurun_out/final_r06 2>&1 | tail -12
-timeout -k 10 600 python bench.py --gpus 1 --steps 20 --warmup 5 > "$out/bench_default_20_steps.json" 2> "$out/bench_default_20_steps.err" || { tail -5 "$out/bench_default_20_steps.err"; exit 1; }
+timeout -k 10 600 python bench.py --full --gpus 1 --steps 20 --warmup 5 > "$out/bench_default_20_steps.json" 2> "$out/bench_default_20_steps.err" || { tail -5 "$out/bench_default_20_steps.err"; exit 1; }
 python - "$out/bench_default_20_steps.json" <<'PY'
 import json, sys
 j = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -13,8 +13,8 @@ s = [j["s_per_step"] for j in rows]; m = [j["insitu_ms_per_step"]["ks_mac"] for 
 print(f"step {min(s):.4f} .. {max(s):.4f} s ({(max(s) / min(s) - 1) * 100:.2f} %), ks_mac {min(m):.1f} .. {max(m):.1f} ms ({(max(m) / min(m) - 1) * 100:.2f} %)")
 PY
 echo "== rehearsals of the N > 1 paths on the one GPU" | tee -a "$out/log.txt"
-timeout -k 10 300 python bench.py --gpus 4 --single-process --share-gpu --config 2048x1024 --steps 3 --no-cpu-baseline > "$out/bench_n4_single_process.json" 2> "$out/bench_n4_single_process.err" || { tail -5 "$out/bench_n4_single_process.err"; exit 1; }
-timeout -k 10 400 python bench.py --gpus 2 --share-gpu --dist-backend gloo --config 2048x1024 --steps 2 --no-cpu-baseline > "$out/bench_n2_gloo.json" 2> "$out/bench_n2_gloo.err" || { tail -5 "$out/bench_n2_gloo.err"; exit 1; }
+timeout -k 10 300 python bench.py --full --gpus 4 --single-process --share-gpu --config 2048x1024 --steps 3 --no-cpu-baseline > "$out/bench_n4_single_process.json" 2> "$out/bench_n4_single_process.err" || { tail -5 "$out/bench_n4_single_process.err"; exit 1; }
+timeout -k 10 400 python bench.py --full --gpus 2 --share-gpu --dist-backend gloo --config 2048x1024 --steps 2 --no-cpu-baseline > "$out/bench_n2_gloo.json" 2> "$out/bench_n2_gloo.err" || { tail -5 "$out/bench_n2_gloo.err"; exit 1; }
 python - "$out" <<'PY' | tee -a "$out/log.txt"
 import json, sys
 for f in ("bench_n4_single_process.json", "bench_n2_gloo.json"):
