@@ -247,7 +247,7 @@ __global__ void k_mul_plain(const u64 *__restrict__ ct, u64 *__restrict__ out, c
 // ---- step 2: digit extension + NTT.  One workgroup per (column b, digit d, target t).
 // coef: [B][L][N] coefficient-domain c1; acc: [B][2][L][N] (c1 NTT values for own limbs); ext: [L+K][B][beta][N] (ks_ext_at)
 template <int LOGN>
-__global__ __launch_bounds__(lm_max_threads(LOGN)) void k_modup_ntt(const u64 *__restrict__ coef, const u64 *__restrict__ acc,
+__global__ __launch_bounds__(lm_fwdw_threads(LOGN), lm_fwdw_waves(LOGN)) void k_modup_ntt(const u64 *__restrict__ coef, const u64 *__restrict__ acc,
                                                     u64 *__restrict__ ext, const bx_t *__restrict__ bx,
                                                     uint32_t B, uint32_t L, uint32_t K, uint32_t beta,
                                                     const uint32_t *__restrict__ work, lm_mods mods,
@@ -271,15 +271,21 @@ __global__ __launch_bounds__(lm_max_threads(LOGN)) void k_modup_ntt(const u64 *_
     // 12 digits of moduli below 2^58.4) and its reduction takes any such sum
     // coalesced stores through the wave's own LDS block (lm_linear_out): -3.5 % on this kernel at N = 2^14 against one 64-byte run per
     // lane straight from the registers (tools/exp_modup_run_store.patch, profiles/r05_exp_linear_store.txt)
-    lm_lds_runs st{sm};
-    auto after = [&](uint32_t, uint32_t) {
-        lm_linear_out<LOGN>(sm, tid, [&](uint32_t j, u64 v0, u64 v1) {
-            ulonglong2 y;
-            y.x = v0, y.y = v1;
-            *reinterpret_cast<ulonglong2 *>(o + j) = y;
-        });
+    auto out = [&](uint32_t j, u64 v0, u64 v1) {
+        ulonglong2 y;
+        y.x = v0, y.y = v1;
+        *reinterpret_cast<ulonglong2 *>(o + j) = y;
     };
-    lm_ntt_forward<LOGN>(sm, tw_all + (size_t)t * N, qc, tid, nthreads, ld, st, after);
+    if constexpr (LOGN == 14) { // limb in registers, two workgroups per CU: the runs go through the wave's slot, half by half
+        (void)nthreads;
+        lm_w14_runs st{sm};
+        auto after = [&](uint32_t i0, uint32_t) { lm_w14_linear_out(sm, tid, i0, out); };
+        lm_ntt_forward_w14(sm, tw_all + (size_t)t * N, qc, tid, ld, st, after);
+    } else {
+        lm_lds_runs st{sm};
+        auto after = [&](uint32_t, uint32_t) { lm_linear_out<LOGN>(sm, tid, out); };
+        lm_ntt_forward<LOGN>(sm, tw_all + (size_t)t * N, qc, tid, nthreads, ld, st, after);
+    }
 }
 
 // ---- step 3: gadget product.  u[b][w][t][i] = sum_d ext[b][d][t][i] * key[d][w][t][i]  (storage: ks_u_at, ks_ext_at, ks_key_at)
@@ -915,11 +921,12 @@ int rotate_accumulate(lumen_ctx *ctx, const u64 *acc, u64 *acc_out, uint32_t B, 
         const uint32_t *work = nullptr;
         if (int rc = modup_work_list(ctx, tb, B, &work)) return rc;
         lm_prof_scope ps(ctx, "ks_modup_ntt", nb);
+        const lm_geom gm = lm_fwdw_geom(ctx->logN);
         switch (ctx->logN) {
 #define LM_CASE(n)                                                                                            \
     case n:                                                                                                   \
-        LM_LDS_ATTR(ctx, k_modup_ntt<n>, lds);               \
-        hipLaunchKernelGGL(k_modup_ntt<n>, dim3((uint32_t)nb), dim3(threads), lds, ctx->stream, s.coef, acc,  \
+        LM_LDS_ATTR(ctx, k_modup_ntt<n>, gm.lds);                                                             \
+        hipLaunchKernelGGL(k_modup_ntt<n>, dim3((uint32_t)nb), dim3(gm.threads), gm.lds, ctx->stream, s.coef, acc, \
                            s.ext, tb->d_bx, B, L, K, beta, work, ctx->mods, ctx->d_tw_fwd);                   \
         break;
             LM_FOR_EACH_LOGN(LM_CASE)

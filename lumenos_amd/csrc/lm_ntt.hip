@@ -8,8 +8,11 @@
 // lazy butterflies and the hand-scheduled Shoup multiplication: lm_ntt_dev.h.
 #include "lm_ntt_dev.h"
 
+// forward transforms run lm_ntt_forward_w14 at N = 2^14 (512 threads, two workgroups per CU): geometry lm_fwdw_geom
+__host__ __device__ constexpr int lm_limb_ntt_threads(int logN, bool inv) { return inv ? lm_max_threads(logN) : lm_fwdw_threads(logN); }
+__host__ __device__ constexpr int lm_limb_ntt_waves(int logN, bool inv) { return inv ? 1 : lm_fwdw_waves(logN); }
 template <int LOGN, bool INV>
-__global__ __launch_bounds__(lm_max_threads(LOGN)) void k_limb_ntt(const u64 *src, size_t src_poly_stride, u64 *dst,
+__global__ __launch_bounds__(lm_limb_ntt_threads(LOGN, INV), lm_limb_ntt_waves(LOGN, INV)) void k_limb_ntt(const u64 *src, size_t src_poly_stride, u64 *dst,
                                                    size_t dst_poly_stride, uint32_t npoly, lm_modmap map,
                                                    lm_mods mods, lm_ninv_t ninv,
                                                    const tw_t *__restrict__ tw_all) {
@@ -43,7 +46,10 @@ __global__ __launch_bounds__(lm_max_threads(LOGN)) void k_limb_ntt(const u64 *sr
                 if (k < count) r[k] = lm_reduce_s(v[k], c.q, c.nq, c.qinv64);
             lm_store_run(o, i0, r, count);
         };
-        lm_ntt_forward<LOGN>(sm, tw, c, tid, nthreads, ld, st);
+        if constexpr (LOGN == 14)
+            lm_ntt_forward_w14(sm, tw, c, tid, ld, st);
+        else
+            lm_ntt_forward<LOGN>(sm, tw, c, tid, nthreads, ld, st);
     }
 }
 
@@ -59,8 +65,8 @@ int lm_launch_ntt_subring(lumen_ctx *ctx, uint32_t logn, const tw_t *tw, tw_t ni
     mods.m[0] = explicit_mod ? *explicit_mod : ctx->mods.m[mod_idx];
     lm_ninv_t ninv = lm_ninv_of(ctx);
     ninv.t[0] = ninv_scale;
-    const size_t lds = inverse ? lm_inv_lds(logn) : lm_fwd_lds(logn);
-    const uint32_t threads = inverse ? lm_inv_threads(logn) : lm_fwd_threads(logn);
+    const size_t lds = inverse ? lm_inv_lds(logn) : lm_fwdw_geom(logn).lds;
+    const uint32_t threads = inverse ? lm_inv_threads(logn) : lm_fwdw_geom(logn).threads;
     const dim3 grid(npoly), block(threads);
 #define LM_LAUNCH(n)                                                                                          \
     case n:                                                                                                   \
@@ -93,8 +99,8 @@ int lm_launch_ntt_strided(lumen_ctx *ctx, const u64 *src, size_t src_poly_stride
     if (!npoly || !map.period) return 0;
     const uint32_t N = ctx->N;
     const lm_ninv_t ninv = inv_scale ? *inv_scale : lm_ninv_of(ctx);
-    const size_t lds = inverse ? lm_inv_lds(ctx->logN) : lm_fwd_lds(ctx->logN);
-    const uint32_t threads = inverse ? lm_inv_threads(ctx->logN) : lm_fwd_threads(ctx->logN);
+    const size_t lds = inverse ? lm_inv_lds(ctx->logN) : lm_fwdw_geom(ctx->logN).lds;
+    const uint32_t threads = inverse ? lm_inv_threads(ctx->logN) : lm_fwdw_geom(ctx->logN).threads;
     (void)N;
     const uint64_t nblocks64 = (uint64_t)npoly * map.period;
     LM_CHECK(ctx, nblocks64 < (1ull << 31), "NTT grid too large: %llu", (unsigned long long)nblocks64);
