@@ -257,6 +257,20 @@ int lumen_encrypt_values(lumen_ctx *ctx, const uint64_t *values, uint32_t rows, 
 int lumen_encrypt_pk(lumen_ctx *ctx, const uint64_t *plaintexts, uint32_t count, const uint8_t seed[32],
                      uint64_t first_index, lumen_set **out);
 
+/* ---- P(z) over a block of witness columns (cmd/server/main.go:255-258, core/poly.go:13-45): the claimed value the
+ * server answers GET /prove?point=z with next to the proof, which the client checks as InnerProduct(MatZ, a) == value,
+ * a = [1, z, z^2, ...] (fhe/ligero.go:569).  P = core.NewDensePolyFromMatrix(matrix): the witness flattened row-major,
+ * coefficient i*cols + j = M[i][j].  values: host, `count` columns of `rows` values each, [count][rows] -- exactly what
+ * lumen_encrypt_values takes -- of which the first is column `first_column` of a matrix of `cols` columns:
+ *     partial = sum_{j<count} sum_{i<rows} (values[j][i] mod T) * z^(i*cols + first_column + j)   (mod T)
+ * T is the context's plaintext modulus; values >= T count as their residue, as in lumen_encrypt_values.  The partials
+ * of disjoint column blocks sum mod T to P(z), so a caller batches the columns as it batches lumen_encrypt_values.
+ * One pass over the 8*rows*count bytes on the device (page-locked values: lumen_host_alloc; pageable ones are
+ * bounced).  Refused with a message: rows outside [1, N], first_column + count > cols, a context without a
+ * plaintext modulus (or one of 2^60 and more), NULL pointers. */
+int lumen_poly_eval_columns(lumen_ctx *ctx, const uint64_t *values, uint32_t rows, uint32_t count,
+                            uint64_t first_column, uint32_t cols, uint64_t z, uint64_t *partial);
+
 /* ---- client-side decryption of the proof's ciphertexts: EncryptedProof.Decrypt /
  * decryptBatchedParallel (fhe/ligero.go:381-502, 577-636) = Decryptor.DecryptNew + Encoder.Decode.
  * For a client that owns a GPU and for end-to-end tests: the proving server never holds sk.
@@ -419,6 +433,15 @@ int lumen_group_digests(lumen_group *g, uint8_t *digests, size_t cap, uint32_t *
  * passing different shapes on different processes is a caller error the library cannot see. */
 int lumen_group_gather(lumen_group *g, const lumen_set *const *src, const uint32_t *idx, uint32_t n,
                        lumen_set **out);
+/* P(z) over a matrix whose columns are spread over the ranks (lumen_poly_eval_columns, cmd/server/main.go:255-258,
+ * core/poly.go:13-45): values[i] / counts[i] = the local rank's block of columns, host [counts[i]][rows], as
+ * ServerGroup's witness encryption splits them (rank r's block follows rank r-1's); the counts of all ranks sum to
+ * cols.  Every rank evaluates its own block; the partials are summed mod T inside the library and *value = P(z) on
+ * every rank.  With one process per GPU (lumen_group_create_rank) the partials, the counts and a fingerprint of
+ * (rows, cols, z) travel in one fixed-size all-gather, and a rank whose own arguments or evaluation fail still takes
+ * part in it: then every rank returns non-zero, none blocks.  Every rank must pass the same rows, cols and z. */
+int lumen_group_poly_eval(lumen_group *g, const uint64_t *const *values, uint32_t rows, const uint32_t *counts,
+                          uint32_t cols, uint64_t z, uint64_t *value);
 /* HIP-event time of the collectives since the last reset: name = "all_to_all" (lumen_group_all_to_all),
  * "all_to_all_1" / "all_to_all_2" (the two exchanges inside lumen_group_encode), "all_gather", "gather_to_root";
  * ms = sum over calls of the slowest local rank's time on its stream (it includes waiting for the peers to

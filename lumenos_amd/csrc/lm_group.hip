@@ -948,6 +948,114 @@ extern "C" int lumen_group_gather(lumen_group *g, const lumen_set *const *src, c
     return 0;
 }
 
+// ---- P(z) over the ranks' column blocks (lm_polyeval.hip).  Every rank evaluates its block as if it began at column 0;
+// the block of rank r begins at c_r = the columns of the ranks before it, and z^(c_r) is applied when the partials are
+// summed -- so a rank of the one-process-per-GPU form needs nothing from its peers before it evaluates, and learns the
+// c_r from the one exchange that also carries the partials.
+int lm_poly_eval_check(lumen_ctx *ctx, const uint64_t *values, uint32_t rows, uint32_t count, uint64_t first_column,
+                       uint32_t cols, const char *what);
+int lm_poly_eval_enqueue(lumen_ctx *ctx, const uint64_t *values, uint32_t rows, uint32_t count, uint64_t first_column,
+                         uint32_t cols, uint64_t z, const char *what);
+int lm_poly_eval_finish(lumen_ctx *ctx, uint64_t *partial);
+bool lm_host_is_pinned(const void *p);
+
+extern "C" int lumen_group_poly_eval(lumen_group *g, const uint64_t *const *values, uint32_t rows, const uint32_t *counts,
+                                     uint32_t cols, uint64_t z, uint64_t *value) {
+    LM_CHECK(nullptr, g, "lumen_group_poly_eval: NULL group");
+    group_lock lk(g);
+    G_USABLE(g, "lumen_group_poly_eval");
+    const uint32_t n = (uint32_t)g->ctx.size(), W = g->W;
+    const uint64_t T = g->ctx[0]->T;
+    // One process per GPU: as in lumen_group_gather, a rank whose own arguments (or evaluation) fail must not return
+    // before the exchange its peers are already waiting in; it only notes what is wrong (`bad`) and says so there.
+    const bool per_rank = n < W && g->transport == LUMEN_TRANSPORT_RCCL;
+    std::string bad;
+    auto note_bad = [&](const std::string &why) {
+        if (bad.empty()) bad = why;
+    };
+    if (!values) note_bad("lumen_group_poly_eval: values is NULL");
+    if (!counts) note_bad("lumen_group_poly_eval: counts is NULL");
+    if (!value) note_bad("lumen_group_poly_eval: value is NULL");
+    std::vector<uint64_t> part(n, 0);
+    if (bad.empty()) {
+        for (uint32_t i = 0; i < n && bad.empty(); i++)
+            if (use(g, i) || lm_poly_eval_check(g->ctx[i], values[i], rows, counts[i], 0, cols, "lumen_group_poly_eval"))
+                note_bad(lm_global_err);
+    }
+    if (bad.empty()) {
+        // page-locked blocks first: they are only enqueued, so the W links of a process that owns W GPUs carry them at
+        // once; pageable ones go through each context's bounce buffers, one rank after the other
+        std::vector<uint32_t> order;
+        for (uint32_t pass = 0; pass < 2; pass++)
+            for (uint32_t i = 0; i < n; i++)
+                if (lm_host_is_pinned(values[i]) == (pass == 0)) order.push_back(i);
+        std::vector<bool> started(n, false);
+        for (uint32_t i : order) {
+            if (!bad.empty()) break;
+            started[i] = true;
+            if (use(g, i) || lm_poly_eval_enqueue(g->ctx[i], values[i], rows, counts[i], 0, cols, z, "lumen_group_poly_eval"))
+                note_bad(lm_global_err);
+        }
+        for (uint32_t i = 0; i < n; i++) // wait for whatever was enqueued, failure or not (the host buffers are the caller's)
+            if (started[i] && (use(g, i) || lm_poly_eval_finish(g->ctx[i], &part[i])) && bad.empty()) note_bad(lm_global_err);
+    }
+    // per global rank: its column count and its partial (the block evaluated from column 0)
+    std::vector<uint64_t> cnt(W, 0), par(W, 0);
+    if (per_rank) {
+        // all-gather { fingerprint of (rows, cols, z, T), "my block is evaluated", count, partial } -- fixed size
+        uint64_t fp = 1469598103934665603ull;
+        for (uint64_t v : {(uint64_t)rows, (uint64_t)cols, T ? z % T : z, T}) fp = (fp ^ v) * 1099511628211ull;
+        std::vector<u64 *> dbuf(n);
+        for (uint32_t i = 0; i < n; i++) {
+            lumen_ctx *c = g->ctx[i];
+            if (use(g, i)) return 1;
+            dbuf[i] = (u64 *)lm_scratch(c, "poly_agree", 32 * (size_t)(W + 1));
+            u64 *h = (u64 *)lm_stage(c, 32);
+            if (!dbuf[i] || !h) return 1;
+            h[0] = fp, h[1] = bad.empty() ? 1 : 0, h[2] = bad.empty() ? counts[i] : 0, h[3] = part[i];
+            G_HIP(hipMemcpyAsync(dbuf[i] + 4 * W, h, 32, hipMemcpyHostToDevice, c->stream));
+            G_HIP(hipEventRecord(c->ev_stage, c->stream));
+        }
+        {
+            rccl_group_scope grp(g);
+            if (grp.begin()) return 1;
+            for (uint32_t i = 0; i < n; i++) {
+                if (use(g, i)) return 1;
+                G_NCCL(g, g->rccl->AllGather(dbuf[i] + 4 * W, dbuf[i], 4, ncclUint64, g->comm[i], g->ctx[i]->stream));
+            }
+            if (grp.end()) return 1;
+        }
+        std::vector<uint64_t> seen(4 * (size_t)W);
+        for (uint32_t i = 0; i < n; i++) {
+            if (use(g, i)) return 1;
+            G_HIP(hipMemcpyAsync(seen.data(), dbuf[i], 32 * (size_t)W, hipMemcpyDeviceToHost, g->ctx[i]->stream));
+            G_HIP(hipStreamSynchronize(g->ctx[i]->stream));
+            LM_CHECK(nullptr, bad.empty(), "%s", bad.c_str()); // (the peers see this rank's flag and fail with it)
+            for (uint32_t p = 0; p < W; p++)
+                LM_CHECK(nullptr, seen[4 * p + 1] == 1, "lumen_group_poly_eval: rank %u rejected its arguments or failed to "
+                         "evaluate (see its own message)", p);
+            for (uint32_t p = 0; p < W; p++)
+                LM_CHECK(nullptr, seen[4 * p] == fp, "lumen_group_poly_eval: rank %u was given another rows, cols or z than rank %u "
+                         "(every rank must pass the same)", p, g->rank[i]);
+        }
+        for (uint32_t p = 0; p < W; p++) cnt[p] = seen[4 * p + 2], par[p] = seen[4 * p + 3];
+    } else {
+        LM_CHECK(nullptr, bad.empty(), "%s", bad.c_str());
+        for (uint32_t i = 0; i < n; i++) cnt[g->rank[i]] = counts[i], par[g->rank[i]] = part[i];
+    }
+    uint64_t total = 0;
+    for (uint64_t c : cnt) total += c;
+    LM_CHECK(nullptr, total == cols, "lumen_group_poly_eval: the ranks' counts sum to %llu columns, cols = %u",
+             (unsigned long long)total, cols);
+    uint64_t v = 0, first = 0;
+    for (uint32_t p = 0; p < W; p++) {
+        v = (v + h_mulmod(h_powmod(z, first, T), par[p], T)) % T;
+        first += cnt[p];
+    }
+    *value = v;
+    return 0;
+}
+
 // ---- host <-> ranks: every local rank's transfer is enqueued before any is waited for, so the W PCIe links of a
 // process that owns W GPUs carry their blocks at the same time (one lumen_set_upload per rank would finish the
 // first DMA before it starts the second: 12.9 GB over one link after the other)

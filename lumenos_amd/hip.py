@@ -97,6 +97,7 @@ SYMBOLS = {
     "lumen_inner_sum": (C.c_int, [_vp, _vp, C.c_uint32, _vpp]),
     "lumen_gather": (C.c_int, [_vp, _vp, _u32p, C.c_uint32, _vpp]),
     "lumen_plain_inner_products": (C.c_int, [_vp, _vp, _u64p, _u64p]),
+    "lumen_poly_eval_columns": (C.c_int, [_vp, _u64p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint64, _u64p]),
     "lumen_ringswitch_rns_digits": (C.c_uint32, [_vp]),
     "lumen_ringswitch_digits": (C.c_uint32, [_vp, C.c_uint32]),
     "lumen_load_ringswitch_key": (C.c_int, [_vp, C.c_uint32, C.c_uint32, _u64p, C.c_size_t]),
@@ -119,6 +120,7 @@ SYMBOLS = {
     "lumen_group_merkle_root": (C.c_int, [_vp, _u8p]),
     "lumen_group_digests": (C.c_int, [_vp, _u8p, C.c_size_t, _u32p]),
     "lumen_group_gather": (C.c_int, [_vp, _vpp, _u32p, C.c_uint32, _vpp]),
+    "lumen_group_poly_eval": (C.c_int, [_vp, _vpp, C.c_uint32, _u32p, C.c_uint32, C.c_uint64, _u64p]),
     "lumen_group_stats": (C.c_int, [_vp, C.c_char_p, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "lumen_group_stats_reset": (C.c_int, [_vp]),
     "lumen_ctx_scratch_info": (C.c_int, [_vp, C.c_char_p, _vpp, C.POINTER(C.c_size_t)]),
@@ -596,6 +598,16 @@ class Context:
         self._ck(self.lib.lumen_plain_inner_products(self.h, s.h, _p64(vec), _p64(out)))
         return out
 
+    def poly_eval_columns(self, values, first_column, cols, z):
+        """P(z)'s part over the witness columns `values` ([count][rows], the layout of encrypt_values), the first of
+        which is column `first_column` of a matrix of `cols` columns (cmd/server/main.go:255-258)"""
+        values = np.ascontiguousarray(values, dtype=np.uint64)  # no copy of a contiguous (e.g. page-locked) array
+        assert values.ndim == 2
+        out = C.c_uint64()
+        self._ck(self.lib.lumen_poly_eval_columns(self.h, _p64(values), values.shape[1], values.shape[0], first_column,
+                                                  cols, z, C.byref(out)))
+        return out.value
+
     def gather(self, s, idx):
         idx = np.ascontiguousarray(idx, dtype=np.uint32)
         h = C.c_void_p()
@@ -768,6 +780,17 @@ class Group:
         h = C.c_void_p()
         self._ck(self.lib.lumen_group_gather(self.h, self._handles(src), idx.ctypes.data_as(_u32p), len(idx), C.byref(h)))
         return DeviceSet(self.ctxs[0], h) if h.value else None
+
+    def poly_eval(self, values, cols, z):
+        """P(z) of a matrix of `cols` columns spread over the ranks: values[i] = local rank i's block [count_i][rows]"""
+        values = [np.ascontiguousarray(v, dtype=np.uint64) for v in values]
+        assert len(values) == len(self.ctxs) and all(v.ndim == 2 and v.shape[1] == values[0].shape[1] for v in values)
+        ptrs = (C.c_void_p * len(values))(*[v.ctypes.data for v in values])
+        counts = np.array([v.shape[0] for v in values], dtype=np.uint32)
+        out = C.c_uint64()
+        self._ck(self.lib.lumen_group_poly_eval(self.h, ptrs, values[0].shape[1], counts.ctypes.data_as(_u32p), cols, z,
+                                                C.byref(out)))
+        return out.value
 
     def stats(self, name):
         ms, b, n = C.c_double(), C.c_uint64(), C.c_uint64()

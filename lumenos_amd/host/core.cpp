@@ -384,6 +384,21 @@ double Span::End() {
     return seconds_;
 }
 
+// ------------------------------------------------------------------ polynomial
+Element DensePoly::Evaluate(const PrimeField &field, Element point) const {
+    const uint64_t q = field.Modulus();
+    point %= q;
+    Element result = 0;
+    for (size_t i = Coefficients.size(); i-- > 0;) result = field.Add(field.Mul(result, point), Coefficients[i] % q);
+    return result;
+}
+
+DensePoly NewDensePolyFromMatrix(const std::vector<Element> &matrix, int rows, int cols) {
+    if (rows < 0 || cols < 0 || matrix.size() != (size_t)rows * (size_t)cols)
+        throw std::invalid_argument("NewDensePolyFromMatrix: the matrix is not rows x cols");
+    return DensePoly(matrix);
+}
+
 // ------------------------------------------------------------------ witness
 static inline uint32_t rotl32(uint32_t x, int n) { return (x << n) | (x >> (32 - n)); }
 #define LM_QR(a, b, c, d)              \

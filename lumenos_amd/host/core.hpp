@@ -107,6 +107,20 @@ class Span {
     double seconds_ = -1;
 };
 
+// core.DensePoly (core/poly.go:3-45): the committed polynomial whose value at the client's point the server returns
+// next to the proof (cmd/server/main.go:255-258).  On the host: the checker of the device evaluation and the
+// reference API (fhe::ServerBFV::EvaluateColumns is the device form).
+class DensePoly {
+  public:
+    explicit DensePoly(std::vector<Element> coefficients) : Coefficients(std::move(coefficients)) {}
+    // Horner from the highest coefficient down (poly.go:21-30); a coefficient >= the modulus counts as its residue
+    Element Evaluate(const PrimeField &field, Element point) const;
+    std::vector<Element> Coefficients;
+};
+// NewDensePolyFromMatrix (poly.go:13-18): the rows one after the other (flattenRowMajor), coefficient i*cols + j =
+// M[i][j]; `matrix` is the row-major [rows][cols] the mirror holds witnesses in (RandomMatrixRowMajor)
+DensePoly NewDensePolyFromMatrix(const std::vector<Element> &matrix, int rows, int cols);
+
 // core.RandomMatrixRowMajor (core/utils.go:46-82): deterministic ChaCha20 witness, row-major
 std::vector<uint64_t> RandomMatrixRowMajor(int rows, int cols, uint64_t modT);
 

@@ -407,6 +407,19 @@ Ciphertexts ServerBFV::EncryptColumnsNew(const std::vector<uint64_t> &values, in
     return Ciphertexts(ctx_, set, md);
 }
 
+core::Element ServerBFV::EvaluateColumns(const std::vector<uint64_t> &values, int rows, int count, int cols, core::Element z,
+                                         uint64_t firstColumn) {
+    if (rows < 0 || count < 0 || cols < 0 || (size_t)rows * count != values.size())
+        throw std::invalid_argument("EvaluateColumns: size mismatch");
+    core::Span *span = core::Span::StartSpan("Evaluate polynomial", nullptr);
+    uint64_t value = 0;
+    check(lumen_poly_eval_columns(ctx_, values.data(), (uint32_t)rows, (uint32_t)count, firstColumn, (uint32_t)cols, z, &value),
+          "lumen_poly_eval_columns");
+    span->End();
+    delete span;
+    return value;
+}
+
 // ------------------------------------------------------------------ ring switch
 RingSwitchServer::RingSwitchServer(ServerBFV &backend, const std::vector<uint64_t> &ringSwitchEvk, int logN,
                                    int baseTwoDecomposition)
@@ -469,6 +482,23 @@ ShardedCiphertexts ServerGroup::EncryptColumnsNew(const std::vector<uint64_t> &v
         out.Blocks.emplace_back(s.Context(), set, md);
     }
     return out;
+}
+
+core::Element ServerGroup::EvaluateColumns(const std::vector<uint64_t> &values, int rows, int count, int cols, core::Element z) {
+    const int W = World();
+    if (rows < 0 || count < 0 || (size_t)rows * count != values.size()) throw std::invalid_argument("EvaluateColumns: size mismatch");
+    if (count % W) throw std::invalid_argument("EvaluateColumns: the columns do not split evenly over the ranks");
+    const int own = count / W; // the split of EncryptColumnsNew
+    std::vector<const uint64_t *> blocks((size_t)W);
+    std::vector<uint32_t> counts((size_t)W, (uint32_t)own);
+    for (int r = 0; r < W; r++) blocks[(size_t)r] = values.data() + (size_t)r * own * rows;
+    core::Span *span = core::Span::StartSpan("Evaluate polynomial", nullptr);
+    uint64_t value = 0;
+    check(lumen_group_poly_eval(group_, blocks.data(), (uint32_t)rows, counts.data(), (uint32_t)cols, z, &value),
+          "lumen_group_poly_eval");
+    span->End();
+    delete span;
+    return value;
 }
 
 // ------------------------------------------------------------------ Encode / NTT

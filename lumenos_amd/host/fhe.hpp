@@ -141,6 +141,13 @@ class ServerBFV {
     Ciphertexts EncryptNewBatch(const std::vector<Plaintext> &pts);
     // Encoder.Encode + EncryptNew of `count` columns of `rows` values ([count][rows]), both on the device
     Ciphertexts EncryptColumnsNew(const std::vector<uint64_t> &values, int rows, int count);
+    // the claimed value of GET /prove?point=z (cmd/server/main.go:255-258: core.NewDensePolyFromMatrix(matrix).Evaluate)
+    // over `count` witness columns of `rows` values ([count][rows], what EncryptColumnsNew takes) that begin at column
+    // `firstColumn` of a matrix of `cols` columns, on the device (lumen_poly_eval_columns): the whole matrix gives
+    // P(z), disjoint column blocks give partials that sum mod T to it.  Prints the reference's span
+    // "Evaluate polynomial".
+    core::Element EvaluateColumns(const std::vector<uint64_t> &values, int rows, int count, int cols, core::Element z,
+                                  uint64_t firstColumn = 0);
     void check(int rc, const char *what) const; // throws std::runtime_error with lumen_last_error
     void SetRingSwitchServer(RingSwitchServer *rs) { rs_ = rs; } // bfv.go:48-50
     RingSwitchServer *RingSwitch() const { return rs_; }          // bfv.go:52-54
@@ -195,6 +202,9 @@ class ServerGroup {
     // the witness encryption loop of cmd/server/main.go:188-208 over the ranks: column j (of `count`, `rows`
     // values each) is encoded and encrypted on rank j / (count/W), with its own place in the encryptor's stream
     ShardedCiphertexts EncryptColumnsNew(const std::vector<uint64_t> &values, int rows, int count);
+    // P(z) of the same witness over the ranks (lumen_group_poly_eval): rank r evaluates the block of columns
+    // EncryptColumnsNew puts on it, the partials are summed inside the library.  Prints "Evaluate polynomial".
+    core::Element EvaluateColumns(const std::vector<uint64_t> &values, int rows, int count, int cols, core::Element z);
 
   private:
     std::vector<ServerBFV *> ranks_;
