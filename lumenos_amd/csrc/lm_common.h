@@ -221,16 +221,6 @@ extern thread_local std::string lm_global_err;
         if (!(cond)) return lm_fail(ctx, __VA_ARGS__); \
     } while (0)
 
-// raise a kernel's dynamic-LDS limit once (hipFuncSetAttribute is not free on the launch path)
-#define LM_LDS_ATTR(ctx, kernel, bytes)                                                                   \
-    do {                                                                                                  \
-        const void *fp_ = reinterpret_cast<const void *>(&kernel);                                        \
-        if (!(ctx)->lds_attr_done.count(fp_)) {                                                           \
-            LM_HIP(ctx, hipFuncSetAttribute(fp_, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); \
-            (ctx)->lds_attr_done.insert(fp_);                                                             \
-        }                                                                                                 \
-    } while (0)
-
 // owns a freshly created set until the entry point hands it to the caller: every early return
 // (LM_HIP / LM_CHECK) gives the storage back instead of leaking it
 struct lm_set_guard {
@@ -314,6 +304,8 @@ void lm_build_tw(uint64_t q, uint64_t psi, uint32_t logN, std::vector<tw_t> &fwd
 int lm_rescale_polys(lumen_ctx *ctx, const u64 *src, uint32_t nl, u64 *dst, uint32_t target,
                      uint32_t npoly, u64 *work, u64 *tbuf);
 lm_modmap lm_map_q(uint32_t nl);
+// the K limbs modulo P of a [K]-periodic buffer: moduli L .. L+K-1
+lm_modmap lm_map_p(const lumen_ctx *ctx);
 // fhe.Encode with Enc(0) resident on the device; never blocks the host (lm_ctntt.hip)
 int lm_encode_dev(lumen_ctx *ctx, const lumen_set *matrix, const u64 *dzero, uint32_t rho_inv, lumen_set **encoded);
 // pooled timing events of a context (lm_ctx.hip)

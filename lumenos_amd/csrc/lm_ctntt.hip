@@ -608,11 +608,9 @@ static int run_plan(lumen_ctx *ctx, Plan *plan, uint32_t count, uint32_t nl, con
         const uint32_t ng = final_pass && final_ng ? final_ng : d.ngroups;
         const uint32_t ntiles = (uint32_t)(ctw / LM_CB_W);
         dim3 grid((ntiles + LM_CB_TILES - 1) / LM_CB_TILES, ng);
-        const size_t lds = (size_t)d.gsize * LM_CB_W * sizeof(u64);
-        LM_LDS_ATTR(ctx, k_ct_blocks, lds);
+        const lm_geom geom{LM_CB_THREADS, 1, (size_t)d.gsize * LM_CB_W * sizeof(u64)};
         lm_prof_scope ps(ctx, "ct_axis_pass", (uint64_t)ng * d.gsize);
-        hipLaunchKernelGGL(k_ct_blocks, grid, dim3(LM_CB_THREADS), lds, ctx->stream, b, ctx->mods);
-        LM_HIP(ctx, hipGetLastError());
+        if (int rc = lm_launch(ctx, k_ct_blocks, geom, grid, b, ctx->mods)) return rc;
         cur = tmp, split = count, curB = nullptr;
     }
     // slots no pass touched (size <= 1, or count == 0): plain permuted copy

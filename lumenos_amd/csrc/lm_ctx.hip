@@ -136,6 +136,13 @@ lm_modmap lm_map_q(uint32_t nl) {
     return m;
 }
 
+lm_modmap lm_map_p(const lumen_ctx *ctx) {
+    lm_modmap m;
+    m.period = ctx->K;
+    for (uint32_t i = 0; i < LM_MAX_LIMBS; i++) m.idx[i] = (uint8_t)(ctx->L + (i < ctx->K ? i : 0));
+    return m;
+}
+
 mod_t lm_make_mod(uint64_t q) {
     mod_t m;
     m.q = q;

@@ -128,14 +128,14 @@ struct enc_tinv_t {
 
 // pk: [2][LK][N] Shoup form (Q limbs times P^-1); out: [count][2][L][N]; upk: [count][2][K][N]
 template <int LOGN>
-__global__ __launch_bounds__(lm_max_threads(LOGN)) void k_enc_u(const int8_t *__restrict__ small,
+__global__ LM_GEOM_BOUNDS(lm_geom_lds(LOGN)) void k_enc_u(const int8_t *__restrict__ small,
                                                                const tw_t *__restrict__ pk, u64 *__restrict__ out,
                                                                u64 *__restrict__ upk, uint32_t count, uint32_t L,
                                                                uint32_t K, lm_mods mods,
                                                                const tw_t *__restrict__ tw_all) {
     extern __shared__ __attribute__((aligned(16))) u64 sm[];
     constexpr uint32_t N = 1u << LOGN;
-    const uint32_t tid = threadIdx.x, nthreads = blockDim.x, LK = L + K;
+    const uint32_t tid = threadIdx.x, LK = L + K;
     const uint32_t t = blockIdx.x / count, c = blockIdx.x % count; // limb-major: one twiddle table hot per XCD
     const lm_qc qc = lm_make_qc(mods.m[t]);
     const int8_t *su = small + (size_t)c * 3 * N;
@@ -163,7 +163,7 @@ __global__ __launch_bounds__(lm_max_threads(LOGN)) void k_enc_u(const int8_t *__
         lm_store_run(o0, i0, a, n);
         lm_store_run(o1, i0, b, n);
     };
-    lm_ntt_forward<LOGN>(sm, tw_all + (size_t)t * N, qc, tid, nthreads, ld, st);
+    lm_ntt_forward<LOGN>(sm, tw_all + (size_t)t * N, qc, tid, ld, st);
 }
 
 // y[c][w][j][i] += e_w[c][i] * hat_j mod p_j  (the INTT before it scaled the products by hat_j =
@@ -192,7 +192,7 @@ __global__ __launch_bounds__(256) void k_enc_add_e(u64 *__restrict__ upk, const 
 // message rides in the load of the w = 0 transform and costs no transform of its own.  pt: the
 // plaintexts in the NTT domain ([count][L][N]), added in the store.  out holds U*pk_w(*P^-1) on entry.
 template <int LOGN, bool HASP>
-__global__ __launch_bounds__(lm_max_threads(LOGN)) void k_enc_down(const int8_t *__restrict__ small,
+__global__ LM_GEOM_BOUNDS(lm_geom_lds(LOGN)) void k_enc_down(const int8_t *__restrict__ small,
                                                                   const u64 *__restrict__ upk,
                                                                   const bx_t *__restrict__ bxp,
                                                                   const tw_t *__restrict__ pinv,
@@ -203,7 +203,7 @@ __global__ __launch_bounds__(lm_max_threads(LOGN)) void k_enc_down(const int8_t 
                                                                   const tw_t *__restrict__ tw_all) {
     extern __shared__ __attribute__((aligned(16))) u64 sm[];
     constexpr uint32_t N = 1u << LOGN;
-    const uint32_t tid = threadIdx.x, nthreads = blockDim.x;
+    const uint32_t tid = threadIdx.x;
     const uint32_t l = blockIdx.x / (2 * count), cw = blockIdx.x % (2 * count), c = cw >> 1, w = cw & 1;
     const lm_qc qc = lm_make_qc(mods.m[l]);
     const int8_t *se = small + ((size_t)c * 3 + 1 + w) * N;
@@ -251,7 +251,7 @@ __global__ __launch_bounds__(lm_max_threads(LOGN)) void k_enc_down(const int8_t 
             }
         lm_store_run(o, i0, a, n);
     };
-    lm_ntt_forward<LOGN, false>(sm, tw_all + (size_t)l * N, qc, tid, nthreads, ld, st); // 111 VGPRs as it is
+    lm_ntt_forward<LOGN, false>(sm, tw_all + (size_t)l * N, qc, tid, ld, st); // 111 VGPRs as it is
 }
 
 struct PkTable {
@@ -352,31 +352,22 @@ template <int LOGN>
 static int encrypt_t(lumen_ctx *ctx, const int8_t *small, const tw_t *pk, const u64 *pt, const u64 *mcoef,
                      const enc_tinv_t &tinv, u64 *out, u64 *upk, uint32_t count) {
     const uint32_t N = ctx->N, L = ctx->L, K = ctx->K, LK = L + K;
-    const size_t lds = lm_fwd_lds(ctx->logN);
-    const uint32_t threads = lm_fwd_threads(ctx->logN);
+    constexpr lm_geom geom = lm_geom_lds(LOGN);
     {
-        LM_LDS_ATTR(ctx, k_enc_u<LOGN>, lds);
         lm_prof_scope ps(ctx, "encrypt_u_ntt", (uint64_t)count * LK);
-        hipLaunchKernelGGL(k_enc_u<LOGN>, dim3(count * LK), dim3(threads), lds, ctx->stream, small, pk, out, upk, count,
-                           L, K, ctx->mods, ctx->d_tw_fwd);
-        LM_HIP(ctx, hipGetLastError());
+        if (int rc = lm_launch(ctx, k_enc_u<LOGN>, geom, count * LK, small, pk, out, upk, count, L, K, ctx->mods,
+                               ctx->d_tw_fwd))
+            return rc;
     }
     if (!K) {
-        LM_LDS_ATTR(ctx, (k_enc_down<LOGN, false>), lds);
         lm_prof_scope ps(ctx, "encrypt_down_ntt", (uint64_t)count * 2 * L);
-        hipLaunchKernelGGL((k_enc_down<LOGN, false>), dim3(count * 2 * L), dim3(threads), lds, ctx->stream, small, upk,
-                           (const bx_t *)nullptr, (const tw_t *)nullptr, pt, mcoef, tinv, out, count, L, K, ctx->mods,
-                           ctx->d_tw_fwd);
-        LM_HIP(ctx, hipGetLastError());
-        return 0;
+        return lm_launch(ctx, k_enc_down<LOGN, false>, geom, count * 2 * L, small, upk, nullptr, nullptr, pt, mcoef, tinv,
+                         out, count, L, K, ctx->mods, ctx->d_tw_fwd);
     }
     lm_ks_view kv;
     if (int rc = lm_ks_tables_view(ctx, &kv)) return rc;
     // the P limbs of u*pk_w to the coefficient domain, scaled for the basis extension
-    lm_modmap mp;
-    mp.period = K;
-    for (uint32_t i = 0; i < LM_MAX_LIMBS; i++) mp.idx[i] = (uint8_t)(L + (i < K ? i : 0));
-    if (int rc = lm_launch_ntt_strided(ctx, upk, (size_t)K * N, upk, (size_t)K * N, count * 2, mp, true,
+    if (int rc = lm_launch_ntt_strided(ctx, upk, (size_t)K * N, upk, (size_t)K * N, count * 2, lm_map_p(ctx), true,
                                        "encrypt_intt_p", kv.yscale))
         return rc;
     {
@@ -393,14 +384,9 @@ static int encrypt_t(lumen_ctx *ctx, const int8_t *small, const tw_t *pk, const 
     }
     if (K == 2)
         if (int rc = lm_launch_pack_v(ctx, upk, (size_t)K * N, count * 2, 1u, K, L, K)) return rc;
-    {
-        LM_LDS_ATTR(ctx, (k_enc_down<LOGN, true>), lds);
-        lm_prof_scope ps(ctx, "encrypt_down_ntt", (uint64_t)count * 2 * L);
-        hipLaunchKernelGGL((k_enc_down<LOGN, true>), dim3(count * 2 * L), dim3(threads), lds, ctx->stream, small, upk,
-                           kv.d_bxp, kv.d_pinv, pt, mcoef, tinv, out, count, L, K, ctx->mods, ctx->d_tw_fwd);
-        LM_HIP(ctx, hipGetLastError());
-    }
-    return 0;
+    lm_prof_scope ps(ctx, "encrypt_down_ntt", (uint64_t)count * 2 * L);
+    return lm_launch(ctx, k_enc_down<LOGN, true>, geom, count * 2 * L, small, upk, kv.d_bxp, kv.d_pinv, pt, mcoef, tinv, out,
+                     count, L, K, ctx->mods, ctx->d_tw_fwd);
 }
 
 // plaintexts (NTT-domain RNS, [count][L][N]) or values ([count][rows] slot values) or neither (zeros)
@@ -481,16 +467,7 @@ static int encrypt_impl(lumen_ctx *ctx, const uint64_t *plaintexts, const uint64
             LM_HIP(ctx, hipGetLastError());
         }
         u64 *dst = o->d + (size_t)first * 2 * L * N;
-        switch (ctx->logN) {
-#define LM_CASE(k) \
-    case k:        \
-        rc = encrypt_t<k>(ctx, small, pkt->d_pk, dpt, dm, tinv, dst, upk, n); \
-        break;
-            LM_FOR_EACH_LOGN(LM_CASE)
-#undef LM_CASE
-        default:
-            rc = lm_fail(ctx, "ring degree 2^%u has no kernel instantiation", ctx->logN);
-        }
+        rc = lm_for_logn(ctx, ctx->logN, [&](auto k) { return encrypt_t<k>(ctx, small, pkt->d_pk, dpt, dm, tinv, dst, upk, n); });
     }
     if (rc) return rc;
     if (plaintexts || values) LM_HIP(ctx, hipStreamSynchronize(ctx->stream)); // caller memory
@@ -551,13 +528,13 @@ struct dec_scale_t {
     tw_t t[LM_MAX_LIMBS];
 };
 template <int LOGN>
-__global__ __launch_bounds__(lm_max_threads(LOGN)) void k_decrypt_phase(const u64 *__restrict__ ct, const tw_t *__restrict__ sk,
+__global__ LM_GEOM_BOUNDS(lm_geom_lds(LOGN)) void k_decrypt_phase(const u64 *__restrict__ ct, const tw_t *__restrict__ sk,
                                                                        u64 *__restrict__ phase, uint32_t count, uint32_t nl,
                                                                        dec_scale_t scale, lm_mods mods,
                                                                        const tw_t *__restrict__ tw_all) {
     extern __shared__ __attribute__((aligned(16))) u64 sm[];
     constexpr uint32_t N = 1u << LOGN;
-    const uint32_t tid = threadIdx.x, nthreads = blockDim.x;
+    const uint32_t tid = threadIdx.x;
     const uint32_t l = blockIdx.x / count, c = blockIdx.x % count;
     const lm_qc qc = lm_make_qc(mods.m[l]);
     const u64 *c0 = ct + ((size_t)c * 2 * nl + l) * N, *c1 = c0 + (size_t)nl * N;
@@ -577,7 +554,7 @@ __global__ __launch_bounds__(lm_max_threads(LOGN)) void k_decrypt_phase(const u6
             }
     };
     auto st = [&](uint32_t i, u64 v) { o[i] = lm_shoup_cs(v, sc, qc.q, qc.nq); };
-    lm_ntt_inverse<LOGN>(sm, tw_all + (size_t)l * N, qc, tid, nthreads, ld, st);
+    lm_ntt_inverse<LOGN>(sm, tw_all + (size_t)l * N, qc, tid, ld, st);
 }
 
 // m[c][k] = centre_Q(CRT(phase limbs)) mod T
@@ -657,13 +634,9 @@ __global__ void k_decrypt_slots(const u64 *__restrict__ t, const uint32_t *__res
 template <int LOGN>
 static int decrypt_phase_t(lumen_ctx *ctx, const u64 *ct, const tw_t *sk, u64 *phase, uint32_t count, uint32_t nl,
                            const dec_scale_t &sc) {
-    const size_t lds = lm_inv_lds(ctx->logN);
-    LM_LDS_ATTR(ctx, k_decrypt_phase<LOGN>, lds);
     lm_prof_scope ps(ctx, "decrypt_phase_intt", (uint64_t)count * nl);
-    hipLaunchKernelGGL(k_decrypt_phase<LOGN>, dim3(count * nl), dim3(lm_inv_threads(ctx->logN)), lds, ctx->stream, ct, sk,
-                       phase, count, nl, sc, ctx->mods, ctx->d_tw_inv);
-    LM_HIP(ctx, hipGetLastError());
-    return 0;
+    return lm_launch(ctx, k_decrypt_phase<LOGN>, lm_geom_lds(LOGN), count * nl, ct, sk, phase, count, nl, sc, ctx->mods,
+                     ctx->d_tw_inv);
 }
 
 extern "C" int lumen_decrypt(lumen_ctx *ctx, const lumen_set *set, uint64_t scale, uint32_t nvalues, uint64_t *values) {
@@ -691,18 +664,8 @@ extern "C" int lumen_decrypt(lumen_ctx *ctx, const lumen_set *set, uint64_t scal
         const uint64_t q = ctx->mod[l < nl ? l : 0];
         sc.t[l] = h_tw(h_mulmod(ctx->ninv[l < nl ? l : 0].w, T % q, q), q);
     }
-    int rc = 0;
-    switch (ctx->logN) {
-#define LM_CASE(k) \
-    case k:        \
-        rc = decrypt_phase_t<k>(ctx, set->d, sk->d_sk, phase, count, nl, sc); \
-        break;
-        LM_FOR_EACH_LOGN(LM_CASE)
-#undef LM_CASE
-    default:
-        rc = lm_fail(ctx, "ring degree 2^%u has no kernel instantiation", ctx->logN);
-    }
-    if (rc) return rc;
+    if (int rc = lm_for_logn(ctx, ctx->logN, [&](auto k) { return decrypt_phase_t<k>(ctx, set->d, sk->d_sk, phase, count, nl, sc); }))
+        return rc;
     if (nl > 2) { // deeper than what Prove returns: exact CRT by mixed radix
         std::vector<garner_t> hg(1);
         garner_t &G = hg[0];

@@ -136,12 +136,12 @@ __global__ __launch_bounds__(256) void k_pack_v(u64 *__restrict__ y, size_t poly
 // transforms fill in behind them as the pairs finish -- the launch is as long as three rounds of single
 // transforms, and two thirds of the packing pass are gone.
 template <int LOGN>
-__global__ __launch_bounds__(lm_max_threads(LOGN)) void k_intt_pack(const u64 *__restrict__ acc, u64 *coef, uint32_t B,
+__global__ LM_GEOM_BOUNDS(lm_geom_lds(LOGN)) void k_intt_pack(const u64 *__restrict__ acc, u64 *coef, uint32_t B,
                                                                   uint32_t L, uint32_t nf, lm_mods mods,
                                                                   lm_ninv_t yscale, const tw_t *__restrict__ tw_all) {
     extern __shared__ __attribute__((aligned(16))) u64 sm[];
     constexpr uint32_t N = 1u << LOGN;
-    const uint32_t tid = threadIdx.x, nthreads = blockDim.x;
+    const uint32_t tid = threadIdx.x;
     if (blockIdx.x >= B * nf) { // a limb of an unfused digit: limb-major, as k_limb_ntt
         const uint32_t k = blockIdx.x - B * nf, l = 2 * nf + k / B, b = k % B;
         const u64 *p = acc + (((size_t)b * 2 + 1) * L + l) * N;
@@ -150,7 +150,7 @@ __global__ __launch_bounds__(lm_max_threads(LOGN)) void k_intt_pack(const u64 *_
         const tw_t sc = yscale.t[l];
         auto ld = [&](uint32_t i0, u64 *v, int count) { lm_load_run(p, i0, v, count); };
         auto st = [&](uint32_t i, u64 v) { o[i] = lm_shoup_cs(v, sc, q.q, q.nq); };
-        lm_ntt_inverse<LOGN>(sm, tw_all + (size_t)l * N, q, tid, nthreads, ld, st);
+        lm_ntt_inverse<LOGN>(sm, tw_all + (size_t)l * N, q, tid, ld, st);
         return;
     }
     const uint32_t d = blockIdx.x / B, b = blockIdx.x % B; // digit-major: two twiddle tables hot per XCD
@@ -163,7 +163,7 @@ __global__ __launch_bounds__(lm_max_threads(LOGN)) void k_intt_pack(const u64 *_
         const u64 *p = c1 + (size_t)l0 * N;
         auto ld = [&](uint32_t i0, u64 *v, int count) { lm_load_run(p, i0, v, count); };
         auto st = [&](uint32_t i, u64 v) { o0[i] = lm_shoup_cs(v, s0, q0.q, q0.nq); };
-        lm_ntt_inverse<LOGN>(sm, tw_all + (size_t)l0 * N, q0, tid, nthreads, ld, st);
+        lm_ntt_inverse<LOGN>(sm, tw_all + (size_t)l0 * N, q0, tid, ld, st);
     }
     __syncthreads(); // the second transform reuses the LDS
     {
@@ -209,7 +209,7 @@ __global__ __launch_bounds__(lm_max_threads(LOGN)) void k_intt_pack(const u64 *_
         } st{o0, q0, q1, s1, M, {}};
         uint32_t tid1 = tid; // nothing derived from the lane index is carried over from the first limb
         asm volatile("" : "+v"(tid1));
-        lm_ntt_inverse<LOGN>(sm, tw_all + (size_t)l1 * N, q1, tid1, nthreads, ld, st);
+        lm_ntt_inverse<LOGN>(sm, tw_all + (size_t)l1 * N, q1, tid1, ld, st);
     }
 }
 
@@ -247,14 +247,14 @@ __global__ void k_mul_plain(const u64 *__restrict__ ct, u64 *__restrict__ out, c
 // ---- step 2: digit extension + NTT.  One workgroup per (column b, digit d, target t).
 // coef: [B][L][N] coefficient-domain c1; acc: [B][2][L][N] (c1 NTT values for own limbs); ext: [L+K][B][beta][N] (ks_ext_at)
 template <int LOGN>
-__global__ __launch_bounds__(lm_fwdw_threads(LOGN), lm_fwdw_waves(LOGN)) void k_modup_ntt(const u64 *__restrict__ coef, const u64 *__restrict__ acc,
+__global__ LM_GEOM_BOUNDS(lm_geom_fwd(LOGN)) void k_modup_ntt(const u64 *__restrict__ coef, const u64 *__restrict__ acc,
                                                     u64 *__restrict__ ext, const bx_t *__restrict__ bx,
                                                     uint32_t B, uint32_t L, uint32_t K, uint32_t beta,
                                                     const uint32_t *__restrict__ work, lm_mods mods,
                                                     const tw_t *__restrict__ tw_all) {
     extern __shared__ __attribute__((aligned(16))) u64 sm[];
     constexpr uint32_t N = 1u << LOGN;
-    const uint32_t tid = threadIdx.x, nthreads = blockDim.x, LK = L + K;
+    const uint32_t tid = threadIdx.x, LK = L + K;
     // The grid only holds the (column, digit, target) triples that need an extension (a digit's own
     // limbs reuse the NTT-domain c1), in the order of a host-built work list (modup_work_list): XCD-
     // aware, so that the targets of one digit run back to back on one XCD and share its L2.
@@ -277,14 +277,13 @@ __global__ __launch_bounds__(lm_fwdw_threads(LOGN), lm_fwdw_waves(LOGN)) void k_
         *reinterpret_cast<ulonglong2 *>(o + j) = y;
     };
     if constexpr (LOGN == 14) { // limb in registers, two workgroups per CU: the runs go through the wave's slot, half by half
-        (void)nthreads;
         lm_w14_runs st{sm};
         auto after = [&](uint32_t i0, uint32_t) { lm_w14_linear_out(sm, tid, i0, out); };
         lm_ntt_forward_w14(sm, tw_all + (size_t)t * N, qc, tid, ld, st, after);
     } else {
         lm_lds_runs st{sm};
         auto after = [&](uint32_t, uint32_t) { lm_linear_out<LOGN>(sm, tid, out); };
-        lm_ntt_forward<LOGN>(sm, tw_all + (size_t)t * N, qc, tid, nthreads, ld, st, after);
+        lm_ntt_forward<LOGN>(sm, tw_all + (size_t)t * N, qc, tid, ld, st, after);
     }
 }
 
@@ -480,7 +479,7 @@ __global__ __launch_bounds__(256) void k_ks_mac(const u64 *__restrict__ ext, con
 // acc_out[j] = acc_in[j] + d[index[j]], the automorphism being a gather out of the wave's own LDS block.  (acc is
 // ping-ponged: an output needs the old accumulator at two positions, j and index[j].)
 template <int LOGN>
-__global__ __launch_bounds__(lm_max_threads(LOGN)) void k_moddown_ntt(const u64 *__restrict__ u, const u64 *__restrict__ acc_in,
+__global__ LM_GEOM_BOUNDS(lm_geom_lds(LOGN)) void k_moddown_ntt(const u64 *__restrict__ u, const u64 *__restrict__ acc_in,
                                                      u64 *__restrict__ acc_out, const bx_t *__restrict__ bxp,
                                                      const tw_t *__restrict__ pinv,
                                                      const uint32_t *__restrict__ index,
@@ -490,7 +489,7 @@ __global__ __launch_bounds__(lm_max_threads(LOGN)) void k_moddown_ntt(const u64 
                                                      const tw_t *__restrict__ tw_all) {
     extern __shared__ __attribute__((aligned(16))) u64 sm[];
     constexpr uint32_t N = 1u << LOGN;
-    const uint32_t tid = threadIdx.x, nthreads = blockDim.x;
+    const uint32_t tid = threadIdx.x;
     // host-built, XCD-aware order (moddown_work_list): the Q limbs of one polynomial, which all lift the
     // same two P-limb words, run back to back on one XCD
     const uint32_t wk = work[blockIdx.x];
@@ -576,7 +575,7 @@ __global__ __launch_bounds__(lm_max_threads(LOGN)) void k_moddown_ntt(const u64 
             *reinterpret_cast<ulonglong2 *>(aout + j) = y;
         }
     };
-    lm_ntt_forward<LOGN>(sm, tw_all + (size_t)t * N, qc, tid, nthreads, ld, st, after);
+    lm_ntt_forward<LOGN>(sm, tw_all + (size_t)t * N, qc, tid, ld, st, after);
 }
 
 // words of a lazy accumulator ([0, 2q), see k_moddown_ntt) to canonical form: for the callers that hand the
@@ -721,6 +720,30 @@ struct KsScratch {
     u64 *coef, *ext, *u, *acc2;
 };
 
+// Tail of both work-list builders below.  Workgroup k of a launch runs on XCD k % 8, so the eight per-XCD lists are
+// interleaved (lists of unequal length -- B not a multiple of 8 -- are drained in turn); the device copy is cached.
+static int interleave_work_lists(lumen_ctx *ctx, const std::vector<std::vector<uint32_t>> &lists, size_t expect,
+                                 const char *what, std::map<uint32_t, uint32_t *> &cache, uint32_t cache_key,
+                                 const uint32_t **out) {
+    std::vector<uint32_t> order;
+    order.reserve(expect);
+    std::vector<size_t> pos(8, 0);
+    for (bool any = true; any;) {
+        any = false;
+        for (uint32_t x = 0; x < 8; x++)
+            if (pos[x] < lists[x].size()) {
+                order.push_back(lists[x][pos[x]++]);
+                any = true;
+            }
+    }
+    LM_CHECK(ctx, order.size() == expect, "%s work list is inconsistent", what);
+    uint32_t *d = nullptr;
+    LM_HIP(ctx, hipMalloc((void **)&d, order.size() * sizeof(uint32_t)));
+    LM_HIP(ctx, hipMemcpy(d, order.data(), order.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    *out = cache[cache_key] = d;
+    return 0;
+}
+
 // Workgroup order of the extension kernel for a batch of B columns.  Workgroup k runs on XCD k % 8
 // (round-robin dispatch), each XCD has its own 4 MB L2, and a digit is read once per target limb:
 // XCD x takes the columns b == x (mod 8); inside it the targets come in groups of LM_MODUP_TGROUP, and
@@ -751,26 +774,7 @@ static int modup_work_list(lumen_ctx *ctx, KsTables *tb, uint32_t B, const uint3
                 for (uint32_t d = 0; d < beta; d++)
                     for (uint8_t t : need[d])
                         if (t >= t0 && t < t0 + LM_MODUP_TGROUP) lists[x].push_back(b | (d << 16) | ((uint32_t)t << 24));
-    // interleave: entry k belongs to XCD k % 8; lists of unequal length (B not a multiple of 8) are
-    // drained in turn
-    std::vector<uint32_t> order;
-    order.reserve((size_t)B * tb->pairs.size());
-    std::vector<size_t> pos(8, 0);
-    for (bool any = true; any;) {
-        any = false;
-        for (uint32_t x = 0; x < 8; x++)
-            if (pos[x] < lists[x].size()) {
-                order.push_back(lists[x][pos[x]++]);
-                any = true;
-            }
-    }
-    LM_CHECK(ctx, order.size() == (size_t)B * tb->pairs.size(), "extension work list is inconsistent");
-    uint32_t *d = nullptr;
-    LM_HIP(ctx, hipMalloc((void **)&d, order.size() * sizeof(uint32_t)));
-    LM_HIP(ctx, hipMemcpy(d, order.data(), order.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    tb->d_work[cache_key] = d;
-    *out = d;
-    return 0;
+    return interleave_work_lists(ctx, lists, (size_t)B * tb->pairs.size(), "extension", tb->d_work, cache_key, out);
 }
 
 // The same for ModDown: (polynomial pw = 2b + w, Q limb t); XCD x takes the polynomials pw == x (mod 8),
@@ -792,24 +796,7 @@ static int moddown_work_list(lumen_ctx *ctx, KsTables *tb, uint32_t B, const uin
         for (uint32_t t0 = 0; t0 < L; t0 += LM_MODDOWN_TGROUP)
             for (uint32_t pw = x; pw < 2 * B; pw += 8)
                 for (uint32_t t = t0; t < std::min<uint32_t>(t0 + LM_MODDOWN_TGROUP, L); t++) lists[x].push_back(pw | (t << 16));
-    std::vector<uint32_t> order;
-    order.reserve((size_t)2 * B * L);
-    std::vector<size_t> pos(8, 0);
-    for (bool any = true; any;) {
-        any = false;
-        for (uint32_t x = 0; x < 8; x++)
-            if (pos[x] < lists[x].size()) {
-                order.push_back(lists[x][pos[x]++]);
-                any = true;
-            }
-    }
-    LM_CHECK(ctx, order.size() == (size_t)2 * B * L, "ModDown work list is inconsistent");
-    uint32_t *d = nullptr;
-    LM_HIP(ctx, hipMalloc((void **)&d, order.size() * sizeof(uint32_t)));
-    LM_HIP(ctx, hipMemcpy(d, order.data(), order.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    tb->d_work_down[cache_key] = d;
-    *out = d;
-    return 0;
+    return interleave_work_lists(ctx, lists, (size_t)2 * B * L, "ModDown", tb->d_work_down, cache_key, out);
 }
 
 // Enqueue on the context's second stream for the lifetime of the guard.  Independent column
@@ -839,10 +826,10 @@ static uint32_t intt_pack_slots(lumen_ctx *ctx) {
         // (the query answers 0 for more than 64 KB of dynamic LDS until the kernel is allowed that much)
         (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_intt_pack<LOGN>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_intt_pack<LOGN>, lm_nthreads(LOGN),
-                                                         lm_lds_for(1u << LOGN)) != hipSuccess || per_cu < 1) {
+        constexpr lm_geom g = lm_geom_lds(LOGN);
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_intt_pack<LOGN>, g.threads, g.lds) != hipSuccess || per_cu < 1) {
             // by hand: LDS (160 KB per CU) and the 2048 lanes of a CU
-            per_cu = (int)std::max<size_t>(1, std::min<size_t>(160 * 1024 / lm_lds_for(1u << LOGN), 2048 / lm_nthreads(LOGN)));
+            per_cu = (int)std::max<size_t>(1, std::min<size_t>(160 * 1024 / g.lds, 2048 / g.threads));
         }
         (void)hipGetLastError();
         if (ctx->tune.debug)
@@ -857,13 +844,7 @@ static uint32_t ks_fused_digits(lumen_ctx *ctx, uint32_t B, uint32_t L) {
     const uint32_t pairs = L / 2; // digits with two limbs
     if (forced >= 0) return std::min<uint32_t>((uint32_t)forced, pairs);
     uint32_t slots = 0;
-    switch (ctx->logN) {
-#define LM_CASE(n) \
-    case n: slots = intt_pack_slots<n>(ctx); break;
-        LM_FOR_EACH_LOGN(LM_CASE)
-#undef LM_CASE
-    default: return 0;
-    }
+    if (lm_for_logn(ctx, ctx->logN, [&](auto n) { return slots = intt_pack_slots<n>(ctx), 0; })) return 0;
     for (uint32_t nf = pairs; nf >= 1; nf--)
         if (((uint64_t)B * nf) % slots == 0) return nf;
     return 0;
@@ -878,32 +859,26 @@ struct LaneGuard {
     ~LaneGuard() { ctx->stream = saved; }
 };
 
+// grid of k_ks_mac for a batch of B columns
+static dim3 ks_mac_grid(const lumen_ctx *ctx, uint32_t B) {
+    return dim3(((ctx->N / LM_MAC_VEC + 255) / 256) * (ctx->L + ctx->K) * ((B + LM_MAC_COLS - 1) / LM_MAC_COLS));
+}
+
 // acc, acc_out: [B][2][L][N] at top level; acc_out = acc + Rot_galEl(acc) for every column
 int rotate_accumulate(lumen_ctx *ctx, const u64 *acc, u64 *acc_out, uint32_t B, const lm_galois_key &gk,
                       KsTables *tb, const KsScratch &s) {
-    const uint32_t N = ctx->N, L = ctx->L, K = ctx->K, LK = L + K, beta = tb->beta;
-    const size_t lds = lm_fwd_lds(ctx->logN);
-    const uint32_t threads = lm_fwd_threads(ctx->logN);
+    const uint32_t N = ctx->N, L = ctx->L, K = ctx->K, beta = tb->beta;
     // 1. c1 -> coefficient domain, scaled for the basis extension, and the (hi, lo) packing of the two-limb
     // digits: fused into the transform for the first nf digits, k_pack_v for the others
     const uint32_t nf = K == 2 ? ks_fused_digits(ctx, B, L) : 0;
     if (nf) {
-        const size_t lds_i = lm_inv_lds(ctx->logN);
         const uint32_t grid = B * nf + B * (L - 2 * nf);
         lm_prof_scope ps(ctx, "ks_intt_c1", (uint64_t)B * L);
-        switch (ctx->logN) {
-#define LM_CASE(n)                                                                                              \
-    case n:                                                                                                     \
-        LM_LDS_ATTR(ctx, k_intt_pack<n>, lds_i);                                                                \
-        hipLaunchKernelGGL(k_intt_pack<n>, dim3(grid), dim3(lm_inv_threads(ctx->logN)), lds_i, ctx->stream, acc, \
-                           s.coef, B, L, nf, ctx->mods, tb->yscale, ctx->d_tw_inv);                             \
-        break;
-            LM_FOR_EACH_LOGN(LM_CASE)
-#undef LM_CASE
-        default:
-            return lm_fail(ctx, "ring degree 2^%u has no kernel instantiation", ctx->logN);
-        }
-        LM_HIP(ctx, hipGetLastError());
+        if (int rc = lm_for_logn(ctx, ctx->logN, [&](auto n) {
+                return lm_launch(ctx, k_intt_pack<n>, lm_geom_lds(n), grid, acc, s.coef, B, L, nf, ctx->mods, tb->yscale,
+                                 ctx->d_tw_inv);
+            }))
+            return rc;
     } else {
         if (int rc = lm_launch_ntt_strided(ctx, acc + (size_t)L * N, (size_t)2 * L * N, s.coef, (size_t)L * N, B,
                                            lm_map_q(L), true, "ks_intt_c1", &tb->yscale))
@@ -921,37 +896,25 @@ int rotate_accumulate(lumen_ctx *ctx, const u64 *acc, u64 *acc_out, uint32_t B, 
         const uint32_t *work = nullptr;
         if (int rc = modup_work_list(ctx, tb, B, &work)) return rc;
         lm_prof_scope ps(ctx, "ks_modup_ntt", nb);
-        const lm_geom gm = lm_fwdw_geom(ctx->logN);
-        switch (ctx->logN) {
-#define LM_CASE(n)                                                                                            \
-    case n:                                                                                                   \
-        LM_LDS_ATTR(ctx, k_modup_ntt<n>, gm.lds);                                                             \
-        hipLaunchKernelGGL(k_modup_ntt<n>, dim3((uint32_t)nb), dim3(gm.threads), gm.lds, ctx->stream, s.coef, acc, \
-                           s.ext, tb->d_bx, B, L, K, beta, work, ctx->mods, ctx->d_tw_fwd);                   \
-        break;
-            LM_FOR_EACH_LOGN(LM_CASE)
-#undef LM_CASE
-        default:
-            return lm_fail(ctx, "ring degree 2^%u has no kernel instantiation", ctx->logN);
-        }
-        LM_HIP(ctx, hipGetLastError());
+        if (int rc = lm_for_logn(ctx, ctx->logN, [&](auto n) {
+                return lm_launch(ctx, k_modup_ntt<n>, lm_geom_fwd(n), (uint32_t)nb, s.coef, acc, s.ext, tb->d_bx, B, L, K, beta,
+                                 work, ctx->mods, ctx->d_tw_fwd);
+            }))
+            return rc;
     }
     // 3. gadget product
     {
         lm_prof_scope ps(ctx, "ks_mac", (uint64_t)B);
-        dim3 grid(((N / LM_MAC_VEC + 255) / 256) * LK * ((B + LM_MAC_COLS - 1) / LM_MAC_COLS));
-        hipLaunchKernelGGL(k_ks_mac, grid, dim3(256), 0, ctx->stream, s.ext, acc, gk.d_key, s.u, B, L, K, beta,
-                           ctx->logN, ctx->mods);
+        hipLaunchKernelGGL(k_ks_mac, ks_mac_grid(ctx, B), dim3(256), 0, ctx->stream, s.ext, acc, gk.d_key, s.u, B, L, K,
+                           beta, ctx->logN, ctx->mods);
         LM_HIP(ctx, hipGetLastError());
     }
     // 4a. P limbs of u -> coefficient domain (in place)
     {
-        lm_modmap mp;
-        mp.period = K;
-        for (uint32_t i = 0; i < LM_MAX_LIMBS; i++) mp.idx[i] = (uint8_t)(L + (i < K ? i : 0));
         u64 *up = s.u + ks_u_at(0, L, B, L, K) * N; // the limbs modulo P: [2B][K]
         const size_t pstride = (size_t)K * N;
-        if (int rc = lm_launch_ntt_strided(ctx, up, pstride, up, pstride, B * 2, mp, true, "ks_intt_p", &tb->yscale))
+        if (int rc = lm_launch_ntt_strided(ctx, up, pstride, up, pstride, B * 2, lm_map_p(ctx), true, "ks_intt_p",
+                                           &tb->yscale))
             return rc;
         if (K == 2) {
             lm_prof_scope ps(ctx, "ks_pack_v", (uint64_t)B);
@@ -965,22 +928,11 @@ int rotate_accumulate(lumen_ctx *ctx, const u64 *acc, u64 *acc_out, uint32_t B, 
         const uint32_t *work_down = nullptr;
         if (int rc = moddown_work_list(ctx, tb, B, &work_down)) return rc;
         lm_prof_scope ps(ctx, "ks_moddown_ntt", (uint64_t)B * 2 * L);
-        switch (ctx->logN) {
-#define LM_CASE(n)                                                                                            \
-    case n:                                                                                                   \
-        LM_LDS_ATTR(ctx, k_moddown_ntt<n>, lds);               \
-        hipLaunchKernelGGL(k_moddown_ntt<n>, dim3(B * 2 * L), dim3(threads), lds, ctx->stream, s.u, acc,      \
-                           acc_out, tb->d_bxp, tb->d_pinv, gk.d_index, gk.d_inv_index, work_down, B, L, K, ctx->mods, \
-                           ctx->d_tw_fwd);                                                                    \
-        break;
-            LM_FOR_EACH_LOGN(LM_CASE)
-#undef LM_CASE
-        default:
-            return lm_fail(ctx, "ring degree 2^%u has no kernel instantiation", ctx->logN);
-        }
-        LM_HIP(ctx, hipGetLastError());
+        return lm_for_logn(ctx, ctx->logN, [&](auto n) {
+            return lm_launch(ctx, k_moddown_ntt<n>, lm_geom_lds(n), B * 2 * L, s.u, acc, acc_out, tb->d_bxp, tb->d_pinv,
+                             gk.d_index, gk.d_inv_index, work_down, B, L, K, ctx->mods, ctx->d_tw_fwd);
+        });
     }
-    return 0;
 }
 
 // ---- the key switch's scratch buffers, and WHERE in HBM they sit.
@@ -1207,7 +1159,7 @@ extern "C" int lumen_ks_mac_probe(lumen_ctx *ctx, uint32_t batch, const void *ex
     LM_ENTER(ctx);
     KsTables *tb = nullptr;
     if (int rc = get_tables(ctx, &tb)) return rc;
-    const uint32_t N = ctx->N, L = ctx->L, K = ctx->K, LK = L + K, B = batch ? batch : ks_batch(ctx);
+    const uint32_t N = ctx->N, L = ctx->L, K = ctx->K, B = batch ? batch : ks_batch(ctx);
     LM_CHECK(ctx, B <= 65535 && reps >= 1 && reps <= 100000, "lumen_ks_mac_probe: batch %u / reps %u out of range", B, reps);
     KsScratch s;
     if (int rc = get_scratch(ctx, B, tb, &s)) return rc;
@@ -1220,7 +1172,7 @@ extern "C" int lumen_ks_mac_probe(lumen_ctx *ctx, uint32_t batch, const void *ex
     }
     const u64 *pe = ext ? (const u64 *)ext : s.ext;
     u64 *pu = u ? (u64 *)u : s.u;
-    dim3 grid(((N / LM_MAC_VEC + 255) / 256) * LK * ((B + LM_MAC_COLS - 1) / LM_MAC_COLS));
+    const dim3 grid = ks_mac_grid(ctx, B);
     auto launch = [&] {
         hipLaunchKernelGGL(k_ks_mac, grid, dim3(256), 0, ctx->stream, pe, (const u64 *)acc, (const u64 *)key, pu, B, L, K,
                            tb->beta, ctx->logN, ctx->mods);

@@ -5,20 +5,21 @@
 // One workgroup of N/16 threads owns one limb of one polynomial and keeps all N coefficients in LDS
 // (N*9 B with padding: 36/72/144 KiB for N = 2^12/2^13/2^14, under the 160 KiB of a gfx950 CU), so a
 // transform reads and writes HBM exactly once: 16*N bytes.  Pass structure, wave-owned blocks,
-// lazy butterflies and the hand-scheduled Shoup multiplication: lm_ntt_dev.h.
+// lazy butterflies and the hand-scheduled Shoup multiplication: lm_ntt_dev.h.  So are the two launch
+// geometries (lm_geom_lds, lm_geom_fwd), the dispatch on the ring degree (lm_for_logn) and the launch (lm_launch).
 #include "lm_ntt_dev.h"
 
-// forward transforms run lm_ntt_forward_w14 at N = 2^14 (512 threads, two workgroups per CU): geometry lm_fwdw_geom
-__host__ __device__ constexpr int lm_limb_ntt_threads(int logN, bool inv) { return inv ? lm_max_threads(logN) : lm_fwdw_threads(logN); }
-__host__ __device__ constexpr int lm_limb_ntt_waves(int logN, bool inv) { return inv ? 1 : lm_fwdw_waves(logN); }
+// forward transforms run lm_ntt_forward_w14 at N = 2^14 (512 threads, two workgroups per CU): lm_geom_fwd
 template <int LOGN, bool INV>
-__global__ __launch_bounds__(lm_limb_ntt_threads(LOGN, INV), lm_limb_ntt_waves(LOGN, INV)) void k_limb_ntt(const u64 *src, size_t src_poly_stride, u64 *dst,
+constexpr lm_geom k_limb_ntt_geom = INV ? lm_geom_lds(LOGN) : lm_geom_fwd(LOGN);
+template <int LOGN, bool INV>
+__global__ LM_GEOM_BOUNDS((k_limb_ntt_geom<LOGN, INV>)) void k_limb_ntt(const u64 *src, size_t src_poly_stride, u64 *dst,
                                                    size_t dst_poly_stride, uint32_t npoly, lm_modmap map,
                                                    lm_mods mods, lm_ninv_t ninv,
                                                    const tw_t *__restrict__ tw_all) {
     extern __shared__ __attribute__((aligned(16))) u64 sm[];
     constexpr uint32_t N = 1u << LOGN;
-    const uint32_t tid = threadIdx.x, nthreads = blockDim.x;
+    const uint32_t tid = threadIdx.x;
     // limb-major block order: consecutive workgroups share a modulus, so only
     // one or two twiddle tables are live in each XCD's L2 at a time
     const uint32_t limb = blockIdx.x / npoly, poly = blockIdx.x % npoly;
@@ -34,7 +35,7 @@ __global__ __launch_bounds__(lm_limb_ntt_threads(LOGN, INV), lm_limb_ntt_waves(L
         // wave's LDS block, the first pass reading its runs from there -- loses 2.7 %: tools/exp_inv_lin_load.patch,
         // profiles/r05_exp_linear_store.txt)
         auto ld = [&](uint32_t i0, u64 *v, int count) { lm_load_run(p, i0, v, count); };
-        lm_ntt_inverse<LOGN>(sm, tw, c, tid, nthreads, ld, st);
+        lm_ntt_inverse<LOGN>(sm, tw, c, tid, ld, st);
     } else {
         auto ld = [&](uint32_t i) { return p[i]; };
         // (coalesced output through LDS, lm_linear_out, was measured here too: 11.5 M transforms/s either way -- the plain
@@ -49,8 +50,21 @@ __global__ __launch_bounds__(lm_limb_ntt_threads(LOGN, INV), lm_limb_ntt_waves(L
         if constexpr (LOGN == 14)
             lm_ntt_forward_w14(sm, tw, c, tid, ld, st);
         else
-            lm_ntt_forward<LOGN>(sm, tw, c, tid, nthreads, ld, st);
+            lm_ntt_forward<LOGN>(sm, tw, c, tid, ld, st);
     }
+}
+
+// `grid` workgroups of k_limb_ntt<logn, inverse>, one limb each
+static int launch_limb_ntt(lumen_ctx *ctx, uint32_t logn, bool inverse, uint32_t grid, const u64 *src,
+                           size_t src_poly_stride, u64 *dst, size_t dst_poly_stride, uint32_t npoly,
+                           const lm_modmap &map, const lm_mods &mods, const lm_ninv_t &ninv, const tw_t *tw) {
+    return lm_for_logn(ctx, logn, [&](auto n) {
+        if (inverse)
+            return lm_launch(ctx, k_limb_ntt<n, true>, k_limb_ntt_geom<n, true>, grid, src, src_poly_stride, dst,
+                             dst_poly_stride, npoly, map, mods, ninv, tw);
+        return lm_launch(ctx, k_limb_ntt<n, false>, k_limb_ntt_geom<n, false>, grid, src, src_poly_stride, dst,
+                         dst_poly_stride, npoly, map, mods, ninv, tw);
+    });
 }
 
 // Transform over a different ring degree (sub-ring of the ring switch): one modulus (mods index
@@ -65,29 +79,7 @@ int lm_launch_ntt_subring(lumen_ctx *ctx, uint32_t logn, const tw_t *tw, tw_t ni
     mods.m[0] = explicit_mod ? *explicit_mod : ctx->mods.m[mod_idx];
     lm_ninv_t ninv = lm_ninv_of(ctx);
     ninv.t[0] = ninv_scale;
-    const size_t lds = inverse ? lm_inv_lds(logn) : lm_fwdw_geom(logn).lds;
-    const uint32_t threads = inverse ? lm_inv_threads(logn) : lm_fwdw_geom(logn).threads;
-    const dim3 grid(npoly), block(threads);
-#define LM_LAUNCH(n)                                                                                          \
-    case n:                                                                                                   \
-        if (inverse) {                                                                                        \
-            LM_LDS_ATTR(ctx, (k_limb_ntt<n, true>), lds);                                                     \
-            hipLaunchKernelGGL((k_limb_ntt<n, true>), grid, block, lds, ctx->stream, src, src_poly_stride,    \
-                               dst, dst_poly_stride, npoly, map, mods, ninv, tw);                             \
-        } else {                                                                                              \
-            LM_LDS_ATTR(ctx, (k_limb_ntt<n, false>), lds);                                                    \
-            hipLaunchKernelGGL((k_limb_ntt<n, false>), grid, block, lds, ctx->stream, src, src_poly_stride,   \
-                               dst, dst_poly_stride, npoly, map, mods, ninv, tw);                             \
-        }                                                                                                     \
-        break;
-    switch (logn) {
-        LM_FOR_EACH_LOGN(LM_LAUNCH)
-    default:
-        return lm_fail(ctx, "ring degree 2^%u has no kernel instantiation", logn);
-    }
-#undef LM_LAUNCH
-    LM_HIP(ctx, hipGetLastError());
-    return 0;
+    return launch_limb_ntt(ctx, logn, inverse, npoly, src, src_poly_stride, dst, dst_poly_stride, npoly, map, mods, ninv, tw);
 }
 
 // Transforms limbs [0, map.period) of `npoly` polynomials; polynomial p's limb
@@ -97,35 +89,12 @@ int lm_launch_ntt_strided(lumen_ctx *ctx, const u64 *src, size_t src_poly_stride
                           size_t dst_poly_stride, uint32_t npoly, const lm_modmap &map, bool inverse,
                           const char *prof_name, const lm_ninv_t *inv_scale) {
     if (!npoly || !map.period) return 0;
-    const uint32_t N = ctx->N;
     const lm_ninv_t ninv = inv_scale ? *inv_scale : lm_ninv_of(ctx);
-    const size_t lds = inverse ? lm_inv_lds(ctx->logN) : lm_fwdw_geom(ctx->logN).lds;
-    const uint32_t threads = inverse ? lm_inv_threads(ctx->logN) : lm_fwdw_geom(ctx->logN).threads;
-    (void)N;
     const uint64_t nblocks64 = (uint64_t)npoly * map.period;
     LM_CHECK(ctx, nblocks64 < (1ull << 31), "NTT grid too large: %llu", (unsigned long long)nblocks64);
     lm_prof_scope ps(ctx, prof_name ? prof_name : (inverse ? "limb_intt" : "limb_ntt"), nblocks64);
-    const dim3 grid((uint32_t)nblocks64), block(threads);
-#define LM_LAUNCH(n)                                                                                          \
-    case n:                                                                                                   \
-        if (inverse) {                                                                                        \
-            LM_LDS_ATTR(ctx, (k_limb_ntt<n, true>), lds);           \
-            hipLaunchKernelGGL((k_limb_ntt<n, true>), grid, block, lds, ctx->stream, src, src_poly_stride,    \
-                               dst, dst_poly_stride, npoly, map, ctx->mods, ninv, ctx->d_tw_inv);             \
-        } else {                                                                                              \
-            LM_LDS_ATTR(ctx, (k_limb_ntt<n, false>), lds);           \
-            hipLaunchKernelGGL((k_limb_ntt<n, false>), grid, block, lds, ctx->stream, src, src_poly_stride,   \
-                               dst, dst_poly_stride, npoly, map, ctx->mods, ninv, ctx->d_tw_fwd);             \
-        }                                                                                                     \
-        break;
-    switch (ctx->logN) {
-        LM_FOR_EACH_LOGN(LM_LAUNCH)
-    default:
-        return lm_fail(ctx, "ring degree 2^%u has no kernel instantiation", ctx->logN);
-    }
-#undef LM_LAUNCH
-    LM_HIP(ctx, hipGetLastError());
-    return 0;
+    return launch_limb_ntt(ctx, ctx->logN, inverse, (uint32_t)nblocks64, src, src_poly_stride, dst, dst_poly_stride, npoly,
+                           map, ctx->mods, ninv, inverse ? ctx->d_tw_inv : ctx->d_tw_fwd);
 }
 
 int lm_launch_ntt(lumen_ctx *ctx, u64 *d, uint32_t npoly, const lm_modmap &map, bool inverse) {

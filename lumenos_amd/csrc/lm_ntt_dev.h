@@ -49,16 +49,23 @@ struct lm_ninv_t {
 };
 
 __host__ __device__ constexpr int lm_ilog2(int x) { return x <= 1 ? 0 : 1 + lm_ilog2(x >> 1); }
-// launch geometry: 16 coefficients per lane, at least one wave, at most 1024 threads
-#ifndef LM_COEFS_PER_LANE
-#define LM_COEFS_PER_LANE 16
-#endif
-__host__ __device__ constexpr int lm_nthreads(int logN) {
-    return (1 << logN) / LM_COEFS_PER_LANE < 64
-               ? 64
-               : ((1 << logN) / LM_COEFS_PER_LANE > 1024 ? 1024 : (1 << logN) / LM_COEFS_PER_LANE);
+__host__ __device__ constexpr size_t lm_lds_for(uint32_t n) { return (size_t)(n + (n >> 3) + 2) * sizeof(u64); }
+// Launch geometry of a limb-transform kernel.  A kernel's __launch_bounds__ (LM_GEOM_BOUNDS), its launches
+// (lm_launch) and any occupancy query all read the SAME one of the two functions below.
+struct lm_geom {
+    int threads; // workgroup size
+    int waves;   // second __launch_bounds__ argument (waves per SIMD); 1 = no constraint
+    size_t lds;  // dynamic LDS bytes
+};
+#define LM_GEOM_BOUNDS(g) __launch_bounds__((g).threads, (g).waves)
+// the LDS-resident form (lm_ntt_forward, lm_ntt_inverse): 16 coefficients per lane, at least one wave, at most
+// 1024 threads, the whole limb in LDS
+__host__ __device__ constexpr lm_geom lm_geom_lds(int logN) {
+    const int nt = (1 << logN) / 16;
+    return lm_geom{nt < 64 ? 64 : (nt > 1024 ? 1024 : nt), 1, lm_lds_for(1u << logN)};
 }
-__host__ __device__ constexpr int lm_max_threads(int logN) { return lm_nthreads(logN); }
+// workgroup size the dealing templates assume (lm_deal, lm_fwd_first, lm_inv_last, lm_linear_out)
+__host__ __device__ constexpr int lm_nthreads(int logN) { return lm_geom_lds(logN).threads; }
 __host__ __device__ constexpr int lm_log_epl(int logN) { // log2 coefficients a work item keeps in VGPRs: at most 16
     return logN - lm_ilog2(lm_nthreads(logN)) > 4 ? 4 : logN - lm_ilog2(lm_nthreads(logN));
 }
@@ -85,18 +92,37 @@ __host__ __device__ constexpr int lm_pass_r(int logN, int i) {
 }
 // ring degrees the kernels are instantiated for
 #define LM_FOR_EACH_LOGN(X) X(8) X(10) X(11) X(12) X(13) X(14)
+// run-time ring degree -> compile-time: f(std::integral_constant<int, n>{}) for the instantiated n
+template <class F>
+static inline int lm_for_logn(lumen_ctx *ctx, uint32_t logN, F &&f) {
+    switch (logN) {
+#define LM_X(n) \
+    case n: return f(std::integral_constant<int, n>{});
+        LM_FOR_EACH_LOGN(LM_X)
+#undef LM_X
+    default: return lm_fail(ctx, "ring degree 2^%u has no kernel instantiation", logN);
+    }
+}
 static inline bool lm_logn_supported(uint32_t logN) {
-#define LM_CASE(n) if (logN == n) return true;
-    LM_FOR_EACH_LOGN(LM_CASE)
-#undef LM_CASE
+#define LM_X(n) if (logN == n) return true;
+    LM_FOR_EACH_LOGN(LM_X)
+#undef LM_X
     return false;
 }
+// Launches a kernel with dynamic LDS on the context's stream: raises the kernel's dynamic-LDS limit once per
+// context (hipFuncSetAttribute is not free on the launch path), fails through lm_fail.
+template <class... P, class... A>
+static inline int lm_launch(lumen_ctx *ctx, void (*kernel)(P...), const lm_geom &g, dim3 grid, A &&...args) {
+    const void *fp = reinterpret_cast<const void *>(kernel);
+    if (!ctx->lds_attr_done.count(fp)) {
+        LM_HIP(ctx, hipFuncSetAttribute(fp, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        ctx->lds_attr_done.insert(fp);
+    }
+    hipLaunchKernelGGL(kernel, grid, dim3(g.threads), g.lds, ctx->stream, std::forward<A>(args)...);
+    LM_HIP(ctx, hipGetLastError());
+    return 0;
+}
 
-static inline uint32_t lm_fwd_threads(uint32_t logN) { return (uint32_t)lm_nthreads((int)logN); }
-static inline uint32_t lm_inv_threads(uint32_t logN) { return (uint32_t)lm_nthreads((int)logN); }
-static inline size_t lm_lds_for(uint32_t n) { return (size_t)(n + (n >> 3) + 2) * sizeof(u64); }
-static inline size_t lm_fwd_lds(uint32_t logN) { return lm_lds_for(1u << logN); }
-static inline size_t lm_inv_lds(uint32_t logN) { return lm_lds_for(1u << logN); }
 static inline lm_ninv_t lm_ninv_of(const lumen_ctx *ctx) {
     lm_ninv_t n;
     for (uint32_t i = 0; i < LM_MAX_LIMBS; i++) n.t[i] = ctx->ninv[i];
@@ -136,34 +162,16 @@ __device__ __forceinline__ u64 lm_keep(u64 x) {
 #ifndef LM_ASM_SHOUP
 #define LM_ASM_SHOUP 1
 #endif
-// the eight temporaries: an even-aligned block v[B:B+7] (LM_SHOUP_TEMP_BASE = 80 by default; a lower
-// block lets a kernel stay under 64 VGPRs)
-#ifndef LM_SHOUP_TEMP_BASE
-#define LM_SHOUP_TEMP_BASE 80
-#endif
-#if LM_SHOUP_TEMP_BASE == 80
-#define LM_T(i) LM_T80_##i
-#define LM_T80_0 "80"
-#define LM_T80_1 "81"
-#define LM_T80_2 "82"
-#define LM_T80_3 "83"
-#define LM_T80_4 "84"
-#define LM_T80_5 "85"
-#define LM_T80_6 "86"
-#define LM_T80_7 "87"
-#elif LM_SHOUP_TEMP_BASE == 56
-#define LM_T(i) LM_T56_##i
-#define LM_T56_0 "56"
-#define LM_T56_1 "57"
-#define LM_T56_2 "58"
-#define LM_T56_3 "59"
-#define LM_T56_4 "60"
-#define LM_T56_5 "61"
-#define LM_T56_6 "62"
-#define LM_T56_7 "63"
-#else
-#error "LM_SHOUP_TEMP_BASE must be 56 or 80"
-#endif
+// the eight temporaries: v[80:87]
+#define LM_T(i) LM_T##i
+#define LM_T0 "80"
+#define LM_T1 "81"
+#define LM_T2 "82"
+#define LM_T3 "83"
+#define LM_T4 "84"
+#define LM_T5 "85"
+#define LM_T6 "86"
+#define LM_T7 "87"
 #define LM_V(i) "v" LM_T(i)
 #define LM_VP(i, j) "v[" LM_T(i) ":" LM_T(j) "]"
 #define LM_SHOUP_CLOBBERS LM_V(0), LM_V(1), LM_V(2), LM_V(3), LM_V(4), LM_V(5), LM_V(6), LM_V(7), "s96", "s97", "s98", "s99"
@@ -612,12 +620,12 @@ __device__ __forceinline__ void lm_fwd14_xpass(u64 *sm, const tw_t *tw, const lm
 // XPASS = false: the generic passes also at N = 2^14 (a kernel whose storer needs the registers the second
 // twiddle set of the last pass would take)
 template <int LOGN, bool XPASS = true, class Loader, class Storer, class After = lm_no_after>
-__device__ __forceinline__ void lm_ntt_forward(u64 *sm, const tw_t *tw, const lm_qc &c, uint32_t tid, uint32_t,
-                                               Loader &ld, Storer &st, After after = After()) {
+__device__ __forceinline__ void lm_ntt_forward(u64 *sm, const tw_t *tw, const lm_qc &c, uint32_t tid, Loader &ld,
+                                               Storer &st, After after = After()) {
     static_assert(lm_npasses(LOGN) >= 2, "a transform needs a loading and a storing pass");
     // (not with a storer that prefetches for itself -- ModDown: its pre() words and two live twiddle sets
     // make 119 VGPRs and the kernel 3 % slower, measured)
-    if constexpr (LOGN == 14 && XPASS && LM_TW_XPASS && LM_COEFS_PER_LANE == 16 && !lm_has_pre<Storer>::value)
+    if constexpr (LOGN == 14 && XPASS && LM_TW_XPASS && !lm_has_pre<Storer>::value)
         lm_fwd14_xpass(sm, tw, c, tid, ld, st);
     else
         lm_fwd_rec<LOGN, 0, 0>(sm, tw, c, tid, ld, st);
@@ -819,18 +827,11 @@ __device__ __forceinline__ void lm_w14_linear_out(const u64 *sm, uint32_t tid, u
     }
 }
 
-// Launch geometry of the forward-transform kernels that run lm_ntt_forward_w14 at N = 2^14 (k_limb_ntt<14, false>,
-// k_modup_ntt<14>) and lm_ntt_forward below it: the kernels' __launch_bounds__ and their launches both read it.
-__host__ __device__ constexpr int lm_fwdw_threads(int logN) { return logN == 14 ? LM_W14_THREADS : lm_nthreads(logN); }
-// second __launch_bounds__ argument (waves per SIMD): 4 caps the N = 2^14 kernels at 128 VGPRs, so that two
-// workgroups of 8 waves fit on a CU; 1 (no constraint) below
-__host__ __device__ constexpr int lm_fwdw_waves(int logN) { return logN == 14 ? 4 : 1; }
-struct lm_geom {
-    uint32_t threads;
-    size_t lds;
-};
-static inline lm_geom lm_fwdw_geom(uint32_t logN) {
-    return logN == 14 ? lm_geom{(uint32_t)LM_W14_THREADS, lm_lds_for(1u << 13)} : lm_geom{lm_fwd_threads(logN), lm_fwd_lds(logN)};
+// Geometry of the forward kernels that run lm_ntt_forward_w14 at N = 2^14 (k_limb_ntt<14, false>, k_modup_ntt<14>)
+// and lm_ntt_forward below it.  4 waves per SIMD caps the N = 2^14 kernels at 128 VGPRs, so that two workgroups of
+// 8 waves fit on a CU.
+__host__ __device__ constexpr lm_geom lm_geom_fwd(int logN) {
+    return logN == 14 ? lm_geom{LM_W14_THREADS, 4, lm_lds_for(1u << 13)} : lm_geom_lds(logN);
 }
 
 // ------------------------------------------------------------------ inverse
@@ -942,8 +943,8 @@ __device__ __forceinline__ void lm_inv_rec(u64 *sm, const tw_t *tw, const lm_qc 
 // N = 2^14: 10.14 against 10.17 M transforms/s with the first pass left as the rolled loop, 9.48 with its two
 // work items unrolled.  Not kept.)
 template <int LOGN, class Loader, class Storer>
-__device__ __forceinline__ void lm_ntt_inverse(u64 *sm, const tw_t *tw, const lm_qc &c, uint32_t tid, uint32_t,
-                                               Loader &ld, Storer &st) {
+__device__ __forceinline__ void lm_ntt_inverse(u64 *sm, const tw_t *tw, const lm_qc &c, uint32_t tid, Loader &ld,
+                                               Storer &st) {
     static_assert(lm_npasses(LOGN) >= 2, "a transform needs a loading and a storing pass");
     lm_inv_rec<LOGN, 0, 0>(sm, tw, c, tid, ld, st);
 }

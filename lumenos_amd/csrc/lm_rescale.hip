@@ -32,28 +32,28 @@ struct rescale_consts {
 };
 
 template <int LOGN>
-__global__ __launch_bounds__(lm_max_threads(LOGN)) void k_rescale_last(const u64 *__restrict__ src, size_t src_poly_stride,
+__global__ LM_GEOM_BOUNDS(lm_geom_lds(LOGN)) void k_rescale_last(const u64 *__restrict__ src, size_t src_poly_stride,
                                                        uint32_t last, u64 *__restrict__ tbuf, mod_t md,
                                                        tw_t ninv, u64 half, const tw_t *__restrict__ tw) {
     extern __shared__ __attribute__((aligned(16))) u64 sm[];
     constexpr uint32_t N = 1u << LOGN;
-    const uint32_t tid = threadIdx.x, nthreads = blockDim.x;
+    const uint32_t tid = threadIdx.x;
     const lm_qc c = lm_make_qc(md);
     const u64 *p = src + (size_t)blockIdx.x * src_poly_stride + (size_t)last * N;
     u64 *o = tbuf + (size_t)blockIdx.x * N;
     auto ld = [&](uint32_t i0, u64 *v, int count) { lm_load_run(p, i0, v, count); };
     auto st = [&](uint32_t i, u64 v) { o[i] = lm_addmod(lm_shoup_cs(v, ninv, c.q, c.nq), half, c.q); };
-    lm_ntt_inverse<LOGN>(sm, tw, c, tid, nthreads, ld, st);
+    lm_ntt_inverse<LOGN>(sm, tw, c, tid, ld, st);
 }
 
 template <int LOGN>
-__global__ __launch_bounds__(lm_max_threads(LOGN)) void k_rescale_limb(const u64 *src, size_t src_poly_stride, u64 *dst,
+__global__ LM_GEOM_BOUNDS(lm_geom_lds(LOGN)) void k_rescale_limb(const u64 *src, size_t src_poly_stride, u64 *dst,
                                                        size_t dst_poly_stride, const u64 *__restrict__ tbuf,
                                                        uint32_t npoly, lm_mods mods, rescale_consts rc,
                                                        const tw_t *__restrict__ tw_all) {
     extern __shared__ __attribute__((aligned(16))) u64 sm[];
     constexpr uint32_t N = 1u << LOGN;
-    const uint32_t tid = threadIdx.x, nthreads = blockDim.x;
+    const uint32_t tid = threadIdx.x;
     const uint32_t limb = blockIdx.x / npoly, poly = blockIdx.x % npoly; // limb-major (L2-friendly twiddles)
     const lm_qc c = lm_make_qc(mods.m[limb]);
     const u64 hm = rc.half_mod[limb];
@@ -70,7 +70,7 @@ __global__ __launch_bounds__(lm_max_threads(LOGN)) void k_rescale_limb(const u64
             if (k < count) r[k] = lm_shoup_cs(lm_submod(cv[k], lm_reduce_s(v[k], c.q, c.nq, c.qinv64), c.q), qlinv, c.q, c.nq);
         lm_store_run(o, i0, r, count);
     };
-    lm_ntt_forward<LOGN>(sm, tw_all + (size_t)limb * N, c, tid, nthreads, ld, st);
+    lm_ntt_forward<LOGN>(sm, tw_all + (size_t)limb * N, c, tid, ld, st);
 }
 
 // ---- multi-step rescale on coefficients
@@ -187,10 +187,6 @@ static int rescale_polys_t(lumen_ctx *ctx, const u64 *src, uint32_t nl, u64 *dst
         if (rc != 2) return rc; // 2: no coefficient-form tables for this modulus chain
     }
     const uint32_t N = ctx->N;
-    const size_t lds_i = lm_inv_lds(ctx->logN), lds_f = lm_fwd_lds(ctx->logN);
-    const uint32_t thr_i = lm_inv_threads(ctx->logN), thr_f = lm_fwd_threads(ctx->logN);
-    LM_LDS_ATTR(ctx, k_rescale_last<LOGN>, lds_i);
-    LM_LDS_ATTR(ctx, k_rescale_limb<LOGN>, lds_f);
     const u64 *cur = src;
     for (uint32_t cur_nl = nl; cur_nl > target; cur_nl--) {
         const uint32_t last = cur_nl - 1;
@@ -207,16 +203,15 @@ static int rescale_polys_t(lumen_ctx *ctx, const u64 *src, uint32_t nl, u64 *dst
         }
         {
             lm_prof_scope ps(ctx, "rescale_last_intt", npoly);
-            hipLaunchKernelGGL(k_rescale_last<LOGN>, dim3(npoly), dim3(thr_i), lds_i, ctx->stream, cur,
-                               (size_t)nl * N, last, tbuf, ctx->mods.m[last], ctx->ninv[last], (u64)rc.half,
-                               ctx->d_tw_inv + (size_t)last * N);
-            LM_HIP(ctx, hipGetLastError());
+            if (int e = lm_launch(ctx, k_rescale_last<LOGN>, lm_geom_lds(LOGN), npoly, cur, (size_t)nl * N, last, tbuf,
+                                  ctx->mods.m[last], ctx->ninv[last], (u64)rc.half, ctx->d_tw_inv + (size_t)last * N))
+                return e;
         }
         {
             lm_prof_scope ps(ctx, "rescale_limb_ntt", (uint64_t)npoly * last);
-            hipLaunchKernelGGL(k_rescale_limb<LOGN>, dim3(npoly * last), dim3(thr_f), lds_f, ctx->stream, cur,
-                               (size_t)nl * N, out, out_stride, tbuf, npoly, ctx->mods, rc, ctx->d_tw_fwd);
-            LM_HIP(ctx, hipGetLastError());
+            if (int e = lm_launch(ctx, k_rescale_limb<LOGN>, lm_geom_lds(LOGN), npoly * last, cur, (size_t)nl * N, out,
+                                  out_stride, tbuf, npoly, ctx->mods, rc, ctx->d_tw_fwd))
+                return e;
         }
         cur = work;
     }
@@ -228,15 +223,7 @@ static int rescale_polys_t(lumen_ctx *ctx, const u64 *src, uint32_t nl, u64 *dst
 // the src layout (may be NULL when nl - target == 1); tbuf: [npoly][N].
 int lm_rescale_polys(lumen_ctx *ctx, const u64 *src, uint32_t nl, u64 *dst, uint32_t target,
                      uint32_t npoly, u64 *work, u64 *tbuf) {
-    switch (ctx->logN) {
-#define LM_CASE(n) \
-    case n:        \
-        return rescale_polys_t<n>(ctx, src, nl, dst, target, npoly, work, tbuf);
-        LM_FOR_EACH_LOGN(LM_CASE)
-#undef LM_CASE
-    default:
-        return lm_fail(ctx, "ring degree 2^%u has no kernel instantiation", ctx->logN);
-    }
+    return lm_for_logn(ctx, ctx->logN, [&](auto n) { return rescale_polys_t<n>(ctx, src, nl, dst, target, npoly, work, tbuf); });
 }
 
 extern "C" int lumen_rescale(lumen_ctx *ctx, const lumen_set *in, uint32_t target_limbs, lumen_set **out) {

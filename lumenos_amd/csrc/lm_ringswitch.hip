@@ -43,7 +43,7 @@ struct RsKey {
 // the load (q_0 has three bits more than a special prime); targets start at t0 = 1, the digit's own limb
 // needs no transform (k_rs_mac reads c1 itself).
 template <int LOGN, bool HYB>
-__global__ __launch_bounds__(lm_max_threads(LOGN)) void k_rs_digit_ntt(const u64 *__restrict__ coef,
+__global__ LM_GEOM_BOUNDS(lm_geom_lds(LOGN)) void k_rs_digit_ntt(const u64 *__restrict__ coef,
                                                                        u64 *__restrict__ ext, uint32_t B,
                                                                        uint32_t nd, uint32_t nt, uint32_t L,
                                                                        uint32_t w, lm_mods mods,
@@ -51,7 +51,7 @@ __global__ __launch_bounds__(lm_max_threads(LOGN)) void k_rs_digit_ntt(const u64
     extern __shared__ __attribute__((aligned(16))) u64 sm[];
     constexpr uint32_t N = 1u << LOGN;
     constexpr uint32_t t0 = HYB ? 1 : 0;
-    const uint32_t tid = threadIdx.x, nthreads = blockDim.x;
+    const uint32_t tid = threadIdx.x;
     uint32_t r = blockIdx.x;
     const uint32_t b = r % B;
     r /= B;
@@ -73,7 +73,7 @@ __global__ __launch_bounds__(lm_max_threads(LOGN)) void k_rs_digit_ntt(const u64
             if (k < count) rr[k] = lm_reduce_s(v[k], qc.q, qc.nq, qc.qinv64);
         lm_store_run(o, i0, rr, count);
     };
-    lm_ntt_forward<LOGN>(sm, tw_all + (size_t)mi * N, qc, tid, nthreads, ld, st);
+    lm_ntt_forward<LOGN>(sm, tw_all + (size_t)mi * N, qc, tid, ld, st);
 }
 
 // u[b][pw][t][i] = sum_j ext[b][j][t][i] * key[j][pw][t][i]
@@ -99,7 +99,7 @@ __global__ __launch_bounds__(256) void k_rs_mac(const u64 *__restrict__ ext, con
 
 // ModDown on q_0 only: lift of the P limbs fused into the load, NTT, (u - lift) * P^-1 (+ c0)
 template <int LOGN>
-__global__ __launch_bounds__(lm_max_threads(LOGN)) void k_rs_moddown(const u64 *__restrict__ u,
+__global__ LM_GEOM_BOUNDS(lm_geom_lds(LOGN)) void k_rs_moddown(const u64 *__restrict__ u,
                                                                      const u64 *__restrict__ in, size_t in_ctw,
                                                                      u64 *__restrict__ big,
                                                                      const bx_t *__restrict__ bxp,
@@ -108,7 +108,7 @@ __global__ __launch_bounds__(lm_max_threads(LOGN)) void k_rs_moddown(const u64 *
                                                                      const tw_t *__restrict__ tw_all) {
     extern __shared__ __attribute__((aligned(16))) u64 sm[];
     constexpr uint32_t N = 1u << LOGN;
-    const uint32_t tid = threadIdx.x, nthreads = blockDim.x;
+    const uint32_t tid = threadIdx.x;
     const uint32_t pw = blockIdx.x, w = pw & 1, b = pw >> 1;
     const bx_t c = bxp[0];
     const lm_qc qc = lm_make_qc(mods.m[0]);
@@ -131,7 +131,7 @@ __global__ __launch_bounds__(lm_max_threads(LOGN)) void k_rs_moddown(const u64 *
             }
         lm_store_run(o, i0, rr, count);
     };
-    lm_ntt_forward<LOGN>(sm, tw_all, qc, tid, nthreads, ld, st);
+    lm_ntt_forward<LOGN>(sm, tw_all, qc, tid, ld, st);
 }
 
 // small[p][i] = big[p][i * gap]
@@ -233,8 +233,7 @@ template <int LOGN>
 static int ring_switch_batch(lumen_ctx *ctx, RsKey *rk, const lm_ks_view &kv, const u64 *in, size_t in_ctw,
                              uint32_t nl, uint32_t B, u64 *coef, u64 *ext, u64 *u, u64 *big, u64 *small) {
     const uint32_t N = ctx->N, K = ctx->K, nt = 1 + K, L = ctx->L, nd = rk->nd;
-    const size_t lds = lm_fwd_lds(ctx->logN);
-    const uint32_t threads = lm_fwd_threads(ctx->logN);
+    constexpr lm_geom geom = lm_geom_lds(LOGN);
     // 1. c1 (limb 0) -> coefficient domain
     if (int rc = lm_launch_ntt_strided(ctx, in + (size_t)nl * N, in_ctw, coef, N, B, lm_map_q(1), true, "rs_intt_c1"))
         return rc;
@@ -242,16 +241,14 @@ static int ring_switch_batch(lumen_ctx *ctx, RsKey *rk, const lm_ks_view &kv, co
     const bool hybrid = rk->w == 0;
     if (hybrid) {
         lm_prof_scope ps(ctx, "rs_digit_ntt", (uint64_t)B * K);
-        LM_LDS_ATTR(ctx, (k_rs_digit_ntt<LOGN, true>), lds);
-        hipLaunchKernelGGL((k_rs_digit_ntt<LOGN, true>), dim3(B * K), dim3(threads), lds, ctx->stream, coef, ext, B, 1u,
-                           nt, L, 0u, ctx->mods, ctx->d_tw_fwd);
-        LM_HIP(ctx, hipGetLastError());
+        if (int rc = lm_launch(ctx, k_rs_digit_ntt<LOGN, true>, geom, B * K, coef, ext, B, 1u, nt, L, 0u, ctx->mods,
+                               ctx->d_tw_fwd))
+            return rc;
     } else {
         lm_prof_scope ps(ctx, "rs_digit_ntt", (uint64_t)B * nd * nt);
-        LM_LDS_ATTR(ctx, (k_rs_digit_ntt<LOGN, false>), lds);
-        hipLaunchKernelGGL((k_rs_digit_ntt<LOGN, false>), dim3(B * nd * nt), dim3(threads), lds, ctx->stream, coef, ext,
-                           B, nd, nt, L, rk->w, ctx->mods, ctx->d_tw_fwd);
-        LM_HIP(ctx, hipGetLastError());
+        if (int rc = lm_launch(ctx, k_rs_digit_ntt<LOGN, false>, geom, B * nd * nt, coef, ext, B, nd, nt, L, rk->w,
+                               ctx->mods, ctx->d_tw_fwd))
+            return rc;
     }
     // 3. gadget product
     {
@@ -262,20 +259,16 @@ static int ring_switch_batch(lumen_ctx *ctx, RsKey *rk, const lm_ks_view &kv, co
     }
     if (K) {
         // 4. P limbs -> coefficient domain with the source-side lift factors, correction bit
-        lm_modmap mp;
-        mp.period = K;
-        for (uint32_t i = 0; i < LM_MAX_LIMBS; i++) mp.idx[i] = (uint8_t)(L + (i < K ? i : 0));
-        if (int rc = lm_launch_ntt_strided(ctx, u + N, (size_t)nt * N, u + N, (size_t)nt * N, B * 2, mp, true,
+        if (int rc = lm_launch_ntt_strided(ctx, u + N, (size_t)nt * N, u + N, (size_t)nt * N, B * 2, lm_map_p(ctx), true,
                                            "rs_intt_p", kv.yscale))
             return rc;
         if (K == 2)
             if (int rc = lm_launch_pack_v(ctx, u + N, (size_t)nt * N, B * 2, 1u, K, L, K)) return rc;
         // 5. ModDown, add c0 -> level-0 ciphertext of the big ring under the embedded small key
         lm_prof_scope ps(ctx, "rs_moddown", (uint64_t)B * 2);
-        LM_LDS_ATTR(ctx, k_rs_moddown<LOGN>, lds);
-        hipLaunchKernelGGL(k_rs_moddown<LOGN>, dim3(B * 2), dim3(threads), lds, ctx->stream, u, in, in_ctw, big,
-                           kv.d_bxp, kv.d_pinv, nt, K, ctx->mods, ctx->d_tw_fwd);
-        LM_HIP(ctx, hipGetLastError());
+        if (int rc = lm_launch(ctx, k_rs_moddown<LOGN>, geom, B * 2, u, in, in_ctw, big, kv.d_bxp, kv.d_pinv, nt, K,
+                               ctx->mods, ctx->d_tw_fwd))
+            return rc;
     } else {
         // no special prime: the gadget product is the result; add c0
         hipLaunchKernelGGL(k_rs_add_c0, dim3(1024), dim3(256), 0, ctx->stream, u, in, in_ctw, big, B, ctx->logN,
@@ -311,19 +304,10 @@ extern "C" int lumen_ring_switch(lumen_ctx *ctx, const lumen_set *in, uint64_t *
     if (!coef || !ext || !u || !big || !small) return 1;
     for (uint32_t first = 0; first < in->count; first += Bmax) {
         const uint32_t B = std::min(Bmax, in->count - first);
-        int rc = 1;
-        switch (ctx->logN) {
-#define LM_CASE(nn)                                                                                          \
-    case nn:                                                                                                 \
-        rc = ring_switch_batch<nn>(ctx, rk, kv, in->d + (size_t)first * in_ctw, in_ctw, nl, B, coef, ext, u, big, \
-                                   small);                                                                   \
-        break;
-            LM_FOR_EACH_LOGN(LM_CASE)
-#undef LM_CASE
-        default:
-            return lm_fail(ctx, "ring degree 2^%u has no kernel instantiation", ctx->logN);
-        }
-        if (rc) return rc;
+        if (int rc = lm_for_logn(ctx, ctx->logN, [&](auto nn) {
+                return ring_switch_batch<nn>(ctx, rk, kv, in->d + (size_t)first * in_ctw, in_ctw, nl, B, coef, ext, u, big, small);
+            }))
+            return rc;
         // page-locked `out`: the copy is enqueued and the next batch's kernels run behind it (they reuse `small`
         // in stream order); a pageable one goes through the bounce buffers
         if (int rc2 = lm_d2h(ctx, out + (size_t)first * 2 * n, small, (size_t)B * 2 * n * 8, false)) return rc2;

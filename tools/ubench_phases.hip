@@ -195,7 +195,7 @@ static u64 powmod(u64 a, u64 e, u64 q) {
 template <bool PERSIST, bool OVERLAP = false, bool PREFETCH = false, bool TWPIPE = false>
 static void run(const char *name, const u64 *src, u64 *dst, uint32_t nlimbs, u64 q, const tw_t *tw, rec_t *drec,
                 uint32_t grid) {
-    const size_t lds = lm_fwd_lds(14);
+    const size_t lds = lm_geom_lds(14).lds;
     hipFuncSetAttribute((const void *)k_fwd<14, PERSIST, OVERLAP, PREFETCH, TWPIPE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     hipEvent_t a, b;
     hipEventCreate(&a), hipEventCreate(&b);
