@@ -3,6 +3,13 @@ by pytest): random ring degrees, limb counts, 1 or 2 special primes, random shap
 digests in random serialisation formats; the ring switch with 0, 1 or 2 special primes into random degrees; W = 2, 4, 8
 ranks behind a lumen_group (Encode between the all-to-alls, digests, root, query gather) against one rank.
 
+What the collected suite has of this since tests/test_degree_matrix.py: the limb transforms' users -- rescale to every level,
+InnerSum (with every forced k_intt_pack split), matrixInnerSumEval, encryption, and also lumen_mul_plain, lumen_encrypt_values and
+lumen_decrypt, which this tool never calls -- at EVERY instantiated degree (2^13 and 2^14 included, which the default FUZZ_LOGN leaves
+out), L = 5, K = 2, on a reference-style chain and on one right under the modulus bound, and the ring switch with 0, 1 and 2 special
+primes from every degree >= 2^10 into 2^8 and into itself at the bound.  Still only here: random limb counts (1 ... 6) with K = 1 for the
+key switch (the suite has L = 1 and 3 with one special prime at every degree), random InnerSum lengths and ciphertext counts, random serialisation formats, and the lumen_group runs.
+
 usage: [FUZZ_LOGN=13,14] [FUZZ_GROUP_TRANSPORT=rccl LD_LIBRARY_PATH=tests/cpp/fake_rccl:...] python tests/dev/fuzz_gpu.py [cases] [seed]
 """
 import os

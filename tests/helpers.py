@@ -37,3 +37,28 @@ def random_cts(P, count, nl, seed):
     for l in range(nl):
         out[:, :, l, :] = rng.integers(0, P.moduli[l], size=(count, 2, P.N), dtype=np.uint64)
     return out
+
+
+def _ntt_primes_near(limit, two_n, count, down=True):
+    """`count` primes == 1 mod 2N just below (or from) `limit`."""
+    from lumenos_amd import params as lp
+    p = limit - ((limit - 1) % two_n) if down else limit + ((1 - limit) % two_n)
+    out = []
+    while len(out) < count:
+        if lp.is_prime(p):
+            out.append(p)
+        p += -two_n if down else two_n
+    return out
+
+
+def _adversarial_cts(P, nl, seed):
+    """Rows: all q-1, all 0, alternating q-1/0, single spike, uniform random."""
+    cts = random_cts(P, 3, nl, seed=seed)
+    for l in range(nl):
+        q = P.moduli[l]
+        cts[0, 0, l, :] = q - 1
+        cts[0, 1, l, :] = 0
+        cts[1, 0, l, ::2], cts[1, 0, l, 1::2] = q - 1, 0
+        cts[1, 1, l, :] = 0
+        cts[1, 1, l, P.N - 1] = q - 1
+    return cts

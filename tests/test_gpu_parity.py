@@ -2,7 +2,7 @@
 import numpy as np
 import pytest
 
-from helpers import T_REF, gen_primes, make_context, make_params, random_cts
+from helpers import T_REF, _adversarial_cts, _ntt_primes_near, gen_primes, make_context, make_params, random_cts
 
 pytestmark = pytest.mark.gpu
 
@@ -610,31 +610,7 @@ def test_ring_switch_reference_test_twin(oracle):
 
 
 # ------------------------------------------------------------------ lazy-arithmetic headroom
-def _ntt_primes_near(limit, two_n, count, down=True):
-    """`count` primes == 1 mod 2N just below (or from) `limit`."""
-    from lumenos_amd import params as lp
-    p = limit - ((limit - 1) % two_n) if down else limit + ((1 - limit) % two_n)
-    out = []
-    while len(out) < count:
-        if lp.is_prime(p):
-            out.append(p)
-        p += -two_n if down else two_n
-    return out
-
-
-def _adversarial_cts(P, nl, seed):
-    """Rows: all q-1, all 0, alternating q-1/0, single spike, uniform random."""
-    cts = random_cts(P, 3, nl, seed=seed)
-    for l in range(nl):
-        q = P.moduli[l]
-        cts[0, 0, l, :] = q - 1
-        cts[0, 1, l, :] = 0
-        cts[1, 0, l, ::2], cts[1, 0, l, 1::2] = q - 1, 0
-        cts[1, 1, l, :] = 0
-        cts[1, 1, l, P.N - 1] = q - 1
-    return cts
-
-
+# (_ntt_primes_near and _adversarial_cts live in helpers.py: test_degree_matrix.py runs these cases at every degree)
 @pytest.mark.parametrize("log_n", [10, 12, 13, 14])
 def test_limb_ntt_largest_moduli_adversarial_inputs(oracle, log_n):
     """Moduli right under the context's bound (3*logN+8)*q < 2^64 and a 21-bit one, inputs that
