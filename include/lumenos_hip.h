@@ -282,6 +282,34 @@ int lumen_poly_eval_columns(lumen_ctx *ctx, const uint64_t *values, uint32_t row
 int lumen_load_secret_key(lumen_ctx *ctx, const uint64_t *sk);
 int lumen_decrypt(lumen_ctx *ctx, const lumen_set *set, uint64_t scale, uint32_t nvalues, uint64_t *values);
 
+/* ---- the client's check of the opened columns: the per-column loop of Proof.Verify (fhe/ligero.go:554-567) over
+ * the `count` opened level-1 ciphertexts of `opened` (what lumen_ct_deserialize or lumen_gather produced), on a
+ * context that holds the secret key and encoder tables.  For every column i, without its values leaving the device:
+ *   core.VerifyMerklePath(Ct_i, paths[i], root, leaf_index[i]) (core/tree.go:225-268): the leaf is SHA-256 of the
+ *     ciphertext in the CONTEXT's serialisation format (lumen_leaf_format_set), hashed up `depth` siblings,
+ *     cur = H(cur | sib) for an even running index, H(sib | cur) for an odd one;
+ *   InnerProduct(Values_i, r) == want_r[i]  with want_r[i] = core.Encode(MatR)[leaf_index[i]]  (ligero.go:559);
+ *   InnerProduct(Values_i, b) == want_z[i]  with b = [1, w, w^2, ...], w = z^cols mod T      (ligero.go:564),
+ * Values_i = the first `rows` slot values lumen_decrypt(ctx, opened, scale, rows, .) gives.  r: host, [rows], the
+ * transcript's words as sampled (reduced mod T inside); b is built on the device from w.
+ * Returns 0 when the checks RAN: a failing column is no error, it is a non-zero status[i], the OR of the bits below.
+ * All three checks are evaluated for every column, so walking status[] in query order and testing PATH, R, B in
+ * that order reproduces the reference's first error.  got (or NULL): host, [count][2] = the two inner products,
+ * canonical mod T; values (or NULL): host, [count][rows], exactly lumen_decrypt's output (Proof.QueriedCols[i].Values).
+ * want_r / want_z are compared as given: a word >= T never matches.  count == 0 succeeds and touches nothing.
+ * The leaves are hashed by a lumen_leaf_digests_begin job on the context's side stream, under the decryption: no
+ * such job of the caller's may be in flight on the context (one job per context).
+ * Refused with a message, before any device work: NULL ctx / opened / r / want_r / want_z / leaf_index / root /
+ * status; NULL paths with depth > 0; rows outside [1, N]; depth > 32; a leaf_index[i] >= 2^depth; scale = 0 mod T;
+ * no secret key; no encoder tables; T >= 2^60; a lane-sharded set; a limb count outside [1, L]. */
+#define LUMEN_VERIFY_BAD_PATH 1u /* "failed to verify merkle path for column %d" */
+#define LUMEN_VERIFY_BAD_R 2u    /* "well-formedness R check failed for column %d" */
+#define LUMEN_VERIFY_BAD_B 4u    /* "well-formedness B check failed for column %d" */
+int lumen_verify_columns(lumen_ctx *ctx, const lumen_set *opened, uint64_t scale, uint32_t rows, const uint64_t *r,
+                         uint64_t w, const uint64_t *want_r, const uint64_t *want_z, const uint32_t *leaf_index,
+                         const uint8_t *paths /* [count][depth][32] */, uint32_t depth, const uint8_t root[32],
+                         uint32_t *status, uint64_t *got, uint64_t *values);
+
 /* ---- the plain prover on the same kernels: LigeroProveReference (fhe/ligero.go:799-953),
  * what the client runs to check a decrypted proof.  A plain matrix over F_T is a set of a context whose
  * ONE modulus is T (num_q = 1, num_p = 0, 2N = rows): column j is one "ciphertext" of 2 x 1 x N words.

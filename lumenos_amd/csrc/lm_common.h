@@ -310,3 +310,19 @@ lm_modmap lm_map_p(const lumen_ctx *ctx);
 int lm_encode_dev(lumen_ctx *ctx, const lumen_set *matrix, const u64 *dzero, uint32_t rho_inv, lumen_set **encoded);
 // pooled timing events of a context (lm_ctx.hip)
 hipEvent_t lm_ev_get(lumen_ctx *ctx);
+// ---- client-side decryption in stages (lm_encrypt.hip), shared by lumen_decrypt and lumen_verify_columns
+// what lumen_decrypt refuses about its set, scale and context (no device work)
+int lm_decrypt_check(lumen_ctx *ctx, const lumen_set *set, uint64_t scale, const char *what);
+// Decryptor.DecryptNew + the decoder's transform over Z_T, enqueued on the context's stream: t = [count][N] words
+// below T in the transform's output order, slot[i] = the position of slot value i in it.  `keep` holds the key and
+// encoder tables for as long as the caller's kernels read them.
+struct lm_decoded {
+    const u64 *t = nullptr;
+    const uint32_t *slot = nullptr;
+    std::shared_ptr<void> keep[2];
+};
+int lm_decrypt_decode(lumen_ctx *ctx, const lumen_set *set, lm_decoded *out);
+// values[c][i] = t[c][slot[i]] * scale^-1 mod T for i < nvalues, copied to the host buffer on the context's stream
+// (not waited for)
+int lm_decrypt_slots(lumen_ctx *ctx, const lm_decoded &dec, uint32_t count, uint64_t scale, uint32_t nvalues,
+                     uint64_t *values);

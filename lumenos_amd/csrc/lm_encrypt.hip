@@ -639,26 +639,26 @@ static int decrypt_phase_t(lumen_ctx *ctx, const u64 *ct, const tw_t *sk, u64 *p
                      ctx->d_tw_inv);
 }
 
-extern "C" int lumen_decrypt(lumen_ctx *ctx, const lumen_set *set, uint64_t scale, uint32_t nvalues, uint64_t *values) {
-    LM_CHECK(nullptr, ctx && set && values, "lumen_decrypt: NULL argument");
-    LM_ENTER(ctx);
-    LM_FULL_WIDTH(ctx, set, "lumen_decrypt");
-    LM_CHECK(ctx, set->nl >= 1 && set->nl <= ctx->L, "lumen_decrypt: %u limbs out of range [1, %u]", set->nl, ctx->L);
-    LM_CHECK(ctx, nvalues >= 1 && nvalues <= ctx->N, "nvalues=%u out of range [1, N]", nvalues);
+int lm_decrypt_check(lumen_ctx *ctx, const lumen_set *set, uint64_t scale, const char *what) {
+    LM_FULL_WIDTH(ctx, set, what);
+    LM_CHECK(ctx, set->nl >= 1 && set->nl <= ctx->L, "%s: %u limbs out of range [1, %u]", what, set->nl, ctx->L);
+    LM_CHECK(ctx, lm_ext_get<SkTable>(ctx, "secret_key"), "no secret key loaded (lumen_load_secret_key)");
+    LM_CHECK(ctx, lm_ext_get<EncoderTables>(ctx, "encoder"), "no encoder tables (lumen_encoder_set)");
+    LM_CHECK(ctx, scale % ctx->T != 0, "scale is 0 modulo T");
+    return 0;
+}
+
+int lm_decrypt_decode(lumen_ctx *ctx, const lumen_set *set, lm_decoded *out) {
     const std::shared_ptr<SkTable> sk_hold = lm_ext_get<SkTable>(ctx, "secret_key");
-    LM_CHECK(ctx, sk_hold, "no secret key loaded (lumen_load_secret_key)");
     const std::shared_ptr<EncoderTables> enc_hold = lm_ext_get<EncoderTables>(ctx, "encoder");
-    LM_CHECK(ctx, enc_hold, "no encoder tables (lumen_encoder_set)");
+    LM_CHECK(ctx, sk_hold && enc_hold, "lm_decrypt_decode without a secret key and encoder tables");
     const SkTable *sk = sk_hold.get();
     const EncoderTables *enc = enc_hold.get();
     const uint32_t N = ctx->N, nl = set->nl, count = set->count;
     const uint64_t T = ctx->T;
-    LM_CHECK(ctx, scale % T != 0, "scale is 0 modulo T");
-    if (!count) return 0;
     u64 *phase = (u64 *)lm_scratch(ctx, "dec_phase", (size_t)count * nl * N * sizeof(u64));
     u64 *m = (u64 *)lm_scratch(ctx, "dec_m", (size_t)count * N * sizeof(u64));
-    u64 *dv = (u64 *)lm_scratch(ctx, "dec_values", (size_t)count * nvalues * sizeof(u64));
-    if (!phase || !m || !dv) return 1;
+    if (!phase || !m) return 1;
     dec_scale_t sc;
     for (uint32_t l = 0; l < LM_MAX_LIMBS; l++) {
         const uint64_t q = ctx->mod[l < nl ? l : 0];
@@ -708,14 +708,34 @@ extern "C" int lumen_decrypt(lumen_ctx *ctx, const lumen_set *set, uint64_t scal
         if (int r2 = lm_launch_ntt_subring(ctx, ctx->logN, enc->d_tw_fwd, enc->ninvT, m, N, m, N, count, 0, false, &enc->modT))
             return r2;
     }
-    {
-        const size_t total = (size_t)count * nvalues;
-        const tw_t sinv = h_tw(h_invmod(scale % T, T), T);
-        hipLaunchKernelGGL(k_decrypt_slots, dim3((uint32_t)((total + 255) / 256)), dim3(256), 0, ctx->stream, m, enc->d_slot,
-                           dv, nvalues, ctx->logN, total, sinv, T);
-        LM_HIP(ctx, hipGetLastError());
-    }
-    LM_HIP(ctx, hipMemcpyAsync(values, dv, (size_t)count * nvalues * sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
+    out->t = m, out->slot = enc->d_slot;
+    out->keep[0] = sk_hold, out->keep[1] = enc_hold;
+    return 0;
+}
+
+int lm_decrypt_slots(lumen_ctx *ctx, const lm_decoded &dec, uint32_t count, uint64_t scale, uint32_t nvalues,
+                     uint64_t *values) {
+    const uint64_t T = ctx->T;
+    u64 *dv = (u64 *)lm_scratch(ctx, "dec_values", (size_t)count * nvalues * sizeof(u64));
+    if (!dv) return 1;
+    const size_t total = (size_t)count * nvalues;
+    const tw_t sinv = h_tw(h_invmod(scale % T, T), T);
+    hipLaunchKernelGGL(k_decrypt_slots, dim3((uint32_t)((total + 255) / 256)), dim3(256), 0, ctx->stream, dec.t, dec.slot, dv,
+                       nvalues, ctx->logN, total, sinv, T);
+    LM_HIP(ctx, hipGetLastError());
+    LM_HIP(ctx, hipMemcpyAsync(values, dv, total * sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
+    return 0;
+}
+
+extern "C" int lumen_decrypt(lumen_ctx *ctx, const lumen_set *set, uint64_t scale, uint32_t nvalues, uint64_t *values) {
+    LM_CHECK(nullptr, ctx && set && values, "lumen_decrypt: NULL argument");
+    LM_ENTER(ctx);
+    if (int rc = lm_decrypt_check(ctx, set, scale, "lumen_decrypt")) return rc;
+    LM_CHECK(ctx, nvalues >= 1 && nvalues <= ctx->N, "nvalues=%u out of range [1, N]", nvalues);
+    if (!set->count) return 0;
+    lm_decoded dec;
+    if (int rc = lm_decrypt_decode(ctx, set, &dec)) return rc;
+    if (int rc = lm_decrypt_slots(ctx, dec, set->count, scale, nvalues, values)) return rc;
     LM_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return 0;
 }

@@ -477,6 +477,55 @@ __global__ void k_merkle_level(const uint8_t *__restrict__ cur, uint8_t *__restr
     for (int k = 0; k < 8; k++) o[k] = bswap32(h[k]);
 }
 
+// ---- the verifier's walk (core.VerifyMerklePath, core/tree.go:225-268) for every opened column at once: one thread per
+// query starts from its leaf digest (device memory, what k_leaf_sha256 wrote) and hashes up its path, cur = H(cur | sib)
+// for an even running index, H(sib | cur) for an odd one, index halved per level; bad[i] = flag where the result is not
+// the root, 0 where it is.  paths: [count][depth][32], root: 32 bytes, both 4-byte aligned.
+__global__ __launch_bounds__(64) void k_verify_paths(const uint8_t *__restrict__ digests, const uint32_t *__restrict__ leaf_index,
+                                                     const uint8_t *__restrict__ paths, uint32_t depth,
+                                                     const uint8_t *__restrict__ root, uint32_t count, uint32_t flag,
+                                                     uint32_t *__restrict__ bad) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= count) return;
+    u32 cur[8];
+    const u32 *pd = reinterpret_cast<const u32 *>(digests + (size_t)i * 32);
+#pragma unroll
+    for (int k = 0; k < 8; k++) cur[k] = bswap32(pd[k]);
+    uint32_t idx = leaf_index[i];
+    for (uint32_t d = 0; d < depth; d++, idx >>= 1) {
+        const u32 *ps = reinterpret_cast<const u32 *>(paths + ((size_t)i * depth + d) * 32);
+        const bool odd = idx & 1;
+        u32 h[8] = {0x6a09e667, 0xbb67ae85, 0x3c6ef372, 0xa54ff53a, 0x510e527f, 0x9b05688c, 0x1f83d9ab, 0x5be0cd19};
+        u32 w[16];
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+            const u32 sib = bswap32(ps[k]);
+            w[k] = odd ? sib : cur[k], w[8 + k] = odd ? cur[k] : sib;
+        }
+        sha256_compress(h, w, c_k256);
+#pragma unroll
+        for (int k = 0; k < 16; k++) w[k] = 0;
+        w[0] = 0x80000000u, w[15] = 512;
+        sha256_compress(h, w, c_k256);
+#pragma unroll
+        for (int k = 0; k < 8; k++) cur[k] = h[k];
+    }
+    const u32 *pr = reinterpret_cast<const u32 *>(root);
+    u32 diff = 0;
+#pragma unroll
+    for (int k = 0; k < 8; k++) diff |= cur[k] ^ bswap32(pr[k]);
+    bad[i] = diff ? flag : 0;
+}
+
+int lm_verify_paths(lumen_ctx *ctx, const uint8_t *digests, const uint32_t *leaf_index, const uint8_t *paths, uint32_t depth,
+                    const uint8_t *root, uint32_t count, uint32_t flag, uint32_t *bad) {
+    lm_prof_scope ps(ctx, "verify_paths", count);
+    hipLaunchKernelGGL(k_verify_paths, dim3((count + 63) / 64), dim3(64), 0, ctx->stream, digests, leaf_index, paths, depth,
+                       root, count, flag, bad);
+    LM_HIP(ctx, hipGetLastError());
+    return 0;
+}
+
 extern "C" int lumen_merkle_root_device(lumen_ctx *ctx, const void *dev_leaf_digests, uint32_t n_leaves, uint8_t *root) {
     LM_CHECK(nullptr, ctx && dev_leaf_digests && root, "lumen_merkle_root_device: NULL argument");
     LM_ENTER(ctx);

@@ -17,34 +17,13 @@
 #include <cstring>
 
 #include "lm_common.h"
+#include "lm_polyeval_dev.h"
 
 bool lm_host_is_pinned(const void *p); // lm_ctx.hip
 int lm_h2d(lumen_ctx *ctx, void *dev, const void *host, size_t bytes);
 
 namespace {
-
-constexpr uint32_t PE_THREADS = 256;
-constexpr uint32_t PE_UNROLL = 4;                 // 16-byte loads in flight per thread and iteration
 constexpr size_t PE_CHUNK_BYTES = (size_t)128 << 20; // columns staged on the device per launch
-// products summed in 128 bits before one reduction: 8 * 2^64 * T < 2^128 and lm_mont_reduce_wide's 8 * T < 2^63
-constexpr uint64_t PE_MAX_T = 1ull << 60;
-
-__device__ __forceinline__ u64 pe_mont_mul(u64 a, u64 b, const mod_t &m) {
-    const u128 p = (u128)a * b;
-    return lm_mont_reduce((u64)p, (u64)(p >> 64), m.q, m.qneg);
-}
-
-// sum of a workgroup's values mod q; the result is valid in thread 0
-__device__ __forceinline__ u64 pe_block_sum(u64 acc, const mod_t &m) {
-    __shared__ u64 wsum[PE_THREADS / 64];
-    for (int off = 32; off; off >>= 1) acc = lm_addmod(acc, __shfl_xor(acc, off), m.q);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0)
-        for (uint32_t k = 1; k < PE_THREADS / 64; k++) acc = lm_addmod(acc, wsum[k], m.q);
-    return acc;
-}
-
 } // namespace
 
 // out[i] = base^(e0 + i) * 2^64 mod q for i < n; baseM = base * 2^64 mod q, oneM = 2^64 mod q
@@ -58,6 +37,14 @@ __global__ __launch_bounds__(256) void k_poly_pow_table(u64 *__restrict__ out, u
         b = pe_mont_mul(b, b, m);
     }
     out[i] = r;
+}
+
+int lm_poly_pow_table(lumen_ctx *ctx, u64 *out, uint32_t n, uint64_t baseM, uint64_t e0) {
+    const uint64_t T = ctx->T;
+    hipLaunchKernelGGL(k_poly_pow_table, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, out, n, baseM, e0,
+                       (uint64_t)((((u128)1) << 64) % T), lm_make_mod(T));
+    LM_HIP(ctx, hipGetLastError());
+    return 0;
 }
 
 // part[j] = z^(c0+j) * sum_i x[j][i] * w^i mod q; wM / zM: the two tables in Montgomery form.  PAIRS: rows is even, so
@@ -155,12 +142,8 @@ int lm_poly_eval_enqueue(lumen_ctx *ctx, const uint64_t *values, uint32_t rows, 
         const uint64_t zMont = h_mulmod(zr, R, T), wMont = h_mulmod(h_powmod(zr, cols, T), R, T);
         {
             lm_prof_scope ps(ctx, "poly_tables", (uint64_t)rows + count);
-            hipLaunchKernelGGL(k_poly_pow_table, dim3((rows + 255) / 256), dim3(256), 0, ctx->stream, dw, rows, wMont,
-                               (uint64_t)0, R, m);
-            LM_HIP(ctx, hipGetLastError());
-            hipLaunchKernelGGL(k_poly_pow_table, dim3((count + 255) / 256), dim3(256), 0, ctx->stream, dz, count, zMont,
-                               first_column, R, m);
-            LM_HIP(ctx, hipGetLastError());
+            if (int rc = lm_poly_pow_table(ctx, dw, rows, wMont, 0)) return rc;
+            if (int rc = lm_poly_pow_table(ctx, dz, count, zMont, first_column)) return rc;
         }
         for (uint32_t c = 0; c < count; c += chunk) {
             const uint32_t n = std::min(chunk, count - c);

@@ -16,6 +16,23 @@ _u32p = C.POINTER(C.c_uint32)
 _u8p = C.POINTER(C.c_uint8)
 LUMEN_MAX_LIMBS = 24
 LUMEN_ABI_VERSION = 4
+# status bits of lumen_verify_columns, with the reference's message for each (fhe/ligero.go:556, 561, 565)
+LUMEN_VERIFY_BAD_PATH, LUMEN_VERIFY_BAD_R, LUMEN_VERIFY_BAD_B = 1, 2, 4
+VERIFY_MESSAGES = (
+    (LUMEN_VERIFY_BAD_PATH, "failed to verify merkle path for column %d"),
+    (LUMEN_VERIFY_BAD_R, "well-formedness R check failed for column %d"),
+    (LUMEN_VERIFY_BAD_B, "well-formedness B check failed for column %d"),
+)
+
+
+def verify_first_error(status, leaf_index):
+    """The error Proof.Verify's loop returns for these statuses (the first failing query, PATH before R before B), or
+    None when every column passed."""
+    for st, idx in zip(status, leaf_index):
+        for bit, msg in VERIFY_MESSAGES:
+            if int(st) & bit:
+                return msg % int(idx)
+    return None
 
 
 class LumenError(RuntimeError):
@@ -98,6 +115,8 @@ SYMBOLS = {
     "lumen_gather": (C.c_int, [_vp, _vp, _u32p, C.c_uint32, _vpp]),
     "lumen_plain_inner_products": (C.c_int, [_vp, _vp, _u64p, _u64p]),
     "lumen_poly_eval_columns": (C.c_int, [_vp, _u64p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint64, _u64p]),
+    "lumen_verify_columns": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint32, _u64p, C.c_uint64, _u64p, _u64p, _u32p, _u8p, C.c_uint32,
+                             _u8p, _u32p, _u64p, _u64p]),
     "lumen_ringswitch_rns_digits": (C.c_uint32, [_vp]),
     "lumen_ringswitch_digits": (C.c_uint32, [_vp, C.c_uint32]),
     "lumen_load_ringswitch_key": (C.c_int, [_vp, C.c_uint32, C.c_uint32, _u64p, C.c_size_t]),
@@ -607,6 +626,28 @@ class Context:
         self._ck(self.lib.lumen_poly_eval_columns(self.h, _p64(values), values.shape[1], values.shape[0], first_column,
                                                   cols, z, C.byref(out)))
         return out.value
+
+    def verify_columns(self, opened, rows, r, w, want_r, want_z, leaf_index, paths, root, scale=1, want_values=False):
+        """Proof.Verify's per-column loop (fhe/ligero.go:554-567) over the opened ciphertexts `opened`: Merkle path,
+        <col, r> == want_r and <col, b> == want_z (b_i = w^i) for every column on the device.  paths: [count][depth][32]
+        bytes.  -> (status[count], got[count][2]) and, with want_values, the decrypted columns [count][rows]."""
+        n = opened.count
+        r = np.ascontiguousarray(r, dtype=np.uint64)
+        want_r = np.ascontiguousarray(want_r, dtype=np.uint64)
+        want_z = np.ascontiguousarray(want_z, dtype=np.uint64)
+        leaf_index = np.ascontiguousarray(leaf_index, dtype=np.uint32)
+        paths = np.ascontiguousarray(paths, dtype=np.uint8)
+        paths = paths.reshape(n, paths.size // (32 * n) if n else 0, 32)
+        root = np.frombuffer(bytes(root), dtype=np.uint8)
+        assert r.size == rows and want_r.size == n and want_z.size == n and leaf_index.size == n and root.size == 32
+        status = np.zeros(n, dtype=np.uint32)
+        got = np.zeros((n, 2), dtype=np.uint64)
+        values = np.zeros((n, rows), dtype=np.uint64) if want_values else None
+        self._ck(self.lib.lumen_verify_columns(self.h, opened.h, scale, rows, _p64(r), w, _p64(want_r), _p64(want_z),
+                                               leaf_index.ctypes.data_as(_u32p), paths.ctypes.data_as(_u8p), paths.shape[1],
+                                               root.ctypes.data_as(_u8p), status.ctypes.data_as(_u32p), _p64(got),
+                                               _p64(values) if want_values else None))
+        return (status, got, values) if want_values else (status, got)
 
     def gather(self, s, idx):
         idx = np.ascontiguousarray(idx, dtype=np.uint32)

@@ -342,6 +342,58 @@ ServerBFV::~ServerBFV() {
 
 int ServerBFV::MulCounter() const { return (int)lumen_mul_counter(ctx_); }
 
+// ------------------------------------------------------------------ ClientBFV
+void ClientBFV::check(int rc, const char *what) const {
+    if (rc) throw std::runtime_error(std::string(what) + ": " + lumen_last_error(ctx_));
+}
+
+ClientBFV::ClientBFV(core::PrimeField *plaintextField, const Parameters &params, const std::vector<uint64_t> &sk, int device)
+    : ptField_(plaintextField), params_(params), device_(device) {
+    const size_t N = (size_t)params.N(), L = params.Q.size();
+    if (sk.size() < L * N) throw std::invalid_argument("NewClientBFV: the secret key has fewer than L * N residues");
+    lumen_params_desc d;
+    memset(&d, 0, sizeof(d));
+    d.abi_version = LUMEN_ABI_VERSION;
+    d.log_n = (uint32_t)params.LogN;
+    d.num_q = (uint32_t)L;
+    d.num_p = (uint32_t)params.P.size();
+    d.plaintext_modulus = params.T;
+    d.device = device;
+    size_t i = 0;
+    for (uint64_t m : params.Q) d.moduli[i++] = m;
+    for (uint64_t m : params.P) d.moduli[i++] = m;
+    for (size_t k = 0; k < params.Psi.size(); k++) d.psi[k] = params.Psi[k];
+    if (lumen_ctx_create(&d, &ctx_)) throw std::runtime_error(std::string("lumen_ctx_create: ") + lumen_last_error(nullptr));
+    g_ring_degree[ctx_] = (uint32_t)N;
+    try {
+        check(lumen_encoder_set(ctx_, PowMod(core::PrimitiveRoot(params.T), (params.T - 1) / (2ull << params.LogN), params.T)),
+              "lumen_encoder_set");
+        check(lumen_load_secret_key(ctx_, sk.data()), "lumen_load_secret_key");
+    } catch (...) {
+        g_ring_degree.erase(ctx_);
+        lumen_ctx_destroy(ctx_);
+        throw;
+    }
+}
+
+ClientBFV::ClientBFV(ClientBFV &src, lumen_ctx *clone)
+    : ptField_(src.ptField_), params_(src.params_), ctx_(clone), device_(src.device_) {
+    g_ring_degree[ctx_] = (uint32_t)params_.N();
+}
+
+std::unique_ptr<ClientBFV> ClientBFV::CopyNew() {
+    lumen_ctx *twin = nullptr;
+    check(lumen_ctx_clone(ctx_, &twin), "lumen_ctx_clone");
+    return std::unique_ptr<ClientBFV>(new ClientBFV(*this, twin));
+}
+
+ClientBFV::~ClientBFV() {
+    if (ctx_) {
+        g_ring_degree.erase(ctx_);
+        lumen_ctx_destroy(ctx_);
+    }
+}
+
 Plaintext ServerBFV::Encode(const std::vector<uint64_t> &values) const {
     const int N = params_.N(), nl = (int)params_.Q.size();
     if ((int)values.size() > N) throw std::invalid_argument("cannot Encode: too many values for the ring degree");
@@ -1008,7 +1060,8 @@ void EncryptedProof::MarshalInto(uint8_t *out, size_t cap, bool pageLocked) cons
     }
 }
 
-EncryptedProof EncryptedProof::UnmarshalBinary(const uint8_t *data, size_t len, ServerBFV &backend, const MetaData &meta) {
+// UnmarshalBinary on one context of ring degree N and plaintext modulus T (a server's or a client's)
+static EncryptedProof unmarshal(const uint8_t *data, size_t len, lumen_ctx *ctx, uint64_t T, uint32_t N, const MetaData &meta) {
     if (len < 11 + 32) throw std::invalid_argument("UnmarshalBinary: too short");
     EncryptedProof p;
     auto le = [&](size_t at, int n) {
@@ -1017,16 +1070,16 @@ EncryptedProof EncryptedProof::UnmarshalBinary(const uint8_t *data, size_t len, 
         return v;
     };
     p.Metadata = {(int)le(0, 4), (int)le(4, 4), (int)le(8, 1), (int)le(9, 2)}; // LigeroMetadata.ReadFrom (ligero.go:763-778)
-    p.PlaintextModulus = backend.GetParameters().T;
-    lumen_ctx *ctx = backend.Context();
-    SetCiphertextFormat(backend, meta, 1);
+    p.PlaintextModulus = T;
+    set_format(ctx, meta, 1, T, N);
     const size_t each = lumen_ct_serialized_size(ctx, 2);
     size_t off = 11;
     auto take = [&](int count) {
         const size_t bytes = each * (size_t)count;
         if (off + bytes > len) throw std::invalid_argument("UnmarshalBinary: truncated ciphertext slice");
         lumen_set *s = nullptr;
-        backend.check(lumen_ct_deserialize(ctx, data + off, bytes, (uint32_t)count, 2, &s), "lumen_ct_deserialize");
+        if (lumen_ct_deserialize(ctx, data + off, bytes, (uint32_t)count, 2, &s))
+            throw std::runtime_error(std::string("lumen_ct_deserialize: ") + lumen_last_error(ctx));
         off += bytes;
         return Ciphertexts(ctx, s, meta);
     };
@@ -1044,6 +1097,169 @@ EncryptedProof EncryptedProof::UnmarshalBinary(const uint8_t *data, size_t len, 
     }
     p.Root.assign(data + off, data + off + 32);
     return p;
+}
+
+EncryptedProof EncryptedProof::UnmarshalBinary(const uint8_t *data, size_t len, ServerBFV &backend, const MetaData &meta) {
+    return unmarshal(data, len, backend.Context(), backend.GetParameters().T, (uint32_t)backend.GetParameters().N(), meta);
+}
+
+EncryptedProof EncryptedProof::UnmarshalBinary(const uint8_t *data, size_t len, ClientBFV &client, const MetaData &meta) {
+    return unmarshal(data, len, client.Context(), client.GetParameters().T, (uint32_t)client.GetParameters().N(), meta);
+}
+
+// ------------------------------------------------------------------ the client: Decrypt and Verify
+Proof EncryptedProof::Decrypt(ClientBFV &client, core::Span *ctx) {
+    if (RingSwitchLogN || !MatRSwitched.empty() || !MatZSwitched.empty())
+        throw std::runtime_error("Decrypt: a ring-switched proof is read with the client's small-ring key; it is not verified "
+                                 "(cmd/client/main.go:210-212) and not supported here");
+    if (MatR.Blocks.size() != 1 || MatZ.Blocks.size() != 1)
+        throw std::runtime_error("Decrypt: MatR / MatZ must be one block on the client's device");
+    const int rows = Metadata.Rows;
+    lumen_ctx *h = client.Context();
+    Proof proof;
+    core::Span *span = core::Span::StartSpan("Decrypt queried columns", ctx);
+    const int nq = QueriedCols.Len();
+    std::vector<uint64_t> values((size_t)nq * (size_t)rows);
+    if (nq) client.check(lumen_decrypt(h, QueriedCols.Handle(), QueriedCols.Scale(), (uint32_t)rows, values.data()), "lumen_decrypt");
+    for (int i = 0; i < nq; i++)
+        proof.QueriedCols.emplace_back(values.begin() + (long)((size_t)i * rows), values.begin() + (long)((size_t)(i + 1) * rows));
+    span->End();
+    delete span;
+
+    span = core::Span::StartSpan("Decrypt row inner products", ctx);
+    auto single = [&](const Ciphertexts &c) { // decodeSingleElement of every ciphertext
+        std::vector<uint64_t> out((size_t)c.Len());
+        if (c.Len()) client.check(lumen_decrypt(h, c.Handle(), c.Scale(), 1, out.data()), "lumen_decrypt");
+        return out;
+    };
+    proof.MatR = single(MatR.Blocks[0]);
+    proof.MatZ = single(MatZ.Blocks[0]);
+    span->End();
+    delete span;
+
+    proof.Metadata = Metadata;
+    proof.Root = Root;
+    proof.MerklePaths = MerklePaths;
+    proof.QueriedCts = std::make_shared<Ciphertexts>(std::move(QueriedCols));
+    return proof;
+}
+
+std::vector<std::vector<core::Element>> EncodeRows(const std::vector<std::vector<core::Element>> &rows, int rhoInv,
+                                                   core::PrimeField &field, int device) {
+    const int logN = 8, N = 1 << logN, lanes = 2 * N; // the smallest degree with kernels: 512 lanes per "ciphertext"
+    if (rows.empty()) return {};
+    const size_t len = rows[0].size();
+    for (const auto &r : rows)
+        if (r.size() != len) throw std::invalid_argument("EncodeRows: rows of unequal length");
+    if ((int)rows.size() > lanes) throw std::invalid_argument("EncodeRows: more than 512 rows");
+    if ((size_t)field.N() != len * (size_t)rhoInv) throw std::invalid_argument("EncodeRows: the field's table is not of len * rhoInv entries");
+    const uint64_t T = field.Modulus();
+    lumen_params_desc d;
+    memset(&d, 0, sizeof(d));
+    d.abi_version = LUMEN_ABI_VERSION, d.log_n = (uint32_t)logN, d.num_q = 1, d.num_p = 0, d.plaintext_modulus = T;
+    d.moduli[0] = T, d.psi[0] = PowMod(core::PrimitiveRoot(T), (T - 1) / (uint64_t)lanes, T), d.device = device;
+    lumen_ctx *ctx = nullptr;
+    if (lumen_ctx_create(&d, &ctx)) throw std::runtime_error(std::string("lumen_ctx_create: ") + lumen_last_error(nullptr));
+    struct Closer {
+        lumen_ctx *c;
+        std::vector<lumen_set *> sets;
+        ~Closer() {
+            for (lumen_set *s : sets) lumen_set_destroy(c, s);
+            lumen_ctx_destroy(c);
+        }
+    } guard{ctx, {}};
+    auto ck = [&](int rc, const char *what) {
+        if (rc) throw std::runtime_error(std::string(what) + ": " + lumen_last_error(ctx));
+    };
+    ck(lumen_field_set(ctx, field.RootsForward().data(), (uint32_t)field.N()), "lumen_field_set");
+    std::vector<uint64_t> columns(len * (size_t)lanes, 0); // column j = lane i holds rows[i][j]
+    for (size_t i = 0; i < rows.size(); i++)
+        for (size_t j = 0; j < len; j++) columns[j * lanes + i] = rows[i][j] % T;
+    lumen_set *m = nullptr, *enc = nullptr;
+    ck(lumen_set_create(ctx, (uint32_t)len, 1, &m), "lumen_set_create");
+    guard.sets.push_back(m);
+    ck(lumen_set_upload(ctx, m, 0, (uint32_t)len, columns.data()), "lumen_set_upload");
+    const std::vector<uint64_t> zero((size_t)lanes, 0);
+    ck(lumen_encode(ctx, m, zero.data(), (uint32_t)rhoInv, &enc), "lumen_encode");
+    guard.sets.push_back(enc);
+    const size_t S = len * (size_t)rhoInv;
+    std::vector<uint64_t> out(S * (size_t)lanes);
+    ck(lumen_set_download(ctx, enc, 0, (uint32_t)S, out.data()), "lumen_set_download");
+    std::vector<std::vector<core::Element>> res(rows.size(), std::vector<core::Element>(S));
+    for (size_t i = 0; i < rows.size(); i++)
+        for (size_t k = 0; k < S; k++) res[i][k] = out[k * lanes + i];
+    return res;
+}
+
+std::string VerifyColumnError(uint32_t status, int queryColIdx) {
+    if (status & LUMEN_VERIFY_BAD_PATH) return "failed to verify merkle path for column " + std::to_string(queryColIdx);
+    if (status & LUMEN_VERIFY_BAD_R) return "well-formedness R check failed for column " + std::to_string(queryColIdx);
+    if (status & LUMEN_VERIFY_BAD_B) return "well-formedness B check failed for column " + std::to_string(queryColIdx);
+    return "";
+}
+
+void Proof::Verify(core::Element point, core::Element value, core::PrimeField &field, core::Transcript &transcript,
+                   ClientBFV &client) const {
+    const int rows = Metadata.Rows, cols = Metadata.Cols;
+    std::vector<uint64_t> r((size_t)rows);
+    transcript.SampleUints("r", r); // raw words (SampleFields), reduced where they are multiplied
+
+    // Encode row inner products
+    const std::vector<std::vector<core::Element>> encoded = EncodeRows({MatR, MatZ}, Metadata.RhoInv, field, client.Device());
+    const std::vector<core::Element> &encodedMatR = encoded[0], &encodedMatZ = encoded[1];
+
+    transcript.AppendField("point", point);
+
+    // a = [1, z, z^2, ..., z^(cols-1)]
+    std::vector<core::Element> a((size_t)cols);
+    core::Element powA = 1;
+    for (core::Element &ai : a) ai = powA, powA = field.Mul(powA, point);
+    // b = [1, z^cols, z^(2 cols), ...] is built on the device from zPow
+    const core::Element zPow = field.Pow((uint64_t)cols, point);
+    if (zPow != powA) throw std::runtime_error("zPow is not equal to powA");
+
+    const int extCols = cols * Metadata.RhoInv;
+    const std::vector<int> queryIndices = sampleQueryIndices(transcript, Metadata.Queries, extCols);
+    const size_t nq = queryIndices.size();
+    if (nq) {
+        if (!QueriedCts || (size_t)QueriedCts->Len() != nq)
+            throw std::runtime_error("Verify: the proof holds " + std::to_string(QueriedCts ? QueriedCts->Len() : 0) +
+                                     " opened ciphertexts for " + std::to_string(nq) + " queries");
+        uint32_t depth = 0;
+        while ((1u << depth) < (uint32_t)extCols) depth++;
+        std::vector<uint8_t> paths(nq * depth * 32, 0);
+        std::vector<uint32_t> idx(nq), status(nq, 0);
+        std::vector<uint64_t> wantR(nq), wantZ(nq), got(2 * nq);
+        if (Root.size() != 32) throw std::runtime_error(VerifyColumnError(LUMEN_VERIFY_BAD_PATH, queryIndices[0])); // no root to reach
+        std::vector<bool> noPath(nq, false); // a missing path, or one of another length: it cannot lead to the root
+        for (size_t i = 0; i < nq; i++) {
+            idx[i] = (uint32_t)queryIndices[i];
+            wantR[i] = encodedMatR[(size_t)queryIndices[i]], wantZ[i] = encodedMatZ[(size_t)queryIndices[i]];
+            if (i >= MerklePaths.size() || MerklePaths[i].size() != depth) {
+                noPath[i] = true;
+                continue;
+            }
+            for (uint32_t k = 0; k < depth; k++) memcpy(&paths[(i * depth + k) * 32], MerklePaths[i][k].data(), 32);
+        }
+        lumen_ctx *h = client.Context();
+        set_format(h, QueriedCts->Meta, QueriedCts->Level(), client.GetParameters().T, (uint32_t)client.GetParameters().N());
+        client.check(lumen_verify_columns(h, QueriedCts->Handle(), QueriedCts->Scale(), (uint32_t)rows, r.data(), zPow, wantR.data(),
+                                          wantZ.data(), idx.data(), paths.data(), depth, Root.data(), status.data(), got.data(),
+                                          nullptr),
+                     "lumen_verify_columns");
+        for (size_t i = 0; i < nq; i++) {
+            const uint32_t st = noPath[i] ? status[i] | LUMEN_VERIFY_BAD_PATH : status[i];
+            if (!st) continue;
+            if (!(st & LUMEN_VERIFY_BAD_PATH) && (st & LUMEN_VERIFY_BAD_R))
+                printf("well-formedness R check failed for column expected %llu got %llu\n", (unsigned long long)wantR[i],
+                       (unsigned long long)got[2 * i]);
+            throw std::runtime_error(VerifyColumnError(st, queryIndices[i]));
+        }
+    }
+
+    core::Element claim = 0;
+    for (int j = 0; j < cols; j++) claim = field.Add(claim, field.Mul(MatZ.at((size_t)j), a[(size_t)j]));
+    if (claim != value) throw std::runtime_error(" claimed value does not match the evaluation of the committed polynomial");
 }
 
 std::vector<uint8_t> EncryptedProof::MarshalBinary() const {

@@ -1,5 +1,6 @@
-// Host-side mirror of the reference's `fhe` package, server half (fhe/bfv.go, fhe/code.go,
-// fhe/ntt.go, fhe/ligero.go:19-370,638-705,755-797), written above the C ABI of
+// Host-side mirror of the reference's `fhe` package: the server half (fhe/bfv.go, fhe/code.go,
+// fhe/ntt.go, fhe/ligero.go:19-370,638-705,755-797) and the client's ClientBFV, EncryptedProof.Decrypt and
+// Proof.Verify (fhe/bfv.go:60-106, fhe/ligero.go:381-502,517-574), written above the C ABI of
 // include/lumenos_hip.h.  Names, argument meaning and error behaviour follow the Go code so that a
 // test written against it reads like fhe/ligero_test.go; where the Go code hands []*rlwe.Ciphertext
 // around, this mirror hands `Ciphertexts` (an HBM-resident lumen_set) around.
@@ -55,7 +56,9 @@ struct Plaintext { // *rlwe.Plaintext: one polynomial, NTT domain, [level+1][N]
 };
 
 class ServerBFV;
+class ClientBFV;
 class RingSwitchServer;
+struct Proof;
 
 // rlwe.MetaData of the ciphertexts of one slice (they are produced by the same calls, so they share it):
 // what the Go shim's download() has to write into every rlwe.Ciphertext it materialises (SURVEY 8b,
@@ -182,6 +185,32 @@ class ServerBFV {
     void RewindEncryptorForTest(uint64_t next = 0) { enc_->next = next; }
 };
 
+// fhe.ClientBFV (fhe/bfv.go:60-106): plaintext field + parameters + encoder / decryptor under the secret key, for a
+// client that owns a GPU: a context with lumen_encoder_set and lumen_load_secret_key.  Key GENERATION is not part of
+// the mirror: the caller hands in sk ([L][N] or [L+K][N], NTT domain, what lumen_load_secret_key takes).
+class ClientBFV {
+  public:
+    // NewClientBFV(plaintextField, paramsFHE, sk)
+    ClientBFV(core::PrimeField *plaintextField, const Parameters &params, const std::vector<uint64_t> &sk, int device = 0);
+    ~ClientBFV();
+    ClientBFV(const ClientBFV &) = delete;
+    core::PrimeField *Field() { return ptField_; }
+    const Parameters &GetParameters() const { return params_; }
+    lumen_ctx *Context() const { return ctx_; }
+    int Device() const { return device_; }
+    void check(int rc, const char *what) const; // throws std::runtime_error with lumen_last_error
+    // ClientBFV.CopyNew (bfv.go:96-98): the same key and tables, its own streams and scratch (lumen_ctx_clone); must
+    // not outlive the client it was made from
+    std::unique_ptr<ClientBFV> CopyNew();
+
+  private:
+    ClientBFV(ClientBFV &src, lumen_ctx *clone);
+    core::PrimeField *ptField_;
+    Parameters params_;
+    lumen_ctx *ctx_ = nullptr;
+    int device_ = 0;
+};
+
 // W = 2^k ServerBFVs behind one lumen_group (include/lumenos_hip.h): the ranks of ONE server process that owns
 // several GPUs -- the reference's server is a single process (cmd/server/main.go:187-266).  ranks[r] is rank r;
 // they hold the same parameters, public key and evaluation keys (one NewBackendBFV per GPU, or CopyNew()s of one
@@ -291,6 +320,14 @@ struct EncryptedProof { // fhe/ligero.go:185-192
     // the backend's parameters (a ring-switched proof is read by the client's small-ring parameters, not here).
     // `meta`: the MetaData the ciphertexts carry (what SetCiphertextFormat frames them with).
     static EncryptedProof UnmarshalBinary(const uint8_t *data, size_t len, ServerBFV &backend, const MetaData &meta);
+    // the same on the client's context (cmd/client/main.go:181-184): what Decrypt then reads
+    static EncryptedProof UnmarshalBinary(const uint8_t *data, size_t len, ClientBFV &client, const MetaData &meta);
+    // EncryptedProof.Decrypt (ligero.go:381-502) on the client's device, under the reference's spans "Decrypt queried
+    // columns" (lumen_decrypt of every opened column, `rows` values each) and "Decrypt row inner products" (MatR and
+    // MatZ, one value per ciphertext: decodeSingleElement).  The opened ciphertexts stay on the device and move into
+    // the proof (ColumnInstance.Ct), so this EncryptedProof gives them up.  A ring-switched proof is refused with a
+    // message (the reference's client skips Verify for it, cmd/client/main.go:210-212).
+    Proof Decrypt(ClientBFV &client, core::Span *ctx);
 };
 
 class LigeroCommitter;
@@ -334,15 +371,37 @@ class LigeroCommitter { // fhe/ligero.go:27-29, 40-63
                                                          core::Span *ctx) const;
 };
 
-// fhe.Proof (ligero.go:372-379) as LigeroProveReference fills it: the plain prover's output
+// fhe.Proof (ligero.go:372-379): the plain prover's output (LigeroProveReference) and what EncryptedProof::Decrypt
+// returns
 struct Proof {
     LigeroMetadata Metadata;
     std::vector<uint8_t> Root;
     std::vector<uint64_t> MatR, MatZ;                  // one field element per column
-    std::vector<std::vector<uint64_t>> QueriedCols;     // `rows` values of every opened encoded column
+    std::vector<std::vector<uint64_t>> QueriedCols;     // `rows` values of every opened encoded column (ColumnInstance.Values)
     std::vector<std::vector<core::Digest>> MerklePaths;
-    std::vector<int> QueryIndices;
+    std::vector<int> QueryIndices;                      // LigeroProveReference only (not part of a proof)
+    // ColumnInstance.Ct of every opened column, in query order, resident on the client's device (Decrypt); empty for
+    // LigeroProveReference, whose leaves are plain columns
+    std::shared_ptr<Ciphertexts> QueriedCts;
+    // Proof.Verify (ligero.go:517-574): the reference's order and its error strings, thrown as std::runtime_error --
+    // sample r; core.Encode of MatR and MatZ; append the point; zPow; sample the query indices; the per-column loop
+    // (Merkle path, <Values, r>, <Values, b>) as ONE lumen_verify_columns over QueriedCts; InnerProduct(MatZ, a) == value.
+    // DEVIATION from the reference's signature: `client` is an extra argument.  There the loop reads the Values
+    // Decrypt left on the host and hashes Ct's bytes on the host; here the opened columns are hashed AND decrypted
+    // again inside the device check (their values never leave it), which needs the context that holds the secret key.
+    // QueriedCols (the host copy Decrypt made for ProveDecrypt) is not read.  Paths of another length than the tree's
+    // depth, or fewer paths than queries, are the Merkle failure of the first such query.
+    void Verify(core::Element point, core::Element value, core::PrimeField &field, core::Transcript &transcript,
+                ClientBFV &client) const;
 };
+// the error Proof.Verify's loop returns for one column's status word of lumen_verify_columns (ligero.go:556, 561, 565:
+// PATH before R before B); empty when the column passed
+std::string VerifyColumnError(uint32_t status, int queryColIdx);
+// core.Encode (core/code.go:3-23) of up to 512 rows of equal length at once, on the device: the rows are the lanes of
+// a plain context whose one modulus is T (the path LigeroProveReference drives, at the smallest ring degree the
+// library instantiates), one lumen_encode for all.  field: N() = len * rhoInv.  -> rows of len * rhoInv elements.
+std::vector<std::vector<core::Element>> EncodeRows(const std::vector<std::vector<core::Element>> &rows, int rhoInv,
+                                                   core::PrimeField &field, int device = 0);
 // LigeroCommitter.LigeroProveReference (ligero.go:799-953): the prover without encryption, on the device
 // through the same C ABI -- a context whose one modulus is T holds the matrix column by column
 // (lumen_plain_inner_products's header comment).  matrix: row-major [rows][cols].

@@ -1,0 +1,85 @@
+"""The client's sequence of cmd/client/main.go:181-221 through the C++ host mirror (fhe::ClientBFV,
+EncryptedProof::Decrypt, Proof::Verify over lumen_verify_columns).  CPU: what Verify derives from the transcript before
+it touches the device, and its error strings, against the oracle's transcript and Python integers.  GPU:
+tests/cpp/test_verify_host.cpp proves at a random z != 1, verifies, and tampers with the marshaled bytes."""
+import os
+import random
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+BIN = os.path.join(ROOT, "tests", "cpp", "test_verify_host")
+T = 144115188075593729  # fhe/ligero_test.go:16
+
+
+def build_binary():
+    """built like tests/test_poly_eval_host.py builds its twin"""
+    from lumenos_amd import _build
+    from oracle import loader
+    host = _build.build_host()
+    loader.build()
+    src = os.path.join(ROOT, "tests", "cpp", "test_verify_host.cpp")
+    deps = [src, host, os.path.join(ROOT, "oracle", "liblumen_oracle.so")]
+    if os.path.exists(BIN) and all(os.path.getmtime(d) < os.path.getmtime(BIN) for d in deps):
+        return BIN
+    hd, cd, od = os.path.dirname(host), os.path.dirname(_build.LIB), os.path.join(ROOT, "oracle")
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", src, "-o", BIN,
+                           "-L" + hd, "-llumenos_host", "-L" + cd, "-llumenos_hip", "-L" + od, "-llumen_oracle",
+                           f"-Wl,-rpath,{hd}:{cd}:{od}"])
+    return BIN
+
+
+@pytest.mark.parametrize("name,rows,cols,queries", [("demo", 2048, 1024, 309), ("test", 512, 16, 24), ("x", 7, 3, 5)])
+def test_what_verify_derives_from_the_transcript_matches_python(oracle, name, rows, cols, queries):
+    """ligero.go:522-552: r (raw words), the point appended, a, b = powers of z^cols, the query indices -- and the three
+    error strings in the reference's order of precedence"""
+    from lumenos_amd.hip import verify_first_error
+    from oracle.loader import Transcript
+    rho = 2
+    z = random.Random(rows * 31 + cols).randrange(2, T - 1)
+    out = subprocess.run([build_binary(), "host", name, str(rows), str(cols), str(rho), str(queries), str(z)],
+                         capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
+    got = {"r": {}, "a": {}, "b": {}, "query": {}, "message": {}}
+    w = None
+    for line in out.stdout.splitlines():
+        kind, _, rest = line.partition(" ")
+        if kind == "w":
+            w = int(rest)
+        elif kind == "message":
+            s, _, text = rest.partition(" ")
+            got["message"][int(s)] = text
+        else:
+            i, v = rest.split()
+            got[kind][int(i)] = int(v)
+    t = Transcript(oracle, name)
+    r = [t.sample_u64("r") for _ in range(rows)]
+    t.append("point", z.to_bytes(8, "little"))
+    idx = [t.sample_u64("query") % (cols * rho) for _ in range(queries)]
+    assert [got["r"][i] for i in range(rows)] == r
+    assert [got["query"][k] for k in range(queries)] == idx
+    assert w == pow(z, cols, T)
+    assert got["a"] == {j: pow(z, j, T) for j in set(range(min(4, cols))) | {cols - 1}}
+    assert got["b"] == {i: pow(w, i, T) for i in set(range(min(4, rows))) | {rows - 1}}
+    for s in range(8):
+        assert got["message"][s] == (verify_first_error([s], [41]) or ""), s
+    assert got["message"][1 | 2 | 4].startswith("failed to verify merkle path") and got["message"][6].startswith("well-formedness R")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("shape", [(12, 2048, 1024, 10), (14, 16384, 4096, 12)])
+def test_client_unmarshals_decrypts_and_verifies_end_to_end(shape):
+    """TestLigeroE2E's shape (2048 x 1024, LogN 12) and the headline one (16384 x 4096, LogN 14): the honest proof
+    verifies under the reference's four client spans; each tampering throws the reference's string for the reference's
+    column."""
+    res = subprocess.run([build_binary(), "e2e"] + [str(x) for x in shape], capture_output=True, text=True, timeout=1500)
+    print(res.stdout)  # the span times, shown with -s
+    assert res.returncode == 0, res.stdout[-3000:] + res.stderr[-3000:]
+    for span in ("Decrypt queried columns (", "Decrypt row inner products (", "Decrypt proof (", "Verify proof ("):
+        assert span in res.stdout, span
+    for what in ("honest proof", "EncodeRows = lo_plain_encode", "ClientBFV::CopyNew verifies", "a limb byte of opened column k",
+                 "a byte of query k's Merkle path", "a byte of the root", "a limb byte of one MatR ciphertext",
+                 "a limb byte of one MatZ ciphertext", "value + 1", "a verifier transcript under another name",
+                 "a framing byte is refused", "client verify"):
+        assert "PASS " + what in res.stdout, what
