@@ -35,7 +35,7 @@ struct lm_prof_entry {
 };
 
 struct lm_galois_key {
-    u64 *d_key = nullptr;   // [L+K][beta][2][N] (lm_keyswitch.hip, ks_key_at), Montgomery form
+    u64 *d_key = nullptr;   // [L+K][beta][2][N] (lm_ks_dev.h, ks_key_at), Montgomery form
     uint32_t *d_index = nullptr; // automorphism gather table, N entries: out[i] = in[index[i]]
     uint32_t *d_inv_index = nullptr; // its inverse: out[inv_index[p]] = in[p]
 };
@@ -86,7 +86,7 @@ struct lm_tuning {
     // two transform kernels of a key switch (lm_keyswitch.hip); 1 .. 31
     uint32_t modup_tgroup = 3, moddown_tgroup = 1; // (round 6, limb-major streams: extension 3 / 4 = 1.7732 / 1.7760 s per step at 2^14, 0.7868 / 0.7915 at 2^13; ModDown 1 / 2 / 3 = 1.7691 / 1.7726 / 1.7711 s per step; 2 / 4 / 6 / 12 = 1.8140 / 1.8258 / 1.8246 / 1.8371 on another box)
     // LUMEN_KS_PLACEMENT: candidate blocks per key-switch scratch buffer among which the first key switch of a context
-    // picks by measurement (lm_keyswitch.hip, select_placement); 0 or 1 = take what hipMalloc returns
+    // picks by measurement (lm_ks_scratch.hip, lm_placement.h); 0 or 1 = take what hipMalloc returns
     uint32_t ks_placement = 6;
     // lumen_test_allow_shared_device_rccl (tests only; not reachable through lumen_ctx_set_tuning or the environment):
     // LUMEN_TRANSPORT_RCCL accepts ranks that share a device, for the test double tests/cpp/fake_rccl.cpp

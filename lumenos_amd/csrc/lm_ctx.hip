@@ -43,7 +43,7 @@ void *lm_scratch(lumen_ctx *ctx, const char *name, size_t bytes) {
 }
 
 // puts a block the caller allocated (hipMalloc) under a scratch name; whatever was there is freed after the context's
-// streams have drained.  For buffers whose PLACEMENT was chosen (lm_keyswitch.hip, select_placement).
+// streams have drained.  For buffers whose PLACEMENT was chosen (lm_ks_scratch.hip, get_scratch).
 void lm_scratch_adopt(lumen_ctx *ctx, const char *name, void *p, size_t bytes) {
     auto &e = ctx->scratch[name];
     if (e.first && e.first != p) {

@@ -24,48 +24,20 @@
 // both kernels are dealt by XCD-aware work lists so that the targets of one digit
 // share an L2; the gadget product keeps key material in Montgomery form and
 // accumulates the beta products of a coefficient in 128 bits, one reduction per output.
+//
+// This file is the rotation: its six kernels, the per-context tables and work lists, rotate_accumulate and the InnerSum
+// entry points.  The other subjects of the key switch live beside it: where the scratch buffers sit in HBM in
+// lm_ks_scratch.hip (mechanism) and lm_placement.h (policy), Galois-key loading in lm_ks_key.hip, the ciphertext x
+// plaintext product (step 0, MulNew) in lm_mulplain.hip, the stream layouts and mul128 in lm_ks_dev.h, and what these
+// units share on the host in lm_ks_host.h.
 #include <cstdlib>
 #include <cstring>
 
-#include "lm_ks_dev.h"
-
-// Layout of the key switch's three big streams, in limbs of N words: LIMB-MAJOR (round 6).  The gadget product walks
-// ONE modulus t at a time over every (column, digit); with the modulus outermost everything one of its workgroups
-// touches -- 4 columns x beta digits of `ext`, the 2 beta key limbs, its 8 output limbs -- sits in a few MB of
-// contiguous addresses (a handful of 2 MB translations), and the chip as a whole streams one 48 MB region of `ext`
-// and one 16 MB region of `u` at a time.  Rounds 1-5 kept the column outermost ([b][d][t], [b][w][t], [d][w][t]:
-// 36 + 8 blocks 1.75 MB apart per workgroup): the gadget product took 5-8 % longer and the extension kernel, which
-// writes `ext`, 3.7 % (profiles/r06_exp_ks_layout.txt; same residues).
-// limb t of digit d of column b in the extended-digit buffer: [L+K][B][beta]
-__host__ __device__ __forceinline__ size_t ks_ext_at(uint32_t b, uint32_t d, uint32_t t, uint32_t B, uint32_t beta) {
-    return ((size_t)t * B + b) * beta + d;
-}
-// limb t of polynomial pw = 2 b + w of the gadget product's output u: the Q limbs [L][2B], behind them the limbs
-// modulo P as [2B][K] -- the K limbs of one polynomial stay adjacent (their inverse transform, the packing pass and
-// ModDown's lift read them as a pair)
-__host__ __device__ __forceinline__ size_t ks_u_at(uint32_t pw, uint32_t t, uint32_t B, uint32_t L, uint32_t K) {
-    return t < L ? (size_t)t * 2 * B + pw : (size_t)L * 2 * B + (size_t)pw * K + (t - L);
-}
-// limb t of polynomial w of digit d of a switching key as the gadget product reads it: [L+K][beta][2]
-// (lumen_load_galois_key takes the caller's [beta][2][L+K] and k_key_prepare permutes)
-__host__ __device__ __forceinline__ size_t ks_key_at(uint32_t d, uint32_t w, uint32_t t, uint32_t beta) {
-    return ((size_t)t * beta + d) * 2 + w;
-}
+#include "lm_ks_host.h"
 
 // columns processed together (scratch ~ 172 limbs per column): 64 by default, LUMEN_KS_BATCH at context
 // creation (lm_tuning)
 static uint32_t ks_batch(const lumen_ctx *ctx) { return ctx->tune.ks_batch; }
-
-// 64 x 64 -> 128-bit product as four 32x32+64 multiply-adds (the compiler's __int128 multiply goes
-// through v_mul_lo/hi_u32, twice as slow each)
-__device__ __forceinline__ void mul128(u64 a, u64 b, u64 &lo, u64 &hi) {
-    const u32 a0 = (u32)a, a1 = (u32)(a >> 32), b0 = (u32)b, b1 = (u32)(b >> 32);
-    const u64 p0 = (u64)a0 * b0;
-    const u64 p1 = lm_keep((u64)a0 * b1 + (p0 >> 32));
-    const u64 p2 = lm_keep((u64)a1 * b0 + (u32)p1);
-    hi = (u64)a1 * b1 + (p1 >> 32) + (p2 >> 32);
-    lo = (p2 << 32) | (u32)p0;
-}
 
 // v = uint64(float64(y0)/float64(m0) + float64(y1)/float64(m1))  ([LATTIGO-RECALL] reconstructRNS).
 // The double expression is within 2^-49 of S = A / M, A = y0*m1 + y1*m0, M = m0*m1, and S < 2: unless
@@ -210,37 +182,6 @@ __global__ LM_GEOM_BOUNDS(lm_geom_lds(LOGN)) void k_intt_pack(const u64 *__restr
         uint32_t tid1 = tid; // nothing derived from the lane index is carried over from the first limb
         asm volatile("" : "+v"(tid1));
         lm_ntt_inverse<LOGN>(sm, tw_all + (size_t)l1 * N, q1, tid1, ld, st);
-    }
-}
-
-// ---- step 0: MulNew(ct, pt): out = ct (.) (pt * T)
-// The plaintext arrives once per call as raw residues; k_pt_prepare turns it into the multiplier in
-// Montgomery form, ptM = pt * T * 2^64 mod q_l (one Montgomery product with c_l = T * 2^128 mod q_l),
-// so that the product over the matrix is one 64x64 multiplication and one Montgomery reduction per
-// residue, canonical result.
-struct pt_consts_t {
-    u64 c[LM_MAX_LIMBS]; // T * 2^128 mod q_l
-};
-__global__ void k_pt_prepare(const u64 *__restrict__ pt, u64 *__restrict__ ptM, uint32_t logN, uint32_t nl,
-                             lm_mods mods, pt_consts_t pc) {
-    const size_t total = (size_t)nl << logN;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-        const uint32_t limb = (uint32_t)(i >> logN);
-        u64 lo, hi;
-        mul128(pt[i], pc.c[limb], lo, hi);
-        ptM[i] = lm_mont_reduce(lo, hi, mods.m[limb].q, mods.m[limb].qneg);
-    }
-}
-__global__ void k_mul_plain(const u64 *__restrict__ ct, u64 *__restrict__ out, const u64 *__restrict__ ptM,
-                            size_t words, uint32_t logN, uint32_t nl, lm_mods mods) {
-    const size_t stride = (size_t)gridDim.x * blockDim.x;
-    const size_t N = (size_t)1 << logN;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < words; i += stride) {
-        const uint32_t limb = (uint32_t)((i >> logN) % nl);
-        const size_t k = i & (N - 1);
-        u64 lo, hi;
-        mul128(ct[i], ptM[(size_t)limb * N + k], lo, hi);
-        out[i] = lm_mont_reduce(lo, hi, mods.m[limb].q, mods.m[limb].qneg);
     }
 }
 
@@ -601,24 +542,6 @@ int acc_canon(lumen_ctx *ctx, u64 *acc, size_t words, uint32_t L) {
     return 0;
 }
 
-struct KsTables {
-    bx_t *d_bx = nullptr;    // [beta][L+K]
-    bx_t *d_bxp = nullptr;   // [L]  (P -> q_t)
-    tw_t *d_pinv = nullptr;  // [L]  P^-1 mod q_t
-    uint32_t beta = 0;
-    lm_ninv_t yscale; // per modulus: N^-1 * (M/m)^-1 mod m of the source group the modulus sits in
-    std::vector<uint16_t> pairs; // (digit | target << 8) of every extension the key switch needs, target-major
-    std::map<uint32_t, uint32_t *> d_work; // per batch size: the workgroup order of the extension kernel
-    std::map<uint32_t, uint32_t *> d_work_down; // ... and of the ModDown kernel
-    ~KsTables() {
-        for (auto &kv : d_work) hipFree(kv.second);
-        for (auto &kv : d_work_down) hipFree(kv.second);
-        hipFree(d_bx);
-        hipFree(d_bxp);
-        hipFree(d_pinv);
-    }
-};
-
 bx_t make_bx(const uint64_t *src, uint32_t ns, uint64_t t) {
     bx_t c;
     memset(&c, 0, sizeof(c));
@@ -637,6 +560,8 @@ uint64_t hat_inv(const uint64_t *src, uint32_t ns, uint32_t a) {
         if (b != a) h = h_mulmod(h, src[b] % src[a], src[a]);
     return h_invmod(h, src[a]);
 }
+
+} // namespace
 
 int get_tables(lumen_ctx *ctx, KsTables **out) {
     LM_SHARED_LOCK(ctx);
@@ -695,8 +620,6 @@ int get_tables(lumen_ctx *ctx, KsTables **out) {
     return 0;
 }
 
-} // namespace
-
 int lm_ks_tables_view(lumen_ctx *ctx, lm_ks_view *out) {
     KsTables *tb = nullptr;
     if (int rc = get_tables(ctx, &tb)) return rc;
@@ -715,10 +638,6 @@ int lm_launch_pack_v(lumen_ctx *ctx, u64 *y, size_t poly_stride, uint32_t npoly,
 }
 
 namespace {
-
-struct KsScratch {
-    u64 *coef, *ext, *u, *acc2;
-};
 
 // Tail of both work-list builders below.  Workgroup k of a launch runs on XCD k % 8, so the eight per-XCD lists are
 // interleaved (lists of unequal length -- B not a multiple of 8 -- are drained in turn); the device copy is cached.
@@ -864,6 +783,8 @@ static dim3 ks_mac_grid(const lumen_ctx *ctx, uint32_t B) {
     return dim3(((ctx->N / LM_MAC_VEC + 255) / 256) * (ctx->L + ctx->K) * ((B + LM_MAC_COLS - 1) / LM_MAC_COLS));
 }
 
+} // namespace
+
 // acc, acc_out: [B][2][L][N] at top level; acc_out = acc + Rot_galEl(acc) for every column
 int rotate_accumulate(lumen_ctx *ctx, const u64 *acc, u64 *acc_out, uint32_t B, const lm_galois_key &gk,
                       KsTables *tb, const KsScratch &s) {
@@ -935,154 +856,7 @@ int rotate_accumulate(lumen_ctx *ctx, const u64 *acc, u64 *acc_out, uint32_t B, 
     }
 }
 
-// ---- the key switch's scratch buffers, and WHERE in HBM they sit.
-// Measured in round 6 (profiles/r06_exp_ks_mac_placement.txt): the time of the gadget product is a deterministic
-// function of the physical placement of its streams -- two processes that draw the same addresses reproduce each
-// other's times to 0.2 %; exchanging only the block `u` is written to, or only the block `ext` is read from, for
-// another allocation of the same size moves the kernel by up to 16 % / 7 %; the relative offset of the two inside
-// one allocation (4 KB .. 64 MB) moves it by nothing, and one stream alone reads / writes every block at the same rate.
-// It is the pairing of a read stream's and a write stream's 2 MB pages (high physical address bits: DRAM rank /
-// bank-group assignment, invisible and uncontrollable from user space) -- which is why `ks_mac` was constant inside
-// a process and 341 .. 381 ms per step between processes.  So the first key switch of a context allocates
-// LUMEN_KS_PLACEMENT (6) candidates per buffer and keeps, buffer by buffer, the one under which two rotations of a
-// whole batch run fastest (coordinate descent in the order the sensitivities were measured: u, ext, then the
-// accumulator's twin and the coefficient buffer); the others are freed.  One-off cost at the headline size: about
-// 0.3 s and 14 GB of transient device memory (never more than half of what is free).  Results do not depend on the choice
-// (same kernels, same residues).
-// group_acc / group_acc_bytes: the caller's accumulator block for a GROUP of batches (lumen_matrix_inner_sum: every batch works in
-// its own slice of it) is placed by the same measurement -- in situ the rotations alternate between reading a slice of it
-// and reading the twin, and with only the four buffers above chosen the gadget product still came out in two modes from
-// process to process (331 / 349 ms per step).
-int get_scratch(lumen_ctx *ctx, uint32_t B, KsTables *tb, KsScratch *s, int lane = 0, u64 **group_acc = nullptr,
-                size_t group_acc_bytes = 0) {
-    const size_t N = ctx->N, L = ctx->L, LK = ctx->L + ctx->K, beta = tb->beta;
-    const char *names[2][5] = {{"ks_coef", "ks_ext", "ks_u", "ks_acc2", "ks_acc"}, {"ks_coef_b", "ks_ext_b", "ks_u_b", "ks_acc2_b", "ks_acc"}};
-    const int NB = group_acc ? 5 : 4;
-    const size_t bytes[5] = {(size_t)B * L * N * 8, (size_t)B * beta * LK * N * 8, (size_t)B * 2 * LK * N * 8, (size_t)B * 2 * L * N * 8,
-                             std::max(group_acc_bytes, (size_t)B * 2 * L * N * 8)};
-    u64 *dummy = nullptr;
-    u64 **slot[5] = {&s->coef, &s->ext, &s->u, &s->acc2, group_acc ? group_acc : &dummy};
-    bool have = true;
-    for (int c = 0; c < NB; c++) {
-        auto it = ctx->scratch.find(names[lane][c]);
-        have = have && it != ctx->scratch.end() && it->second.first && it->second.second >= bytes[c];
-    }
-    lm_galois_key gk;
-    {
-        LM_SHARED_LOCK(ctx);
-        if (!ctx->gkeys.empty()) gk = ctx->gkeys.begin()->second;
-    }
-    const uint32_t Kc = ctx->tune.ks_placement;
-    auto plain = [&]() -> int {
-        bool ok = true;
-        for (int c = 0; c < NB; c++) ok = (*slot[c] = (u64 *)lm_scratch(ctx, names[lane][c], bytes[c])) != nullptr && ok;
-        return ok ? 0 : 1;
-    };
-    // small buffers live in the caches, and without a key no rotation can be timed: plain allocation
-    if (have || Kc < 2 || bytes[1] < ((size_t)64 << 20) || !gk.d_key) return plain();
-    // what is already there and large enough stays (a buffer shared with the other lane, a context whose batch size grew):
-    // only the missing buffers are drawn
-    std::vector<void *> cand[5];
-    bool fixed[5] = {false, false, false, false, false};
-    for (int c = 0; c < NB; c++) {
-        auto it = ctx->scratch.find(names[lane][c]);
-        if (it != ctx->scratch.end() && it->second.first && it->second.second >= bytes[c]) cand[c].push_back(it->second.first), fixed[c] = true;
-    }
-    void *probe_acc = nullptr;
-    auto free_all = [&] {
-        for (int c = 0; c < NB; c++)
-            if (!fixed[c])
-                for (void *p : cand[c]) hipFree(p);
-        hipFree(probe_acc);
-        (void)hipGetLastError();
-    };
-    size_t free_b = 0, total_b = 0, drawn = 0;
-    (void)hipMemGetInfo(&free_b, &total_b);
-    if (!group_acc && hipMalloc(&probe_acc, bytes[3]) != hipSuccess) probe_acc = nullptr;
-    for (uint32_t k = 0; k < Kc; k++) // round-robin over the buffers: the candidates of one buffer are spread out
-        for (int c = 0; c < NB; c++) {
-            if (fixed[c] || (c == 4 && k >= 4)) continue;                 // (the group accumulator is the big one: four draws)
-            if (!cand[c].empty() && drawn + bytes[c] > free_b / 2) continue; // never more than half of what is free
-            void *p = nullptr;
-            if (hipMalloc(&p, bytes[c]) == hipSuccess) cand[c].push_back(p), drawn += bytes[c];
-        }
-    (void)hipGetLastError();
-    bool complete = group_acc || probe_acc;
-    for (int c = 0; c < NB; c++) complete = complete && !cand[c].empty();
-    if (!complete) { // memory is short: no choice to make
-        free_all();
-        return plain();
-    }
-    const bool prof = ctx->prof;
-    ctx->prof = false; // the rotations below are not part of anybody's measurement
-    hipEvent_t e0 = lm_ev_get(ctx), e1 = lm_ev_get(ctx);
-    size_t pick[5] = {0, 0, 0, 0, 0};
-    int rc = 0;
-    // two rotations of a batch (the accumulator ping-pongs with its twin): one pair untimed, two timed -- in the first
-    // and in the last batch slice of the group accumulator
-    auto eval = [&](float *ms) -> int {
-        KsScratch t;
-        t.coef = (u64 *)cand[0][pick[0]], t.ext = (u64 *)cand[1][pick[1]], t.u = (u64 *)cand[2][pick[2]], t.acc2 = (u64 *)cand[3][pick[3]];
-        u64 *a0 = group_acc ? (u64 *)cand[4][pick[4]] : (u64 *)probe_acc;
-        u64 *a1 = group_acc ? a0 + (bytes[4] - bytes[3]) / 8 : a0;
-        for (int r = 0; r < 3; r++) {
-            if (r == 1) LM_HIP(ctx, hipEventRecord(e0, ctx->stream));
-            u64 *a = r == 2 ? a1 : a0;
-            if (int e = rotate_accumulate(ctx, a, t.acc2, B, gk, tb, t)) return e;
-            if (int e = rotate_accumulate(ctx, t.acc2, a, B, gk, tb, t)) return e;
-        }
-        LM_HIP(ctx, hipEventRecord(e1, ctx->stream));
-        LM_HIP(ctx, hipEventSynchronize(e1));
-        LM_HIP(ctx, hipEventElapsedTime(ms, e0, e1));
-        return 0;
-    };
-    float first = 0, best_all = 0;
-    static const int order[5] = {2, 1, 4, 3, 0}; // u, ext, the group accumulator, its twin, coef
-    bool measured = false;
-    for (int oi = 0; oi < 5 && !rc; oi++) {
-        const int c = order[oi];
-        if (c >= NB) continue;
-        float best = 0;
-        size_t arg = pick[c];
-        for (size_t k = 0; k < cand[c].size() && !rc; k++) {
-            if (measured && k == pick[c]) continue; // timed already: it is the configuration `best_all` belongs to
-            const size_t keep = pick[c];
-            pick[c] = k;
-            float ms = 0;
-            rc = eval(&ms);
-            pick[c] = keep;
-            if (first == 0) first = ms;
-            if (best == 0 || ms < best) best = ms, arg = k;
-        }
-        if (best == 0 || (measured && best_all <= best)) arg = pick[c]; // nothing beat the configuration already measured
-        else best_all = best;
-        if (best != 0) measured = true;
-        pick[c] = arg;
-    }
-    ctx->ev_pool.push_back(e0);
-    ctx->ev_pool.push_back(e1);
-    ctx->prof = prof;
-    if (rc) {
-        lm_sync_all(ctx);
-        free_all();
-        return rc;
-    }
-    if (ctx->tune.debug)
-        fprintf(stderr, "[lumenos_hip] key-switch scratch placement (lane %d, %u columns): %zu / %zu / %zu candidates for u / ext / the group "
-                        "accumulator, 4 rotations of the first draw %.3f ms, of the chosen blocks %.3f ms\n", lane, B, cand[2].size(),
-                cand[1].size(), NB == 5 ? cand[4].size() : (size_t)0, first, best_all);
-    LM_HIP(ctx, hipStreamSynchronize(ctx->stream)); // nothing may still run on a block that is about to be freed
-    for (int c = 0; c < NB; c++) {
-        void *chosen = cand[c][pick[c]];
-        if (!fixed[c]) {
-            cand[c][pick[c]] = nullptr; // hipFree(nullptr) is a no-op
-            lm_scratch_adopt(ctx, names[lane][c], chosen, bytes[c]);
-        }
-        *slot[c] = (u64 *)chosen;
-    }
-    free_all();
-    return 0;
-}
+namespace {
 
 int inner_sum_batch(lumen_ctx *ctx, u64 *acc, uint32_t B, uint32_t n, KsTables *tb, const KsScratch &s) {
     uint64_t gal[64];
@@ -1103,47 +877,6 @@ int inner_sum_batch(lumen_ctx *ctx, u64 *acc, uint32_t B, uint32_t n, KsTables *
     if (cnt & 1)
         LM_HIP(ctx, hipMemcpyAsync(acc, s.acc2, (size_t)B * 2 * ctx->L * ctx->N * 8, hipMemcpyDeviceToDevice,
                                    ctx->stream));
-    return 0;
-}
-
-int upload_ptT(lumen_ctx *ctx, const uint64_t *pt, uint32_t nl, u64 **out) {
-    // pt * T in Montgomery form: the multiplier MulNew(ct, pt) applies
-    // ([LATTIGO-RECALL] bgv tensorStandard, ciphertext x plaintext branch).  The host only checks the
-    // range and stages the residues in pinned memory; the products are formed on the device, and the
-    // call does not wait for the copy.
-    const uint32_t N = ctx->N;
-    const size_t words = (size_t)nl * N;
-    u64 *h = (u64 *)lm_stage(ctx, words * sizeof(u64));
-    u64 *draw = (u64 *)lm_scratch(ctx, "pt_raw", words * sizeof(u64));
-    u64 *d = (u64 *)lm_scratch(ctx, "ptT", words * sizeof(u64));
-    if (!h || !draw || !d) return 1;
-    pt_consts_t pc;
-    memset(&pc, 0, sizeof(pc));
-    for (uint32_t l = 0; l < nl; l++) {
-        const uint64_t q = ctx->mod[l];
-        const uint64_t *src = pt + (size_t)l * N;
-        uint64_t bad = 0;
-        for (uint32_t k = 0; k < N; k++) bad |= (uint64_t)(src[k] >= q);
-        if (bad) return lm_fail(ctx, "plaintext residue out of range at limb %u", l);
-        memcpy(h + (size_t)l * N, src, (size_t)N * sizeof(u64));
-        const uint64_t r = (uint64_t)((((u128)1) << 64) % q);
-        pc.c[l] = h_mulmod(ctx->T % q, h_mulmod(r, r, q), q);
-    }
-    LM_HIP(ctx, hipMemcpyAsync(draw, h, words * sizeof(u64), hipMemcpyHostToDevice, ctx->stream));
-    LM_HIP(ctx, hipEventRecord(ctx->ev_stage, ctx->stream));
-    hipLaunchKernelGGL(k_pt_prepare, dim3(256), dim3(256), 0, ctx->stream, draw, d, ctx->logN, nl, ctx->mods, pc);
-    LM_HIP(ctx, hipGetLastError());
-    *out = d;
-    return 0;
-}
-
-int launch_mul_plain(lumen_ctx *ctx, const u64 *ct, u64 *out, const u64 *ptT, size_t words, uint32_t nl,
-                     uint32_t ncts) {
-    lm_prof_scope ps(ctx, "mul_plain", ncts);
-    hipLaunchKernelGGL(k_mul_plain, dim3(4096), dim3(256), 0, ctx->stream, ct, out, ptT, words, ctx->logN, nl,
-                       ctx->mods);
-    LM_HIP(ctx, hipGetLastError());
-    ctx->mul_counter += ncts;
     return 0;
 }
 
@@ -1187,140 +920,6 @@ extern "C" int lumen_ks_mac_probe(lumen_ctx *ctx, uint32_t batch, const void *ex
     float ms = 0;
     LM_HIP(ctx, hipEventElapsedTime(&ms, ctx->tm0, ctx->tm1));
     *ms_per_launch = ms / (float)reps;
-    return 0;
-}
-
-extern "C" uint32_t lumen_inner_sum_galois_elements(const lumen_ctx *ctx, uint32_t n, uint64_t *gal_els) {
-    // InnerSum(ct, 1, n), n a power of two: rotations by 2^i; when n == N the
-    // column rotations span one slot row (N/2) and the rows are folded with the
-    // row-swap element 2N-1.  5 generates the column group.
-    if (!ctx || !gal_els || n == 0 || (n & (n - 1))) return 0;
-    const uint64_t two_n = 2ull * ctx->N;
-    const uint32_t span = n == ctx->N ? n >> 1 : n;
-    uint32_t cnt = 0;
-    uint64_t g = 5; // 5^(2^i)
-    for (uint32_t r = 1; r < span; r <<= 1) {
-        gal_els[cnt++] = g;
-        g = (g * g) & (two_n - 1);
-    }
-    if (n == ctx->N) gal_els[cnt++] = two_n - 1;
-    return cnt;
-}
-
-// key words -> the form the gadget product multiplies with, on the device: dst = src * fac[limb] mod q (canonical).
-// A residue >= q is reported through `bad` (the smallest offending row [digit][b|a][limb]).
-__global__ __launch_bounds__(256) void k_key_prepare(const u64 *__restrict__ src, u64 *__restrict__ dst, uint32_t logN, uint32_t LK,
-                                                     size_t words, lm_mods mods, lm_ninv_t fac, uint32_t *__restrict__ bad) {
-    const uint32_t beta = (uint32_t)((words >> logN) / (2 * LK));
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < words; i += (size_t)gridDim.x * blockDim.x) {
-        const uint32_t row = (uint32_t)(i >> logN), t = row % LK; // row = (d * 2 + w) * LK + t: the caller's order
-        const u64 q = mods.m[t].q, x = src[i];
-        if (x >= q) atomicMin(bad, row);
-        const size_t o = (ks_key_at(row / (2 * LK), (row / LK) & 1, t, beta) << logN) + (i & (((size_t)1 << logN) - 1));
-        dst[o] = lm_shoup_cs(x, fac.t[t], q, 0 - q);
-    }
-}
-
-int lm_h2d(lumen_ctx *ctx, void *dev, const void *host, size_t bytes);
-
-extern "C" int lumen_load_galois_key_ex(lumen_ctx *ctx, uint64_t gal_el, const uint64_t *evk, uint32_t flags) {
-    LM_CHECK(nullptr, ctx && evk, "lumen_load_galois_key: NULL argument");
-    LM_ENTER(ctx);
-    const uint32_t N = ctx->N, L = ctx->L, K = ctx->K, LK = L + K;
-    LM_CHECK(ctx, K >= 1, "parameters have no special primes: key switching unavailable");
-    LM_CHECK(ctx, (gal_el & 1) && gal_el < 2ull * N, "Galois element %llu is not an odd residue mod 2N",
-             (unsigned long long)gal_el);
-    LM_CHECK(ctx, !(flags & ~(uint32_t)LUMEN_KEY_MONTGOMERY), "lumen_load_galois_key_ex: unknown flags 0x%x", flags);
-    const uint32_t beta = (L + K - 1) / K;
-    const size_t words = (size_t)beta * 2 * LK * N;
-    // To Montgomery form (one-off per key), on the device since round 4: the host loop of 128-bit divisions cost
-    // ~70 ms per key at the headline size, 14 keys per client.  The Q limbs also absorb P^-1 mod q_t: the
-    // gadget product then yields u * P^-1 directly and ModDown is u' - lift * P^-1, one multiplication
-    // on the unreduced lift (exact: (sum x*k) * P^-1 == sum x * (k * P^-1) mod q_t).  A key that already is in
-    // Lattigo's Montgomery form (x * 2^64 mod q: what GadgetCiphertext holds) only takes the P^-1 factor.
-    lm_ninv_t fac;
-    for (uint32_t t = 0; t < LM_MAX_LIMBS; t++) fac.t[t] = h_tw(1, ctx->mod[0] ? ctx->mod[0] : 3);
-    for (uint32_t t = 0; t < LK; t++) {
-        const uint64_t q = ctx->mod[t];
-        uint64_t r = (flags & LUMEN_KEY_MONTGOMERY) ? 1 : (uint64_t)((((u128)1) << 64) % q);
-        if (t < L) {
-            uint64_t P = 1;
-            for (uint32_t a = 0; a < K; a++) P = h_mulmod(P, ctx->mod[L + a] % q, q);
-            r = h_mulmod(r, h_invmod(P, q), q);
-        }
-        fac.t[t] = h_tw(r, q);
-    }
-    u64 *raw = (u64 *)lm_scratch(ctx, "key_raw", words * 8);
-    uint32_t *bad = (uint32_t *)lm_scratch(ctx, "key_bad", 4);
-    if (!raw || !bad) return 1;
-    LM_HIP(ctx, hipMemsetAsync(bad, 0xFF, 4, ctx->stream));
-    if (int rc = lm_h2d(ctx, raw, evk, words * 8)) return rc; // returns when evk may be reused
-    u64 *d_new = nullptr;
-    LM_HIP(ctx, hipMalloc((void **)&d_new, words * 8));
-    hipLaunchKernelGGL(k_key_prepare, dim3(2048), dim3(256), 0, ctx->stream, raw, d_new, ctx->logN, LK, words, ctx->mods, fac, bad);
-    uint32_t first_bad = 0;
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(&first_bad, bad, 4, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess || first_bad != 0xFFFFFFFFu) {
-        hipFree(d_new);
-        if (e != hipSuccess) return lm_fail(ctx, "key conversion failed: %s", hipGetErrorString(e));
-        return lm_fail(ctx, "key residue out of range (digit %u limb %u)", first_bad / (2 * LK), first_bad % LK);
-    }
-    std::vector<uint32_t> index(N);
-    const uint64_t mask = 2ull * N - 1;
-    for (uint32_t i = 0; i < N; i++) { // [LATTIGO-RECALL] ring.AutomorphismNTTIndex
-        const uint64_t t1 = 2ull * h_bitrev(i, (int)ctx->logN) + 1;
-        const uint64_t t2 = ((gal_el * t1 & mask) - 1) >> 1;
-        index[i] = h_bitrev((uint32_t)t2, (int)ctx->logN);
-    }
-    { // the staging copy of the host words has served (the stream is idle): do not keep a key-sized block per context
-        auto it = ctx->scratch.find("key_raw");
-        if (it != ctx->scratch.end()) {
-            hipFree(it->second.first);
-            ctx->scratch.erase(it);
-        }
-    }
-    LM_SHARED_LOCK(ctx);
-    lm_galois_key &gk = ctx->gkeys[gal_el];
-    if (gk.d_key) {
-        // a key loaded again.  The table is shared with every clone (group ranks on one GPU, CopyNew): its device
-        // pointer must stay what a clone may have read a moment ago, so the new words are copied INTO the old
-        // block (same size: it only depends on the parameters).  A clone computing at this very moment sees old or
-        // new words -- the documented "do not reconfigure under a running clone" -- but never freed memory.
-        lm_sync_all(ctx);
-        hipError_t ce = hipMemcpyAsync(gk.d_key, d_new, words * 8, hipMemcpyDeviceToDevice, ctx->stream);
-        if (ce == hipSuccess) ce = hipStreamSynchronize(ctx->stream);
-        hipFree(d_new);
-        LM_CHECK(ctx, ce == hipSuccess, "replacing Galois key %llu failed: %s", (unsigned long long)gal_el, hipGetErrorString(ce));
-    } else {
-        gk.d_key = d_new;
-    }
-    if (!gk.d_index) LM_HIP(ctx, hipMalloc((void **)&gk.d_index, (size_t)N * 4));
-    if (!gk.d_inv_index) LM_HIP(ctx, hipMalloc((void **)&gk.d_inv_index, (size_t)N * 4));
-    std::vector<uint32_t> inv_index(N);
-    for (uint32_t i = 0; i < N; i++) inv_index[index[i]] = i;
-    LM_HIP(ctx, hipMemcpy(gk.d_inv_index, inv_index.data(), (size_t)N * 4, hipMemcpyHostToDevice));
-    LM_HIP(ctx, hipMemcpy(gk.d_index, index.data(), (size_t)N * 4, hipMemcpyHostToDevice));
-    return 0;
-}
-
-extern "C" int lumen_load_galois_key(lumen_ctx *ctx, uint64_t gal_el, const uint64_t *evk) {
-    return lumen_load_galois_key_ex(ctx, gal_el, evk, 0);
-}
-
-extern "C" int lumen_mul_plain(lumen_ctx *ctx, const lumen_set *in, const uint64_t *pt, lumen_set **out) {
-    LM_CHECK(nullptr, ctx && in && pt && out, "lumen_mul_plain: NULL argument");
-    LM_ENTER(ctx);
-    LM_FULL_WIDTH(ctx, in, "lumen_mul_plain");
-    u64 *ptT = nullptr;
-    if (int rc = upload_ptT(ctx, pt, in->nl, &ptT)) return rc;
-    lumen_set *o = nullptr;
-    if (int rc = lumen_set_create(ctx, in->count, in->nl, &o)) return rc;
-    lm_set_guard og(ctx, o);
-    if (in->words)
-        if (int rc = launch_mul_plain(ctx, in->d, o->d, ptT, in->words, in->nl, in->count)) return rc;
-    *out = og.release();
     return 0;
 }
 

@@ -1,0 +1,41 @@
+// Host-side declarations shared by the units of the Galois key switch: the rotation (lm_keyswitch.hip), the placement of
+// its scratch buffers (lm_ks_scratch.hip) and the ciphertext x plaintext product that precedes it (lm_mulplain.hip).
+#pragma once
+#include "lm_ks_dev.h"
+
+// per-context constants of the key switch and its cached work lists (lm_keyswitch.hip)
+struct KsTables {
+    bx_t *d_bx = nullptr;    // [beta][L+K]
+    bx_t *d_bxp = nullptr;   // [L]  (P -> q_t)
+    tw_t *d_pinv = nullptr;  // [L]  P^-1 mod q_t
+    uint32_t beta = 0;
+    lm_ninv_t yscale; // per modulus: N^-1 * (M/m)^-1 mod m of the source group the modulus sits in
+    std::vector<uint16_t> pairs; // (digit | target << 8) of every extension the key switch needs, target-major
+    std::map<uint32_t, uint32_t *> d_work; // per batch size: the workgroup order of the extension kernel
+    std::map<uint32_t, uint32_t *> d_work_down; // ... and of the ModDown kernel
+    ~KsTables() {
+        for (auto &kv : d_work) hipFree(kv.second);
+        for (auto &kv : d_work_down) hipFree(kv.second);
+        hipFree(d_bx);
+        hipFree(d_bxp);
+        hipFree(d_pinv);
+    }
+};
+int get_tables(lumen_ctx *ctx, KsTables **out);
+
+// the scratch buffers of one lane
+struct KsScratch {
+    u64 *coef, *ext, *u, *acc2;
+};
+
+// acc, acc_out: [B][2][L][N] at top level; acc_out = acc + Rot_galEl(acc) for every column (lm_keyswitch.hip)
+int rotate_accumulate(lumen_ctx *ctx, const u64 *acc, u64 *acc_out, uint32_t B, const lm_galois_key &gk,
+                      KsTables *tb, const KsScratch &s);
+// the scratch of a batch of B columns on `lane`, placed by measurement at a context's first key switch (lm_ks_scratch.hip)
+int get_scratch(lumen_ctx *ctx, uint32_t B, KsTables *tb, KsScratch *s, int lane = 0, u64 **group_acc = nullptr,
+                size_t group_acc_bytes = 0);
+
+// step 0, MulNew(ct, pt) (lm_mulplain.hip): the plaintext as the device multiplier pt * T, and out = ct (.) it
+int upload_ptT(lumen_ctx *ctx, const uint64_t *pt, uint32_t nl, u64 **out);
+int launch_mul_plain(lumen_ctx *ctx, const u64 *ct, u64 *out, const u64 *ptT, size_t words, uint32_t nl,
+                     uint32_t ncts);

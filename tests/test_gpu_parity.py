@@ -700,7 +700,7 @@ def test_lazy_accumulator_at_the_modulus_bound(oracle, nq, npr):
 
 def test_scratch_placement_is_chosen_by_measurement_and_changes_no_residue(oracle):
     """Round 6: a context's first key switch draws LUMEN_KS_PLACEMENT candidates per scratch buffer and keeps the blocks
-    under which rotations run fastest (lm_keyswitch.hip, get_scratch).  The choice must not show in the results: the same
+    under which rotations run fastest (lm_ks_scratch.hip, get_scratch).  The choice must not show in the results: the same
     matrixInnerSumEval with the selection off, on, and on again after lumen_ctx_trim gives the oracle's residues; the
     chosen blocks are where lumen_ctx_scratch_info says, large enough, and stay put from one call to the next; the
     diagnostic probe runs on them."""
