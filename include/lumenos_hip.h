@@ -366,6 +366,48 @@ int lumen_load_ringswitch_key(lumen_ctx *ctx, uint32_t log_n_small, uint32_t bas
                               const uint64_t *key, size_t key_words);
 int lumen_ring_switch(lumen_ctx *ctx, const lumen_set *in, uint64_t *out);
 
+/* ---- the client's keys, generated on the device (cmd/client/main.go:74-81, fhe/ring_switch.go:16-57):
+ * kgen.GenKeyPairNew(), GenRelinearizationKeyNew(sk), GenGaloisKeysNew(galEls, sk), GenEvaluationKeyNew(sk, skNew).
+ * Every key is an array of gadget entries (b, a) = (NTT(e) - a*s_out + fac*s_in, a) over the whole basis QP, in exactly
+ * the layout its loader takes (lumen_load_public_key, lumen_load_galois_key[_ex], lumen_load_ringswitch_key), so a
+ * generated key goes straight into them -- or, with LUMEN_KEY_MONTGOMERY, into Lattigo's GadgetCiphertext as it is.
+ * SAMPLING CONTRACT.  Deterministic in (seed, key id, entry, limb, coefficient): keys generated one at a time, in one
+ * batched call or on another GPU are the same bytes.
+ *   keystream(I, s) = ChaCha20(key = seed, nonce = LE64(I) || LE32(s), counter = 0, 1, ...), the encryptor's;
+ *   sample index I(key_id, e) = key_id * 4096 + e, e = i * pw2 + j the gadget entry (RNS digit i, power-of-two digit j;
+ *     pw2 = 1 everywhere except the ring-switch key with K <= 1);
+ *   key ids: secret 0, public 1, relinearisation 2, ring switch 3, Galois key of element g: 0x10000 + g;
+ *   ternary secret s: stream 0 of I(0, 0), 32-bit word w -> ((w * 3) >> 32) - 1; the ring switch's small secret: the
+ *     first 2^log_n_small coefficients of stream 0 of I(3, 0);
+ *   Gaussian error of entry e: stream 1 of I(key_id, e), the encryptor's CDT rule, one N-coefficient sample per entry
+ *     extended to every limb;
+ *   uniform a of limb m (Q limbs, then P limbs) of entry e: stream 16 + m of I(key_id, e) read as little-endian 64-bit
+ *     words; attempt t = 0, 1, ... for coefficient k is word number t * N + k; the first attempt with
+ *     x < 2^64 - (2^64 mod q_m) is kept and a[k] = x mod q_m (unbiased).  a is sampled in the NTT domain.
+ * The seed is key material: take it from the OS CSPRNG and use it for nothing else.  Streams 0-2 of an index are the
+ * ones lumen_encrypt_* would draw: a keygen seed MUST NOT be passed to lumen_encrypt_*.
+ * lumen_keygen_secret generates s on the device, installs it as the context's secret key (the first L limbs, exactly
+ * what lumen_load_secret_key would hold) and keeps its L+K-limb table for the other four calls, which need it and take
+ * the same seed; clones share it like the other key tables.  sk leaves the device only when a buffer is given.
+ * fac = P * 2^(w j) mod q_m on the Q limbs m of the entry's RNS digit (i * alpha <= m < (i+1) * alpha, alpha = max(K, 1)),
+ * 0 elsewhere.  public key: one entry, fac = 0, s_out = s.  Galois key of g: s_out = pi_{g^-1}(s), s_in = s.
+ * relinearisation key: s_out = s, s_in = s^2.  ring-switch key: s_out = skNew(X^(N/n)), s_in = s, shape
+ * lumen_ringswitch_rns_digits() x lumen_ringswitch_digits(w) (K >= 2: w ignored).
+ * flags: LUMEN_KEY_MONTGOMERY = both halves leave multiplied by 2^64 mod q_m (what lumen_load_galois_key_ex accepts).
+ * All keys of a call are produced by one launch of each kernel and reach `evk` in one transfer (page-locked memory
+ * from lumen_host_alloc directly, pageable memory through the bounce buffers).
+ * Refused with a message, before any device work: no generated secret on the context; NULL ctx / seed / output; an even
+ * gal_el or one >= 2N; K = 0 for Galois and relinearisation keys; a wrong key_words; log_n_small >= logN; unknown flag
+ * bits.  count == 0 succeeds and touches nothing. */
+int lumen_keygen_secret(lumen_ctx *ctx, const uint8_t seed[32], uint64_t *sk /* NULL or host [L+K][N], NTT */);
+int lumen_keygen_public(lumen_ctx *ctx, const uint8_t seed[32], uint64_t *pk /* [2][L+K][N] */);
+int lumen_keygen_galois(lumen_ctx *ctx, const uint8_t seed[32], const uint64_t *gal_els, uint32_t count,
+                        uint64_t *evk /* [count][beta][b|a][L+K][N] */, uint32_t flags);
+int lumen_keygen_relin(lumen_ctx *ctx, const uint8_t seed[32], uint64_t *evk /* [beta][b|a][L+K][N] */, uint32_t flags);
+int lumen_keygen_ringswitch(lumen_ctx *ctx, const uint8_t seed[32], uint32_t log_n_small, uint32_t base_two_w,
+                            uint64_t *key, size_t key_words /* the full [rns][pw2][b|a][L+K][N] size */,
+                            int8_t *sk_small /* host [2^log_n_small] */);
+
 /* ---- query loop of Prove (fhe/ligero.go:268-279): gather ciphertexts idx[i]
  * of a set into a new set (duplicates allowed). */
 int lumen_gather(lumen_ctx *ctx, const lumen_set *src, const uint32_t *idx, uint32_t n,

@@ -1,0 +1,513 @@
+// Client-side key generation (cmd/client/main.go:74-81, fhe/ring_switch.go:16-57): KeyGenerator.GenKeyPairNew,
+// GenRelinearizationKeyNew, GenGaloisKeysNew and the ring switch's GenEvaluationKeyNew [LATTIGO-RECALL], every
+// key an array of gadget entries
+//     (b, a) = (NTT(e) - a * s_out + fac * s_in,  a),      a uniform mod q_m, e Gaussian, over the whole basis QP
+// in exactly the layouts lumen_load_public_key / lumen_load_galois_key[_ex] / lumen_load_ringswitch_key take.
+//
+// THE SAMPLING CONTRACT.  Everything is deterministic in (seed, key id, entry, limb, coefficient): keys generated one
+// at a time, in one batched call or on another GPU are the same bytes.
+//     keystream(I, s) = ChaCha20(key = seed, nonce = LE64(I) || LE32(s), counter = 0, 1, ...)   (lm_sample_dev.h)
+//     sample index     I(key_id, e) = key_id * 4096 + e,   e = i * pw2 + j the gadget entry (RNS digit i, power-of-two
+//                      digit j; pw2 = 1 everywhere but the ring-switch key with K <= 1)
+//     key ids          secret 0, public 1, relinearisation 2, ring switch 3, Galois key of element g: 0x10000 + g
+//     ternary secret   s = stream 0 of I(0, 0), word w -> ((w * 3) >> 32) - 1          (lo_det_small)
+//     small secret     of the ring switch: the first n = 2^log_n_small coefficients of stream 0 of I(3, 0)
+//     Gaussian error   of entry e: stream 1 of I(key_id, e), the CDT rule of the encryptor; ONE N-coefficient sample
+//                      per entry, extended to every limb
+//     uniform a        for limb m (Q limbs, then P limbs) of entry e: stream 16 + m of I(key_id, e) read as little-endian
+//                      64-bit words; attempt t = 0, 1, ... for coefficient k is word number t * N + k; the first attempt
+//                      with x < 2^64 - (2^64 mod q_m) is kept and a[k] = x mod q_m (unbiased; a redraw has probability
+//                      below 2^-6).  a is sampled directly in the NTT domain.
+// A keygen seed is key material (OS CSPRNG) and is used for nothing else: streams 0-2 of an index are the ones
+// lumen_encrypt_* would draw, so a keygen seed must never be passed to lumen_encrypt_*.
+//
+// Kernels: k_keygen_small (one thread per ChaCha20 block -> int8 coefficients), k_keygen_uniform (one thread per
+// block = 8 coefficients of attempt 0; attempt t of those coefficients is block t * N/8 + the same),
+// k_keygen_secret_ntt (NTT(s) and NTT(skNew(X^(N/n))) over QP), k_keygen_gather / _square / _shoup (the secret's
+// images), k_keygen_evk (one workgroup per (key, entry, limb): lift + NTT of e, the products fused into the store).
+#include <cstring>
+
+#include "lm_ks_dev.h"
+#include "lm_sample_dev.h"
+
+#define LM_KG_INDEX_STRIDE 4096ull
+#define LM_KG_ID_SECRET 0ull
+#define LM_KG_ID_PUBLIC 1ull
+#define LM_KG_ID_RELIN 2ull
+#define LM_KG_ID_RINGSWITCH 3ull
+#define LM_KG_ID_GALOIS 0x10000ull
+#define LM_KG_UNIFORM_STREAM 16u
+
+int lm_d2h(lumen_ctx *ctx, void *host, const void *dev, size_t bytes, bool wait); // lm_ctx.hip
+void lm_install_secret_key_dev(lumen_ctx *ctx, tw_t *d_sk);                         // lm_encrypt.hip
+
+struct kg_lim_t {
+    u64 t[LM_MAX_LIMBS]; // 2^64 - (2^64 mod q_m): words below it are kept
+};
+
+// out: [nitems][N] int8; item i draws `stream` (0: ternary, else Gaussian) of sample index index[i]
+__global__ __launch_bounds__(256) void k_keygen_small(int8_t *__restrict__ out, const u64 *__restrict__ index,
+                                                      uint32_t nitems, uint32_t stream, uint32_t logN, enc_seed_t seed,
+                                                      enc_cdt_t cdt) {
+    const uint32_t N = 1u << logN, per = stream == 0 ? N >> 4 : N >> 3;
+    const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= (size_t)nitems * per) return;
+    const uint32_t it = (uint32_t)(g / per), blk = (uint32_t)(g % per);
+    const u64 I = index[it];
+    u32 w[16];
+    chacha20_block(seed, blk, (u32)I, (u32)(I >> 32), stream, w);
+    int8_t *o = out + (size_t)it * N;
+    if (stream == 0)
+        *reinterpret_cast<uint4 *>(o + (size_t)blk * 16) = lm_ternary16(w);
+    else
+        *reinterpret_cast<uint2 *>(o + (size_t)blk * 8) = lm_gauss8(w, cdt);
+}
+
+// The `a` half of every entry: out is [nitems][b|a][LK][N].  blockIdx.y = item * LK + limb, one thread per block of 8
+// coefficients.  Attempt t of coefficients 8 blk .. 8 blk + 7 is words of block t * N/8 + blk.
+__global__ __launch_bounds__(256) void k_keygen_uniform(u64 *__restrict__ out, const u64 *__restrict__ index, uint32_t LK,
+                                                        uint32_t logN, lm_mods mods, kg_lim_t lim, enc_seed_t seed) {
+    const uint32_t N = 1u << logN, blk = blockIdx.x * blockDim.x + threadIdx.x;
+    if (blk >= (N >> 3)) return;
+    const uint32_t it = blockIdx.y / LK, m = blockIdx.y % LK;
+    const u64 I = index[it], q = mods.m[m].q, qinv64 = mods.m[m].qinv64, bound = lim.t[m];
+    u64 r[8];
+    uint32_t pending = 0xFFu;
+    for (uint32_t t = 0; pending; t++) {
+        u32 w[16];
+        chacha20_block(seed, t * (N >> 3) + blk, (u32)I, (u32)(I >> 32), LM_KG_UNIFORM_STREAM + m, w);
+#pragma unroll
+        for (int i = 0; i < 8; i++) {
+            const u64 x = (u64)w[2 * i] | ((u64)w[2 * i + 1] << 32);
+            if (((pending >> i) & 1u) && x < bound) {
+                r[i] = lm_reduce(x, q, qinv64);
+                pending &= ~(1u << i);
+            }
+        }
+    }
+    lm_store_run(out + (((size_t)it * 2 + 1) * LK + m) * N, blk * 8, r, 8);
+}
+
+// NTT of small polynomials over QP: slot j of `small` ([nslots][*] int8) -> mont[j][m] = NTT(.) * 2^64 mod q_m (the form
+// the storer of k_keygen_evk multiplies with) and, when given, std[j][m] = NTT(.).  loggap > 0: the polynomial is
+// skNew(X^gap), coefficient i * gap = small[i].  One workgroup per (limb, slot).
+template <int LOGN>
+__global__ LM_GEOM_BOUNDS(lm_geom_lds(LOGN)) void k_keygen_secret_ntt(const int8_t *__restrict__ small, u64 *__restrict__ mont,
+                                                                       u64 *__restrict__ stdf, uint32_t nslots, uint32_t LK,
+                                                                       uint32_t loggap, lm_mods mods, lm_ninv_t rmont,
+                                                                       const tw_t *__restrict__ tw_all) {
+    extern __shared__ __attribute__((aligned(16))) u64 sm[];
+    constexpr uint32_t N = 1u << LOGN;
+    const uint32_t tid = threadIdx.x, m = blockIdx.x / nslots, j = blockIdx.x % nslots;
+    const lm_qc qc = lm_make_qc(mods.m[m]);
+    const int8_t *s = small + (size_t)j * N;
+    u64 *om = mont + ((size_t)j * LK + m) * N, *os = stdf ? stdf + ((size_t)j * LK + m) * N : nullptr;
+    const tw_t R = rmont.t[m];
+    const uint32_t gmask = (1u << loggap) - 1;
+    auto ld = [&](uint32_t i) -> u64 {
+        if (i & gmask) return 0;
+        const int8_t v = s[i >> loggap];
+        return v >= 0 ? (u64)v : qc.q - (u64)(-(int)v);
+    };
+    auto st = [&](uint32_t i0, const u64 *v, int n) {
+        u64 a[8], b[8];
+#pragma unroll
+        for (int k = 0; k < 8; k++)
+            if (k < n) {
+                a[k] = lm_reduce_s(v[k], qc.q, qc.nq, qc.qinv64);
+                b[k] = lm_shoup_cs(a[k], R, qc.q, qc.nq);
+            }
+        lm_store_run(om, i0, b, n);
+        if (os) lm_store_run(os, i0, a, n);
+    };
+    lm_ntt_forward<LOGN>(sm, tw_all + (size_t)m * N, qc, tid, ld, st);
+}
+
+// out[key][m][k] = s[m][index[key][k]]: pi_{g^-1}(s) in the NTT domain (lo_keygen_galois: the index table of g^-1 mod 2N)
+__global__ __launch_bounds__(256) void k_keygen_gather(const u64 *__restrict__ s, const uint32_t *__restrict__ index,
+                                                       u64 *__restrict__ out, uint32_t LK, uint32_t logN, size_t total) {
+    const size_t N = (size_t)1 << logN;
+    for (size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x; g < total; g += (size_t)gridDim.x * blockDim.x) {
+        const size_t k = g & (N - 1), row = g >> logN, m = row % LK, key = row / LK;
+        out[g] = s[(m << logN) + index[(key << logN) + k]];
+    }
+}
+
+// out[m][k] = s[m][k]^2 (Montgomery form in, Montgomery form out): the relinearisation key's s_in
+__global__ __launch_bounds__(256) void k_keygen_square(const u64 *__restrict__ s, u64 *__restrict__ out, uint32_t logN,
+                                                       size_t total, lm_mods mods) {
+    for (size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x; g < total; g += (size_t)gridDim.x * blockDim.x) {
+        const mod_t md = mods.m[g >> logN];
+        u64 lo, hi;
+        mul128(s[g], s[g], lo, hi);
+        out[g] = lm_mont_reduce(lo, hi, md.q, md.qneg);
+    }
+}
+
+// the decryptor's table: tw[l][k] = (x, floor(x * 2^64 / q_l)) for x = stdf[l][k], by long division (x < q < 2^58)
+__global__ __launch_bounds__(256) void k_keygen_shoup(const u64 *__restrict__ stdf, tw_t *__restrict__ tw, uint32_t logN,
+                                                      size_t total, lm_mods mods) {
+    for (size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x; g < total; g += (size_t)gridDim.x * blockDim.x) {
+        const u64 q = mods.m[g >> logN].q, x = stdf[g];
+        u64 r = x, wp = 0;
+        for (int b = 0; b < 64; b++) {
+            r <<= 1;
+            const u64 ge = r >= q;
+            r -= ge ? q : 0;
+            wp = (wp << 1) | ge;
+        }
+        tw_t t;
+        t.w = x, t.wp = wp;
+        tw[g] = t;
+    }
+}
+
+// One workgroup per (key, entry, limb), dealt limb-major like k_enc_u: one twiddle table stays hot per XCD.
+//   small [nitems][N] int8 errors; out [nitems][b|a][LK][N] with the `a` halves filled by k_keygen_uniform;
+//   s_out + key * sout_stride and s_in: [LK][N] secrets in Montgomery form; fac [nent][LK]: P * 2^(w j) mod q_m on the
+//   Q limbs of the entry's RNS digit, 0 elsewhere (NULL: 0 everywhere, the public key).
+//   b = NTT(e) - a * s_out + fac * s_in, canonical; MONT: both halves leave multiplied by 2^64 mod q_m.
+template <int LOGN>
+__global__ LM_GEOM_BOUNDS(lm_geom_lds(LOGN)) void k_keygen_evk(const int8_t *__restrict__ small, u64 *__restrict__ out,
+                                                                const u64 *__restrict__ s_out, size_t sout_stride,
+                                                                const u64 *__restrict__ s_in, const u64 *__restrict__ fac,
+                                                                uint32_t nitems, uint32_t nent, uint32_t LK, uint32_t mont,
+                                                                lm_mods mods, lm_ninv_t rmont,
+                                                                const tw_t *__restrict__ tw_all) {
+    extern __shared__ __attribute__((aligned(16))) u64 sm[];
+    constexpr uint32_t N = 1u << LOGN;
+    const uint32_t tid = threadIdx.x, m = blockIdx.x / nitems, it = blockIdx.x % nitems, key = it / nent, e = it % nent;
+    const mod_t md = mods.m[m];
+    const lm_qc qc = lm_make_qc(md);
+    const int8_t *se = small + (size_t)it * N;
+    u64 *ob = out + ((size_t)it * 2 * LK + m) * N, *oa = ob + (size_t)LK * N;
+    const u64 *so = s_out + (size_t)key * sout_stride + (size_t)m * N, *si = s_in ? s_in + (size_t)m * N : nullptr;
+    const u64 f = fac ? fac[(size_t)e * LK + m] : 0;
+    const tw_t R = rmont.t[m];
+    auto ld = [&](uint32_t i) -> u64 {
+        const int8_t v = se[i];
+        return v >= 0 ? (u64)v : qc.q - (u64)(-(int)v);
+    };
+    auto st = [&](uint32_t i0, const u64 *v, int n) {
+        u64 a[8], b[8], x[8], y[8];
+        lm_load_run(oa, i0, a, n);
+        lm_load_run(so, i0, x, n);
+        if (f) lm_load_run(si, i0, y, n);
+#pragma unroll
+        for (int k = 0; k < 8; k++)
+            if (k < n) {
+                u64 lo, hi;
+                mul128(qc.q - a[k], x[k], lo, hi); // -a * s_out * 2^64
+                if (f) {
+                    u64 l2, h2;
+                    mul128(f, y[k], l2, h2);
+                    lo += l2;
+                    hi += h2 + (lo < l2);
+                }
+                u64 r = lm_mont_reduce_wide(lo, hi, md.q, md.qneg, md.qinv64, 2);
+                r = lm_addmod(r, lm_reduce_s(v[k], qc.q, qc.nq, qc.qinv64), qc.q);
+                if (mont) {
+                    r = lm_shoup_cs(r, R, qc.q, qc.nq);
+                    a[k] = lm_shoup_cs(a[k], R, qc.q, qc.nq);
+                }
+                b[k] = r;
+            }
+        lm_store_run(ob, i0, b, n);
+        if (mont) lm_store_run(oa, i0, a, n);
+    };
+    lm_ntt_forward<LOGN>(sm, tw_all + (size_t)m * N, qc, tid, ld, st);
+}
+
+// ------------------------------------------------------------------------------------------------- host side
+// NTT(s) over QP in Montgomery form, kept by the context (and its clones) for the other keygen calls
+struct KgSecret {
+    u64 *d_mont = nullptr;
+    size_t bytes = 0;
+    ~KgSecret() {
+        if (d_mont) {
+            (void)hipMemset(d_mont, 0, bytes);
+            hipFree(d_mont);
+        }
+    }
+};
+
+// a device temporary; `secret` ones (s, its images, the errors) are zeroed before the block is given back
+struct kg_tmp {
+    lumen_ctx *ctx;
+    void *p = nullptr;
+    size_t bytes = 0;
+    bool secret;
+    kg_tmp(lumen_ctx *c, bool s) : ctx(c), secret(s) {}
+    int alloc(size_t n) {
+        bytes = n;
+        if (hipMalloc(&p, n ? n : 1) != hipSuccess) {
+            (void)hipGetLastError();
+            p = nullptr;
+            return lm_fail(ctx, "hipMalloc(%zu) for key generation failed", n);
+        }
+        return 0;
+    }
+    ~kg_tmp() {
+        if (!p) return;
+        if (secret) (void)hipMemsetAsync(p, 0, bytes, ctx->stream);
+        (void)hipStreamSynchronize(ctx->stream);
+        hipFree(p);
+    }
+    kg_tmp(const kg_tmp &) = delete;
+    kg_tmp &operator=(const kg_tmp &) = delete;
+};
+
+static enc_seed_t kg_seed(const uint8_t seed[32]) {
+    enc_seed_t k;
+    memcpy(k.k, seed, 32);
+    return k;
+}
+static enc_cdt_t kg_cdt() {
+    enc_cdt_t c;
+    memcpy(c.t, H_GAUSS_CDT, sizeof(c.t));
+    return c;
+}
+static lm_ninv_t kg_rmont(const lumen_ctx *ctx) { // 2^64 mod q_m
+    lm_ninv_t r;
+    for (uint32_t t = 0; t < LM_MAX_LIMBS; t++) {
+        const uint64_t q = ctx->mod[t < ctx->L + ctx->K ? t : 0];
+        r.t[t] = h_tw((uint64_t)((((u128)1) << 64) % q), q);
+    }
+    return r;
+}
+static uint64_t kg_p_mod(const lumen_ctx *ctx, uint64_t q) {
+    uint64_t P = 1 % q;
+    for (uint32_t a = 0; a < ctx->K; a++) P = h_mulmod(P, ctx->mod[ctx->L + a] % q, q);
+    return P;
+}
+
+static int kg_small(lumen_ctx *ctx, int8_t *out, const u64 *d_index, uint32_t nitems, uint32_t stream, const uint8_t seed[32]) {
+    const size_t threads = (size_t)nitems * (stream == 0 ? ctx->N >> 4 : ctx->N >> 3);
+    hipLaunchKernelGGL(k_keygen_small, dim3((uint32_t)((threads + 255) / 256)), dim3(256), 0, ctx->stream, out, d_index, nitems,
+                       stream, ctx->logN, kg_seed(seed), kg_cdt());
+    LM_HIP(ctx, hipGetLastError());
+    return 0;
+}
+
+// host words -> a device temporary, through the pinned staging buffer
+static int kg_upload(lumen_ctx *ctx, void *dev, const void *host, size_t bytes) {
+    void *h = lm_stage(ctx, bytes);
+    if (!h) return 1;
+    memcpy(h, host, bytes);
+    LM_HIP(ctx, hipMemcpyAsync(dev, h, bytes, hipMemcpyHostToDevice, ctx->stream));
+    LM_HIP(ctx, hipEventRecord(ctx->ev_stage, ctx->stream));
+    return 0;
+}
+
+template <int LOGN>
+static int kg_secret_ntt_t(lumen_ctx *ctx, const int8_t *small, u64 *mont, u64 *stdf, uint32_t nslots, uint32_t loggap) {
+    const uint32_t LK = ctx->L + ctx->K;
+    lm_prof_scope ps(ctx, "keygen_secret_ntt", (uint64_t)nslots * LK);
+    return lm_launch(ctx, k_keygen_secret_ntt<LOGN>, lm_geom_lds(LOGN), nslots * LK, small, mont, stdf, nslots, LK, loggap,
+                     ctx->mods, kg_rmont(ctx), ctx->d_tw_fwd);
+}
+template <int LOGN>
+static int kg_evk_t(lumen_ctx *ctx, const int8_t *small, u64 *out, const u64 *s_out, size_t sout_stride, const u64 *s_in,
+                    const u64 *fac, uint32_t nitems, uint32_t nent, uint32_t mont) {
+    const uint32_t LK = ctx->L + ctx->K;
+    lm_prof_scope ps(ctx, "keygen_evk_ntt", (uint64_t)nitems * LK);
+    return lm_launch(ctx, k_keygen_evk<LOGN>, lm_geom_lds(LOGN), nitems * LK, small, out, s_out, sout_stride, s_in, fac, nitems,
+                     nent, LK, mont, ctx->mods, kg_rmont(ctx), ctx->d_tw_fwd);
+}
+
+// nkeys keys of nent entries each in ONE launch of each kernel, then one download into the caller's buffer.
+// s_out: the keys' own secrets, sout_stride words apart (0: shared); fac: host [nent][LK] or NULL
+static int kg_run(lumen_ctx *ctx, const uint8_t seed[32], const std::vector<u64> &key_ids, uint32_t nent, const u64 *s_out,
+                  size_t sout_stride, const u64 *s_in, const std::vector<u64> *fac, uint32_t flags, uint64_t *host_out) {
+    const uint32_t N = ctx->N, LK = ctx->L + ctx->K, nkeys = (uint32_t)key_ids.size(), nitems = nkeys * nent;
+    const size_t out_words = (size_t)nitems * 2 * LK * N;
+    LM_CHECK(ctx, nent <= LM_KG_INDEX_STRIDE && (uint64_t)nitems * LK <= 65535, "key generation: %u keys of %u entries exceed one launch",
+             nkeys, nent);
+    std::vector<u64> tab(nitems); // sample indices, then the gadget factors
+    for (uint32_t k = 0; k < nkeys; k++)
+        for (uint32_t e = 0; e < nent; e++) tab[(size_t)k * nent + e] = key_ids[k] * LM_KG_INDEX_STRIDE + e;
+    if (fac) tab.insert(tab.end(), fac->begin(), fac->end());
+    kg_tmp d_tab(ctx, false), d_out(ctx, false), d_e(ctx, true);
+    if (d_tab.alloc(tab.size() * 8) || d_out.alloc(out_words * 8) || d_e.alloc((size_t)nitems * N)) return 1;
+    if (int rc = kg_upload(ctx, d_tab.p, tab.data(), tab.size() * 8)) return rc;
+    const u64 *d_index = (const u64 *)d_tab.p, *d_fac = fac ? d_index + nitems : nullptr;
+    {
+        lm_prof_scope ps(ctx, "keygen_sample", nitems);
+        if (int rc = kg_small(ctx, (int8_t *)d_e.p, d_index, nitems, 1, seed)) return rc;
+    }
+    {
+        lm_prof_scope ps(ctx, "keygen_uniform", (uint64_t)nitems * LK);
+        kg_lim_t lim;
+        for (uint32_t t = 0; t < LM_MAX_LIMBS; t++) {
+            const uint64_t q = ctx->mod[t < LK ? t : 0];
+            lim.t[t] = 0 - ((0 - q) % q); // 2^64 - (2^64 mod q)
+        }
+        const uint32_t nb = N >> 3, bs = nb < 256 ? nb : 256;
+        hipLaunchKernelGGL(k_keygen_uniform, dim3(nb / bs, nitems * LK), dim3(bs), 0, ctx->stream, (u64 *)d_out.p, d_index, LK,
+                           ctx->logN, ctx->mods, lim, kg_seed(seed));
+        LM_HIP(ctx, hipGetLastError());
+    }
+    if (int rc = lm_for_logn(ctx, ctx->logN, [&](auto k) {
+            return kg_evk_t<k>(ctx, (const int8_t *)d_e.p, (u64 *)d_out.p, s_out, sout_stride, s_in, d_fac, nitems, nent,
+                               (flags & LUMEN_KEY_MONTGOMERY) ? 1u : 0u);
+        }))
+        return rc;
+    lm_prof_scope ps(ctx, "keygen_download", nitems);
+    return lm_d2h(ctx, host_out, d_out.p, out_words * 8, true);
+}
+
+static std::shared_ptr<KgSecret> kg_secret_of(lumen_ctx *ctx) { return lm_ext_get<KgSecret>(ctx, "keygen_secret"); }
+#define LM_KG_NEED_SECRET(ctx, hold, what) \
+    LM_CHECK(ctx, hold, "%s: no generated secret on the context (lumen_keygen_secret)", what)
+
+// gadget factors [nent = rns * pw2][LK]: P * 2^(w j) mod q_m for m < L inside RNS digit i, alpha = max(K, 1)
+static std::vector<u64> kg_gadget(const lumen_ctx *ctx, uint32_t rns, uint32_t pw2, uint32_t w) {
+    const uint32_t L = ctx->L, LK = L + ctx->K, alpha = ctx->K ? ctx->K : 1;
+    std::vector<u64> fac((size_t)rns * pw2 * LK, 0);
+    for (uint32_t i = 0; i < rns; i++)
+        for (uint32_t j = 0; j < pw2; j++)
+            for (uint32_t m = i * alpha; m < L && m < (i + 1) * alpha; m++) {
+                const uint64_t q = ctx->mod[m];
+                fac[((size_t)i * pw2 + j) * LK + m] = h_mulmod(kg_p_mod(ctx, q), h_powmod(2, (uint64_t)w * j, q), q);
+            }
+    return fac;
+}
+
+extern "C" int lumen_keygen_secret(lumen_ctx *ctx, const uint8_t seed[32], uint64_t *sk) {
+    LM_CHECK(nullptr, ctx, "lumen_keygen_secret: NULL ctx");
+    LM_ENTER(ctx);
+    LM_CHECK(ctx, seed, "lumen_keygen_secret: NULL argument");
+    const uint32_t N = ctx->N, L = ctx->L, LK = L + ctx->K;
+    const size_t words = (size_t)LK * N;
+    auto sp = std::make_shared<KgSecret>();
+    sp->bytes = words * 8;
+    LM_HIP(ctx, hipMalloc((void **)&sp->d_mont, sp->bytes));
+    kg_tmp d_idx(ctx, false), d_small(ctx, true), d_std(ctx, true);
+    if (d_idx.alloc(8) || d_small.alloc(N) || d_std.alloc(words * 8)) return 1;
+    const u64 index = LM_KG_ID_SECRET * LM_KG_INDEX_STRIDE;
+    if (int rc = kg_upload(ctx, d_idx.p, &index, 8)) return rc;
+    if (int rc = kg_small(ctx, (int8_t *)d_small.p, (const u64 *)d_idx.p, 1, 0, seed)) return rc;
+    if (int rc = lm_for_logn(ctx, ctx->logN, [&](auto k) {
+            return kg_secret_ntt_t<k>(ctx, (const int8_t *)d_small.p, sp->d_mont, (u64 *)d_std.p, 1, 0);
+        }))
+        return rc;
+    // the decryptor's table: the first L limbs, exactly what lumen_load_secret_key would hold
+    tw_t *d_sk = nullptr;
+    LM_HIP(ctx, hipMalloc((void **)&d_sk, (size_t)L * N * sizeof(tw_t)));
+    hipLaunchKernelGGL(k_keygen_shoup, dim3(256), dim3(256), 0, ctx->stream, (const u64 *)d_std.p, d_sk, ctx->logN,
+                       (size_t)L * N, ctx->mods);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess && sk) {
+        if (lm_d2h(ctx, sk, d_std.p, words * 8, true)) e = hipErrorUnknown;
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) {
+        hipFree(d_sk);
+        return lm_fail(ctx, "lumen_keygen_secret failed: %s", hipGetErrorString(e));
+    }
+    lm_install_secret_key_dev(ctx, d_sk);
+    lm_ext_put(ctx, "keygen_secret", sp);
+    return 0;
+}
+
+extern "C" int lumen_keygen_public(lumen_ctx *ctx, const uint8_t seed[32], uint64_t *pk) {
+    LM_CHECK(nullptr, ctx, "lumen_keygen_public: NULL ctx");
+    LM_ENTER(ctx);
+    LM_CHECK(ctx, seed && pk, "lumen_keygen_public: NULL argument");
+    const std::shared_ptr<KgSecret> s = kg_secret_of(ctx);
+    LM_KG_NEED_SECRET(ctx, s, "lumen_keygen_public");
+    return kg_run(ctx, seed, {LM_KG_ID_PUBLIC}, 1, s->d_mont, 0, nullptr, nullptr, 0, pk);
+}
+
+extern "C" int lumen_keygen_relin(lumen_ctx *ctx, const uint8_t seed[32], uint64_t *evk, uint32_t flags) {
+    LM_CHECK(nullptr, ctx, "lumen_keygen_relin: NULL ctx");
+    LM_ENTER(ctx);
+    LM_CHECK(ctx, seed && evk, "lumen_keygen_relin: NULL argument");
+    const std::shared_ptr<KgSecret> s = kg_secret_of(ctx);
+    LM_KG_NEED_SECRET(ctx, s, "lumen_keygen_relin");
+    LM_CHECK(ctx, ctx->K >= 1, "lumen_keygen_relin: parameters have no special primes: key switching unavailable");
+    LM_CHECK(ctx, !(flags & ~(uint32_t)LUMEN_KEY_MONTGOMERY), "lumen_keygen_relin: unknown flags 0x%x", flags);
+    const uint32_t N = ctx->N, L = ctx->L, K = ctx->K, LK = L + K, beta = (L + K - 1) / K;
+    const size_t words = (size_t)LK * N;
+    kg_tmp d_s2(ctx, true);
+    if (d_s2.alloc(words * 8)) return 1;
+    hipLaunchKernelGGL(k_keygen_square, dim3(256), dim3(256), 0, ctx->stream, s->d_mont, (u64 *)d_s2.p, ctx->logN, words,
+                       ctx->mods);
+    LM_HIP(ctx, hipGetLastError());
+    const std::vector<u64> fac = kg_gadget(ctx, beta, 1, 0);
+    return kg_run(ctx, seed, {LM_KG_ID_RELIN}, beta, s->d_mont, 0, (const u64 *)d_s2.p, &fac, flags, evk);
+}
+
+extern "C" int lumen_keygen_galois(lumen_ctx *ctx, const uint8_t seed[32], const uint64_t *gal_els, uint32_t count,
+                                   uint64_t *evk, uint32_t flags) {
+    LM_CHECK(nullptr, ctx, "lumen_keygen_galois: NULL ctx");
+    LM_ENTER(ctx);
+    LM_CHECK(ctx, seed && (count == 0 || (gal_els && evk)), "lumen_keygen_galois: NULL argument");
+    const std::shared_ptr<KgSecret> s = kg_secret_of(ctx);
+    LM_KG_NEED_SECRET(ctx, s, "lumen_keygen_galois");
+    LM_CHECK(ctx, ctx->K >= 1, "lumen_keygen_galois: parameters have no special primes: key switching unavailable");
+    LM_CHECK(ctx, !(flags & ~(uint32_t)LUMEN_KEY_MONTGOMERY), "lumen_keygen_galois: unknown flags 0x%x", flags);
+    const uint32_t N = ctx->N, L = ctx->L, K = ctx->K, LK = L + K, beta = (L + K - 1) / K;
+    const uint64_t mask = 2ull * N - 1;
+    for (uint32_t i = 0; i < count; i++)
+        LM_CHECK(ctx, (gal_els[i] & 1) && gal_els[i] <= mask, "lumen_keygen_galois: Galois element %llu is not an odd residue mod 2N",
+                 (unsigned long long)gal_els[i]);
+    if (!count) return 0;
+    // s_out = pi_{g^-1}(s): a gather with the automorphism's index table of g^-1 ([LATTIGO-RECALL] AutomorphismNTTIndex)
+    std::vector<uint32_t> index((size_t)count * N);
+    std::vector<u64> ids(count);
+    for (uint32_t c = 0; c < count; c++) {
+        const uint64_t g = gal_els[c];
+        uint64_t inv = 1;
+        for (int i = 0; i < 6; i++) inv = (inv * (2 - g * inv)) & mask;
+        for (uint32_t i = 0; i < N; i++) {
+            const uint64_t t1 = 2ull * h_bitrev(i, (int)ctx->logN) + 1;
+            index[(size_t)c * N + i] = h_bitrev((uint32_t)((((inv * t1) & mask) - 1) >> 1), (int)ctx->logN);
+        }
+        ids[c] = LM_KG_ID_GALOIS + g;
+    }
+    const size_t words = (size_t)count * LK * N;
+    kg_tmp d_index(ctx, false), d_sout(ctx, true);
+    if (d_index.alloc(index.size() * 4) || d_sout.alloc(words * 8)) return 1;
+    LM_HIP(ctx, hipMemcpyAsync(d_index.p, index.data(), index.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+    LM_HIP(ctx, hipStreamSynchronize(ctx->stream)); // `index` is pageable host memory
+    hipLaunchKernelGGL(k_keygen_gather, dim3(1024), dim3(256), 0, ctx->stream, s->d_mont, (const uint32_t *)d_index.p,
+                       (u64 *)d_sout.p, LK, ctx->logN, words);
+    LM_HIP(ctx, hipGetLastError());
+    const std::vector<u64> fac = kg_gadget(ctx, beta, 1, 0);
+    return kg_run(ctx, seed, ids, beta, (const u64 *)d_sout.p, (size_t)LK * N, s->d_mont, &fac, flags, evk);
+}
+
+extern "C" int lumen_keygen_ringswitch(lumen_ctx *ctx, const uint8_t seed[32], uint32_t log_n_small, uint32_t base_two_w,
+                                       uint64_t *key, size_t key_words, int8_t *sk_small) {
+    LM_CHECK(nullptr, ctx, "lumen_keygen_ringswitch: NULL ctx");
+    LM_ENTER(ctx);
+    LM_CHECK(ctx, seed && key && sk_small, "lumen_keygen_ringswitch: NULL argument");
+    const std::shared_ptr<KgSecret> s = kg_secret_of(ctx);
+    LM_KG_NEED_SECRET(ctx, s, "lumen_keygen_ringswitch");
+    LM_CHECK(ctx, log_n_small < ctx->logN, "lumen_keygen_ringswitch: target ring degree 2^%u is not below 2^%u", log_n_small,
+             ctx->logN);
+    const bool hybrid = ctx->K >= 2;
+    LM_CHECK(ctx, hybrid || (base_two_w >= 1 && base_two_w <= 32), "lumen_keygen_ringswitch: BaseTwoDecomposition %u out of range",
+             base_two_w);
+    const uint32_t N = ctx->N, LK = ctx->L + ctx->K;
+    const uint32_t rns = lumen_ringswitch_rns_digits(ctx), pw2 = lumen_ringswitch_digits(ctx, base_two_w);
+    const size_t whole = (size_t)rns * pw2 * 2 * LK * N;
+    LM_CHECK(ctx, key_words == whole, "lumen_keygen_ringswitch: key of %zu words: expected %zu ([rns = %u][pw2 = %u][2][L+K = %u][N = %u])",
+             key_words, whole, rns, pw2, LK, N);
+    const size_t n = (size_t)1 << log_n_small, words = (size_t)LK * N;
+    kg_tmp d_idx(ctx, false), d_small(ctx, true), d_sout(ctx, true);
+    if (d_idx.alloc(8) || d_small.alloc(N) || d_sout.alloc(words * 8)) return 1;
+    const u64 index = LM_KG_ID_RINGSWITCH * LM_KG_INDEX_STRIDE;
+    if (int rc = kg_upload(ctx, d_idx.p, &index, 8)) return rc;
+    if (int rc = kg_small(ctx, (int8_t *)d_small.p, (const u64 *)d_idx.p, 1, 0, seed)) return rc;
+    // skNew(X^(N/n)) over QP
+    if (int rc = lm_for_logn(ctx, ctx->logN, [&](auto k) {
+            return kg_secret_ntt_t<k>(ctx, (const int8_t *)d_small.p, (u64 *)d_sout.p, nullptr, 1, ctx->logN - log_n_small);
+        }))
+        return rc;
+    LM_HIP(ctx, hipMemcpyAsync(sk_small, d_small.p, n, hipMemcpyDeviceToHost, ctx->stream));
+    LM_HIP(ctx, hipStreamSynchronize(ctx->stream)); // caller memory
+    const std::vector<u64> fac = kg_gadget(ctx, rns, pw2, hybrid ? 0 : base_two_w);
+    return kg_run(ctx, seed, {LM_KG_ID_RINGSWITCH}, rns * pw2, (const u64 *)d_sout.p, 0, s->d_mont, &fac, 0, key);
+}

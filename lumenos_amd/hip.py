@@ -16,6 +16,7 @@ _u32p = C.POINTER(C.c_uint32)
 _u8p = C.POINTER(C.c_uint8)
 LUMEN_MAX_LIMBS = 24
 LUMEN_ABI_VERSION = 4
+LUMEN_KEY_MONTGOMERY = 1  # key words in Lattigo's storage form, x * 2^64 mod q_i
 # status bits of lumen_verify_columns, with the reference's message for each (fhe/ligero.go:556, 561, 565)
 LUMEN_VERIFY_BAD_PATH, LUMEN_VERIFY_BAD_R, LUMEN_VERIFY_BAD_B = 1, 2, 4
 VERIFY_MESSAGES = (
@@ -121,6 +122,11 @@ SYMBOLS = {
     "lumen_ringswitch_digits": (C.c_uint32, [_vp, C.c_uint32]),
     "lumen_load_ringswitch_key": (C.c_int, [_vp, C.c_uint32, C.c_uint32, _u64p, C.c_size_t]),
     "lumen_ring_switch": (C.c_int, [_vp, _vp, _u64p]),
+    "lumen_keygen_secret": (C.c_int, [_vp, _u8p, _u64p]),
+    "lumen_keygen_public": (C.c_int, [_vp, _u8p, _u64p]),
+    "lumen_keygen_galois": (C.c_int, [_vp, _u8p, _u64p, C.c_uint32, _u64p, C.c_uint32]),
+    "lumen_keygen_relin": (C.c_int, [_vp, _u8p, _u64p, C.c_uint32]),
+    "lumen_keygen_ringswitch": (C.c_int, [_vp, _u8p, C.c_uint32, C.c_uint32, _u64p, C.c_size_t, C.POINTER(C.c_int8)]),
     "lumen_group_create": (C.c_int, [_vpp, C.c_uint32, C.c_uint32, _vpp]),
     "lumen_group_unique_id": (C.c_int, [_u8p]),
     "lumen_group_create_rank": (C.c_int, [_vp, C.c_uint32, C.c_uint32, _u8p, _vpp]),
@@ -676,6 +682,62 @@ class Context:
         assert out.shape == (s.count, 2, 1 << self._rs_logn) and out.dtype == np.uint64 and out.flags["C_CONTIGUOUS"]
         self._ck(self.lib.lumen_ring_switch(self.h, s.h, _p64(out)))
         return out
+
+    # key generation on the device (cmd/client/main.go:74-81): deterministic in the 32-byte seed, which is key material
+    # and must never be handed to encrypt_pk / encrypt_values
+    @staticmethod
+    def _seed(seed):
+        seed = np.ascontiguousarray(np.frombuffer(bytes(seed), dtype=np.uint8))
+        assert seed.size == 32
+        return seed
+
+    def keygen_secret(self, seed, want_sk=True):
+        """Generates the ternary secret on the device and installs it (decrypt works afterwards); with want_sk the
+        [L+K][N] NTT-domain residues come back, otherwise the secret never leaves the device."""
+        seed = self._seed(seed)
+        sk = np.zeros((self.L + self.K, self.N), dtype=np.uint64) if want_sk else None
+        self._ck(self.lib.lumen_keygen_secret(self.h, seed.ctypes.data_as(_u8p), _p64(sk) if want_sk else None))
+        return sk
+
+    def keygen_public(self, seed, out=None):
+        """[2][L+K][N]: what load_public_key takes"""
+        seed = self._seed(seed)
+        pk = np.zeros((2, self.L + self.K, self.N), dtype=np.uint64) if out is None else out
+        assert pk.shape == (2, self.L + self.K, self.N) and pk.dtype == np.uint64 and pk.flags["C_CONTIGUOUS"]
+        self._ck(self.lib.lumen_keygen_public(self.h, seed.ctypes.data_as(_u8p), _p64(pk)))
+        return pk
+
+    def evk_shape(self):
+        return ((self.L + self.K - 1) // max(self.K, 1), 2, self.L + self.K, self.N)
+
+    def keygen_galois(self, seed, gal_els, montgomery=False, out=None):
+        """[count][beta][2][L+K][N]: entry i is what load_galois_key(gal_els[i], ., montgomery) takes; all keys come out
+        of one launch of each kernel and one transfer (`out`: e.g. a page-locked array)"""
+        seed = self._seed(seed)
+        g = np.ascontiguousarray(gal_els, dtype=np.uint64).reshape(-1)
+        shape = (g.size,) + self.evk_shape()
+        evk = np.zeros(shape, dtype=np.uint64) if out is None else out
+        assert evk.shape == shape and evk.dtype == np.uint64 and evk.flags["C_CONTIGUOUS"]
+        self._ck(self.lib.lumen_keygen_galois(self.h, seed.ctypes.data_as(_u8p), _p64(g), g.size, _p64(evk),
+                                              LUMEN_KEY_MONTGOMERY if montgomery else 0))
+        return evk
+
+    def keygen_relin(self, seed, montgomery=False):
+        """[beta][2][L+K][N]: rlwe.RelinearizationKey (s^2 -> s)"""
+        seed = self._seed(seed)
+        evk = np.zeros(self.evk_shape(), dtype=np.uint64)
+        self._ck(self.lib.lumen_keygen_relin(self.h, seed.ctypes.data_as(_u8p), _p64(evk),
+                                             LUMEN_KEY_MONTGOMERY if montgomery else 0))
+        return evk
+
+    def keygen_ringswitch(self, seed, log_n_small, w=13):
+        """-> (key [rns][pw2][2][L+K][N] as load_ringswitch_key takes it, sk_small int8 [2^log_n_small])"""
+        seed = self._seed(seed)
+        key = np.zeros(self.ringswitch_key_shape(w), dtype=np.uint64)
+        sk_small = np.zeros(1 << log_n_small, dtype=np.int8)
+        self._ck(self.lib.lumen_keygen_ringswitch(self.h, seed.ctypes.data_as(_u8p), log_n_small, w, _p64(key), key.size,
+                                                  sk_small.ctypes.data_as(C.POINTER(C.c_int8))))
+        return key, sk_small
 
     def mul_counter(self):
         return int(self.lib.lumen_mul_counter(self.h))

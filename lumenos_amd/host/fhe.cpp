@@ -347,15 +347,12 @@ void ClientBFV::check(int rc, const char *what) const {
     if (rc) throw std::runtime_error(std::string(what) + ": " + lumen_last_error(ctx_));
 }
 
-ClientBFV::ClientBFV(core::PrimeField *plaintextField, const Parameters &params, const std::vector<uint64_t> &sk, int device)
-    : ptField_(plaintextField), params_(params), device_(device) {
-    const size_t N = (size_t)params.N(), L = params.Q.size();
-    if (sk.size() < L * N) throw std::invalid_argument("NewClientBFV: the secret key has fewer than L * N residues");
+static lumen_ctx *new_context(const Parameters &params, int device) {
     lumen_params_desc d;
     memset(&d, 0, sizeof(d));
     d.abi_version = LUMEN_ABI_VERSION;
     d.log_n = (uint32_t)params.LogN;
-    d.num_q = (uint32_t)L;
+    d.num_q = (uint32_t)params.Q.size();
     d.num_p = (uint32_t)params.P.size();
     d.plaintext_modulus = params.T;
     d.device = device;
@@ -363,8 +360,17 @@ ClientBFV::ClientBFV(core::PrimeField *plaintextField, const Parameters &params,
     for (uint64_t m : params.Q) d.moduli[i++] = m;
     for (uint64_t m : params.P) d.moduli[i++] = m;
     for (size_t k = 0; k < params.Psi.size(); k++) d.psi[k] = params.Psi[k];
-    if (lumen_ctx_create(&d, &ctx_)) throw std::runtime_error(std::string("lumen_ctx_create: ") + lumen_last_error(nullptr));
-    g_ring_degree[ctx_] = (uint32_t)N;
+    lumen_ctx *ctx = nullptr;
+    if (lumen_ctx_create(&d, &ctx)) throw std::runtime_error(std::string("lumen_ctx_create: ") + lumen_last_error(nullptr));
+    g_ring_degree[ctx] = (uint32_t)params.N();
+    return ctx;
+}
+
+ClientBFV::ClientBFV(core::PrimeField *plaintextField, const Parameters &params, const std::vector<uint64_t> &sk, int device)
+    : ptField_(plaintextField), params_(params), device_(device) {
+    const size_t N = (size_t)params.N(), L = params.Q.size();
+    if (sk.size() < L * N) throw std::invalid_argument("NewClientBFV: the secret key has fewer than L * N residues");
+    ctx_ = new_context(params, device);
     try {
         check(lumen_encoder_set(ctx_, PowMod(core::PrimitiveRoot(params.T), (params.T - 1) / (2ull << params.LogN), params.T)),
               "lumen_encoder_set");
@@ -376,8 +382,40 @@ ClientBFV::ClientBFV(core::PrimeField *plaintextField, const Parameters &params,
     }
 }
 
+ClientBFV::ClientBFV(core::PrimeField *plaintextField, const Parameters &params, int device)
+    : ptField_(plaintextField), params_(params), device_(device) {
+    ctx_ = new_context(params, device);
+    try {
+        check(lumen_encoder_set(ctx_, PowMod(core::PrimitiveRoot(params.T), (params.T - 1) / (2ull << params.LogN), params.T)),
+              "lumen_encoder_set");
+        keySeed_ = std::make_shared<KeySeedBytes>();
+        OsRandom(keySeed_->b, sizeof(keySeed_->b));
+        check(lumen_keygen_secret(ctx_, keySeed_->b, nullptr), "lumen_keygen_secret");
+    } catch (...) {
+        g_ring_degree.erase(ctx_);
+        lumen_ctx_destroy(ctx_);
+        throw;
+    }
+}
+
+std::unique_ptr<ClientBFV> ClientBFV::NewWithGeneratedSecret(core::PrimeField *plaintextField, const Parameters &params,
+                                                             int device) {
+    return std::unique_ptr<ClientBFV>(new ClientBFV(plaintextField, params, device));
+}
+
+const uint8_t *ClientBFV::KeySeed() const {
+    if (!keySeed_) throw std::invalid_argument("ClientBFV: the secret key was handed in, not generated on the device");
+    return keySeed_->b;
+}
+
+std::vector<uint64_t> ClientBFV::SecretKeyForTest() {
+    std::vector<uint64_t> sk((params_.Q.size() + params_.P.size()) * (size_t)params_.N());
+    check(lumen_keygen_secret(ctx_, KeySeed(), sk.data()), "lumen_keygen_secret");
+    return sk;
+}
+
 ClientBFV::ClientBFV(ClientBFV &src, lumen_ctx *clone)
-    : ptField_(src.ptField_), params_(src.params_), ctx_(clone), device_(src.device_) {
+    : ptField_(src.ptField_), params_(src.params_), ctx_(clone), device_(src.device_), keySeed_(src.keySeed_) {
     g_ring_degree[ctx_] = (uint32_t)params_.N();
 }
 
@@ -392,6 +430,86 @@ ClientBFV::~ClientBFV() {
         g_ring_degree.erase(ctx_);
         lumen_ctx_destroy(ctx_);
     }
+}
+
+// ------------------------------------------------------------------ KeyGenerator (cmd/client/main.go:74-81)
+static size_t evk_words(const Parameters &P) {
+    const size_t L = P.Q.size(), K = P.P.size();
+    return K ? (L + K - 1) / K * 2 * (L + K) * (size_t)P.N() : 0;
+}
+
+KeyGenerator::KeyGenerator(ClientBFV &client) : client_(client) {
+    if (!client.HasGeneratedSecret())
+        throw std::invalid_argument("NewKeyGenerator: the client's secret key was handed in, not generated on the device");
+}
+
+std::vector<uint64_t> KeyGenerator::GenKeyPairNew() {
+    const Parameters &P = client_.GetParameters();
+    std::vector<uint64_t> pk((size_t)2 * (P.Q.size() + P.P.size()) * (size_t)P.N());
+    client_.check(lumen_keygen_public(client_.Context(), client_.KeySeed(), pk.data()), "lumen_keygen_public");
+    return pk;
+}
+
+std::vector<uint64_t> KeyGenerator::GenRelinearizationKeyNew(uint32_t flags) {
+    std::vector<uint64_t> rlk(std::max<size_t>(evk_words(client_.GetParameters()), 1));
+    client_.check(lumen_keygen_relin(client_.Context(), client_.KeySeed(), rlk.data(), flags), "lumen_keygen_relin");
+    return rlk;
+}
+
+std::map<uint64_t, std::vector<uint64_t>> KeyGenerator::GenGaloisKeysNew(const std::vector<uint64_t> &galEls, uint32_t flags) {
+    const std::set<uint64_t> distinct(galEls.begin(), galEls.end());
+    const std::vector<uint64_t> els(distinct.begin(), distinct.end());
+    const size_t words = evk_words(client_.GetParameters());
+    // one page-locked block for the whole batch: the transfer is a single DMA
+    WireBuffer flat(std::max<size_t>(els.size() * words, 1) * 8);
+    uint64_t *w = reinterpret_cast<uint64_t *>(flat.data());
+    client_.check(lumen_keygen_galois(client_.Context(), client_.KeySeed(), els.data(), (uint32_t)els.size(), w, flags),
+                  "lumen_keygen_galois");
+    std::map<uint64_t, std::vector<uint64_t>> out;
+    for (size_t i = 0; i < els.size(); i++) out[els[i]].assign(w + i * words, w + (i + 1) * words);
+    return out;
+}
+
+KeySet KeyGenerator::GenKeySetNew(int rows, uint32_t flags) {
+    KeySet ks;
+    ks.Flags = flags;
+    ks.Pk = GenKeyPairNew();
+    ks.GaloisElements = client_.GetParameters().GaloisElementsForInnerSum(1, rows);
+    const auto keys = GenGaloisKeysNew(ks.GaloisElements, flags);
+    for (uint64_t g : ks.GaloisElements) ks.GaloisKeys.push_back(keys.at(g));
+    return ks;
+}
+
+RingSwitchClient NewRingSwitchClient(ClientBFV &client, int logN, int baseTwoDecomposition) {
+    if (logN < 0 || logN > 30) throw std::invalid_argument("NewRingSwitchClient: logN out of range");
+    const Parameters &P = client.GetParameters();
+    RingSwitchClient rs;
+    rs.LogN = logN, rs.BaseTwoDecomposition = baseTwoDecomposition;
+    rs.SkNew.resize((size_t)1 << logN);
+    rs.Evk.resize((size_t)lumen_ringswitch_rns_digits(client.Context()) *
+                  lumen_ringswitch_digits(client.Context(), (uint32_t)baseTwoDecomposition) * 2 * (P.Q.size() + P.P.size()) *
+                  (size_t)P.N());
+    client.check(lumen_keygen_ringswitch(client.Context(), client.KeySeed(), (uint32_t)logN, (uint32_t)baseTwoDecomposition,
+                                         rs.Evk.data(), rs.Evk.size(), rs.SkNew.data()),
+                 "lumen_keygen_ringswitch");
+    return rs;
+}
+
+std::unique_ptr<ServerBFV> ServerBFV::NewFromKeySet(core::PrimeField *plaintextField, const Parameters &params, int rows,
+                                                    const KeySet &keys, int device) {
+    if (keys.GaloisElements != params.GaloisElementsForInnerSum(1, rows))
+        throw std::invalid_argument("NewFromKeySet: the Galois elements are not GaloisElementsForInnerSum(1, rows)");
+    if (keys.Pk.size() != (size_t)2 * (params.Q.size() + params.P.size()) * (size_t)params.N())
+        throw std::invalid_argument("NewFromKeySet: the public key is not [2][L+K][N]");
+    if (keys.GaloisKeys.size() != keys.GaloisElements.size())
+        throw std::invalid_argument("NewFromKeySet: one Galois key per element expected");
+    for (const auto &k : keys.GaloisKeys)
+        if (k.size() != evk_words(params)) throw std::invalid_argument("NewFromKeySet: a Galois key has the wrong size");
+    std::unique_ptr<ServerBFV> s(new ServerBFV(plaintextField, params, keys.Pk, {}, device));
+    for (size_t i = 0; i < keys.GaloisKeys.size(); i++)
+        s->check(lumen_load_galois_key_ex(s->ctx_, keys.GaloisElements[i], keys.GaloisKeys[i].data(), keys.Flags),
+                 "lumen_load_galois_key_ex");
+    return s;
 }
 
 Plaintext ServerBFV::Encode(const std::vector<uint64_t> &values) const {

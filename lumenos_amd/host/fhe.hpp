@@ -60,6 +60,17 @@ class ClientBFV;
 class RingSwitchServer;
 struct Proof;
 
+// What a client posts to /keys (cmd/client/main.go:74-81, 124-131) before it is marshalled: the public key and one
+// Galois key per entry of params.GaloisElementsForInnerSum(1, rows), in that order (rotations by N/2 and by N both
+// map to the element 1, so an element may appear twice, with the same key).  Flags: 0 = standard-form words,
+// LUMEN_KEY_MONTGOMERY = Lattigo's storage form (x * 2^64 mod q_i), what rlwe.GaloisKey holds.
+struct KeySet {
+    std::vector<uint64_t> Pk;                      // [2][L+K][N]
+    std::vector<uint64_t> GaloisElements;          // GaloisElementsForInnerSum(1, rows)
+    std::vector<std::vector<uint64_t>> GaloisKeys; // [beta][b|a][L+K][N] each
+    uint32_t Flags = 0;
+};
+
 // rlwe.MetaData of the ciphertexts of one slice (they are produced by the same calls, so they share it):
 // what the Go shim's download() has to write into every rlwe.Ciphertext it materialises (SURVEY 8b,
 // "Ownership").  Scale is bgv's plaintext scale modulo T: 1 after EncryptNew, multiplied by the
@@ -130,6 +141,10 @@ class ServerBFV {
     // the layout of lumen_load_galois_key.
     ServerBFV(core::PrimeField *plaintextField, const Parameters &params, std::vector<uint64_t> pk,
               const std::map<uint64_t, std::vector<uint64_t>> &evk, int device = 0);
+    // the same from a posted key set (cmd/server/main.go:100-140 after unmarshalling): keys.GaloisElements must be
+    // params.GaloisElementsForInnerSum(1, rows); the keys go to the device in keys.Flags' form (lumen_load_galois_key_ex)
+    static std::unique_ptr<ServerBFV> NewFromKeySet(core::PrimeField *plaintextField, const Parameters &params, int rows,
+                                                    const KeySet &keys, int device = 0);
     ~ServerBFV();
     core::PrimeField *Field() { return ptField_; }
     const Parameters &GetParameters() const { return params_; }
@@ -186,12 +201,18 @@ class ServerBFV {
 };
 
 // fhe.ClientBFV (fhe/bfv.go:60-106): plaintext field + parameters + encoder / decryptor under the secret key, for a
-// client that owns a GPU: a context with lumen_encoder_set and lumen_load_secret_key.  Key GENERATION is not part of
-// the mirror: the caller hands in sk ([L][N] or [L+K][N], NTT domain, what lumen_load_secret_key takes).
+// client that owns a GPU: a context with lumen_encoder_set and a secret key.  The key is either handed in (sk: [L][N] or
+// [L+K][N], NTT domain, what lumen_load_secret_key takes) or GENERATED ON THE DEVICE (NewWithGeneratedSecret:
+// lumen_keygen_secret under a 32-byte seed from getrandom(2)); a client of the second kind is what fhe::KeyGenerator
+// and NewRingSwitchClient derive the public, relinearisation, Galois and ring-switch keys from.
 class ClientBFV {
   public:
     // NewClientBFV(plaintextField, paramsFHE, sk)
     ClientBFV(core::PrimeField *plaintextField, const Parameters &params, const std::vector<uint64_t> &sk, int device = 0);
+    // kgen.GenSecretKeyNew() + NewClientBFV (cmd/client/main.go:74-76, 90): the secret never leaves the device.  The
+    // seed is key material: it comes from the kernel's CSPRNG, as ServerBFV's encryptor seed does, and keys nothing else.
+    static std::unique_ptr<ClientBFV> NewWithGeneratedSecret(core::PrimeField *plaintextField, const Parameters &params,
+                                                             int device = 0);
     ~ClientBFV();
     ClientBFV(const ClientBFV &) = delete;
     core::PrimeField *Field() { return ptField_; }
@@ -202,14 +223,53 @@ class ClientBFV {
     // ClientBFV.CopyNew (bfv.go:96-98): the same key and tables, its own streams and scratch (lumen_ctx_clone); must
     // not outlive the client it was made from
     std::unique_ptr<ClientBFV> CopyNew();
+    bool HasGeneratedSecret() const { return (bool)keySeed_; }
+    // the seed of a generated secret (what the KeyGenerator passes on); throws for a client that was handed its key
+    const uint8_t *KeySeed() const;
+    // test hook: the generated secret as [L+K][N] NTT-domain residues (regenerated from the seed into a host buffer:
+    // the one way it leaves the device)
+    std::vector<uint64_t> SecretKeyForTest();
 
   private:
+    ClientBFV(core::PrimeField *plaintextField, const Parameters &params, int device);
     ClientBFV(ClientBFV &src, lumen_ctx *clone);
     core::PrimeField *ptField_;
     Parameters params_;
     lumen_ctx *ctx_ = nullptr;
     int device_ = 0;
+    struct KeySeedBytes {
+        uint8_t b[32];
+    };
+    std::shared_ptr<KeySeedBytes> keySeed_; // shared with every CopyNew
 };
+
+// rlwe.NewKeyGenerator(params) (cmd/client/main.go:74) bound to a client with a generated secret: every key is derived
+// on the device from the client's seed (include/lumenos_hip.h, "SAMPLING CONTRACT"), so generating a key twice, one
+// at a time or in a batch gives the same words.  flags: 0 or LUMEN_KEY_MONTGOMERY.
+class KeyGenerator {
+  public:
+    explicit KeyGenerator(ClientBFV &client); // throws std::invalid_argument for a client that was handed its key
+    // GenKeyPairNew(): the secret is the client's own and stays where it is; returns pk, [2][L+K][N]
+    std::vector<uint64_t> GenKeyPairNew();
+    // GenRelinearizationKeyNew(sk): [beta][b|a][L+K][N]
+    std::vector<uint64_t> GenRelinearizationKeyNew(uint32_t flags = 0);
+    // GenGaloisKeysNew(galEls, sk): one launch of each kernel and one transfer for all the (distinct) elements
+    std::map<uint64_t, std::vector<uint64_t>> GenGaloisKeysNew(const std::vector<uint64_t> &galEls, uint32_t flags = 0);
+    // pk + the Galois keys of params.GaloisElementsForInnerSum(1, rows) in that order: the body of POST /keys
+    KeySet GenKeySetNew(int rows, uint32_t flags = 0);
+
+  private:
+    ClientBFV &client_;
+};
+
+// fhe.NewRingSwitchClient (fhe/ring_switch.go:16-57): the small-ring secret skNew (2^logN ternary coefficients) and the
+// evaluation key sk -> skNew(X^(N/n)), [rns][pw2][b|a][L+K][N] as NewRingSwitchServer / lumen_load_ringswitch_key take it
+struct RingSwitchClient {
+    int LogN = 0, BaseTwoDecomposition = 13;
+    std::vector<int8_t> SkNew;
+    std::vector<uint64_t> Evk;
+};
+RingSwitchClient NewRingSwitchClient(ClientBFV &client, int logN, int baseTwoDecomposition = 13);
 
 // W = 2^k ServerBFVs behind one lumen_group (include/lumenos_hip.h): the ranks of ONE server process that owns
 // several GPUs -- the reference's server is a single process (cmd/server/main.go:187-266).  ranks[r] is rank r;
