@@ -15,6 +15,7 @@
 
 #include "../../include/lumenos_hip.h"
 #include "lm_arith.h"
+#include "lm_dev.h"
 
 #define LM_MAX_LIMBS LUMEN_MAX_LIMBS
 
@@ -35,9 +36,9 @@ struct lm_prof_entry {
 };
 
 struct lm_galois_key {
-    u64 *d_key = nullptr;   // [L+K][beta][2][N] (lm_ks_dev.h, ks_key_at), Montgomery form
-    uint32_t *d_index = nullptr; // automorphism gather table, N entries: out[i] = in[index[i]]
-    uint32_t *d_inv_index = nullptr; // its inverse: out[inv_index[p]] = in[p]
+    lm_dev<u64> d_key;   // [L+K][beta][2][N] (lm_ks_dev.h, ks_key_at), Montgomery form
+    lm_dev<uint32_t> d_index; // automorphism gather table, N entries: out[i] = in[index[i]]
+    lm_dev<uint32_t> d_inv_index; // its inverse: out[inv_index[p]] = in[p]
 };
 
 struct lumen_set {
@@ -60,17 +61,16 @@ struct lumen_set {
 struct lm_shared {
     std::recursive_mutex mu;
     // twiddle tables, device: [L+K][N] tw_t
-    tw_t *d_tw_fwd = nullptr;
-    tw_t *d_tw_inv = nullptr;
+    lm_dev<tw_t> tw_fwd;
+    lm_dev<tw_t> tw_inv;
     // plaintext field table (core.PrimeField)
     std::vector<uint64_t> roots;
     uint32_t fieldN = 0;
-    tw_t *d_scal = nullptr; // [L][fieldN+1] centred twiddle scalars per limb
+    lm_dev<tw_t> scal; // [L][fieldN+1] centred twiddle scalars per limb
     std::map<uint64_t, lm_galois_key> gkeys;
     // derived tables owned by other translation units (key-switch constants, ciphertext-transform
     // plans, public/secret/ring-switch keys)
     std::map<std::string, std::shared_ptr<void>> ext;
-    ~lm_shared();
 };
 
 // Tuning switches of the A/B tools ("Run-time switches").  The environment is read ONCE, in
@@ -125,16 +125,13 @@ struct lumen_ctx {
     lm_mods mods; // device-side constants by value
     tw_t ninv[LM_MAX_LIMBS]; // N^-1 mod q_i
     // views of the shared tables (same names as before the split)
-    tw_t *&d_tw_fwd;
-    tw_t *&d_tw_inv;
     std::vector<uint64_t> &roots;
     uint32_t &fieldN;
-    tw_t *&d_scal;
     std::map<uint64_t, lm_galois_key> &gkeys;
     std::map<std::string, std::shared_ptr<void>> &ext;
     uint64_t mul_counter = 0;
-    // scratch
-    std::map<std::string, std::pair<void *, size_t>> scratch;
+    // scratch: named byte blocks (lm_scratch, lm_scratch_adopt)
+    std::map<std::string, lm_dev<unsigned char>> scratch;
     // freed set storage kept for reuse: a prover run allocates the same set sizes every time, and
     // mapping/unmapping tens of GB of HBM per call costs more than the kernels that fill it
     // A block may come back in STREAM ORDER (lm_set_release_async: the temporaries of a group call): `ready` is then
@@ -163,8 +160,7 @@ struct lumen_ctx {
     hipEvent_t tm0 = nullptr, tm1 = nullptr;
     std::string err;
     explicit lumen_ctx(std::shared_ptr<lm_shared> s)
-        : sh(std::move(s)), d_tw_fwd(sh->d_tw_fwd), d_tw_inv(sh->d_tw_inv), roots(sh->roots), fieldN(sh->fieldN),
-          d_scal(sh->d_scal), gkeys(sh->gkeys), ext(sh->ext) {}
+        : sh(std::move(s)), roots(sh->roots), fieldN(sh->fieldN), gkeys(sh->gkeys), ext(sh->ext) {}
 };
 
 // words of one ciphertext of a set (lane shards are narrower)

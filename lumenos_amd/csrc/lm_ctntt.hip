@@ -162,23 +162,15 @@ struct Plan {
     // device copies, one per pass
     struct Dev {
         uint32_t ngroups, gsize;
-        uint32_t *d_slots = nullptr; // [ngroups][gsize]
+        lm_dev<uint32_t> d_slots; // [ngroups][gsize]
         // the pass as work items of the register-blocked kernel
-        uint32_t *d_mops = nullptr;   // [ngroups][mtotal][LM_MOP_WORDS]
-        uint32_t *d_mlayer = nullptr; // [mlayers][2]: offset, count (padded)
+        lm_dev<uint32_t> d_mops;   // [ngroups][mtotal][LM_MOP_WORDS]
+        lm_dev<uint32_t> d_mlayer; // [mlayers][2]: offset, count (padded)
         uint32_t mtotal = 0, mlayers = 0;
     };
     std::vector<Dev> dev;
-    uint32_t *d_out_pos = nullptr;
+    lm_dev<uint32_t> d_out_pos;
     std::vector<std::vector<uint32_t>> final_groups; // slots of every group of the final pass
-    ~Plan() {
-        for (Dev &d : dev) {
-            hipFree(d.d_slots);
-            hipFree(d.d_mops);
-            hipFree(d.d_mlayer);
-        }
-        hipFree(d_out_pos);
-    }
 };
 
 struct UF {
@@ -376,19 +368,14 @@ int upload_plan(lumen_ctx *ctx, Plan *plan, uint32_t count) {
                     for (int k = 0; k < 8; k++) o[4 + k] = k < m.n ? m.pre[k] : LM_NOSLOT;
                 }
         }
-        LM_HIP(ctx, hipMalloc((void **)&d.d_mops, std::max<size_t>(mops.size(), 1) * 4));
-        LM_HIP(ctx, hipMalloc((void **)&d.d_mlayer, std::max<size_t>(mlayer.size(), 1) * 4));
-        if (!mops.empty()) LM_HIP(ctx, hipMemcpy(d.d_mops, mops.data(), mops.size() * 4, hipMemcpyHostToDevice));
-        if (!mlayer.empty()) LM_HIP(ctx, hipMemcpy(d.d_mlayer, mlayer.data(), mlayer.size() * 4, hipMemcpyHostToDevice));
-        LM_HIP(ctx, hipMalloc((void **)&d.d_slots, slots.size() * 4));
-        LM_HIP(ctx, hipMemcpy(d.d_slots, slots.data(), slots.size() * 4, hipMemcpyHostToDevice));
-        plan->dev.push_back(d);
+        if (d.d_mops.upload(ctx, mops, "a transform plan's work items") || d.d_mlayer.upload(ctx, mlayer, "a transform plan's layers") ||
+            d.d_slots.upload(ctx, slots, "a transform plan's slots"))
+            return 1;
+        plan->dev.push_back(std::move(d));
     }
     if (!plan->passes.empty())
         for (Group &g : plan->passes.back().groups) plan->final_groups.push_back(g.slots);
-    LM_HIP(ctx, hipMalloc((void **)&plan->d_out_pos, std::max<size_t>(count, 1) * 4));
-    LM_HIP(ctx, hipMemcpy(plan->d_out_pos, plan->out_pos.data(), (size_t)count * 4, hipMemcpyHostToDevice));
-    return 0;
+    return plan->d_out_pos.upload(ctx, plan->out_pos, "a transform plan's output order");
 }
 
 int get_plan(lumen_ctx *ctx, uint32_t count, uint32_t size, Plan **out) {
@@ -598,11 +585,11 @@ static int run_plan(lumen_ctx *ctx, Plan *plan, uint32_t count, uint32_t nl, con
         ct_blocks_args b;
         b.srcA = cur, b.srcB = curB, b.splitA = split;
         b.dst = final_pass ? out : tmp;
-        b.slots = d.d_slots;
-        b.out_pos = final_pass ? (final_pos ? final_pos : plan->d_out_pos) : (p + 2 == P ? keep_pos : nullptr);
+        b.slots = d.d_slots.get();
+        b.out_pos = final_pass ? (final_pos ? final_pos : plan->d_out_pos.get()) : (p + 2 == P ? keep_pos : nullptr);
         b.group0 = final_pass && final_ng ? final_g0 : 0;
-        b.scal = ctx->d_scal;
-        b.mops = d.d_mops, b.mlayer = d.d_mlayer, b.mtotal = d.mtotal, b.mlayers = d.mlayers;
+        b.scal = ctx->sh->scal.get();
+        b.mops = d.d_mops.get(), b.mlayer = d.d_mlayer.get(), b.mtotal = d.mtotal, b.mlayers = d.mlayers;
         b.gsize = d.gsize, b.fieldN1 = ctx->fieldN + 1, b.logN = ctx->logN - logw, b.nl = nl, b.ctw = ctw; // logN: limb width of THESE sets
         b.src_tiled = p > 0, b.dst_tiled = !final_pass, b.count = count;
         const uint32_t ng = final_pass && final_ng ? final_ng : d.ngroups;
@@ -622,7 +609,7 @@ static int run_plan(lumen_ctx *ctx, Plan *plan, uint32_t count, uint32_t nl, con
 }
 
 static int check_field(lumen_ctx *ctx, uint32_t size) {
-    LM_CHECK(ctx, ctx->fieldN && ctx->d_scal, "lumen_field_set must be called before the ciphertext transform");
+    LM_CHECK(ctx, ctx->fieldN && ctx->sh->scal, "lumen_field_set must be called before the ciphertext transform");
     LM_CHECK(ctx, size && (size & (size - 1)) == 0, "transform size %u is not a power of two", size);
     LM_CHECK(ctx, size <= ctx->fieldN, "transform size %u exceeds the field table (%u)", size, ctx->fieldN);
     return 0;
@@ -653,14 +640,8 @@ extern "C" int lumen_field_set(lumen_ctx *ctx, const uint64_t *roots_forward, ui
         }
     }
     LM_SHARED_LOCK(ctx);
-    if (ctx->d_scal) {
-        lm_sync_all(ctx);
-        LM_HIP(ctx, hipFree(ctx->d_scal));
-        ctx->d_scal = nullptr;
-    }
-    LM_HIP(ctx, hipMalloc((void **)&ctx->d_scal, tab.size() * sizeof(tw_t)));
-    LM_HIP(ctx, hipMemcpy(ctx->d_scal, tab.data(), tab.size() * sizeof(tw_t), hipMemcpyHostToDevice));
-    return 0;
+    if (ctx->sh->scal) lm_sync_all(ctx); // upload frees the old table before it draws the new one
+    return ctx->sh->scal.upload(ctx, tab, "the field's twiddle scalars");
 }
 
 extern "C" int lumen_ct_ntt(lumen_ctx *ctx, lumen_set *values, uint32_t size) {

@@ -25,45 +25,18 @@ int lm_fail(lumen_ctx *ctx, const char *fmt, ...) {
 
 void *lm_scratch(lumen_ctx *ctx, const char *name, size_t bytes) {
     auto &e = ctx->scratch[name];
-    if (e.second >= bytes && e.first) return e.first;
-    if (e.first) {
-        lm_sync_all(ctx); // the old block may still be read on any of the context's streams
-        hipFree(e.first);
-        e.first = nullptr;
-        e.second = 0;
-    }
-    void *p = nullptr;
-    if (hipMalloc(&p, bytes) != hipSuccess) {
-        lm_fail(ctx, "hipMalloc(%zu) for scratch '%s' failed", bytes, name);
-        return nullptr;
-    }
-    e.first = p;
-    e.second = bytes;
-    return p;
+    if (e && e.count() >= bytes) return e.get();
+    if (e) lm_sync_all(ctx); // the old block may still be read on any of the context's streams
+    return e.alloc(ctx, bytes, name) ? nullptr : e.get();
 }
 
-// puts a block the caller allocated (hipMalloc) under a scratch name; whatever was there is freed after the context's
+// puts a block the caller drew (hipMalloc) under a scratch name; whatever was there is freed after the context's
 // streams have drained.  For buffers whose PLACEMENT was chosen (lm_ks_scratch.hip, get_scratch).
 void lm_scratch_adopt(lumen_ctx *ctx, const char *name, void *p, size_t bytes) {
     auto &e = ctx->scratch[name];
-    if (e.first && e.first != p) {
-        lm_sync_all(ctx);
-        hipFree(e.first);
-    }
-    e.first = p;
-    e.second = bytes;
-}
-
-lm_shared::~lm_shared() {
-    hipFree(d_tw_fwd);
-    hipFree(d_tw_inv);
-    hipFree(d_scal);
-    for (auto &kv : gkeys) {
-        hipFree(kv.second.d_key);
-        hipFree(kv.second.d_index);
-        hipFree(kv.second.d_inv_index);
-    }
-    ext.clear();
+    if (e.get() == p) (void)e.release(); // the same block under a new size
+    if (e) lm_sync_all(ctx);
+    e = lm_dev<unsigned char>((unsigned char *)p, bytes);
 }
 
 void lm_sync_all(lumen_ctx *ctx) {
@@ -323,14 +296,13 @@ extern "C" int lumen_ctx_create(const lumen_params_desc *desc, lumen_ctx **out) 
     }
     for (uint32_t i = LK; i < LM_MAX_LIMBS; i++) ctx->mods.m[i] = ctx->mods.m[0];
     if (int rc = ctx_private_init(ctx)) return rc;
-    LM_HIP(ctx, hipMalloc((void **)&ctx->d_tw_fwd, (size_t)LK * N * sizeof(tw_t)));
-    LM_HIP(ctx, hipMalloc((void **)&ctx->d_tw_inv, (size_t)LK * N * sizeof(tw_t)));
-    std::vector<tw_t> f, b;
+    std::vector<tw_t> f, b, fwd, inv;
     for (uint32_t i = 0; i < LK; i++) {
         lm_build_tw(ctx->mod[i], ctx->psi[i], ctx->logN, f, b);
-        LM_HIP(ctx, hipMemcpy(ctx->d_tw_fwd + (size_t)i * N, f.data(), N * sizeof(tw_t), hipMemcpyHostToDevice));
-        LM_HIP(ctx, hipMemcpy(ctx->d_tw_inv + (size_t)i * N, b.data(), N * sizeof(tw_t), hipMemcpyHostToDevice));
+        fwd.insert(fwd.end(), f.begin(), f.end());
+        inv.insert(inv.end(), b.begin(), b.end());
     }
+    if (ctx->sh->tw_fwd.upload(ctx, fwd, "the forward twiddles") || ctx->sh->tw_inv.upload(ctx, inv, "the inverse twiddles")) return 1;
     *out = guard.release();
     return 0;
 }
@@ -364,7 +336,7 @@ extern "C" void lumen_ctx_destroy(lumen_ctx *ctx) {
     {
         LM_ENTER(ctx);
         lm_sync_all(ctx);
-        for (auto &kv : ctx->scratch) hipFree(kv.second.first);
+        ctx->scratch.clear();
         pool_drain(ctx);
         lm_prof_resolve(ctx);
         for (hipEvent_t e : ctx->ev_pool) hipEventDestroy(e);
@@ -404,7 +376,6 @@ extern "C" int lumen_ctx_trim(lumen_ctx *ctx) {
             ++it;
             continue;
         }
-        hipFree(it->second.first);
         it = ctx->scratch.erase(it);
     }
     pool_drain(ctx);
@@ -417,8 +388,8 @@ extern "C" int lumen_ctx_scratch_info(lumen_ctx *ctx, const char *name, void **p
     LM_CHECK(nullptr, ctx && name && ptr, "lumen_ctx_scratch_info: NULL argument");
     LM_ENTER(ctx);
     auto it = ctx->scratch.find(name);
-    *ptr = it == ctx->scratch.end() ? nullptr : it->second.first;
-    if (bytes) *bytes = it == ctx->scratch.end() ? 0 : it->second.second;
+    *ptr = it == ctx->scratch.end() ? nullptr : it->second.get();
+    if (bytes) *bytes = it == ctx->scratch.end() ? 0 : it->second.count();
     return 0;
 }
 

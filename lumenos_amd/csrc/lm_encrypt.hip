@@ -214,10 +214,7 @@ __global__ LM_GEOM_BOUNDS(lm_geom_lds(LOGN)) void k_enc_down(const int8_t *__res
 }
 
 struct PkTable {
-    tw_t *d_pk = nullptr; // [2][L+K][N] Shoup form; Q limbs carry P^-1
-    ~PkTable() {
-        if (d_pk) hipFree(d_pk);
-    }
+    lm_dev<tw_t> d_pk; // [2][L+K][N] Shoup form; Q limbs carry P^-1
 };
 
 extern "C" int lumen_load_public_key(lumen_ctx *ctx, const uint64_t *pk) {
@@ -240,8 +237,7 @@ extern "C" int lumen_load_public_key(lumen_ctx *ctx, const uint64_t *pk) {
             }
         }
     auto sp = std::make_shared<PkTable>();
-    LM_HIP(ctx, hipMalloc((void **)&sp->d_pk, tab.size() * sizeof(tw_t)));
-    LM_HIP(ctx, hipMemcpy(sp->d_pk, tab.data(), tab.size() * sizeof(tw_t), hipMemcpyHostToDevice));
+    if (int rc = sp->d_pk.upload(ctx, tab, "the public key")) return rc;
     lm_ext_put(ctx, "public_key", sp);
     return 0;
 }
@@ -249,17 +245,12 @@ extern "C" int lumen_load_public_key(lumen_ctx *ctx, const uint64_t *pk) {
 // ---- Encoder.Encode on the device ([LATTIGO-RECALL] bgv.Encoder: slot i of row 0 sits at the
 // evaluation point 5^i, row 1 at -5^i; slots -> INTT over Z_T -> scale by T^-1 mod q_l -> NTT)
 struct EncoderTables {
-    uint32_t *d_slot = nullptr; // [N] slot -> coefficient position of the Z_T transform
-    tw_t *d_tw_inv = nullptr;   // [N] inverse twiddles modulo T
-    tw_t *d_tw_fwd = nullptr;   // [N] forward twiddles modulo T (Encoder.Decode)
+    lm_dev<uint32_t> d_slot; // [N] slot -> coefficient position of the Z_T transform
+    lm_dev<tw_t> d_tw_inv;   // [N] inverse twiddles modulo T
+    lm_dev<tw_t> d_tw_fwd;   // [N] forward twiddles modulo T (Encoder.Decode)
     mod_t modT;
     tw_t ninvT;
     enc_tinv_t tinv; // T^-1 mod q_l
-    ~EncoderTables() {
-        if (d_slot) hipFree(d_slot);
-        if (d_tw_inv) hipFree(d_tw_inv);
-        if (d_tw_fwd) hipFree(d_tw_fwd);
-    }
 };
 
 extern "C" int lumen_encoder_set(lumen_ctx *ctx, uint64_t psi_t) {
@@ -287,12 +278,9 @@ extern "C" int lumen_encoder_set(lumen_ctx *ctx, uint64_t psi_t) {
         slot[i | (N / 2)] = h_bitrev((uint32_t)((m - pos - 1) >> 1), (int)logN);
         pos = (pos * 5) & (m - 1);
     }
-    LM_HIP(ctx, hipMalloc((void **)&sp->d_slot, (size_t)N * 4));
-    LM_HIP(ctx, hipMalloc((void **)&sp->d_tw_inv, (size_t)N * sizeof(tw_t)));
-    LM_HIP(ctx, hipMemcpy(sp->d_slot, slot.data(), (size_t)N * 4, hipMemcpyHostToDevice));
-    LM_HIP(ctx, hipMemcpy(sp->d_tw_inv, b.data(), (size_t)N * sizeof(tw_t), hipMemcpyHostToDevice));
-    LM_HIP(ctx, hipMalloc((void **)&sp->d_tw_fwd, (size_t)N * sizeof(tw_t)));
-    LM_HIP(ctx, hipMemcpy(sp->d_tw_fwd, f.data(), (size_t)N * sizeof(tw_t), hipMemcpyHostToDevice));
+    if (sp->d_slot.upload(ctx, slot, "the encoder's slot table") || sp->d_tw_inv.upload(ctx, b, "the encoder's inverse twiddles") ||
+        sp->d_tw_fwd.upload(ctx, f, "the encoder's forward twiddles"))
+        return 1;
     lm_ext_put(ctx, "encoder", sp);
     return 0;
 }
@@ -315,13 +303,13 @@ static int encrypt_t(lumen_ctx *ctx, const int8_t *small, const tw_t *pk, const 
     {
         lm_prof_scope ps(ctx, "encrypt_u_ntt", (uint64_t)count * LK);
         if (int rc = lm_launch(ctx, k_enc_u<LOGN>, geom, count * LK, small, pk, out, upk, count, L, K, ctx->mods,
-                               ctx->d_tw_fwd))
+                               ctx->sh->tw_fwd.get()))
             return rc;
     }
     if (!K) {
         lm_prof_scope ps(ctx, "encrypt_down_ntt", (uint64_t)count * 2 * L);
         return lm_launch(ctx, k_enc_down<LOGN, false>, geom, count * 2 * L, small, upk, nullptr, nullptr, pt, mcoef, tinv,
-                         out, count, L, K, ctx->mods, ctx->d_tw_fwd);
+                         out, count, L, K, ctx->mods, ctx->sh->tw_fwd.get());
     }
     lm_ks_view kv;
     if (int rc = lm_ks_tables_view(ctx, &kv)) return rc;
@@ -345,7 +333,7 @@ static int encrypt_t(lumen_ctx *ctx, const int8_t *small, const tw_t *pk, const 
         if (int rc = lm_launch_pack_v(ctx, upk, (size_t)K * N, count * 2, 1u, K, L, K)) return rc;
     lm_prof_scope ps(ctx, "encrypt_down_ntt", (uint64_t)count * 2 * L);
     return lm_launch(ctx, k_enc_down<LOGN, true>, geom, count * 2 * L, small, upk, kv.d_bxp, kv.d_pinv, pt, mcoef, tinv, out,
-                     count, L, K, ctx->mods, ctx->d_tw_fwd);
+                     count, L, K, ctx->mods, ctx->sh->tw_fwd.get());
 }
 
 // plaintexts (NTT-domain RNS, [count][L][N]) or values ([count][rows] slot values) or neither (zeros)
@@ -411,11 +399,11 @@ static int encrypt_impl(lumen_ctx *ctx, const uint64_t *plaintexts, const uint64
             {
                 lm_prof_scope ps(ctx, "encode_scatter", n);
                 hipLaunchKernelGGL(k_scatter_slots, dim3((uint32_t)((total + 255) / 256)), dim3(256), 0, ctx->stream, dval,
-                                   dm, enc->d_slot, rows, ctx->logN, total, enc->modT);
+                                   dm, enc->d_slot.get(), rows, ctx->logN, total, enc->modT);
                 LM_HIP(ctx, hipGetLastError());
             }
             lm_prof_scope ps(ctx, "encode_intt_T", n);
-            rc = lm_launch_ntt_subring(ctx, ctx->logN, enc->d_tw_inv, enc->ninvT, dm, N, dm, N, n, 0, true, &enc->modT);
+            rc = lm_launch_ntt_subring(ctx, ctx->logN, enc->d_tw_inv.get(), enc->ninvT, dm, N, dm, N, n, 0, true, &enc->modT);
             if (rc) break;
         }
         {
@@ -426,7 +414,7 @@ static int encrypt_impl(lumen_ctx *ctx, const uint64_t *plaintexts, const uint64
             LM_HIP(ctx, hipGetLastError());
         }
         u64 *dst = o->d + (size_t)first * 2 * L * N;
-        rc = lm_for_logn(ctx, ctx->logN, [&](auto k) { return encrypt_t<k>(ctx, small, pkt->d_pk, dpt, dm, tinv, dst, upk, n); });
+        rc = lm_for_logn(ctx, ctx->logN, [&](auto k) { return encrypt_t<k>(ctx, small, pkt->d_pk.get(), dpt, dm, tinv, dst, upk, n); });
     }
     if (rc) return rc;
     if (plaintexts || values) LM_HIP(ctx, hipStreamSynchronize(ctx->stream)); // caller memory
@@ -456,16 +444,13 @@ extern "C" int lumen_encrypt_values(lumen_ctx *ctx, const uint64_t *values, uint
 // the rescales left behind.  The secret key lives with the client: this entry point is for a client
 // that owns a GPU and for end-to-end tests, not for the proving server.
 struct SkTable {
-    tw_t *d_sk = nullptr; // [L][N] Shoup form
-    ~SkTable() {
-        if (d_sk) hipFree(d_sk);
-    }
+    lm_dev<tw_t> d_sk; // [L][N] Shoup form
 };
 
-// a secret generated on the device (lm_keygen.hip): takes ownership of d_sk, [L][N] Shoup form
-void lm_install_secret_key_dev(lumen_ctx *ctx, tw_t *d_sk) {
+// a secret generated on the device (lm_keygen.hip): [L][N] Shoup form
+void lm_install_secret_key_dev(lumen_ctx *ctx, lm_dev<tw_t> &&d_sk) {
     auto sp = std::make_shared<SkTable>();
-    sp->d_sk = d_sk;
+    sp->d_sk = std::move(d_sk);
     lm_ext_put(ctx, "secret_key", sp);
 }
 
@@ -483,8 +468,7 @@ extern "C" int lumen_load_secret_key(lumen_ctx *ctx, const uint64_t *sk) {
         }
     }
     auto sp = std::make_shared<SkTable>();
-    LM_HIP(ctx, hipMalloc((void **)&sp->d_sk, tab.size() * sizeof(tw_t)));
-    LM_HIP(ctx, hipMemcpy(sp->d_sk, tab.data(), tab.size() * sizeof(tw_t), hipMemcpyHostToDevice));
+    if (int rc = sp->d_sk.upload(ctx, tab, "the secret key")) return rc;
     lm_ext_put(ctx, "secret_key", sp);
     return 0;
 }
@@ -602,7 +586,7 @@ static int decrypt_phase_t(lumen_ctx *ctx, const u64 *ct, const tw_t *sk, u64 *p
                            const dec_scale_t &sc) {
     lm_prof_scope ps(ctx, "decrypt_phase_intt", (uint64_t)count * nl);
     return lm_launch(ctx, k_decrypt_phase<LOGN>, lm_geom_lds(LOGN), count * nl, ct, sk, phase, count, nl, sc, ctx->mods,
-                     ctx->d_tw_inv);
+                     ctx->sh->tw_inv.get());
 }
 
 int lm_decrypt_check(lumen_ctx *ctx, const lumen_set *set, uint64_t scale, const char *what) {
@@ -630,7 +614,7 @@ int lm_decrypt_decode(lumen_ctx *ctx, const lumen_set *set, lm_decoded *out) {
         const uint64_t q = ctx->mod[l < nl ? l : 0];
         sc.t[l] = h_tw(h_mulmod(ctx->ninv[l < nl ? l : 0].w, T % q, q), q);
     }
-    if (int rc = lm_for_logn(ctx, ctx->logN, [&](auto k) { return decrypt_phase_t<k>(ctx, set->d, sk->d_sk, phase, count, nl, sc); }))
+    if (int rc = lm_for_logn(ctx, ctx->logN, [&](auto k) { return decrypt_phase_t<k>(ctx, set->d, sk->d_sk.get(), phase, count, nl, sc); }))
         return rc;
     if (nl > 2) { // deeper than what Prove returns: exact CRT by mixed radix
         std::vector<garner_t> hg(1);
@@ -671,10 +655,10 @@ int lm_decrypt_decode(lumen_ctx *ctx, const lumen_set *set, lm_decoded *out) {
     }
     {
         lm_prof_scope ps(ctx, "decode_ntt_T", count);
-        if (int r2 = lm_launch_ntt_subring(ctx, ctx->logN, enc->d_tw_fwd, enc->ninvT, m, N, m, N, count, 0, false, &enc->modT))
+        if (int r2 = lm_launch_ntt_subring(ctx, ctx->logN, enc->d_tw_fwd.get(), enc->ninvT, m, N, m, N, count, 0, false, &enc->modT))
             return r2;
     }
-    out->t = m, out->slot = enc->d_slot;
+    out->t = m, out->slot = enc->d_slot.get();
     out->keep[0] = sk_hold, out->keep[1] = enc_hold;
     return 0;
 }

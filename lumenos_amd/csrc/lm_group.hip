@@ -739,8 +739,8 @@ extern "C" int lumen_group_all_gather_digests(lumen_group *g) {
         lumen_ctx *c = g->ctx[i];
         if (use(g, i)) return 1;
         auto it = c->scratch.find("digests_async");
-        LM_CHECK(nullptr, it != c->scratch.end() && it->second.first, "digest buffer missing");
-        src[i] = (const uint8_t *)it->second.first;
+        LM_CHECK(nullptr, it != c->scratch.end() && it->second, "digest buffer missing");
+        src[i] = it->second.get();
         g->d_digests[i] = (uint8_t *)lm_scratch(c, "group_digests", part * W);
         if (!g->d_digests[i]) return 1;
         // the job ends on the device: the main stream waits for the side stream, the host does not

@@ -559,8 +559,8 @@ extern "C" int lumen_leaf_digests_end_device(lumen_ctx *ctx, void **dev_digests)
     ctx->aux_lo = ctx->aux_hi = nullptr;
     LM_HIP(ctx, hipStreamSynchronize(ctx->stream_aux));
     auto it = ctx->scratch.find("digests_async");
-    LM_CHECK(ctx, it != ctx->scratch.end() && it->second.first, "digest buffer missing");
-    *dev_digests = it->second.first;
+    LM_CHECK(ctx, it != ctx->scratch.end() && it->second, "digest buffer missing");
+    *dev_digests = it->second.get();
     return 0;
 }
 

@@ -39,7 +39,7 @@
 #define LM_KG_UNIFORM_STREAM 16u
 
 int lm_d2h(lumen_ctx *ctx, void *host, const void *dev, size_t bytes, bool wait); // lm_ctx.hip
-void lm_install_secret_key_dev(lumen_ctx *ctx, tw_t *d_sk);                         // lm_encrypt.hip
+void lm_install_secret_key_dev(lumen_ctx *ctx, lm_dev<tw_t> &&d_sk);               // lm_encrypt.hip
 
 struct kg_lim_t {
     u64 t[LM_MAX_LIMBS]; // 2^64 - (2^64 mod q_m): words below it are kept
@@ -221,41 +221,16 @@ __global__ LM_GEOM_BOUNDS(lm_geom_lds(LOGN)) void k_keygen_evk(const int8_t *__r
 // ------------------------------------------------------------------------------------------------- host side
 // NTT(s) over QP in Montgomery form, kept by the context (and its clones) for the other keygen calls
 struct KgSecret {
-    u64 *d_mont = nullptr;
-    size_t bytes = 0;
-    ~KgSecret() {
-        if (d_mont) {
-            (void)hipMemset(d_mont, 0, bytes);
-            hipFree(d_mont);
-        }
-    }
+    lm_dev<u64> d_mont;
+    KgSecret() { d_mont.release_on(nullptr, true); } // zeroed (blocking) before the block is given back
 };
 
-// a device temporary; `secret` ones (s, its images, the errors) are zeroed before the block is given back
-struct kg_tmp {
-    lumen_ctx *ctx;
-    void *p = nullptr;
-    size_t bytes = 0;
-    bool secret;
-    kg_tmp(lumen_ctx *c, bool s) : ctx(c), secret(s) {}
-    int alloc(size_t n) {
-        bytes = n;
-        if (hipMalloc(&p, n ? n : 1) != hipSuccess) {
-            (void)hipGetLastError();
-            p = nullptr;
-            return lm_fail(ctx, "hipMalloc(%zu) for key generation failed", n);
-        }
-        return 0;
-    }
-    ~kg_tmp() {
-        if (!p) return;
-        if (secret) (void)hipMemsetAsync(p, 0, bytes, ctx->stream);
-        (void)hipStreamSynchronize(ctx->stream);
-        hipFree(p);
-    }
-    kg_tmp(const kg_tmp &) = delete;
-    kg_tmp &operator=(const kg_tmp &) = delete;
-};
+// a device temporary of a call: the context's stream is waited for before the block is given back, and `secret` ones
+// (s, its images, the errors) are zeroed on it first
+template <class T>
+static int kg_alloc(lumen_ctx *ctx, lm_dev<T> &d, size_t count, bool secret) {
+    return d.release_on(ctx->stream, secret).alloc(ctx, count, "key generation");
+}
 
 static enc_seed_t kg_seed(const uint8_t seed[32]) {
     enc_seed_t k;
@@ -304,7 +279,7 @@ static int kg_secret_ntt_t(lumen_ctx *ctx, const int8_t *small, u64 *mont, u64 *
     const uint32_t LK = ctx->L + ctx->K;
     lm_prof_scope ps(ctx, "keygen_secret_ntt", (uint64_t)nslots * LK);
     return lm_launch(ctx, k_keygen_secret_ntt<LOGN>, lm_geom_lds(LOGN), nslots * LK, small, mont, stdf, nslots, LK, loggap,
-                     ctx->mods, kg_rmont(ctx), ctx->d_tw_fwd);
+                     ctx->mods, kg_rmont(ctx), ctx->sh->tw_fwd.get());
 }
 template <int LOGN>
 static int kg_evk_t(lumen_ctx *ctx, const int8_t *small, u64 *out, const u64 *s_out, size_t sout_stride, const u64 *s_in,
@@ -312,7 +287,7 @@ static int kg_evk_t(lumen_ctx *ctx, const int8_t *small, u64 *out, const u64 *s_
     const uint32_t LK = ctx->L + ctx->K;
     lm_prof_scope ps(ctx, "keygen_evk_ntt", (uint64_t)nitems * LK);
     return lm_launch(ctx, k_keygen_evk<LOGN>, lm_geom_lds(LOGN), nitems * LK, small, out, s_out, sout_stride, s_in, fac, nitems,
-                     nent, LK, mont, ctx->mods, kg_rmont(ctx), ctx->d_tw_fwd);
+                     nent, LK, mont, ctx->mods, kg_rmont(ctx), ctx->sh->tw_fwd.get());
 }
 
 // nkeys keys of nent entries each in ONE launch of each kernel, then one download into the caller's buffer.
@@ -327,13 +302,14 @@ static int kg_run(lumen_ctx *ctx, const uint8_t seed[32], const std::vector<u64>
     for (uint32_t k = 0; k < nkeys; k++)
         for (uint32_t e = 0; e < nent; e++) tab[(size_t)k * nent + e] = key_ids[k] * LM_KG_INDEX_STRIDE + e;
     if (fac) tab.insert(tab.end(), fac->begin(), fac->end());
-    kg_tmp d_tab(ctx, false), d_out(ctx, false), d_e(ctx, true);
-    if (d_tab.alloc(tab.size() * 8) || d_out.alloc(out_words * 8) || d_e.alloc((size_t)nitems * N)) return 1;
-    if (int rc = kg_upload(ctx, d_tab.p, tab.data(), tab.size() * 8)) return rc;
-    const u64 *d_index = (const u64 *)d_tab.p, *d_fac = fac ? d_index + nitems : nullptr;
+    lm_dev<u64> d_tab, d_out;
+    lm_dev<int8_t> d_e;
+    if (kg_alloc(ctx, d_tab, tab.size(), false) || kg_alloc(ctx, d_out, out_words, false) || kg_alloc(ctx, d_e, (size_t)nitems * N, true)) return 1;
+    if (int rc = kg_upload(ctx, d_tab.get(), tab.data(), tab.size() * 8)) return rc;
+    const u64 *d_index = d_tab.get(), *d_fac = fac ? d_index + nitems : nullptr;
     {
         lm_prof_scope ps(ctx, "keygen_sample", nitems);
-        if (int rc = kg_small(ctx, (int8_t *)d_e.p, d_index, nitems, 1, seed)) return rc;
+        if (int rc = kg_small(ctx, d_e.get(), d_index, nitems, 1, seed)) return rc;
     }
     {
         lm_prof_scope ps(ctx, "keygen_uniform", (uint64_t)nitems * LK);
@@ -343,17 +319,17 @@ static int kg_run(lumen_ctx *ctx, const uint8_t seed[32], const std::vector<u64>
             lim.t[t] = 0 - ((0 - q) % q); // 2^64 - (2^64 mod q)
         }
         const uint32_t nb = N >> 3, bs = nb < 256 ? nb : 256;
-        hipLaunchKernelGGL(k_keygen_uniform, dim3(nb / bs, nitems * LK), dim3(bs), 0, ctx->stream, (u64 *)d_out.p, d_index, LK,
+        hipLaunchKernelGGL(k_keygen_uniform, dim3(nb / bs, nitems * LK), dim3(bs), 0, ctx->stream, d_out.get(), d_index, LK,
                            ctx->logN, ctx->mods, lim, kg_seed(seed));
         LM_HIP(ctx, hipGetLastError());
     }
     if (int rc = lm_for_logn(ctx, ctx->logN, [&](auto k) {
-            return kg_evk_t<k>(ctx, (const int8_t *)d_e.p, (u64 *)d_out.p, s_out, sout_stride, s_in, d_fac, nitems, nent,
+            return kg_evk_t<k>(ctx, d_e.get(), d_out.get(), s_out, sout_stride, s_in, d_fac, nitems, nent,
                                (flags & LUMEN_KEY_MONTGOMERY) ? 1u : 0u);
         }))
         return rc;
     lm_prof_scope ps(ctx, "keygen_download", nitems);
-    return lm_d2h(ctx, host_out, d_out.p, out_words * 8, true);
+    return lm_d2h(ctx, host_out, d_out.get(), out_words * 8, true);
 }
 
 static std::shared_ptr<KgSecret> kg_secret_of(lumen_ctx *ctx) { return lm_ext_get<KgSecret>(ctx, "keygen_secret"); }
@@ -380,32 +356,28 @@ extern "C" int lumen_keygen_secret(lumen_ctx *ctx, const uint8_t seed[32], uint6
     const uint32_t N = ctx->N, L = ctx->L, LK = L + ctx->K;
     const size_t words = (size_t)LK * N;
     auto sp = std::make_shared<KgSecret>();
-    sp->bytes = words * 8;
-    LM_HIP(ctx, hipMalloc((void **)&sp->d_mont, sp->bytes));
-    kg_tmp d_idx(ctx, false), d_small(ctx, true), d_std(ctx, true);
-    if (d_idx.alloc(8) || d_small.alloc(N) || d_std.alloc(words * 8)) return 1;
+    // d_sk, the decryptor's table: the first L limbs, exactly what lumen_load_secret_key would hold
+    lm_dev<tw_t> d_sk;
+    lm_dev<u64> d_idx, d_std;
+    lm_dev<int8_t> d_small;
+    if (sp->d_mont.alloc(ctx, words, "the generated secret") || d_sk.alloc(ctx, (size_t)L * N, "the secret key")) return 1;
+    if (kg_alloc(ctx, d_idx, 1, false) || kg_alloc(ctx, d_small, N, true) || kg_alloc(ctx, d_std, words, true)) return 1;
     const u64 index = LM_KG_ID_SECRET * LM_KG_INDEX_STRIDE;
-    if (int rc = kg_upload(ctx, d_idx.p, &index, 8)) return rc;
-    if (int rc = kg_small(ctx, (int8_t *)d_small.p, (const u64 *)d_idx.p, 1, 0, seed)) return rc;
+    if (int rc = kg_upload(ctx, d_idx.get(), &index, 8)) return rc;
+    if (int rc = kg_small(ctx, d_small.get(), d_idx.get(), 1, 0, seed)) return rc;
     if (int rc = lm_for_logn(ctx, ctx->logN, [&](auto k) {
-            return kg_secret_ntt_t<k>(ctx, (const int8_t *)d_small.p, sp->d_mont, (u64 *)d_std.p, 1, 0);
+            return kg_secret_ntt_t<k>(ctx, d_small.get(), sp->d_mont.get(), d_std.get(), 1, 0);
         }))
         return rc;
-    // the decryptor's table: the first L limbs, exactly what lumen_load_secret_key would hold
-    tw_t *d_sk = nullptr;
-    LM_HIP(ctx, hipMalloc((void **)&d_sk, (size_t)L * N * sizeof(tw_t)));
-    hipLaunchKernelGGL(k_keygen_shoup, dim3(256), dim3(256), 0, ctx->stream, (const u64 *)d_std.p, d_sk, ctx->logN,
-                       (size_t)L * N, ctx->mods);
+    hipLaunchKernelGGL(k_keygen_shoup, dim3(256), dim3(256), 0, ctx->stream, d_std.get(), d_sk.get(), ctx->logN, (size_t)L * N,
+                       ctx->mods);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess && sk) {
-        if (lm_d2h(ctx, sk, d_std.p, words * 8, true)) e = hipErrorUnknown;
+        if (lm_d2h(ctx, sk, d_std.get(), words * 8, true)) e = hipErrorUnknown;
     }
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) {
-        hipFree(d_sk);
-        return lm_fail(ctx, "lumen_keygen_secret failed: %s", hipGetErrorString(e));
-    }
-    lm_install_secret_key_dev(ctx, d_sk);
+    if (e != hipSuccess) return lm_fail(ctx, "lumen_keygen_secret failed: %s", hipGetErrorString(e));
+    lm_install_secret_key_dev(ctx, std::move(d_sk));
     lm_ext_put(ctx, "keygen_secret", sp);
     return 0;
 }
@@ -416,7 +388,7 @@ extern "C" int lumen_keygen_public(lumen_ctx *ctx, const uint8_t seed[32], uint6
     LM_CHECK(ctx, seed && pk, "lumen_keygen_public: NULL argument");
     const std::shared_ptr<KgSecret> s = kg_secret_of(ctx);
     LM_KG_NEED_SECRET(ctx, s, "lumen_keygen_public");
-    return kg_run(ctx, seed, {LM_KG_ID_PUBLIC}, 1, s->d_mont, 0, nullptr, nullptr, 0, pk);
+    return kg_run(ctx, seed, {LM_KG_ID_PUBLIC}, 1, s->d_mont.get(), 0, nullptr, nullptr, 0, pk);
 }
 
 extern "C" int lumen_keygen_relin(lumen_ctx *ctx, const uint8_t seed[32], uint64_t *evk, uint32_t flags) {
@@ -429,13 +401,13 @@ extern "C" int lumen_keygen_relin(lumen_ctx *ctx, const uint8_t seed[32], uint64
     LM_CHECK(ctx, !(flags & ~(uint32_t)LUMEN_KEY_MONTGOMERY), "lumen_keygen_relin: unknown flags 0x%x", flags);
     const uint32_t N = ctx->N, L = ctx->L, K = ctx->K, LK = L + K, beta = (L + K - 1) / K;
     const size_t words = (size_t)LK * N;
-    kg_tmp d_s2(ctx, true);
-    if (d_s2.alloc(words * 8)) return 1;
-    hipLaunchKernelGGL(k_keygen_square, dim3(256), dim3(256), 0, ctx->stream, s->d_mont, (u64 *)d_s2.p, ctx->logN, words,
+    lm_dev<u64> d_s2;
+    if (kg_alloc(ctx, d_s2, words, true)) return 1;
+    hipLaunchKernelGGL(k_keygen_square, dim3(256), dim3(256), 0, ctx->stream, s->d_mont.get(), d_s2.get(), ctx->logN, words,
                        ctx->mods);
     LM_HIP(ctx, hipGetLastError());
     const std::vector<u64> fac = kg_gadget(ctx, beta, 1, 0);
-    return kg_run(ctx, seed, {LM_KG_ID_RELIN}, beta, s->d_mont, 0, (const u64 *)d_s2.p, &fac, flags, evk);
+    return kg_run(ctx, seed, {LM_KG_ID_RELIN}, beta, s->d_mont.get(), 0, d_s2.get(), &fac, flags, evk);
 }
 
 extern "C" int lumen_keygen_galois(lumen_ctx *ctx, const uint8_t seed[32], const uint64_t *gal_els, uint32_t count,
@@ -467,15 +439,16 @@ extern "C" int lumen_keygen_galois(lumen_ctx *ctx, const uint8_t seed[32], const
         ids[c] = LM_KG_ID_GALOIS + g;
     }
     const size_t words = (size_t)count * LK * N;
-    kg_tmp d_index(ctx, false), d_sout(ctx, true);
-    if (d_index.alloc(index.size() * 4) || d_sout.alloc(words * 8)) return 1;
-    LM_HIP(ctx, hipMemcpyAsync(d_index.p, index.data(), index.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+    lm_dev<uint32_t> d_index;
+    lm_dev<u64> d_sout;
+    if (kg_alloc(ctx, d_index, index.size(), false) || kg_alloc(ctx, d_sout, words, true)) return 1;
+    LM_HIP(ctx, hipMemcpyAsync(d_index.get(), index.data(), index.size() * 4, hipMemcpyHostToDevice, ctx->stream));
     LM_HIP(ctx, hipStreamSynchronize(ctx->stream)); // `index` is pageable host memory
-    hipLaunchKernelGGL(k_keygen_gather, dim3(1024), dim3(256), 0, ctx->stream, s->d_mont, (const uint32_t *)d_index.p,
-                       (u64 *)d_sout.p, LK, ctx->logN, words);
+    hipLaunchKernelGGL(k_keygen_gather, dim3(1024), dim3(256), 0, ctx->stream, s->d_mont.get(), d_index.get(), d_sout.get(),
+                       LK, ctx->logN, words);
     LM_HIP(ctx, hipGetLastError());
     const std::vector<u64> fac = kg_gadget(ctx, beta, 1, 0);
-    return kg_run(ctx, seed, ids, beta, (const u64 *)d_sout.p, (size_t)LK * N, s->d_mont, &fac, flags, evk);
+    return kg_run(ctx, seed, ids, beta, d_sout.get(), (size_t)LK * N, s->d_mont.get(), &fac, flags, evk);
 }
 
 extern "C" int lumen_keygen_ringswitch(lumen_ctx *ctx, const uint8_t seed[32], uint32_t log_n_small, uint32_t base_two_w,
@@ -496,18 +469,19 @@ extern "C" int lumen_keygen_ringswitch(lumen_ctx *ctx, const uint8_t seed[32], u
     LM_CHECK(ctx, key_words == whole, "lumen_keygen_ringswitch: key of %zu words: expected %zu ([rns = %u][pw2 = %u][2][L+K = %u][N = %u])",
              key_words, whole, rns, pw2, LK, N);
     const size_t n = (size_t)1 << log_n_small, words = (size_t)LK * N;
-    kg_tmp d_idx(ctx, false), d_small(ctx, true), d_sout(ctx, true);
-    if (d_idx.alloc(8) || d_small.alloc(N) || d_sout.alloc(words * 8)) return 1;
+    lm_dev<u64> d_idx, d_sout;
+    lm_dev<int8_t> d_small;
+    if (kg_alloc(ctx, d_idx, 1, false) || kg_alloc(ctx, d_small, N, true) || kg_alloc(ctx, d_sout, words, true)) return 1;
     const u64 index = LM_KG_ID_RINGSWITCH * LM_KG_INDEX_STRIDE;
-    if (int rc = kg_upload(ctx, d_idx.p, &index, 8)) return rc;
-    if (int rc = kg_small(ctx, (int8_t *)d_small.p, (const u64 *)d_idx.p, 1, 0, seed)) return rc;
+    if (int rc = kg_upload(ctx, d_idx.get(), &index, 8)) return rc;
+    if (int rc = kg_small(ctx, d_small.get(), d_idx.get(), 1, 0, seed)) return rc;
     // skNew(X^(N/n)) over QP
     if (int rc = lm_for_logn(ctx, ctx->logN, [&](auto k) {
-            return kg_secret_ntt_t<k>(ctx, (const int8_t *)d_small.p, (u64 *)d_sout.p, nullptr, 1, ctx->logN - log_n_small);
+            return kg_secret_ntt_t<k>(ctx, d_small.get(), d_sout.get(), nullptr, 1, ctx->logN - log_n_small);
         }))
         return rc;
-    LM_HIP(ctx, hipMemcpyAsync(sk_small, d_small.p, n, hipMemcpyDeviceToHost, ctx->stream));
+    LM_HIP(ctx, hipMemcpyAsync(sk_small, d_small.get(), n, hipMemcpyDeviceToHost, ctx->stream));
     LM_HIP(ctx, hipStreamSynchronize(ctx->stream)); // caller memory
     const std::vector<u64> fac = kg_gadget(ctx, rns, pw2, hybrid ? 0 : base_two_w);
-    return kg_run(ctx, seed, {LM_KG_ID_RINGSWITCH}, rns * pw2, (const u64 *)d_sout.p, 0, s->d_mont, &fac, 0, key);
+    return kg_run(ctx, seed, {LM_KG_ID_RINGSWITCH}, rns * pw2, d_sout.get(), 0, s->d_mont.get(), &fac, 0, key);
 }

@@ -609,12 +609,9 @@ int get_tables(lumen_ctx *ctx, KsTables **out) {
         for (uint32_t d = 0; d < tb.beta; d++)
             if (!bx[(size_t)d * LK + t].own) pairs.push_back((uint16_t)(d | (t << 8)));
     tb.pairs = pairs;
-    LM_HIP(ctx, hipMalloc((void **)&tb.d_bx, bx.size() * sizeof(bx_t)));
-    LM_HIP(ctx, hipMalloc((void **)&tb.d_bxp, bxp.size() * sizeof(bx_t)));
-    LM_HIP(ctx, hipMalloc((void **)&tb.d_pinv, pinv.size() * sizeof(tw_t)));
-    LM_HIP(ctx, hipMemcpy(tb.d_bx, bx.data(), bx.size() * sizeof(bx_t), hipMemcpyHostToDevice));
-    LM_HIP(ctx, hipMemcpy(tb.d_bxp, bxp.data(), bxp.size() * sizeof(bx_t), hipMemcpyHostToDevice));
-    LM_HIP(ctx, hipMemcpy(tb.d_pinv, pinv.data(), pinv.size() * sizeof(tw_t), hipMemcpyHostToDevice));
+    if (tb.d_bx.upload(ctx, bx, "the key switch's extension constants") || tb.d_bxp.upload(ctx, bxp, "the key switch's lift constants") ||
+        tb.d_pinv.upload(ctx, pinv, "the key switch's P^-1 table"))
+        return 1;
     ctx->ext["ks_tables"] = sp;
     *out = sp.get();
     return 0;
@@ -623,8 +620,8 @@ int get_tables(lumen_ctx *ctx, KsTables **out) {
 int lm_ks_tables_view(lumen_ctx *ctx, lm_ks_view *out) {
     KsTables *tb = nullptr;
     if (int rc = get_tables(ctx, &tb)) return rc;
-    out->d_bxp = tb->d_bxp;
-    out->d_pinv = tb->d_pinv;
+    out->d_bxp = tb->d_bxp.get();
+    out->d_pinv = tb->d_pinv.get();
     out->yscale = &tb->yscale;
     return 0;
 }
@@ -642,7 +639,7 @@ namespace {
 // Tail of both work-list builders below.  Workgroup k of a launch runs on XCD k % 8, so the eight per-XCD lists are
 // interleaved (lists of unequal length -- B not a multiple of 8 -- are drained in turn); the device copy is cached.
 static int interleave_work_lists(lumen_ctx *ctx, const std::vector<std::vector<uint32_t>> &lists, size_t expect,
-                                 const char *what, std::map<uint32_t, uint32_t *> &cache, uint32_t cache_key,
+                                 const char *what, std::map<uint32_t, lm_dev<uint32_t>> &cache, uint32_t cache_key,
                                  const uint32_t **out) {
     std::vector<uint32_t> order;
     order.reserve(expect);
@@ -656,10 +653,9 @@ static int interleave_work_lists(lumen_ctx *ctx, const std::vector<std::vector<u
             }
     }
     LM_CHECK(ctx, order.size() == expect, "%s work list is inconsistent", what);
-    uint32_t *d = nullptr;
-    LM_HIP(ctx, hipMalloc((void **)&d, order.size() * sizeof(uint32_t)));
-    LM_HIP(ctx, hipMemcpy(d, order.data(), order.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    *out = cache[cache_key] = d;
+    lm_dev<uint32_t> d;
+    if (int rc = d.upload(ctx, order, "a key-switch work list")) return rc;
+    *out = (cache[cache_key] = std::move(d)).get();
     return 0;
 }
 
@@ -680,7 +676,7 @@ static int modup_work_list(lumen_ctx *ctx, KsTables *tb, uint32_t B, const uint3
     const uint32_t cache_key = B | (LM_MODUP_TGROUP << 16);
     auto it = tb->d_work.find(cache_key);
     if (it != tb->d_work.end()) {
-        *out = it->second;
+        *out = it->second.get();
         return 0;
     }
     const uint32_t LK = ctx->L + ctx->K, beta = tb->beta;
@@ -706,7 +702,7 @@ static int moddown_work_list(lumen_ctx *ctx, KsTables *tb, uint32_t B, const uin
     const uint32_t cache_key = B | (LM_MODDOWN_TGROUP << 17);
     auto it = tb->d_work_down.find(cache_key);
     if (it != tb->d_work_down.end()) {
-        *out = it->second;
+        *out = it->second.get();
         return 0;
     }
     const uint32_t L = ctx->L;
@@ -797,7 +793,7 @@ int rotate_accumulate(lumen_ctx *ctx, const u64 *acc, u64 *acc_out, uint32_t B, 
         lm_prof_scope ps(ctx, "ks_intt_c1", (uint64_t)B * L);
         if (int rc = lm_for_logn(ctx, ctx->logN, [&](auto n) {
                 return lm_launch(ctx, k_intt_pack<n>, lm_geom_lds(n), grid, acc, s.coef, B, L, nf, ctx->mods, tb->yscale,
-                                 ctx->d_tw_inv);
+                                 ctx->sh->tw_inv.get());
             }))
             return rc;
     } else {
@@ -818,15 +814,15 @@ int rotate_accumulate(lumen_ctx *ctx, const u64 *acc, u64 *acc_out, uint32_t B, 
         if (int rc = modup_work_list(ctx, tb, B, &work)) return rc;
         lm_prof_scope ps(ctx, "ks_modup_ntt", nb);
         if (int rc = lm_for_logn(ctx, ctx->logN, [&](auto n) {
-                return lm_launch(ctx, k_modup_ntt<n>, lm_geom_fwd(n), (uint32_t)nb, s.coef, acc, s.ext, tb->d_bx, B, L, K, beta,
-                                 work, ctx->mods, ctx->d_tw_fwd);
+                return lm_launch(ctx, k_modup_ntt<n>, lm_geom_fwd(n), (uint32_t)nb, s.coef, acc, s.ext, tb->d_bx.get(), B, L, K, beta,
+                                 work, ctx->mods, ctx->sh->tw_fwd.get());
             }))
             return rc;
     }
     // 3. gadget product
     {
         lm_prof_scope ps(ctx, "ks_mac", (uint64_t)B);
-        hipLaunchKernelGGL(k_ks_mac, ks_mac_grid(ctx, B), dim3(256), 0, ctx->stream, s.ext, acc, gk.d_key, s.u, B, L, K,
+        hipLaunchKernelGGL(k_ks_mac, ks_mac_grid(ctx, B), dim3(256), 0, ctx->stream, s.ext, acc, gk.d_key.get(), s.u, B, L, K,
                            beta, ctx->logN, ctx->mods);
         LM_HIP(ctx, hipGetLastError());
     }
@@ -850,8 +846,8 @@ int rotate_accumulate(lumen_ctx *ctx, const u64 *acc, u64 *acc_out, uint32_t B, 
         if (int rc = moddown_work_list(ctx, tb, B, &work_down)) return rc;
         lm_prof_scope ps(ctx, "ks_moddown_ntt", (uint64_t)B * 2 * L);
         return lm_for_logn(ctx, ctx->logN, [&](auto n) {
-            return lm_launch(ctx, k_moddown_ntt<n>, lm_geom_lds(n), B * 2 * L, s.u, acc, acc_out, tb->d_bxp, tb->d_pinv,
-                             gk.d_index, gk.d_inv_index, work_down, B, L, K, ctx->mods, ctx->d_tw_fwd);
+            return lm_launch(ctx, k_moddown_ntt<n>, lm_geom_lds(n), B * 2 * L, s.u, acc, acc_out, tb->d_bxp.get(), tb->d_pinv.get(),
+                             gk.d_index.get(), gk.d_inv_index.get(), work_down, B, L, K, ctx->mods, ctx->sh->tw_fwd.get());
         });
     }
 }
@@ -862,17 +858,17 @@ int inner_sum_batch(lumen_ctx *ctx, u64 *acc, uint32_t B, uint32_t n, KsTables *
     uint64_t gal[64];
     const uint32_t cnt = lumen_inner_sum_galois_elements(ctx, n, gal);
     for (uint32_t r = 0; r < cnt; r++) {
-        lm_galois_key gk;
+        const lm_galois_key *gk; // (an entry of the map never moves or goes, and a key loaded again keeps its blocks)
         {
             LM_SHARED_LOCK(ctx);
             auto it = ctx->gkeys.find(gal[r]);
             LM_CHECK(ctx, it != ctx->gkeys.end(), "Galois key for element %llu not loaded",
                      (unsigned long long)gal[r]);
-            gk = it->second;
+            gk = &it->second;
         }
         // ping-pong: the automorphism reads two positions of the old accumulator per output
         u64 *src = (r & 1) ? s.acc2 : acc, *dst = (r & 1) ? acc : s.acc2;
-        if (int rc = rotate_accumulate(ctx, src, dst, B, gk, tb, s)) return rc;
+        if (int rc = rotate_accumulate(ctx, src, dst, B, *gk, tb, s)) return rc;
     }
     if (cnt & 1)
         LM_HIP(ctx, hipMemcpyAsync(acc, s.acc2, (size_t)B * 2 * ctx->L * ctx->N * 8, hipMemcpyDeviceToDevice,
@@ -901,7 +897,7 @@ extern "C" int lumen_ks_mac_probe(lumen_ctx *ctx, uint32_t batch, const void *ex
     if (!key) {
         LM_SHARED_LOCK(ctx);
         LM_CHECK(ctx, !ctx->gkeys.empty(), "lumen_ks_mac_probe: no Galois key loaded");
-        key = ctx->gkeys.begin()->second.d_key;
+        key = ctx->gkeys.begin()->second.d_key.get();
     }
     const u64 *pe = ext ? (const u64 *)ext : s.ext;
     u64 *pu = u ? (u64 *)u : s.u;

@@ -5,21 +5,14 @@
 
 // per-context constants of the key switch and its cached work lists (lm_keyswitch.hip)
 struct KsTables {
-    bx_t *d_bx = nullptr;    // [beta][L+K]
-    bx_t *d_bxp = nullptr;   // [L]  (P -> q_t)
-    tw_t *d_pinv = nullptr;  // [L]  P^-1 mod q_t
+    lm_dev<bx_t> d_bx;   // [beta][L+K]
+    lm_dev<bx_t> d_bxp;  // [L]  (P -> q_t)
+    lm_dev<tw_t> d_pinv; // [L]  P^-1 mod q_t
     uint32_t beta = 0;
     lm_ninv_t yscale; // per modulus: N^-1 * (M/m)^-1 mod m of the source group the modulus sits in
     std::vector<uint16_t> pairs; // (digit | target << 8) of every extension the key switch needs, target-major
-    std::map<uint32_t, uint32_t *> d_work; // per batch size: the workgroup order of the extension kernel
-    std::map<uint32_t, uint32_t *> d_work_down; // ... and of the ModDown kernel
-    ~KsTables() {
-        for (auto &kv : d_work) hipFree(kv.second);
-        for (auto &kv : d_work_down) hipFree(kv.second);
-        hipFree(d_bx);
-        hipFree(d_bxp);
-        hipFree(d_pinv);
-    }
+    std::map<uint32_t, lm_dev<uint32_t>> d_work; // per batch size: the workgroup order of the extension kernel
+    std::map<uint32_t, lm_dev<uint32_t>> d_work_down; // ... and of the ModDown kernel
 };
 int get_tables(lumen_ctx *ctx, KsTables **out);
 

@@ -63,23 +63,21 @@ extern "C" int lumen_load_galois_key_ex(lumen_ctx *ctx, uint64_t gal_el, const u
         }
         fac.t[t] = h_tw(r, q);
     }
-    u64 *raw = (u64 *)lm_scratch(ctx, "key_raw", words * 8);
+    lm_dev<u64> raw, d_new; // the staging copy of the host words, and the key in the gadget product's form
     uint32_t *bad = (uint32_t *)lm_scratch(ctx, "key_bad", 4);
-    if (!raw || !bad) return 1;
+    if (!bad || raw.alloc(ctx, words, "the staging copy of a Galois key")) return 1;
     LM_HIP(ctx, hipMemsetAsync(bad, 0xFF, 4, ctx->stream));
-    if (int rc = lm_h2d(ctx, raw, evk, words * 8)) return rc; // returns when evk may be reused
-    u64 *d_new = nullptr;
-    LM_HIP(ctx, hipMalloc((void **)&d_new, words * 8));
-    hipLaunchKernelGGL(k_key_prepare, dim3(2048), dim3(256), 0, ctx->stream, raw, d_new, ctx->logN, LK, words, ctx->mods, fac, bad);
+    if (int rc = lm_h2d(ctx, raw.get(), evk, words * 8)) return rc; // returns when evk may be reused
+    if (int rc = d_new.alloc(ctx, words, "a Galois key")) return rc;
+    hipLaunchKernelGGL(k_key_prepare, dim3(2048), dim3(256), 0, ctx->stream, raw.get(), d_new.get(), ctx->logN, LK, words, ctx->mods, fac,
+                       bad);
     uint32_t first_bad = 0;
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(&first_bad, bad, 4, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess || first_bad != 0xFFFFFFFFu) {
-        hipFree(d_new);
-        if (e != hipSuccess) return lm_fail(ctx, "key conversion failed: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return lm_fail(ctx, "key conversion failed: %s", hipGetErrorString(e));
+    if (first_bad != 0xFFFFFFFFu)
         return lm_fail(ctx, "key residue out of range (digit %u limb %u)", first_bad / (2 * LK), first_bad % LK);
-    }
     std::vector<uint32_t> index(N);
     const uint64_t mask = 2ull * N - 1;
     for (uint32_t i = 0; i < N; i++) { // [LATTIGO-RECALL] ring.AutomorphismNTTIndex
@@ -87,13 +85,7 @@ extern "C" int lumen_load_galois_key_ex(lumen_ctx *ctx, uint64_t gal_el, const u
         const uint64_t t2 = ((gal_el * t1 & mask) - 1) >> 1;
         index[i] = h_bitrev((uint32_t)t2, (int)ctx->logN);
     }
-    { // the staging copy of the host words has served (the stream is idle): do not keep a key-sized block per context
-        auto it = ctx->scratch.find("key_raw");
-        if (it != ctx->scratch.end()) {
-            hipFree(it->second.first);
-            ctx->scratch.erase(it);
-        }
-    }
+    raw.reset(); // the staging copy has served (the stream is idle)
     LM_SHARED_LOCK(ctx);
     lm_galois_key &gk = ctx->gkeys[gal_el];
     if (gk.d_key) {
@@ -102,19 +94,18 @@ extern "C" int lumen_load_galois_key_ex(lumen_ctx *ctx, uint64_t gal_el, const u
         // block (same size: it only depends on the parameters).  A clone computing at this very moment sees old or
         // new words -- the documented "do not reconfigure under a running clone" -- but never freed memory.
         lm_sync_all(ctx);
-        hipError_t ce = hipMemcpyAsync(gk.d_key, d_new, words * 8, hipMemcpyDeviceToDevice, ctx->stream);
+        hipError_t ce = hipMemcpyAsync(gk.d_key.get(), d_new.get(), words * 8, hipMemcpyDeviceToDevice, ctx->stream);
         if (ce == hipSuccess) ce = hipStreamSynchronize(ctx->stream);
-        hipFree(d_new);
+        d_new.reset();
         LM_CHECK(ctx, ce == hipSuccess, "replacing Galois key %llu failed: %s", (unsigned long long)gal_el, hipGetErrorString(ce));
     } else {
-        gk.d_key = d_new;
+        gk.d_key = std::move(d_new);
     }
-    if (!gk.d_index) LM_HIP(ctx, hipMalloc((void **)&gk.d_index, (size_t)N * 4));
-    if (!gk.d_inv_index) LM_HIP(ctx, hipMalloc((void **)&gk.d_inv_index, (size_t)N * 4));
+    // the gather tables depend on the element alone: a key loaded again keeps them
     std::vector<uint32_t> inv_index(N);
     for (uint32_t i = 0; i < N; i++) inv_index[index[i]] = i;
-    LM_HIP(ctx, hipMemcpy(gk.d_inv_index, inv_index.data(), (size_t)N * 4, hipMemcpyHostToDevice));
-    LM_HIP(ctx, hipMemcpy(gk.d_index, index.data(), (size_t)N * 4, hipMemcpyHostToDevice));
+    if (!gk.d_inv_index && gk.d_inv_index.upload(ctx, inv_index, "an automorphism's index table")) return 1;
+    if (!gk.d_index && gk.d_index.upload(ctx, index, "an automorphism's index table")) return 1;
     return 0;
 }
 

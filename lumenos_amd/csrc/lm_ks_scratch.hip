@@ -18,13 +18,6 @@ struct EventPair { // two pooled events
     explicit EventPair(lumen_ctx *c) : ctx(c), e0(lm_ev_get(c)), e1(lm_ev_get(c)) {}
     ~EventPair() { ctx->ev_pool.push_back(e0), ctx->ev_pool.push_back(e1); }
 };
-struct DevBlock { // the probe accumulator
-    void *p = nullptr;
-    ~DevBlock() {
-        hipFree(p);
-        (void)hipGetLastError();
-    }
-};
 
 } // namespace
 
@@ -61,14 +54,14 @@ int get_scratch(lumen_ctx *ctx, uint32_t B, KsTables *tb, KsScratch *s, int lane
     bool have = true;
     for (int c = 0; c < NB; c++) {
         auto it = ctx->scratch.find(names[lane][c]);
-        const bool there = it != ctx->scratch.end() && it->second.first && it->second.second >= bytes[c];
-        bufs.push_back({bytes[c], there ? it->second.first : nullptr, c == 4 ? 4u : Kc}); // (the group accumulator is the big one: four draws)
+        const bool there = it != ctx->scratch.end() && it->second && it->second.count() >= bytes[c];
+        bufs.push_back({bytes[c], there ? it->second.get() : nullptr, c == 4 ? 4u : Kc}); // (the group accumulator is the big one: four draws)
         have = have && there;
     }
-    lm_galois_key gk;
+    const lm_galois_key *gk = nullptr;
     {
         LM_SHARED_LOCK(ctx);
-        if (!ctx->gkeys.empty()) gk = ctx->gkeys.begin()->second;
+        if (!ctx->gkeys.empty()) gk = &ctx->gkeys.begin()->second;
     }
     auto plain = [&]() -> int {
         bool ok = true;
@@ -76,19 +69,19 @@ int get_scratch(lumen_ctx *ctx, uint32_t B, KsTables *tb, KsScratch *s, int lane
         return ok ? 0 : 1;
     };
     // small buffers live in the caches, and without a key no rotation can be timed: plain allocation
-    if (have || Kc < 2 || bytes[1] < ((size_t)64 << 20) || !gk.d_key) return plain();
+    if (have || Kc < 2 || bytes[1] < ((size_t)64 << 20) || !gk || !gk->d_key) return plain();
     { // the selection: whatever it drew and did not hand out is freed when this scope ends, on every path
         size_t free_b = 0, total_b = 0;
         (void)hipMemGetInfo(&free_b, &total_b);
-        DevBlock probe_acc;
-        if (!group_acc && hipMalloc(&probe_acc.p, bytes[3]) != hipSuccess) probe_acc.p = nullptr;
+        lm_dev<u64> probe_acc;
+        if (!group_acc) (void)probe_acc.alloc(ctx, bytes[3] / 8, "the placement's probe accumulator");
         lm_placement place(bufs, [](void *p) { hipFree(p); });
         const bool drew = place.draw(Kc, free_b, [&](size_t c) {
             void *p = nullptr;
             return hipMalloc(&p, bytes[c]) == hipSuccess ? p : nullptr;
         });
         (void)hipGetLastError();
-        if (drew && (group_acc || probe_acc.p)) { // otherwise memory is short: no choice to make
+        if (drew && (group_acc || probe_acc)) { // otherwise memory is short: no choice to make
             int rc;
             {
                 ProfOff quiet(ctx);
@@ -99,13 +92,13 @@ int get_scratch(lumen_ctx *ctx, uint32_t B, KsTables *tb, KsScratch *s, int lane
                     KsScratch t;
                     t.coef = (u64 *)place.block(0, pick[0]), t.ext = (u64 *)place.block(1, pick[1]), t.u = (u64 *)place.block(2, pick[2]),
                     t.acc2 = (u64 *)place.block(3, pick[3]);
-                    u64 *a0 = group_acc ? (u64 *)place.block(4, pick[4]) : (u64 *)probe_acc.p;
+                    u64 *a0 = group_acc ? (u64 *)place.block(4, pick[4]) : probe_acc.get();
                     u64 *a1 = group_acc ? a0 + (bytes[4] - bytes[3]) / 8 : a0;
                     for (int r = 0; r < 3; r++) {
                         if (r == 1) LM_HIP(ctx, hipEventRecord(ev.e0, ctx->stream));
                         u64 *a = r == 2 ? a1 : a0;
-                        if (int e = rotate_accumulate(ctx, a, t.acc2, B, gk, tb, t)) return e;
-                        if (int e = rotate_accumulate(ctx, t.acc2, a, B, gk, tb, t)) return e;
+                        if (int e = rotate_accumulate(ctx, a, t.acc2, B, *gk, tb, t)) return e;
+                        if (int e = rotate_accumulate(ctx, t.acc2, a, B, *gk, tb, t)) return e;
                     }
                     LM_HIP(ctx, hipEventRecord(ev.e1, ctx->stream));
                     LM_HIP(ctx, hipEventSynchronize(ev.e1));

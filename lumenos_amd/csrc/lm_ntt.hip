@@ -94,7 +94,7 @@ int lm_launch_ntt_strided(lumen_ctx *ctx, const u64 *src, size_t src_poly_stride
     LM_CHECK(ctx, nblocks64 < (1ull << 31), "NTT grid too large: %llu", (unsigned long long)nblocks64);
     lm_prof_scope ps(ctx, prof_name ? prof_name : (inverse ? "limb_intt" : "limb_ntt"), nblocks64);
     return launch_limb_ntt(ctx, ctx->logN, inverse, (uint32_t)nblocks64, src, src_poly_stride, dst, dst_poly_stride, npoly,
-                           map, ctx->mods, ninv, inverse ? ctx->d_tw_inv : ctx->d_tw_fwd);
+                           map, ctx->mods, ninv, inverse ? ctx->sh->tw_inv.get() : ctx->sh->tw_fwd.get());
 }
 
 int lm_launch_ntt(lumen_ctx *ctx, u64 *d, uint32_t npoly, const lm_modmap &map, bool inverse) {

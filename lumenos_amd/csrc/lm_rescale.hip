@@ -83,11 +83,8 @@ struct rs_half_t {
     u64 h[LM_MAX_LIMBS]; // (q_l - 1) / 2
 };
 struct RescaleTables {
-    rs_step_t *d_steps = nullptr; // [LM_MAX_LIMBS][LM_MAX_LIMBS], entry l * LM_MAX_LIMBS + j for j < l
+    lm_dev<rs_step_t> d_steps; // [LM_MAX_LIMBS][LM_MAX_LIMBS], entry l * LM_MAX_LIMBS + j for j < l
     rs_half_t half;
-    ~RescaleTables() {
-        if (d_steps) hipFree(d_steps);
-    }
 };
 
 static int get_rescale_tables(lumen_ctx *ctx, RescaleTables **out) {
@@ -115,8 +112,7 @@ static int get_rescale_tables(lumen_ctx *ctx, RescaleTables **out) {
             e.inv = h_tw(h_invmod(ql % qj, qj), qj);
         }
     }
-    LM_HIP(ctx, hipMalloc((void **)&sp->d_steps, steps.size() * sizeof(rs_step_t)));
-    LM_HIP(ctx, hipMemcpy(sp->d_steps, steps.data(), steps.size() * sizeof(rs_step_t), hipMemcpyHostToDevice));
+    if (int rc = sp->d_steps.upload(ctx, steps, "the rescale tables")) return rc;
     ctx->ext["rescale_tables"] = sp;
     *out = sp.get();
     return 0;
@@ -171,7 +167,7 @@ static int rescale_polys_coef(lumen_ctx *ctx, const u64 *src, uint32_t nl, u64 *
         const size_t total = (size_t)npoly * N;
         hipLaunchKernelGGL(k_rescale_coef, dim3((uint32_t)((total + 255) / 256)), dim3(256), 0, ctx->stream, work,
                            (size_t)nl * N, dst, (size_t)target * N, nl, target, ctx->logN, total, ctx->mods,
-                           tb->d_steps, tb->half);
+                           tb->d_steps.get(), tb->half);
         LM_HIP(ctx, hipGetLastError());
     }
     return lm_launch_ntt_strided(ctx, dst, (size_t)target * N, dst, (size_t)target * N, npoly, lm_map_q(target), false,
@@ -204,13 +200,13 @@ static int rescale_polys_t(lumen_ctx *ctx, const u64 *src, uint32_t nl, u64 *dst
         {
             lm_prof_scope ps(ctx, "rescale_last_intt", npoly);
             if (int e = lm_launch(ctx, k_rescale_last<LOGN>, lm_geom_lds(LOGN), npoly, cur, (size_t)nl * N, last, tbuf,
-                                  ctx->mods.m[last], ctx->ninv[last], (u64)rc.half, ctx->d_tw_inv + (size_t)last * N))
+                                  ctx->mods.m[last], ctx->ninv[last], (u64)rc.half, ctx->sh->tw_inv.get() + (size_t)last * N))
                 return e;
         }
         {
             lm_prof_scope ps(ctx, "rescale_limb_ntt", (uint64_t)npoly * last);
             if (int e = lm_launch(ctx, k_rescale_limb<LOGN>, lm_geom_lds(LOGN), npoly * last, cur, (size_t)nl * N, out,
-                                  out_stride, tbuf, npoly, ctx->mods, rc, ctx->d_tw_fwd))
+                                  out_stride, tbuf, npoly, ctx->mods, rc, ctx->sh->tw_fwd.get()))
                 return e;
         }
         cur = work;

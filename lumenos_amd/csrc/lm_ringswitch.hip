@@ -25,15 +25,10 @@ int lm_d2h(lumen_ctx *ctx, void *host, const void *dev, size_t bytes, bool wait)
 namespace {
 
 struct RsKey {
-    u64 *d_key = nullptr; // [nd][2][1+K][N], Montgomery form: RNS digit 0 of the key, limbs {q_0, P}
-    tw_t *d_tw_small = nullptr, *d_tw_small_inv = nullptr;
+    lm_dev<u64> d_key; // [nd][2][1+K][N], Montgomery form: RNS digit 0 of the key, limbs {q_0, P}
+    lm_dev<tw_t> d_tw_small, d_tw_small_inv;
     uint32_t nd = 0, w = 0, logn = 0; // nd power-of-two digits of w bits (nd = 1, w = 0: the hybrid path)
     tw_t ninv_small;
-    ~RsKey() {
-        hipFree(d_key);
-        hipFree(d_tw_small);
-        hipFree(d_tw_small_inv);
-    }
 };
 
 } // namespace
@@ -213,17 +208,14 @@ extern "C" int lumen_load_ringswitch_key(lumen_ctx *ctx, uint32_t log_n_small, u
                     mont[off + k] = h_mulmod(src[k], r, q);
                 }
             }
-    LM_HIP(ctx, hipMalloc((void **)&sp->d_key, words * 8));
-    LM_HIP(ctx, hipMemcpy(sp->d_key, mont.data(), words * 8, hipMemcpyHostToDevice));
+    if (int rc = sp->d_key.upload(ctx, mont, "the ring-switch key")) return rc;
     // small ring tables on q_0: psi_small = psi^(N/n)
     const uint32_t n = 1u << log_n_small;
     const uint64_t q0 = ctx->mod[0], psi = h_powmod(ctx->psi[0], N / n, q0);
     std::vector<tw_t> f, b;
     lm_build_tw(q0, psi, log_n_small, f, b); // the layout the transforms of that degree expect
-    LM_HIP(ctx, hipMalloc((void **)&sp->d_tw_small, n * sizeof(tw_t)));
-    LM_HIP(ctx, hipMalloc((void **)&sp->d_tw_small_inv, n * sizeof(tw_t)));
-    LM_HIP(ctx, hipMemcpy(sp->d_tw_small, f.data(), n * sizeof(tw_t), hipMemcpyHostToDevice));
-    LM_HIP(ctx, hipMemcpy(sp->d_tw_small_inv, b.data(), n * sizeof(tw_t), hipMemcpyHostToDevice));
+    if (sp->d_tw_small.upload(ctx, f, "the small ring's twiddles") || sp->d_tw_small_inv.upload(ctx, b, "the small ring's twiddles"))
+        return 1;
     sp->ninv_small = h_tw(h_invmod(n % q0, q0), q0);
     lm_ext_put(ctx, "ringswitch_key", sp);
     return 0;
@@ -242,18 +234,18 @@ static int ring_switch_batch(lumen_ctx *ctx, RsKey *rk, const lm_ks_view &kv, co
     if (hybrid) {
         lm_prof_scope ps(ctx, "rs_digit_ntt", (uint64_t)B * K);
         if (int rc = lm_launch(ctx, k_rs_digit_ntt<LOGN, true>, geom, B * K, coef, ext, B, 1u, nt, L, 0u, ctx->mods,
-                               ctx->d_tw_fwd))
+                               ctx->sh->tw_fwd.get()))
             return rc;
     } else {
         lm_prof_scope ps(ctx, "rs_digit_ntt", (uint64_t)B * nd * nt);
         if (int rc = lm_launch(ctx, k_rs_digit_ntt<LOGN, false>, geom, B * nd * nt, coef, ext, B, nd, nt, L, rk->w,
-                               ctx->mods, ctx->d_tw_fwd))
+                               ctx->mods, ctx->sh->tw_fwd.get()))
             return rc;
     }
     // 3. gadget product
     {
         lm_prof_scope ps(ctx, "rs_mac", (uint64_t)B);
-        hipLaunchKernelGGL(k_rs_mac, dim3((N + 255) / 256, nt, B), dim3(256), 0, ctx->stream, ext, rk->d_key, u, B, nd,
+        hipLaunchKernelGGL(k_rs_mac, dim3((N + 255) / 256, nt, B), dim3(256), 0, ctx->stream, ext, rk->d_key.get(), u, B, nd,
                            nt, L, ctx->logN, ctx->mods, hybrid ? in + (size_t)nl * N : (const u64 *)nullptr, in_ctw);
         LM_HIP(ctx, hipGetLastError());
     }
@@ -267,7 +259,7 @@ static int ring_switch_batch(lumen_ctx *ctx, RsKey *rk, const lm_ks_view &kv, co
         // 5. ModDown, add c0 -> level-0 ciphertext of the big ring under the embedded small key
         lm_prof_scope ps(ctx, "rs_moddown", (uint64_t)B * 2);
         if (int rc = lm_launch(ctx, k_rs_moddown<LOGN>, geom, B * 2, u, in, in_ctw, big, kv.d_bxp, kv.d_pinv, nt, K,
-                               ctx->mods, ctx->d_tw_fwd))
+                               ctx->mods, ctx->sh->tw_fwd.get()))
             return rc;
     } else {
         // no special prime: the gadget product is the result; add c0
@@ -280,7 +272,7 @@ static int ring_switch_batch(lumen_ctx *ctx, RsKey *rk, const lm_ks_view &kv, co
     hipLaunchKernelGGL(k_rs_project, dim3(1024), dim3(256), 0, ctx->stream, big, small, B * 2, ctx->logN, rk->logn);
     LM_HIP(ctx, hipGetLastError());
     const size_t n = (size_t)1 << rk->logn;
-    return lm_launch_ntt_subring(ctx, rk->logn, rk->d_tw_small, rk->ninv_small, small, n, small, n, B * 2, 0, false);
+    return lm_launch_ntt_subring(ctx, rk->logn, rk->d_tw_small.get(), rk->ninv_small, small, n, small, n, B * 2, 0, false);
 }
 
 extern "C" int lumen_ring_switch(lumen_ctx *ctx, const lumen_set *in, uint64_t *out) {
