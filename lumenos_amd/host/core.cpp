@@ -384,6 +384,14 @@ double Span::End() {
     return seconds_;
 }
 
+ScopedSpan::ScopedSpan(const std::string &name, Span *parent, const std::string &start_msg)
+    : span_(Span::StartSpan(name, parent, start_msg)) {}
+ScopedSpan::~ScopedSpan() {
+    span_->End();
+    delete span_;
+}
+double ScopedSpan::End() { return span_->End(); }
+
 // ------------------------------------------------------------------ polynomial
 Element DensePoly::Evaluate(const PrimeField &field, Element point) const {
     const uint64_t q = field.Modulus();

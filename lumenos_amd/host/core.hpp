@@ -107,6 +107,22 @@ class Span {
     double seconds_ = -1;
 };
 
+// `span := core.StartSpan(...); defer span.End()` (fhe/ligero.go:97-98): a span that ends when its scope does, also
+// when an exception leaves the scope -- the line is printed then too -- and frees itself.  End() before that gives the
+// seconds and prints; ending twice prints once.  A child names its parent with get().
+class ScopedSpan {
+  public:
+    ScopedSpan(const std::string &name, Span *parent, const std::string &start_msg = "");
+    ~ScopedSpan();
+    ScopedSpan(const ScopedSpan &) = delete;
+    ScopedSpan &operator=(const ScopedSpan &) = delete;
+    double End();
+    Span *get() const { return span_; }
+
+  private:
+    Span *span_;
+};
+
 // core.DensePoly (core/poly.go:3-45): the committed polynomial whose value at the client's point the server returns
 // next to the proof (cmd/server/main.go:255-258).  On the host: the checker of the device evaluation and the
 // reference API (fhe::ServerBFV::EvaluateColumns is the device form).

@@ -6,6 +6,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <mutex>
 #include <set>
 #include <stdexcept>
 #include <thread>
@@ -19,8 +20,71 @@ using core::InvMod;
 using core::MulMod;
 using core::PowMod;
 
-// ring degree per context (the C ABI does not expose it; this mirror created the context)
-static std::map<lumen_ctx *, uint32_t> g_ring_degree;
+// the one throwing helper behind every `check`: ctx NULL reads the library's thread-wide message
+static void throw_on(int rc, const char *what, const lumen_ctx *ctx) {
+    if (rc) throw std::runtime_error(std::string(what) + ": " + lumen_last_error(ctx));
+}
+
+// ------------------------------------------------------------------ OwnedContext
+// the contexts this mirror owns and their ring degrees; written by OwnedContext alone, read through ring_degree
+static std::mutex g_contexts_mu;
+static std::map<lumen_ctx *, uint32_t> g_contexts;
+
+static lumen_ctx *adopt(lumen_ctx *ctx, uint32_t N) {
+    std::lock_guard<std::mutex> lock(g_contexts_mu);
+    g_contexts[ctx] = N;
+    return ctx;
+}
+static uint32_t ring_degree(lumen_ctx *ctx) {
+    std::lock_guard<std::mutex> lock(g_contexts_mu);
+    return g_contexts.at(ctx);
+}
+size_t LiveContextsForTest() {
+    std::lock_guard<std::mutex> lock(g_contexts_mu);
+    return g_contexts.size();
+}
+
+OwnedContext::OwnedContext(const Parameters &params, int device) {
+    lumen_params_desc d;
+    memset(&d, 0, sizeof(d));
+    d.abi_version = LUMEN_ABI_VERSION;
+    d.log_n = (uint32_t)params.LogN;
+    d.num_q = (uint32_t)params.Q.size();
+    d.num_p = (uint32_t)params.P.size();
+    d.plaintext_modulus = params.T;
+    d.device = device;
+    size_t i = 0;
+    for (uint64_t m : params.Q) d.moduli[i++] = m;
+    for (uint64_t m : params.P) d.moduli[i++] = m;
+    for (size_t k = 0; k < params.Psi.size(); k++) d.psi[k] = params.Psi[k];
+    lumen_ctx *ctx = nullptr;
+    throw_on(lumen_ctx_create(&d, &ctx), "lumen_ctx_create", nullptr);
+    ctx_ = adopt(ctx, (uint32_t)params.N());
+}
+
+OwnedContext OwnedContext::Clone() const {
+    lumen_ctx *twin = nullptr;
+    check(lumen_ctx_clone(ctx_, &twin), "lumen_ctx_clone");
+    OwnedContext c;
+    c.ctx_ = adopt(twin, ring_degree(ctx_));
+    return c;
+}
+
+OwnedContext &OwnedContext::operator=(OwnedContext &&o) noexcept {
+    std::swap(ctx_, o.ctx_); // what this one held goes with `o`
+    return *this;
+}
+
+OwnedContext::~OwnedContext() {
+    if (!ctx_) return;
+    {
+        std::lock_guard<std::mutex> lock(g_contexts_mu);
+        g_contexts.erase(ctx_);
+    }
+    lumen_ctx_destroy(ctx_);
+}
+
+void OwnedContext::check(int rc, const char *what) const { throw_on(rc, what, ctx_); }
 
 // ------------------------------------------------------------------ parameters
 ParametersLiteral GenerateBGVParamsForNTT(int nttSize, int logN, uint64_t plaintextModulus) {
@@ -146,10 +210,8 @@ Ciphertexts Ciphertexts::Upload(ServerBFV &backend, const std::vector<uint64_t> 
 std::vector<uint64_t> Ciphertexts::Download() const {
     if (!set_) return {};
     const uint32_t count = lumen_set_count(set_), nl = lumen_set_limbs(set_);
-    const uint32_t N = g_ring_degree.at(ctx_);
-    std::vector<uint64_t> out((size_t)count * 2 * nl * N);
-    if (count && lumen_set_download(ctx_, set_, 0, count, out.data()))
-        throw std::runtime_error(std::string("lumen_set_download: ") + lumen_last_error(ctx_));
+    std::vector<uint64_t> out((size_t)count * 2 * nl * ring_degree(ctx_));
+    if (count) throw_on(lumen_set_download(ctx_, set_, 0, count, out.data()), "lumen_set_download", ctx_);
     return out;
 }
 
@@ -220,9 +282,9 @@ static void set_format(lumen_ctx *ctx, const MetaData &md, int level, uint64_t T
     le64(head, 2); // structs.Vector[ring.Poly]: two polynomials
     le64(poly, (uint64_t)level + 1);
     le64(limb, (uint64_t)N);
-    if (lumen_leaf_format_set(ctx, head.data(), (uint32_t)head.size(), poly.data(), (uint32_t)poly.size(), limb.data(),
-                              (uint32_t)limb.size()))
-        throw std::runtime_error(std::string("lumen_leaf_format_set: ") + lumen_last_error(ctx));
+    throw_on(lumen_leaf_format_set(ctx, head.data(), (uint32_t)head.size(), poly.data(), (uint32_t)poly.size(), limb.data(),
+                                   (uint32_t)limb.size()),
+             "lumen_leaf_format_set", ctx);
 }
 
 void SetCiphertextFormat(ServerBFV &backend, const MetaData &md, int level) {
@@ -277,40 +339,35 @@ void OsRandom(uint8_t *out, size_t n) {
     }
 }
 
-void ServerBFV::check(int rc, const char *what) const {
-    if (rc) throw std::runtime_error(std::string(what) + ": " + lumen_last_error(ctx_));
+void ServerBFV::check(int rc, const char *what) const { ctx_.check(rc, what); }
+
+// the encoder's root: a primitive 2N-th root of unity modulo T
+static uint64_t encoder_root(const Parameters &params) {
+    return PowMod(core::PrimitiveRoot(params.T), (params.T - 1) / (2ull << params.LogN), params.T);
+}
+
+// rlwe.MetaData of a fresh encryption: Scale 1, NTT domain, batched 2 x N/2 slots
+static MetaData fresh_meta(const Parameters &params) {
+    MetaData md;
+    md.LogCols = params.LogN - 1;
+    return md;
 }
 
 ServerBFV::ServerBFV(core::PrimeField *plaintextField, const Parameters &params, std::vector<uint64_t> pk,
                      const std::map<uint64_t, std::vector<uint64_t>> &evk, int device)
-    : ptField_(plaintextField), params_(params), pk_(std::move(pk)) {
-    lumen_params_desc d;
-    memset(&d, 0, sizeof(d));
-    d.abi_version = LUMEN_ABI_VERSION;
-    d.log_n = (uint32_t)params.LogN;
-    d.num_q = (uint32_t)params.Q.size();
-    d.num_p = (uint32_t)params.P.size();
-    d.plaintext_modulus = params.T;
-    d.device = device;
-    size_t i = 0;
-    for (uint64_t m : params.Q) d.moduli[i++] = m;
-    for (uint64_t m : params.P) d.moduli[i++] = m;
-    for (size_t k = 0; k < params.Psi.size(); k++) d.psi[k] = params.Psi[k];
-    if (lumen_ctx_create(&d, &ctx_)) throw std::runtime_error(std::string("lumen_ctx_create: ") + lumen_last_error(nullptr));
-    g_ring_degree[ctx_] = (uint32_t)params.N();
-    check(lumen_field_set(ctx_, plaintextField->RootsForward().data(), (uint32_t)plaintextField->N()), "lumen_field_set");
-    for (const auto &kv : evk) check(lumen_load_galois_key(ctx_, kv.first, kv.second.data()), "lumen_load_galois_key");
-    check(lumen_load_public_key(ctx_, pk_.data()), "lumen_load_public_key");
-    check(lumen_encoder_set(ctx_, PowMod(core::PrimitiveRoot(params.T), (params.T - 1) / (2ull << params.LogN), params.T)),
-          "lumen_encoder_set");
+    : ptField_(plaintextField), params_(params), pk_(std::move(pk)), ctx_(params, device), psiT_(encoder_root(params)) {
+    // a throw below unwinds ctx_: the context and every key already loaded leave the device
+    check(lumen_field_set(Context(), plaintextField->RootsForward().data(), (uint32_t)plaintextField->N()), "lumen_field_set");
+    for (const auto &kv : evk) check(lumen_load_galois_key(Context(), kv.first, kv.second.data()), "lumen_load_galois_key");
+    check(lumen_load_public_key(Context(), pk_.data()), "lumen_load_public_key");
+    check(lumen_encoder_set(Context(), psiT_), "lumen_encoder_set");
     // the reference keys Lattigo's sampler from crypto/rand: all encryption randomness (u, e0, e1 of every
     // ciphertext this server makes) is the ChaCha20 stream under this key, so the key comes from the
     // kernel's CSPRNG and from nowhere else -- no user-space generator in between
     enc_ = std::make_shared<EncryptorState>();
     OsRandom(enc_->seed, sizeof(enc_->seed));
     // encoder tables ([LATTIGO-RECALL] bgv.Encoder: slot i of row 0 sits at 5^i, row 1 at -5^i)
-    const uint64_t T = params.T, two_n = 2ull << params.LogN;
-    psiT_ = PowMod(core::PrimitiveRoot(T), (T - 1) / two_n, T);
+    const uint64_t two_n = 2ull << params.LogN;
     const int N = params.N(), row = N >> 1;
     slot_index_.resize(N);
     uint64_t pos = 1;
@@ -321,81 +378,34 @@ ServerBFV::ServerBFV(core::PrimeField *plaintextField, const Parameters &params,
     }
 }
 
-ServerBFV::ServerBFV(ServerBFV &src, lumen_ctx *clone)
-    : ptField_(src.ptField_), params_(src.params_), pk_(src.pk_), ctx_(clone), psiT_(src.psiT_),
-      slot_index_(src.slot_index_), rs_(src.rs_), enc_(src.enc_) {
-    g_ring_degree[ctx_] = (uint32_t)params_.N();
-}
+ServerBFV::ServerBFV(ServerBFV &src, OwnedContext clone)
+    : ptField_(src.ptField_), params_(src.params_), pk_(src.pk_), ctx_(std::move(clone)), psiT_(src.psiT_),
+      slot_index_(src.slot_index_), rs_(src.rs_), enc_(src.enc_) {}
 
-std::unique_ptr<ServerBFV> ServerBFV::CopyNew() {
-    lumen_ctx *twin = nullptr;
-    check(lumen_ctx_clone(ctx_, &twin), "lumen_ctx_clone");
-    return std::unique_ptr<ServerBFV>(new ServerBFV(*this, twin));
-}
+std::unique_ptr<ServerBFV> ServerBFV::CopyNew() { return std::unique_ptr<ServerBFV>(new ServerBFV(*this, ctx_.Clone())); }
 
-ServerBFV::~ServerBFV() {
-    if (ctx_) {
-        g_ring_degree.erase(ctx_);
-        lumen_ctx_destroy(ctx_);
-    }
-}
+ServerBFV::~ServerBFV() = default;
 
-int ServerBFV::MulCounter() const { return (int)lumen_mul_counter(ctx_); }
+int ServerBFV::MulCounter() const { return (int)lumen_mul_counter(Context()); }
 
 // ------------------------------------------------------------------ ClientBFV
-void ClientBFV::check(int rc, const char *what) const {
-    if (rc) throw std::runtime_error(std::string(what) + ": " + lumen_last_error(ctx_));
-}
-
-static lumen_ctx *new_context(const Parameters &params, int device) {
-    lumen_params_desc d;
-    memset(&d, 0, sizeof(d));
-    d.abi_version = LUMEN_ABI_VERSION;
-    d.log_n = (uint32_t)params.LogN;
-    d.num_q = (uint32_t)params.Q.size();
-    d.num_p = (uint32_t)params.P.size();
-    d.plaintext_modulus = params.T;
-    d.device = device;
-    size_t i = 0;
-    for (uint64_t m : params.Q) d.moduli[i++] = m;
-    for (uint64_t m : params.P) d.moduli[i++] = m;
-    for (size_t k = 0; k < params.Psi.size(); k++) d.psi[k] = params.Psi[k];
-    lumen_ctx *ctx = nullptr;
-    if (lumen_ctx_create(&d, &ctx)) throw std::runtime_error(std::string("lumen_ctx_create: ") + lumen_last_error(nullptr));
-    g_ring_degree[ctx] = (uint32_t)params.N();
-    return ctx;
-}
+void ClientBFV::check(int rc, const char *what) const { ctx_.check(rc, what); }
 
 ClientBFV::ClientBFV(core::PrimeField *plaintextField, const Parameters &params, const std::vector<uint64_t> &sk, int device)
     : ptField_(plaintextField), params_(params), device_(device) {
     const size_t N = (size_t)params.N(), L = params.Q.size();
     if (sk.size() < L * N) throw std::invalid_argument("NewClientBFV: the secret key has fewer than L * N residues");
-    ctx_ = new_context(params, device);
-    try {
-        check(lumen_encoder_set(ctx_, PowMod(core::PrimitiveRoot(params.T), (params.T - 1) / (2ull << params.LogN), params.T)),
-              "lumen_encoder_set");
-        check(lumen_load_secret_key(ctx_, sk.data()), "lumen_load_secret_key");
-    } catch (...) {
-        g_ring_degree.erase(ctx_);
-        lumen_ctx_destroy(ctx_);
-        throw;
-    }
+    ctx_ = OwnedContext(params, device);
+    check(lumen_encoder_set(Context(), encoder_root(params)), "lumen_encoder_set");
+    check(lumen_load_secret_key(Context(), sk.data()), "lumen_load_secret_key");
 }
 
 ClientBFV::ClientBFV(core::PrimeField *plaintextField, const Parameters &params, int device)
-    : ptField_(plaintextField), params_(params), device_(device) {
-    ctx_ = new_context(params, device);
-    try {
-        check(lumen_encoder_set(ctx_, PowMod(core::PrimitiveRoot(params.T), (params.T - 1) / (2ull << params.LogN), params.T)),
-              "lumen_encoder_set");
-        keySeed_ = std::make_shared<KeySeedBytes>();
-        OsRandom(keySeed_->b, sizeof(keySeed_->b));
-        check(lumen_keygen_secret(ctx_, keySeed_->b, nullptr), "lumen_keygen_secret");
-    } catch (...) {
-        g_ring_degree.erase(ctx_);
-        lumen_ctx_destroy(ctx_);
-        throw;
-    }
+    : ptField_(plaintextField), params_(params), ctx_(params, device), device_(device) {
+    check(lumen_encoder_set(Context(), encoder_root(params)), "lumen_encoder_set");
+    keySeed_ = std::make_shared<KeySeedBytes>();
+    OsRandom(keySeed_->b, sizeof(keySeed_->b));
+    check(lumen_keygen_secret(Context(), keySeed_->b, nullptr), "lumen_keygen_secret");
 }
 
 std::unique_ptr<ClientBFV> ClientBFV::NewWithGeneratedSecret(core::PrimeField *plaintextField, const Parameters &params,
@@ -410,27 +420,16 @@ const uint8_t *ClientBFV::KeySeed() const {
 
 std::vector<uint64_t> ClientBFV::SecretKeyForTest() {
     std::vector<uint64_t> sk((params_.Q.size() + params_.P.size()) * (size_t)params_.N());
-    check(lumen_keygen_secret(ctx_, KeySeed(), sk.data()), "lumen_keygen_secret");
+    check(lumen_keygen_secret(Context(), KeySeed(), sk.data()), "lumen_keygen_secret");
     return sk;
 }
 
-ClientBFV::ClientBFV(ClientBFV &src, lumen_ctx *clone)
-    : ptField_(src.ptField_), params_(src.params_), ctx_(clone), device_(src.device_), keySeed_(src.keySeed_) {
-    g_ring_degree[ctx_] = (uint32_t)params_.N();
-}
+ClientBFV::ClientBFV(ClientBFV &src, OwnedContext clone)
+    : ptField_(src.ptField_), params_(src.params_), ctx_(std::move(clone)), device_(src.device_), keySeed_(src.keySeed_) {}
 
-std::unique_ptr<ClientBFV> ClientBFV::CopyNew() {
-    lumen_ctx *twin = nullptr;
-    check(lumen_ctx_clone(ctx_, &twin), "lumen_ctx_clone");
-    return std::unique_ptr<ClientBFV>(new ClientBFV(*this, twin));
-}
+std::unique_ptr<ClientBFV> ClientBFV::CopyNew() { return std::unique_ptr<ClientBFV>(new ClientBFV(*this, ctx_.Clone())); }
 
-ClientBFV::~ClientBFV() {
-    if (ctx_) {
-        g_ring_degree.erase(ctx_);
-        lumen_ctx_destroy(ctx_);
-    }
-}
+ClientBFV::~ClientBFV() = default;
 
 // ------------------------------------------------------------------ KeyGenerator (cmd/client/main.go:74-81)
 static size_t evk_words(const Parameters &P) {
@@ -507,7 +506,7 @@ std::unique_ptr<ServerBFV> ServerBFV::NewFromKeySet(core::PrimeField *plaintextF
         if (k.size() != evk_words(params)) throw std::invalid_argument("NewFromKeySet: a Galois key has the wrong size");
     std::unique_ptr<ServerBFV> s(new ServerBFV(plaintextField, params, keys.Pk, {}, device));
     for (size_t i = 0; i < keys.GaloisKeys.size(); i++)
-        s->check(lumen_load_galois_key_ex(s->ctx_, keys.GaloisElements[i], keys.GaloisKeys[i].data(), keys.Flags),
+        s->check(lumen_load_galois_key_ex(s->Context(), keys.GaloisElements[i], keys.GaloisKeys[i].data(), keys.Flags),
                  "lumen_load_galois_key_ex");
     return s;
 }
@@ -536,15 +535,10 @@ std::vector<uint64_t> ServerBFV::EncryptNew(const Plaintext &pt) {
     // One ciphertext of the device encryptor: its samples are ChaCha20(seed, index) of the shared encryptor state, the same
     // stream EncryptNewBatch / EncryptColumnsNew draw from, never a host-side generator.  The path only
     // encrypts at MaxLevel (fhe/code.go:15-19: NewPlaintext(params, MaxLevel)).
-    const size_t N = (size_t)params_.N(), L = params_.Q.size();
-    if ((size_t)pt.Level + 1 != L) throw std::invalid_argument("EncryptNew: plaintext must be at MaxLevel");
+    if ((size_t)pt.Level + 1 != params_.Q.size()) throw std::invalid_argument("EncryptNew: plaintext must be at MaxLevel");
     lumen_set *set = nullptr;
-    check(lumen_encrypt_pk(ctx_, pt.Value.data(), 1, enc_->seed, enc_->next.fetch_add(1), &set), "lumen_encrypt_pk");
-    std::vector<uint64_t> ct(2 * L * N);
-    const int rc = lumen_set_download(ctx_, set, 0, 1, ct.data());
-    lumen_set_destroy(ctx_, set);
-    check(rc, "lumen_set_download");
-    return ct;
+    check(lumen_encrypt_pk(Context(), pt.Value.data(), 1, enc_->seed, enc_->next.fetch_add(1), &set), "lumen_encrypt_pk");
+    return Ciphertexts(Context(), set).Download();
 }
 
 Ciphertexts ServerBFV::EncryptNewBatch(const std::vector<Plaintext> &pts) {
@@ -557,11 +551,9 @@ Ciphertexts ServerBFV::EncryptNewBatch(const std::vector<Plaintext> &pts) {
         memcpy(&flat[i * L * N], pts[i].Value.data(), L * N * 8);
     }
     lumen_set *set = nullptr;
-    check(lumen_encrypt_pk(ctx_, flat.data(), (uint32_t)pts.size(), enc_->seed, enc_->next.fetch_add(pts.size()), &set),
+    check(lumen_encrypt_pk(Context(), flat.data(), (uint32_t)pts.size(), enc_->seed, enc_->next.fetch_add(pts.size()), &set),
           "lumen_encrypt_pk");
-    MetaData md; // fresh encryption: Scale 1, NTT domain, batched 2 x N/2 slots
-    md.LogCols = params_.LogN - 1;
-    return Ciphertexts(ctx_, set, md);
+    return Ciphertexts(Context(), set, fresh_meta(params_));
 }
 
 Ciphertexts ServerBFV::EncryptColumnsNew(const std::vector<uint64_t> &values, int rows, int count) {
@@ -569,24 +561,20 @@ Ciphertexts ServerBFV::EncryptColumnsNew(const std::vector<uint64_t> &values, in
     // in one device call: only the raw values cross PCIe
     if ((size_t)rows * count != values.size()) throw std::invalid_argument("EncryptColumnsNew: size mismatch");
     lumen_set *set = nullptr;
-    check(lumen_encrypt_values(ctx_, values.data(), (uint32_t)rows, (uint32_t)count, enc_->seed,
+    check(lumen_encrypt_values(Context(), values.data(), (uint32_t)rows, (uint32_t)count, enc_->seed,
                                enc_->next.fetch_add((uint64_t)count), &set),
           "lumen_encrypt_values");
-    MetaData md;
-    md.LogCols = params_.LogN - 1;
-    return Ciphertexts(ctx_, set, md);
+    return Ciphertexts(Context(), set, fresh_meta(params_));
 }
 
 core::Element ServerBFV::EvaluateColumns(const std::vector<uint64_t> &values, int rows, int count, int cols, core::Element z,
                                          uint64_t firstColumn) {
     if (rows < 0 || count < 0 || cols < 0 || (size_t)rows * count != values.size())
         throw std::invalid_argument("EvaluateColumns: size mismatch");
-    core::Span *span = core::Span::StartSpan("Evaluate polynomial", nullptr);
+    core::ScopedSpan span("Evaluate polynomial", nullptr);
     uint64_t value = 0;
-    check(lumen_poly_eval_columns(ctx_, values.data(), (uint32_t)rows, (uint32_t)count, firstColumn, (uint32_t)cols, z, &value),
+    check(lumen_poly_eval_columns(Context(), values.data(), (uint32_t)rows, (uint32_t)count, firstColumn, (uint32_t)cols, z, &value),
           "lumen_poly_eval_columns");
-    span->End();
-    delete span;
     return value;
 }
 
@@ -629,9 +617,7 @@ ServerGroup::ServerGroup(std::vector<ServerBFV *> ranks, uint32_t transport) : r
     check(lumen_group_create(ctxs.data(), logw, transport, &group_), "lumen_group_create");
 }
 ServerGroup::~ServerGroup() { lumen_group_destroy(group_); }
-void ServerGroup::check(int rc, const char *what) const {
-    if (rc) throw std::runtime_error(std::string(what) + ": " + lumen_last_error(nullptr));
-}
+void ServerGroup::check(int rc, const char *what) const { throw_on(rc, what, nullptr); }
 void ServerGroup::Sync() const { check(lumen_group_sync(group_), "lumen_group_sync"); }
 
 ShardedCiphertexts ServerGroup::EncryptColumnsNew(const std::vector<uint64_t> &values, int rows, int count) {
@@ -647,9 +633,7 @@ ShardedCiphertexts ServerGroup::EncryptColumnsNew(const std::vector<uint64_t> &v
         s.check(lumen_encrypt_values(s.Context(), values.data() + (size_t)r * own * rows, (uint32_t)rows, (uint32_t)own,
                                      s.enc_->seed, first + (uint64_t)r * own, &set),
                 "lumen_encrypt_values");
-        MetaData md;
-        md.LogCols = s.GetParameters().LogN - 1;
-        out.Blocks.emplace_back(s.Context(), set, md);
+        out.Blocks.emplace_back(s.Context(), set, fresh_meta(s.GetParameters()));
     }
     return out;
 }
@@ -662,12 +646,10 @@ core::Element ServerGroup::EvaluateColumns(const std::vector<uint64_t> &values, 
     std::vector<const uint64_t *> blocks((size_t)W);
     std::vector<uint32_t> counts((size_t)W, (uint32_t)own);
     for (int r = 0; r < W; r++) blocks[(size_t)r] = values.data() + (size_t)r * own * rows;
-    core::Span *span = core::Span::StartSpan("Evaluate polynomial", nullptr);
+    core::ScopedSpan span("Evaluate polynomial", nullptr);
     uint64_t value = 0;
     check(lumen_group_poly_eval(group_, blocks.data(), (uint32_t)rows, counts.data(), (uint32_t)cols, z, &value),
           "lumen_group_poly_eval");
-    span->End();
-    delete span;
     return value;
 }
 
@@ -724,16 +706,29 @@ void LigeroMetadata::WriteTo(std::vector<uint8_t> &buf) const {
     le((uint32_t)Rows, 4), le((uint32_t)Cols, 4), le((uint8_t)RhoInv, 1), le((uint16_t)Queries, 2);
 }
 
+// the end of both Commits: the prover's state around the level-1 columns and their tree, and the root
+static std::pair<LigeroProver, std::vector<uint8_t>> make_prover(const LigeroCommitter *committer, const Ciphertexts *matrix,
+                                                                 const ShardedCiphertexts *shards, ShardedCiphertexts level1,
+                                                                 core::MerkleTree tree) {
+    LigeroProver prover;
+    prover.Committer = committer;
+    prover.Matrix = matrix;
+    prover.MatrixShards = shards;
+    prover.EncodedLevel1 = std::move(level1);
+    prover.Tree = std::move(tree);
+    std::vector<uint8_t> root = prover.Tree.MerkleRoot();
+    return {std::move(prover), std::move(root)};
+}
+
 std::pair<LigeroProver, std::vector<uint8_t>> LigeroCommitter::Commit(const Ciphertexts &matrix, ServerBFV &backend,
                                                                        core::Span *ctx) const {
     lumen_ctx *h = backend.Context();
-    core::Span *span = core::Span::StartSpan("Encode", ctx);
+    core::ScopedSpan encodeSpan("Encode", ctx);
     Ciphertexts encoded = Encode(matrix, Metadata.Rows, Metadata.RhoInv, backend);
     backend.check(lumen_sync(h), "lumen_sync");
-    span->End();
-    delete span;
+    encodeSpan.End();
 
-    span = core::Span::StartSpan("Merkle tree built", ctx);
+    core::ScopedSpan treeSpan("Merkle tree built", ctx);
     // processLeafParallel (ligero.go:126-183): mod-switch every column to level 1, serialise, hash
     lumen_set *lvl1 = nullptr;
     backend.check(lumen_rescale(h, encoded.Handle(), 2, &lvl1), "lumen_rescale");
@@ -744,28 +739,20 @@ std::pair<LigeroProver, std::vector<uint8_t>> LigeroCommitter::Commit(const Ciph
     std::vector<core::Digest> leaves((size_t)level1.Len());
     if (!leaves.empty()) backend.check(lumen_leaf_digests(h, lvl1, leaves[0].data()), "lumen_leaf_digests");
     core::MerkleTree tree = core::MerkleTree::FromLeafDigests(std::move(leaves)); // core.NewTree
-    span->End();
-    delete span;
+    treeSpan.End();
 
-    LigeroProver prover;
-    prover.Committer = this;
-    prover.Matrix = &matrix;
-    prover.EncodedLevel1 = ShardedCiphertexts(std::move(level1));
-    prover.Tree = std::move(tree);
-    std::vector<uint8_t> root = prover.Tree.MerkleRoot();
-    return {std::move(prover), std::move(root)};
+    return make_prover(this, &matrix, nullptr, ShardedCiphertexts(std::move(level1)), std::move(tree));
 }
 
 std::pair<LigeroProver, std::vector<uint8_t>> LigeroCommitter::Commit(const ShardedCiphertexts &matrix, ServerGroup &group,
                                                                        core::Span *ctx) const {
     const int W = group.World();
-    core::Span *span = core::Span::StartSpan("Encode", ctx);
+    core::ScopedSpan encodeSpan("Encode", ctx);
     ShardedCiphertexts encoded = Encode(matrix, Metadata.Rows, Metadata.RhoInv, group);
     group.Sync();
-    span->End();
-    delete span;
+    encodeSpan.End();
 
-    span = core::Span::StartSpan("Merkle tree built", ctx);
+    core::ScopedSpan treeSpan("Merkle tree built", ctx);
     // processLeafParallel (ligero.go:126-183) on every rank's block of encoded columns; the leaves are hashed on
     // the ranks' side streams, then ONE all-gather puts the S digests on every rank
     MetaData md = encoded.Meta();
@@ -789,16 +776,9 @@ std::pair<LigeroProver, std::vector<uint8_t>> LigeroCommitter::Commit(const Shar
     uint8_t droot[32];
     group.check(lumen_group_merkle_root(group.Handle(), droot), "lumen_group_merkle_root");
     if (memcmp(droot, tree.MerkleRoot().data(), 32)) throw std::runtime_error("Commit: device and host Merkle roots differ");
-    span->End();
-    delete span;
+    treeSpan.End();
 
-    LigeroProver prover;
-    prover.Committer = this;
-    prover.MatrixShards = &matrix;
-    prover.EncodedLevel1 = std::move(level1);
-    prover.Tree = std::move(tree);
-    std::vector<uint8_t> root = prover.Tree.MerkleRoot();
-    return {std::move(prover), std::move(root)};
+    return make_prover(this, nullptr, &matrix, std::move(level1), std::move(tree));
 }
 
 Ciphertexts matrixInnerSumEval(const Ciphertexts &matrix, const Plaintext &plaintext, int rows, ServerBFV &backend) {
@@ -817,36 +797,65 @@ std::vector<int> sampleQueryIndices(core::Transcript &transcript, int queries, i
     return idx;
 }
 
+// The prover's challenge (ligero.go:198-222, 880-890): r comes out of the transcript before anything else, as raw u64
+// words that are reduced where they are multiplied (ligero.go:202-203); b_i = (z^cols)^i reads no transcript.  The root
+// is not written to the transcript, for compatibility with LigeroProveReference (ligero.go:198-199).
+struct Challenge {
+    std::vector<uint64_t> r, b;
+};
+static Challenge sample_challenge(core::Transcript &transcript, const core::PrimeField &field, int rows, int cols,
+                                  core::Element point) {
+    Challenge c{std::vector<uint64_t>((size_t)rows), std::vector<uint64_t>((size_t)rows)};
+    transcript.SampleUints("r", c.r);
+    const core::Element zPow = field.Pow((uint64_t)cols, point);
+    core::Element powB = 1;
+    for (uint64_t &bi : c.b) bi = powB, powB = field.Mul(powB, zPow);
+    return c;
+}
+
+// The opening step of both Proves (ligero.go:262-290), entered once `point` is in the transcript: the query indices are the
+// last thing drawn from it.  gather(idx) collects those columns of EncodedLevel1 into one set on `ctx`; which call does
+// that is the caller's (lumen_gather on one GPU, lumen_group_gather onto rank 0 of a group).
+template <class Gather>
+static EncryptedProof open_columns(const LigeroProver &prover, core::Transcript &transcript, lumen_ctx *ctx, uint64_t T,
+                                   core::Span *parent, Gather gather) {
+    const LigeroMetadata &md = prover.Committer->Metadata;
+    EncryptedProof proof;
+    core::ScopedSpan span("Query columns", parent);
+    proof.QueryIndices = sampleQueryIndices(transcript, md.Queries, md.Cols * md.RhoInv);
+    const std::vector<uint32_t> idx(proof.QueryIndices.begin(), proof.QueryIndices.end());
+    proof.QueriedCols = Ciphertexts(ctx, gather(idx), prover.EncodedLevel1.Meta());
+    for (int i : proof.QueryIndices) proof.MerklePaths.push_back(prover.Tree.GetMerklePath((unsigned)i));
+    span.End();
+    proof.Metadata = md;
+    proof.Root = prover.Tree.MerkleRoot();
+    proof.PlaintextModulus = T;
+    return proof;
+}
+
 EncryptedProof LigeroProver::Prove(core::Element point, ServerBFV &backend, core::Transcript &transcript, core::Span *ctx) {
     const int cols = Committer->Metadata.Cols, rows = Committer->Metadata.Rows;
-    // don't write root to transcript for compatibility with LigeroProveReference (ligero.go:198-199)
-    std::vector<uint64_t> r((size_t)rows);
-    transcript.SampleUints("r", r); // raw u64, not reduced (ligero.go:202-203)
-    Plaintext rPt = backend.Encode(r);
-    std::vector<uint64_t> b((size_t)rows);
-    const core::Element zPow = backend.Field()->Pow((uint64_t)cols, point);
-    core::Element powB = 1;
-    for (uint64_t &bi : b) {
-        bi = powB;
-        powB = backend.Field()->Mul(powB, zPow);
-    }
-    Plaintext bPt = backend.Encode(b);
+    const Challenge ch = sample_challenge(transcript, *backend.Field(), rows, cols, point);
+    const Plaintext rPt = backend.Encode(ch.r), bPt = backend.Encode(ch.b);
 
     if (!Matrix) throw std::invalid_argument("Prove: this prover was committed on a ServerGroup; prove on that group");
+    auto inner = [&](const Plaintext &pt, ServerBFV &s) {
+        Ciphertexts out = matrixInnerSumEval(*Matrix, pt, rows, s);
+        s.check(lumen_sync(s.Context()), "lumen_sync");
+        return out;
+    };
     Ciphertexts matR, matZ;
     if (ConcurrentRZ) {
         // ligero.go:231-242 as written: two goroutines, each on its own CopyNew (here: the server itself and one
         // copy -- a lumen_ctx_clone with its own streams); both spans cover the overlapped evaluation
         std::unique_ptr<ServerBFV> copy = backend.CopyNew();
-        core::Span *spanR = core::Span::StartSpan("InnerProduct(Matrix, r)", ctx);
-        core::Span *spanZ = core::Span::StartSpan("InnerProduct(Matrix, b)", ctx);
+        core::ScopedSpan spanR("InnerProduct(Matrix, r)", ctx), spanZ("InnerProduct(Matrix, b)", ctx);
         std::exception_ptr errZ;
         lumen_set *zset = nullptr;
         MetaData zmeta;
         std::thread tz([&] {
             try {
-                Ciphertexts z = matrixInnerSumEval(*Matrix, bPt, rows, *copy);
-                copy->check(lumen_sync(copy->Context()), "lumen_sync");
+                Ciphertexts z = inner(bPt, *copy);
                 zmeta = z.Meta;
                 zset = z.Release(); // the set outlives the copy: from here on it is the server's to destroy
             } catch (...) {
@@ -854,52 +863,38 @@ EncryptedProof LigeroProver::Prove(core::Element point, ServerBFV &backend, core
             }
         });
         try {
-            matR = matrixInnerSumEval(*Matrix, rPt, rows, backend);
-            backend.check(lumen_sync(backend.Context()), "lumen_sync");
+            matR = inner(rPt, backend);
         } catch (...) {
             tz.join();
             throw;
         }
-        spanR->End();
-        delete spanR;
+        spanR.End();
         tz.join();
         if (errZ) std::rethrow_exception(errZ);
         matZ = Ciphertexts(backend.Context(), zset, zmeta);
-        spanZ->End();
-        delete spanZ;
+        spanZ.End();
     } else {
         // one device context runs them back to back on its stream
-        core::Span *spanR = core::Span::StartSpan("InnerProduct(Matrix, r)", ctx);
-        matR = matrixInnerSumEval(*Matrix, rPt, rows, backend);
-        backend.check(lumen_sync(backend.Context()), "lumen_sync");
-        spanR->End();
-        delete spanR;
-        core::Span *spanZ = core::Span::StartSpan("InnerProduct(Matrix, b)", ctx);
-        matZ = matrixInnerSumEval(*Matrix, bPt, rows, backend);
-        backend.check(lumen_sync(backend.Context()), "lumen_sync");
-        spanZ->End();
-        delete spanZ;
+        core::ScopedSpan spanR("InnerProduct(Matrix, r)", ctx);
+        matR = inner(rPt, backend);
+        spanR.End();
+        core::ScopedSpan spanZ("InnerProduct(Matrix, b)", ctx);
+        matZ = inner(bPt, backend);
+        spanZ.End();
     }
 
     transcript.AppendField("point", point);
 
-    core::Span *querySpan = core::Span::StartSpan("Query columns", ctx);
-    const int extCols = cols * Committer->Metadata.RhoInv;
-    EncryptedProof proof;
-    proof.QueryIndices = sampleQueryIndices(transcript, Committer->Metadata.Queries, extCols);
-    std::vector<uint32_t> idx(proof.QueryIndices.begin(), proof.QueryIndices.end());
-    lumen_set *q = nullptr;
     // the reference rescales the queried entries of its top-level EncodedMatrix in place (ligero.go:268-273); the
     // level-1 columns Commit hashed are those very ciphertexts
-    backend.check(lumen_gather(backend.Context(), EncodedLevel1.Blocks.at(0).Handle(), idx.data(), (uint32_t)idx.size(), &q), "lumen_gather");
-    proof.QueriedCols = Ciphertexts(backend.Context(), q, EncodedLevel1.Meta());
-    for (int i : proof.QueryIndices) proof.MerklePaths.push_back(Tree.GetMerklePath((unsigned)i));
-    querySpan->End();
-    delete querySpan;
-
-    proof.Metadata = Committer->Metadata;
-    proof.Root = Tree.MerkleRoot();
-    proof.PlaintextModulus = backend.GetParameters().T;
+    EncryptedProof proof = open_columns(*this, transcript, backend.Context(), backend.GetParameters().T, ctx,
+                                        [&](const std::vector<uint32_t> &idx) {
+                                            lumen_set *q = nullptr;
+                                            backend.check(lumen_gather(backend.Context(), EncodedLevel1.Blocks.at(0).Handle(),
+                                                                       idx.data(), (uint32_t)idx.size(), &q),
+                                                          "lumen_gather");
+                                            return q;
+                                        });
     if (RingSwitchServer *rs = backend.RingSwitch()) { // ligero.go:336-342: RingSwitchNew on every inner-product output
         proof.RingSwitchLogN = rs->LogN();
         proof.MatRSwitched = rs->RingSwitchNew(matR, backend);
@@ -915,18 +910,8 @@ EncryptedProof LigeroProver::Prove(core::Element point, ServerGroup &group, core
     if (!MatrixShards || (int)MatrixShards->Blocks.size() != W || (int)EncodedLevel1.Blocks.size() != W)
         throw std::invalid_argument("Prove: this prover was not committed on a group of this size");
     ServerBFV &lead = group.Rank(0);
-    // don't write root to transcript for compatibility with LigeroProveReference (ligero.go:198-199)
-    std::vector<uint64_t> r((size_t)rows);
-    transcript.SampleUints("r", r);
-    Plaintext rPt = lead.Encode(r);
-    std::vector<uint64_t> b((size_t)rows);
-    const core::Element zPow = lead.Field()->Pow((uint64_t)cols, point);
-    core::Element powB = 1;
-    for (uint64_t &bi : b) {
-        bi = powB;
-        powB = lead.Field()->Mul(powB, zPow);
-    }
-    Plaintext bPt = lead.Encode(b);
+    const Challenge ch = sample_challenge(transcript, *lead.Field(), rows, cols, point);
+    const Plaintext rPt = lead.Encode(ch.r), bPt = lead.Encode(ch.b);
 
     // every rank evaluates its own block of columns; the calls only enqueue, so the W GPUs run side by side
     auto inner = [&](const Plaintext &pt) {
@@ -935,34 +920,25 @@ EncryptedProof LigeroProver::Prove(core::Element point, ServerGroup &group, core
         group.Sync();
         return out;
     };
-    core::Span *spanR = core::Span::StartSpan("InnerProduct(Matrix, r)", ctx);
+    core::ScopedSpan spanR("InnerProduct(Matrix, r)", ctx);
     ShardedCiphertexts matR = inner(rPt);
-    spanR->End();
-    delete spanR;
-    core::Span *spanZ = core::Span::StartSpan("InnerProduct(Matrix, b)", ctx);
+    spanR.End();
+    core::ScopedSpan spanZ("InnerProduct(Matrix, b)", ctx);
     ShardedCiphertexts matZ = inner(bPt);
-    spanZ->End();
-    delete spanZ;
+    spanZ.End();
 
     transcript.AppendField("point", point);
 
-    core::Span *querySpan = core::Span::StartSpan("Query columns", ctx);
-    const int extCols = cols * Committer->Metadata.RhoInv;
-    EncryptedProof proof;
-    proof.QueryIndices = sampleQueryIndices(transcript, Committer->Metadata.Queries, extCols);
-    std::vector<uint32_t> idx(proof.QueryIndices.begin(), proof.QueryIndices.end());
-    std::vector<const lumen_set *> blocks;
-    for (const Ciphertexts &c : EncodedLevel1.Blocks) blocks.push_back(c.Handle());
-    lumen_set *q = nullptr;
-    group.check(lumen_group_gather(group.Handle(), blocks.data(), idx.data(), (uint32_t)idx.size(), &q), "lumen_group_gather");
-    proof.QueriedCols = Ciphertexts(lead.Context(), q, EncodedLevel1.Meta());
-    for (int i : proof.QueryIndices) proof.MerklePaths.push_back(Tree.GetMerklePath((unsigned)i));
-    querySpan->End();
-    delete querySpan;
-
-    proof.Metadata = Committer->Metadata;
-    proof.Root = Tree.MerkleRoot();
-    proof.PlaintextModulus = lead.GetParameters().T;
+    EncryptedProof proof = open_columns(*this, transcript, lead.Context(), lead.GetParameters().T, ctx,
+                                        [&](const std::vector<uint32_t> &idx) {
+                                            std::vector<const lumen_set *> blocks;
+                                            for (const Ciphertexts &c : EncodedLevel1.Blocks) blocks.push_back(c.Handle());
+                                            lumen_set *q = nullptr;
+                                            group.check(lumen_group_gather(group.Handle(), blocks.data(), idx.data(),
+                                                                           (uint32_t)idx.size(), &q),
+                                                        "lumen_group_gather");
+                                            return q;
+                                        });
     if (lead.RingSwitch()) { // ligero.go:336-342 on every rank's block (the key is loaded on every rank's context)
         proof.RingSwitchLogN = lead.RingSwitch()->LogN();
         for (int k = 0; k < W; k++) {
@@ -978,67 +954,60 @@ EncryptedProof LigeroProver::Prove(core::Element point, ServerGroup &group, core
     return proof;
 }
 
+// The plain backend of LigeroProveReference and EncodeRows: a context of ring degree 2^logN whose one modulus is T with
+// the field's table on it, `count` columns of 2^(logN+1) lanes uploaded as a one-limb set, and their core.Encode
+struct PlainEncoded {
+    OwnedContext ctx; // declared first: the sets go before their context
+    Ciphertexts columns, encoded;
+};
+static PlainEncoded plain_encode(core::PrimeField &field, int logN, int device, const std::vector<uint64_t> &columns,
+                                 size_t count, int rhoInv) {
+    PlainEncoded p;
+    p.ctx = OwnedContext(field.Modulus(), logN, device);
+    lumen_ctx *h = p.ctx.get();
+    p.ctx.check(lumen_field_set(h, field.RootsForward().data(), (uint32_t)field.N()), "lumen_field_set");
+    lumen_set *m = nullptr, *enc = nullptr;
+    p.ctx.check(lumen_set_create(h, (uint32_t)count, 1, &m), "lumen_set_create");
+    p.columns = Ciphertexts(h, m);
+    p.ctx.check(lumen_set_upload(h, m, 0, (uint32_t)count, columns.data()), "lumen_set_upload");
+    const std::vector<uint64_t> zero((size_t)2 << logN, 0);
+    p.ctx.check(lumen_encode(h, m, zero.data(), (uint32_t)rhoInv, &enc), "lumen_encode");
+    p.encoded = Ciphertexts(h, enc);
+    return p;
+}
+
 Proof LigeroProveReference(const LigeroCommitter &c, const std::vector<uint64_t> &matrix, core::Element point,
                            core::PrimeField &field, core::Transcript &transcript, int device) {
     const int rows = c.Metadata.Rows, cols = c.Metadata.Cols, rhoInv = c.Metadata.RhoInv, S = cols * rhoInv;
-    const uint64_t T = field.Modulus();
     if ((size_t)rows * cols != matrix.size()) throw std::invalid_argument("LigeroProveReference: matrix size mismatch");
     if (rows < 512 || (rows & (rows - 1))) throw std::invalid_argument("LigeroProveReference: rows must be a power of two >= 512");
     // the plain backend: ring degree rows/2, the one modulus T
     int logN = 0;
     while ((2 << logN) < rows) logN++;
-    lumen_params_desc d;
-    memset(&d, 0, sizeof(d));
-    d.abi_version = LUMEN_ABI_VERSION, d.log_n = (uint32_t)logN, d.num_q = 1, d.num_p = 0, d.plaintext_modulus = T;
-    d.moduli[0] = T, d.psi[0] = PowMod(core::PrimitiveRoot(T), (T - 1) / (uint64_t)rows, T), d.device = device;
-    lumen_ctx *ctx = nullptr;
-    if (lumen_ctx_create(&d, &ctx)) throw std::runtime_error(std::string("lumen_ctx_create: ") + lumen_last_error(nullptr));
-    struct Closer {
-        lumen_ctx *c;
-        std::vector<lumen_set *> sets;
-        ~Closer() {
-            for (lumen_set *s : sets) lumen_set_destroy(c, s);
-            lumen_ctx_destroy(c);
-        }
-    } guard{ctx, {}};
-    auto ck = [&](int rc, const char *what) {
-        if (rc) throw std::runtime_error(std::string(what) + ": " + lumen_last_error(ctx));
-    };
-    ck(lumen_field_set(ctx, field.RootsForward().data(), (uint32_t)field.N()), "lumen_field_set");
     // Commit: columns as lanes, core.Encode of every row (ligero.go:806-857), leaves = column bytes (866-872)
     std::vector<uint64_t> columns((size_t)cols * rows);
     for (int i = 0; i < rows; i++)
         for (int j = 0; j < cols; j++) columns[(size_t)j * rows + i] = matrix[(size_t)i * cols + j];
-    lumen_set *m = nullptr, *enc = nullptr, *q = nullptr;
-    ck(lumen_set_create(ctx, (uint32_t)cols, 1, &m), "lumen_set_create");
-    guard.sets.push_back(m);
-    ck(lumen_set_upload(ctx, m, 0, (uint32_t)cols, columns.data()), "lumen_set_upload");
-    const std::vector<uint64_t> zero((size_t)rows, 0);
-    ck(lumen_encode(ctx, m, zero.data(), (uint32_t)rhoInv, &enc), "lumen_encode");
-    guard.sets.push_back(enc);
+    const PlainEncoded plain = plain_encode(field, logN, device, columns, (size_t)cols, rhoInv);
+    lumen_ctx *ctx = plain.ctx.get();
     const uint8_t none = 0;
-    ck(lumen_leaf_format_set(ctx, &none, 0, &none, 0, &none, 0), "lumen_leaf_format_set");
+    plain.ctx.check(lumen_leaf_format_set(ctx, &none, 0, &none, 0, &none, 0), "lumen_leaf_format_set");
     std::vector<core::Digest> leaves((size_t)S);
-    ck(lumen_leaf_digests(ctx, enc, leaves[0].data()), "lumen_leaf_digests");
+    plain.ctx.check(lumen_leaf_digests(ctx, plain.encoded.Handle(), leaves[0].data()), "lumen_leaf_digests");
     core::MerkleTree tree = core::MerkleTree::FromLeafDigests(std::move(leaves));
-    // Prove (ligero.go:880-918): r sampled as field elements (raw words, reduced by the multiplication), b_i = (z^cols)^i
+    // Prove (ligero.go:880-918)
     Proof proof;
     proof.Metadata = c.Metadata;
-    std::vector<uint64_t> r((size_t)rows), b((size_t)rows);
-    transcript.SampleUints("r", r);
-    const core::Element zPow = field.Pow((uint64_t)cols, point);
-    core::Element powB = 1;
-    for (uint64_t &bi : b) bi = powB, powB = field.Mul(powB, zPow);
+    const Challenge ch = sample_challenge(transcript, field, rows, cols, point);
     proof.MatR.resize((size_t)cols), proof.MatZ.resize((size_t)cols);
-    ck(lumen_plain_inner_products(ctx, m, r.data(), proof.MatR.data()), "lumen_plain_inner_products");
-    ck(lumen_plain_inner_products(ctx, m, b.data(), proof.MatZ.data()), "lumen_plain_inner_products");
+    plain.ctx.check(lumen_plain_inner_products(ctx, plain.columns.Handle(), ch.r.data(), proof.MatR.data()), "lumen_plain_inner_products");
+    plain.ctx.check(lumen_plain_inner_products(ctx, plain.columns.Handle(), ch.b.data(), proof.MatZ.data()), "lumen_plain_inner_products");
     transcript.AppendField("point", point);
     proof.QueryIndices = sampleQueryIndices(transcript, c.Metadata.Queries, S);
     const std::vector<uint32_t> idx(proof.QueryIndices.begin(), proof.QueryIndices.end());
-    ck(lumen_gather(ctx, enc, idx.data(), (uint32_t)idx.size(), &q), "lumen_gather");
-    guard.sets.push_back(q);
-    std::vector<uint64_t> opened(idx.size() * (size_t)rows);
-    if (!idx.empty()) ck(lumen_set_download(ctx, q, 0, (uint32_t)idx.size(), opened.data()), "lumen_set_download");
+    lumen_set *q = nullptr;
+    plain.ctx.check(lumen_gather(ctx, plain.encoded.Handle(), idx.data(), (uint32_t)idx.size(), &q), "lumen_gather");
+    const std::vector<uint64_t> opened = Ciphertexts(ctx, q).Download(); // [queries][rows]
     for (size_t k = 0; k < idx.size(); k++) {
         proof.QueriedCols.emplace_back(opened.begin() + (long)(k * rows), opened.begin() + (long)((k + 1) * rows));
         proof.MerklePaths.push_back(tree.GetMerklePath((unsigned)proof.QueryIndices[k]));
@@ -1103,7 +1072,7 @@ static uint8_t *write_small_cts(uint8_t *o, const std::vector<uint64_t> &res, co
 // last Commit / Unmarshal left there): each ciphertext is MetaData | LE64(2) | 2 x (LE64(limbs) | limbs x (LE64(N) | N words))
 static size_t slice_size(const Ciphertexts &c, uint64_t T) {
     if (!c.Len()) return 0;
-    const size_t N = g_ring_degree.at(c.Context()), nl = (size_t)c.Level() + 1;
+    const size_t N = ring_degree(c.Context()), nl = (size_t)c.Level() + 1;
     return (MetaDataJSON(c.Meta, T).size() + 8 + 2 * (8 + nl * (8 + N * 8))) * (size_t)c.Len();
 }
 static size_t slice_size(const ShardedCiphertexts &s, uint64_t T) {
@@ -1135,12 +1104,12 @@ void EncryptedProof::MarshalInto(uint8_t *out, size_t cap, bool pageLocked) cons
         const size_t bytes = slice_size(c, PlaintextModulus);
         if (bytes) {
             // the framing of THIS slice's MetaData and level, not whatever format the context was left with
-            set_format(c.Context(), c.Meta, c.Level(), PlaintextModulus, g_ring_degree.at(c.Context()));
+            set_format(c.Context(), c.Meta, c.Level(), PlaintextModulus, ring_degree(c.Context()));
             if (lumen_ct_serialized_size(c.Context(), (uint32_t)c.Level() + 1) * (size_t)c.Len() != bytes)
                 throw std::runtime_error("MarshalInto: the device's serialised size differs from the framing's");
-            const int rc = pageLocked ? lumen_ct_serialize_async(c.Context(), c.Handle(), 0, (uint32_t)c.Len(), o, bytes)
-                                      : lumen_ct_serialize(c.Context(), c.Handle(), 0, (uint32_t)c.Len(), o, bytes);
-            if (rc) throw std::runtime_error(std::string("lumen_ct_serialize: ") + lumen_last_error(c.Context()));
+            throw_on(pageLocked ? lumen_ct_serialize_async(c.Context(), c.Handle(), 0, (uint32_t)c.Len(), o, bytes)
+                                : lumen_ct_serialize(c.Context(), c.Handle(), 0, (uint32_t)c.Len(), o, bytes),
+                     "lumen_ct_serialize", c.Context());
             used.insert(c.Context());
         }
         o += bytes;
@@ -1169,8 +1138,7 @@ void EncryptedProof::MarshalInto(uint8_t *out, size_t cap, bool pageLocked) cons
     // the bytes are in place once EVERY context that moved a slice has drained (MatR / MatZ may live on clones
     // or on other GPUs than the queried columns)
     if (pageLocked)
-        for (lumen_ctx *c : used)
-            if (lumen_sync(c)) throw std::runtime_error(std::string("lumen_sync: ") + lumen_last_error(c));
+        for (lumen_ctx *c : used) throw_on(lumen_sync(c), "lumen_sync", c);
     if (!core::Span::quiet) {
         printf("Marshaled MatR: %s\n", HumanizeBytes(szR).c_str());
         printf("Marshaled MatZ: %s\n", HumanizeBytes(szZ).c_str());
@@ -1196,8 +1164,7 @@ static EncryptedProof unmarshal(const uint8_t *data, size_t len, lumen_ctx *ctx,
         const size_t bytes = each * (size_t)count;
         if (off + bytes > len) throw std::invalid_argument("UnmarshalBinary: truncated ciphertext slice");
         lumen_set *s = nullptr;
-        if (lumen_ct_deserialize(ctx, data + off, bytes, (uint32_t)count, 2, &s))
-            throw std::runtime_error(std::string("lumen_ct_deserialize: ") + lumen_last_error(ctx));
+        throw_on(lumen_ct_deserialize(ctx, data + off, bytes, (uint32_t)count, 2, &s), "lumen_ct_deserialize", ctx);
         off += bytes;
         return Ciphertexts(ctx, s, meta);
     };
@@ -1235,16 +1202,15 @@ Proof EncryptedProof::Decrypt(ClientBFV &client, core::Span *ctx) {
     const int rows = Metadata.Rows;
     lumen_ctx *h = client.Context();
     Proof proof;
-    core::Span *span = core::Span::StartSpan("Decrypt queried columns", ctx);
+    core::ScopedSpan colSpan("Decrypt queried columns", ctx);
     const int nq = QueriedCols.Len();
     std::vector<uint64_t> values((size_t)nq * (size_t)rows);
     if (nq) client.check(lumen_decrypt(h, QueriedCols.Handle(), QueriedCols.Scale(), (uint32_t)rows, values.data()), "lumen_decrypt");
     for (int i = 0; i < nq; i++)
         proof.QueriedCols.emplace_back(values.begin() + (long)((size_t)i * rows), values.begin() + (long)((size_t)(i + 1) * rows));
-    span->End();
-    delete span;
+    colSpan.End();
 
-    span = core::Span::StartSpan("Decrypt row inner products", ctx);
+    core::ScopedSpan rowSpan("Decrypt row inner products", ctx);
     auto single = [&](const Ciphertexts &c) { // decodeSingleElement of every ciphertext
         std::vector<uint64_t> out((size_t)c.Len());
         if (c.Len()) client.check(lumen_decrypt(h, c.Handle(), c.Scale(), 1, out.data()), "lumen_decrypt");
@@ -1252,8 +1218,7 @@ Proof EncryptedProof::Decrypt(ClientBFV &client, core::Span *ctx) {
     };
     proof.MatR = single(MatR.Blocks[0]);
     proof.MatZ = single(MatZ.Blocks[0]);
-    span->End();
-    delete span;
+    rowSpan.End();
 
     proof.Metadata = Metadata;
     proof.Root = Root;
@@ -1272,37 +1237,12 @@ std::vector<std::vector<core::Element>> EncodeRows(const std::vector<std::vector
     if ((int)rows.size() > lanes) throw std::invalid_argument("EncodeRows: more than 512 rows");
     if ((size_t)field.N() != len * (size_t)rhoInv) throw std::invalid_argument("EncodeRows: the field's table is not of len * rhoInv entries");
     const uint64_t T = field.Modulus();
-    lumen_params_desc d;
-    memset(&d, 0, sizeof(d));
-    d.abi_version = LUMEN_ABI_VERSION, d.log_n = (uint32_t)logN, d.num_q = 1, d.num_p = 0, d.plaintext_modulus = T;
-    d.moduli[0] = T, d.psi[0] = PowMod(core::PrimitiveRoot(T), (T - 1) / (uint64_t)lanes, T), d.device = device;
-    lumen_ctx *ctx = nullptr;
-    if (lumen_ctx_create(&d, &ctx)) throw std::runtime_error(std::string("lumen_ctx_create: ") + lumen_last_error(nullptr));
-    struct Closer {
-        lumen_ctx *c;
-        std::vector<lumen_set *> sets;
-        ~Closer() {
-            for (lumen_set *s : sets) lumen_set_destroy(c, s);
-            lumen_ctx_destroy(c);
-        }
-    } guard{ctx, {}};
-    auto ck = [&](int rc, const char *what) {
-        if (rc) throw std::runtime_error(std::string(what) + ": " + lumen_last_error(ctx));
-    };
-    ck(lumen_field_set(ctx, field.RootsForward().data(), (uint32_t)field.N()), "lumen_field_set");
     std::vector<uint64_t> columns(len * (size_t)lanes, 0); // column j = lane i holds rows[i][j]
     for (size_t i = 0; i < rows.size(); i++)
         for (size_t j = 0; j < len; j++) columns[j * lanes + i] = rows[i][j] % T;
-    lumen_set *m = nullptr, *enc = nullptr;
-    ck(lumen_set_create(ctx, (uint32_t)len, 1, &m), "lumen_set_create");
-    guard.sets.push_back(m);
-    ck(lumen_set_upload(ctx, m, 0, (uint32_t)len, columns.data()), "lumen_set_upload");
-    const std::vector<uint64_t> zero((size_t)lanes, 0);
-    ck(lumen_encode(ctx, m, zero.data(), (uint32_t)rhoInv, &enc), "lumen_encode");
-    guard.sets.push_back(enc);
+    const PlainEncoded plain = plain_encode(field, logN, device, columns, len, rhoInv);
     const size_t S = len * (size_t)rhoInv;
-    std::vector<uint64_t> out(S * (size_t)lanes);
-    ck(lumen_set_download(ctx, enc, 0, (uint32_t)S, out.data()), "lumen_set_download");
+    const std::vector<uint64_t> out = plain.encoded.Download(); // [S][lanes]
     std::vector<std::vector<core::Element>> res(rows.size(), std::vector<core::Element>(S));
     for (size_t i = 0; i < rows.size(); i++)
         for (size_t k = 0; k < S; k++) res[i][k] = out[k * lanes + i];

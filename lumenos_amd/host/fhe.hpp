@@ -81,6 +81,29 @@ struct MetaData {
     int LogRows = 1, LogCols = 0; // LogDimensions of the 2 x N/2 slot matrix
 };
 
+// The one owner of a lumen_ctx in this mirror: ServerBFV, ClientBFV and the plain backend of LigeroProveReference /
+// EncodeRows each hold one.  It creates the context, records its ring degree (the C ABI does not give it back; what
+// Ciphertexts::Download and the wire format size their buffers by) and destroys it, so an owner whose constructor
+// throws half-way leaves nothing on the device.  Move-only.
+class OwnedContext {
+  public:
+    OwnedContext() = default;
+    OwnedContext(const Parameters &params, int device); // lumen_ctx_create of `params`
+    // the plain context: ring degree 2^logN, the one modulus T (T = 1 mod 2^(logN+1)), no special primes
+    OwnedContext(uint64_t T, int logN, int device) : OwnedContext(Parameters::FromModuli(logN, {T}, {}, T), device) {}
+    OwnedContext(OwnedContext &&o) noexcept : ctx_(o.ctx_) { o.ctx_ = nullptr; }
+    OwnedContext &operator=(OwnedContext &&o) noexcept;
+    ~OwnedContext();
+    OwnedContext Clone() const; // lumen_ctx_clone: the same tables and keys, its own streams and scratch
+    lumen_ctx *get() const { return ctx_; }
+    void check(int rc, const char *what) const; // throws std::runtime_error with lumen_last_error
+
+  private:
+    lumen_ctx *ctx_ = nullptr;
+};
+// test hook: the number of contexts the mirror's OwnedContexts hold at this moment
+size_t LiveContextsForTest();
+
 // []*rlwe.Ciphertext resident in HBM
 class Ciphertexts {
   public:
@@ -149,7 +172,7 @@ class ServerBFV {
     core::PrimeField *Field() { return ptField_; }
     const Parameters &GetParameters() const { return params_; }
     int MulCounter() const; // bfv.go:44-46
-    lumen_ctx *Context() const { return ctx_; }
+    lumen_ctx *Context() const { return ctx_.get(); }
     // Encoder.Encode(values, pt) at MaxLevel ([LATTIGO-RECALL] m * T^-1 form, slot index matrix)
     Plaintext Encode(const std::vector<uint64_t> &values) const;
     // Encryptor.EncryptNew(pt) under pk, host layout [2][L][N]
@@ -176,12 +199,12 @@ class ServerBFV {
     std::unique_ptr<ServerBFV> CopyNew();
 
   private:
-    ServerBFV(ServerBFV &src, lumen_ctx *clone);
+    ServerBFV(ServerBFV &src, OwnedContext clone);
     friend class ServerGroup;
     core::PrimeField *ptField_;
     Parameters params_;
     std::vector<uint64_t> pk_;
-    lumen_ctx *ctx_ = nullptr;
+    OwnedContext ctx_;
     uint64_t psiT_ = 0;
     std::vector<uint32_t> slot_index_;
     RingSwitchServer *rs_ = nullptr;
@@ -217,7 +240,7 @@ class ClientBFV {
     ClientBFV(const ClientBFV &) = delete;
     core::PrimeField *Field() { return ptField_; }
     const Parameters &GetParameters() const { return params_; }
-    lumen_ctx *Context() const { return ctx_; }
+    lumen_ctx *Context() const { return ctx_.get(); }
     int Device() const { return device_; }
     void check(int rc, const char *what) const; // throws std::runtime_error with lumen_last_error
     // ClientBFV.CopyNew (bfv.go:96-98): the same key and tables, its own streams and scratch (lumen_ctx_clone); must
@@ -232,10 +255,10 @@ class ClientBFV {
 
   private:
     ClientBFV(core::PrimeField *plaintextField, const Parameters &params, int device);
-    ClientBFV(ClientBFV &src, lumen_ctx *clone);
+    ClientBFV(ClientBFV &src, OwnedContext clone);
     core::PrimeField *ptField_;
     Parameters params_;
-    lumen_ctx *ctx_ = nullptr;
+    OwnedContext ctx_;
     int device_ = 0;
     struct KeySeedBytes {
         uint8_t b[32];

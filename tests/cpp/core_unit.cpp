@@ -3,11 +3,14 @@
 // known answers only -- no GPU, no oracle: SHA-256 (FIPS 180-4), Merlin v0.1.1's test vector (core/transcript.go:43-63
 // sits on it), core.PrimeField's table (core/field.go:138-197; SURVEY App. B.5 values), SqrtFactor (core/math.go:25-36),
 // core.NewTree / GetMerklePath / VerifyMerklePath on ragged leaf counts (core/tree.go:76-268), and the ChaCha20 witness
-// with the reference's logged P(1) for 2048 x 1024 (results/baseline/client/bench_2048x1024_12.txt:22).
+// with the reference's logged P(1) for 2048 x 1024 (results/baseline/client/bench_2048x1024_12.txt:22); and ScopedSpan
+// (core/tracer.go's span under `defer span.End()`) by the lines it prints.
 #include <cstdio>
 #include <cstring>
 #include <stdexcept>
 #include <string>
+
+#include <unistd.h>
 
 #include "../../lumenos_amd/host/core.hpp"
 
@@ -29,8 +32,67 @@ static std::string hex(const uint8_t *p, size_t n) {
     return s;
 }
 
+// what `body` prints to stdout, line by line
+template <class F>
+static std::vector<std::string> printed_lines(F body) {
+    fflush(stdout);
+    FILE *tmp = tmpfile();
+    const int saved = dup(1);
+    if (!tmp || saved < 0 || dup2(fileno(tmp), 1) < 0) throw std::runtime_error("cannot capture stdout");
+    try {
+        body();
+    } catch (...) {
+    }
+    fflush(stdout);
+    dup2(saved, 1);
+    close(saved);
+    rewind(tmp);
+    std::vector<std::string> lines;
+    char buf[256];
+    while (fgets(buf, sizeof(buf), tmp)) lines.emplace_back(buf, strcspn(buf, "\n"));
+    fclose(tmp);
+    return lines;
+}
+
+// "<indent><name> (<seconds>s)" with exactly `indent` leading blanks
+static bool is_span_line(const std::string &line, size_t indent, const std::string &name) {
+    const std::string head = std::string(indent, ' ') + name + " (";
+    if (line.compare(0, head.size(), head) != 0 || line.size() < head.size() + 3 || line.substr(line.size() - 2) != "s)") return false;
+    return line.find_first_not_of("0123456789.", head.size()) == line.size() - 2;
+}
+
 int main() {
     const uint64_t T = 144115188075593729ull; // cmd/server/main.go:22
+    { // ScopedSpan: one line per span, whichever way its scope is left
+        const bool was = Span::quiet;
+        Span::quiet = false;
+        std::vector<std::string> out = printed_lines([] { ScopedSpan s("left by scope", nullptr); });
+        CHECK(out.size() == 1 && is_span_line(out[0], 0, "left by scope"));
+        out = printed_lines([] {
+            ScopedSpan s("left by exception", nullptr);
+            throw std::runtime_error("unwinding");
+        });
+        CHECK(out.size() == 1 && is_span_line(out[0], 0, "left by exception"));
+        double first = -1, second = -1;
+        out = printed_lines([&] {
+            ScopedSpan s("ended by hand", nullptr);
+            first = s.End();
+            second = s.End();
+        });
+        CHECK(out.size() == 1 && is_span_line(out[0], 0, "ended by hand"));
+        CHECK(first >= 0 && first == second);
+        out = printed_lines([] {
+            ScopedSpan parent("parent", nullptr, "parent...");
+            ScopedSpan child("child", parent.get());
+            ScopedSpan grandchild("grandchild", child.get(), "grandchild...");
+        });
+        CHECK(out.size() == 5 && out[0] == "parent..." && out[1] == "    grandchild...");
+        CHECK(out.size() == 5 && is_span_line(out[2], 4, "grandchild") && is_span_line(out[3], 2, "child") && is_span_line(out[4], 0, "parent"));
+        Span::quiet = true;
+        out = printed_lines([] { ScopedSpan s("quiet", nullptr, "quiet..."); });
+        CHECK(out.empty());
+        Span::quiet = was;
+    }
     { // SHA-256
         const Digest a = Sha256((const uint8_t *)"abc", 3);
         CHECK(hex(a.data(), 32) == "ba7816bf8f01cfea414140de5dae2223b00361a396177a9cb410ff61f20015ad");

@@ -9,6 +9,10 @@
 //       verifies.  With ringSwitchLogN: NewRingSwitchClient's key is loaded as well and MatR / MatZ come back switched
 //       into the small ring, where they are decrypted under skNew (the reference skips Verify there,
 //       cmd/client/main.go:210-212).
+//   test_keygen_host refuse
+//       GPU: a ServerBFV that the library refuses half-way through its constructor (an even Galois element, after the
+//       context and the field table exist) leaves no context behind; servers and CopyNews made and destroyed on two
+//       threads at once leave none either (fhe::LiveContextsForTest).
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -16,6 +20,7 @@
 #include <map>
 #include <memory>
 #include <string>
+#include <thread>
 #include <vector>
 
 #include "../../lumenos_amd/host/fhe.hpp"
@@ -101,15 +106,14 @@ static int e2e_mode(int argc, char **argv) {
     core::PrimeField ptField(params.PlaintextModulus(), cols * rhoInv);
 
     // ---- the client's keys (cmd/client/main.go:64-81): nothing below comes from a CPU key generator
-    core::Span *span = core::Span::StartSpan("Generate keys", nullptr);
+    core::ScopedSpan keySpan("Generate keys", nullptr);
     std::unique_ptr<fhe::ClientBFV> client = fhe::ClientBFV::NewWithGeneratedSecret(&ptField, params);
     fhe::KeyGenerator kgen(*client);
     // the Montgomery (Lattigo storage) form on the ring-switch run, the standard form otherwise: both reach the server
     const uint32_t flags = rsLogN ? LUMEN_KEY_MONTGOMERY : 0;
     fhe::KeySet keys = kgen.GenKeySetNew(rows, flags);
     const std::vector<uint64_t> rlk = kgen.GenRelinearizationKeyNew(flags);
-    span->End();
-    delete span;
+    keySpan.End();
     const size_t evkWords = (size_t)((L + K - 1) / K) * 2 * (L + K) * N;
     REQUIRE(keys.Pk.size() == (size_t)2 * (L + K) * N && rlk.size() == evkWords, "key sizes");
     REQUIRE(keys.GaloisElements == params.GaloisElementsForInnerSum(1, rows) && keys.GaloisKeys.size() == keys.GaloisElements.size(),
@@ -173,19 +177,17 @@ static int e2e_mode(int argc, char **argv) {
         const fhe::MetaData meta = proof.QueriedCols.Meta;
         const std::vector<uint8_t> marshaled = proof.MarshalBinary();
         fhe::EncryptedProof ep = fhe::EncryptedProof::UnmarshalBinary(marshaled.data(), marshaled.size(), *client, meta);
-        span = core::Span::StartSpan("Decrypt proof", nullptr, "Decrypting proof...");
-        fhe::Proof plain = ep.Decrypt(*client, span);
-        span->End();
-        delete span;
+        core::ScopedSpan decryptSpan("Decrypt proof", nullptr, "Decrypting proof...");
+        fhe::Proof plain = ep.Decrypt(*client, decryptSpan.get());
+        decryptSpan.End();
         REQUIRE(plain.MatR == ref.MatR && plain.MatZ == ref.MatZ, "MatR / MatZ differ from LigeroProveReference's");
         for (size_t k = 0; k < ref.QueriedCols.size(); k++)
             REQUIRE(plain.QueriedCols[k] == ref.QueriedCols[k], "opened column %zu decrypts to other values than the plain prover's", k);
         printf("PASS decrypt under the generated secret: MatR / MatZ / opened columns = LigeroProveReference's\n");
         core::Transcript vt("demo");
-        span = core::Span::StartSpan("Verify proof", nullptr);
+        core::ScopedSpan verifySpan("Verify proof", nullptr);
         plain.Verify(z, value, *client->Field(), vt, *client);
-        span->End();
-        delete span;
+        verifySpan.End();
         printf("PASS client verify: rows=%d cols=%d LogN=%d, every key generated on the device\n", rows, cols, LogN);
         // the claim is bound to the keys: value + 1 fails
         bool threw = false;
@@ -241,14 +243,67 @@ static int e2e_mode(int argc, char **argv) {
     return 0;
 }
 
+static int refuse_mode() {
+    // LogN 10, L = 2, K = 2: the smallest parameters that have a key switch
+    const int cols = 16;
+    fhe::ParametersLiteral lit = fhe::GenerateBGVParamsForNTT(4, 10, Modulus);
+    const fhe::Parameters params = fhe::Parameters::FromLiteral(lit);
+    const size_t N = (size_t)params.N(), L = params.Q.size(), K = params.P.size();
+    REQUIRE(L == 2 && K == 2, "L = %zu K = %zu", L, K);
+    const size_t evkWords = (L + K - 1) / K * 2 * (L + K) * N;
+    core::PrimeField ptField(Modulus, cols * rhoInv);
+    const size_t n0 = fhe::LiveContextsForTest();
+
+    std::string what;
+    try {
+        const std::map<uint64_t, std::vector<uint64_t>> even = {{2, std::vector<uint64_t>(evkWords, 0)}};
+        fhe::ServerBFV refused(&ptField, params, std::vector<uint64_t>(2 * (L + K) * N, 0), even);
+        REQUIRE(false, "a server with the Galois element 2 was constructed");
+    } catch (const std::runtime_error &e) {
+        what = e.what();
+    }
+    REQUIRE(what.find("not an odd residue mod 2N") != std::string::npos, "refused with another message: %s", what.c_str());
+    REQUIRE(fhe::LiveContextsForTest() == n0, "the refused server left %zu context(s) behind", fhe::LiveContextsForTest() - n0);
+
+    {
+        std::unique_ptr<fhe::ClientBFV> client = fhe::ClientBFV::NewWithGeneratedSecret(&ptField, params);
+        fhe::KeyGenerator kgen(*client);
+        const std::vector<uint64_t> pk = kgen.GenKeyPairNew();
+        const std::map<uint64_t, std::vector<uint64_t>> evk = kgen.GenGaloisKeysNew({params.GaloisElement(1)});
+        size_t seen[2] = {0, 0};
+        std::string err[2];
+        auto run = [&](int t) {
+            try {
+                fhe::ServerBFV server(&ptField, params, pk, evk);
+                std::unique_ptr<fhe::ServerBFV> copy = server.CopyNew();
+                seen[t] = fhe::LiveContextsForTest();
+            } catch (const std::exception &e) {
+                err[t] = e.what();
+            }
+        };
+        std::thread a(run, 0), b(run, 1);
+        a.join(), b.join();
+        for (int t = 0; t < 2; t++) {
+            REQUIRE(err[t].empty(), "thread %d: %s", t, err[t].c_str());
+            // the client's, this thread's server and its copy at the least; the other thread's two at the most
+            REQUIRE(seen[t] >= n0 + 3 && seen[t] <= n0 + 5, "thread %d saw %zu live contexts over %zu", t, seen[t], n0);
+        }
+        REQUIRE(fhe::LiveContextsForTest() == n0 + 1, "servers and copies of two threads left contexts behind");
+    }
+    REQUIRE(fhe::LiveContextsForTest() == n0, "%zu context(s) left at the end", fhe::LiveContextsForTest() - n0);
+    printf("PASS refused server leaves no context\n");
+    return 0;
+}
+
 int main(int argc, char **argv) {
     try {
         if (argc >= 2 && !strcmp(argv[1], "elements")) return elements_mode(argc, argv);
         if (argc >= 2 && !strcmp(argv[1], "e2e")) return e2e_mode(argc, argv);
+        if (argc >= 2 && !strcmp(argv[1], "refuse")) return refuse_mode();
     } catch (const std::exception &e) {
         fprintf(stderr, "FAIL exception: %s\n", e.what());
         return 1;
     }
-    fprintf(stderr, "usage: test_keygen_host elements|e2e ...\n");
+    fprintf(stderr, "usage: test_keygen_host elements|e2e|refuse ...\n");
     return 2;
 }

@@ -1,11 +1,34 @@
 """Shared test helpers: one parameter set drives both the CPU oracle and the HIP context."""
 import ctypes as C
+import os
+import subprocess
 
 import numpy as np
 
 from oracle.loader import Params
 
 T_REF = 144115188075593729  # cmd/server/main.go:22, fhe/ligero_test.go:16
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def build_cpp_twin(name, with_oracle=True):
+    """tests/cpp/<name>.cpp -> tests/cpp/<name>, linked against the host mirror, the HIP library and (with_oracle) the
+    CPU oracle, each built first; rebuilt only when the source or one of those libraries is newer."""
+    from lumenos_amd import _build
+    host = _build.build_host()
+    src, exe = os.path.join(ROOT, "tests", "cpp", name + ".cpp"), os.path.join(ROOT, "tests", "cpp", name)
+    dirs, libs, deps = [os.path.dirname(host), os.path.dirname(_build.LIB)], ["-llumenos_host", "-llumenos_hip"], [src, host]
+    if with_oracle:
+        from oracle import loader
+        loader.build()
+        dirs.append(os.path.join(ROOT, "oracle"))
+        libs.append("-llumen_oracle")
+        deps.append(os.path.join(ROOT, "oracle", "liblumen_oracle.so"))
+    if os.path.exists(exe) and all(os.path.getmtime(d) < os.path.getmtime(exe) for d in deps):
+        return exe
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", src, "-o", exe] + ["-L" + d for d in dirs] + libs +
+                          ["-Wl,-rpath," + ":".join(dirs)])
+    return exe
 
 
 def gen_primes(oracle, bits, n, two_n, exclude=(T_REF,)):

@@ -5,24 +5,11 @@ import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "tests", "cpp", "test_ligero_host")
+from helpers import ROOT, build_cpp_twin
 
 
 def build_binary():
-    from lumenos_amd import _build
-    from oracle import loader
-    host = _build.build_host()
-    loader.build()
-    src = os.path.join(ROOT, "tests", "cpp", "test_ligero_host.cpp")
-    deps = [src, host, os.path.join(ROOT, "oracle", "liblumen_oracle.so")]
-    if os.path.exists(BIN) and all(os.path.getmtime(d) < os.path.getmtime(BIN) for d in deps):
-        return BIN
-    hd, cd, od = os.path.dirname(host), os.path.dirname(_build.LIB), os.path.join(ROOT, "oracle")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", src, "-o", BIN,
-                           "-L" + hd, "-llumenos_host", "-L" + cd, "-llumenos_hip", "-L" + od, "-llumen_oracle",
-                           f"-Wl,-rpath,{hd}:{cd}:{od}"])
-    return BIN
+    return build_cpp_twin("test_ligero_host")
 
 
 def test_host_mirror_builds():

@@ -2,32 +2,15 @@
 fhe::ClientBFV::NewWithGeneratedSecret, fhe::KeyGenerator, fhe::NewRingSwitchClient and the server's
 ServerBFV::NewFromKeySet.  CPU: the key set's Galois elements cover what InnerSum applies.  GPU:
 tests/cpp/test_keygen_host.cpp runs the whole protocol with no CPU-generated key anywhere."""
-import os
 import subprocess
 
 import pytest
 
-from helpers import make_params
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "tests", "cpp", "test_keygen_host")
+from helpers import build_cpp_twin, make_params
 
 
 def build_binary():
-    """built like tests/test_verify_host.py builds its twin"""
-    from lumenos_amd import _build
-    from oracle import loader
-    host = _build.build_host()
-    loader.build()
-    src = os.path.join(ROOT, "tests", "cpp", "test_keygen_host.cpp")
-    deps = [src, host, os.path.join(ROOT, "oracle", "liblumen_oracle.so")]
-    if os.path.exists(BIN) and all(os.path.getmtime(d) < os.path.getmtime(BIN) for d in deps):
-        return BIN
-    hd, cd, od = os.path.dirname(host), os.path.dirname(_build.LIB), os.path.join(ROOT, "oracle")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", src, "-o", BIN,
-                           "-L" + hd, "-llumenos_host", "-L" + cd, "-llumenos_hip", "-L" + od, "-llumen_oracle",
-                           f"-Wl,-rpath,{hd}:{cd}:{od}"])
-    return BIN
+    return build_cpp_twin("test_keygen_host")
 
 
 @pytest.mark.parametrize("log_n,rows", [(12, 2048), (12, 4096), (14, 16384), (10, 8)])
@@ -60,3 +43,14 @@ def test_client_generates_keys_server_proves_client_verifies(ring_switch):
         ["decrypt under the generated secret", "client verify", "value + 1 is refused"]
     for what in want:
         assert "PASS " + what in res.stdout, what
+
+
+@pytest.mark.gpu
+def test_refused_server_leaves_no_context():
+    """LogN 10, L 2, K 2 (the smallest parameters with a key switch): the library refuses the even Galois element 2
+    after the server's context and field table exist; the constructor throws that message and
+    fhe::LiveContextsForTest() is back where it was.  Then a server and a CopyNew of it on each of two threads at once,
+    destroyed there: the count returns again."""
+    res = subprocess.run([build_binary(), "refuse"], capture_output=True, text=True, timeout=300)
+    assert res.returncode == 0, res.stdout[-3000:] + res.stderr[-3000:]
+    assert "PASS refused server leaves no context" in res.stdout

@@ -2,33 +2,19 @@
 through the C++ host mirror.  CPU: core::DensePoly::Evaluate against Horner in Python integers over the row-major
 flattening.  GPU: tests/cpp/test_poly_eval_host.cpp proves at a random z != 1 and holds the verifier's claim
 InnerProduct(MatZ, [1, z, z^2, ...]) (fhe/ligero.go:569) to the device P(z) and the host Horner."""
-import os
 import random
 import subprocess
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "tests", "cpp", "test_poly_eval_host")
+from helpers import build_cpp_twin
+
 T = 144115188075593729  # fhe/ligero_test.go:16
 
 
 def build_binary():
-    """built like tests/test_host_mirror.py builds the TestLigeroE2E twin"""
-    from lumenos_amd import _build
-    from oracle import loader
-    host = _build.build_host()
-    loader.build()
-    src = os.path.join(ROOT, "tests", "cpp", "test_poly_eval_host.cpp")
-    deps = [src, host, os.path.join(ROOT, "oracle", "liblumen_oracle.so")]
-    if os.path.exists(BIN) and all(os.path.getmtime(d) < os.path.getmtime(BIN) for d in deps):
-        return BIN
-    hd, cd, od = os.path.dirname(host), os.path.dirname(_build.LIB), os.path.join(ROOT, "oracle")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", src, "-o", BIN,
-                           "-L" + hd, "-llumenos_host", "-L" + cd, "-llumenos_hip", "-L" + od, "-llumen_oracle",
-                           f"-Wl,-rpath,{hd}:{cd}:{od}"])
-    return BIN
+    return build_cpp_twin("test_poly_eval_host")
 
 
 def horner(coefficients, z, t=T):

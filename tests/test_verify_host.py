@@ -2,32 +2,18 @@
 EncryptedProof::Decrypt, Proof::Verify over lumen_verify_columns).  CPU: what Verify derives from the transcript before
 it touches the device, and its error strings, against the oracle's transcript and Python integers.  GPU:
 tests/cpp/test_verify_host.cpp proves at a random z != 1, verifies, and tampers with the marshaled bytes."""
-import os
 import random
 import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "tests", "cpp", "test_verify_host")
+from helpers import build_cpp_twin
+
 T = 144115188075593729  # fhe/ligero_test.go:16
 
 
 def build_binary():
-    """built like tests/test_poly_eval_host.py builds its twin"""
-    from lumenos_amd import _build
-    from oracle import loader
-    host = _build.build_host()
-    loader.build()
-    src = os.path.join(ROOT, "tests", "cpp", "test_verify_host.cpp")
-    deps = [src, host, os.path.join(ROOT, "oracle", "liblumen_oracle.so")]
-    if os.path.exists(BIN) and all(os.path.getmtime(d) < os.path.getmtime(BIN) for d in deps):
-        return BIN
-    hd, cd, od = os.path.dirname(host), os.path.dirname(_build.LIB), os.path.join(ROOT, "oracle")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", src, "-o", BIN,
-                           "-L" + hd, "-llumenos_host", "-L" + cd, "-llumenos_hip", "-L" + od, "-llumen_oracle",
-                           f"-Wl,-rpath,{hd}:{cd}:{od}"])
-    return BIN
+    return build_cpp_twin("test_verify_host")
 
 
 @pytest.mark.parametrize("name,rows,cols,queries", [("demo", 2048, 1024, 309), ("test", 512, 16, 24), ("x", 7, 3, 5)])
