@@ -408,6 +408,51 @@ int lumen_keygen_ringswitch(lumen_ctx *ctx, const uint8_t seed[32], uint32_t log
                             uint64_t *key, size_t key_words /* the full [rns][pw2][b|a][L+K][N] size */,
                             int8_t *sk_small /* host [2^log_n_small] */);
 
+/* ---- the client's encryptor: witness encryption under the SECRET key, and seeded ciphertexts (fhe/bfv.go:77: the
+ * rlwe.NewEncryptor(paramsFHE, sk) that ClientBFV embeds; client.EncryptNew, vdec/batching_test.go:56).  In the protocol
+ * the witness belongs to the client; a client that holds its secret on the device (lumen_load_secret_key or
+ * lumen_keygen_secret) encrypts under it: `count` columns of `rows` slot values, host [count][rows], exactly what
+ * lumen_encrypt_values takes, to top-level ciphertexts
+ *     c1[l] = a_l,    c0[l] = NTT_l(e) + pt_l - a_l (.) NTT_l(s)      (canonical residues)
+ * -- L limb transforms per ciphertext against the (L+K) + 2K + 2L of the public-key path, and no public key at all.
+ * c1 is pure randomness regenerated from a PUBLIC 32-byte seed, so a ciphertext travels as its c0 half and that seed:
+ * lumen_encrypt_sk_seeded returns only the c0 halves (half the bytes over PCIe and the network) and the server rebuilds
+ * the set with lumen_ct_expand_seeded, which needs no key of any kind.
+ * CONTRACT.  Deterministic in (seeds, first_index + i, limb, coefficient): chunked, one ciphertext at a time or on
+ * another GPU the bits are the same.
+ *   keystream(I, s) = ChaCha20(key, nonce = LE64(I) || LE32(s), counter = 0, 1, ...), the library's one keystream;
+ *     ciphertext i has index I = first_index + i;
+ *   error e: stream 3 of keystream(I, .) under secret_seed, the encryptor's CDT rule (sigma 3.2, |e| <= 19), one
+ *     N-coefficient sample per ciphertext extended to every limb.  The public-key encryptor draws streams 0-2 and key
+ *     generation streams 16 + m, so the stream number separates the domains; a seed is still key material taken from
+ *     the OS CSPRNG and used for ONE purpose only;
+ *   c1[l] = a_l: uniform mod q_l, sampled in the NTT domain from stream 16 + l of keystream(I, .) under a_seed by key
+ *     generation's exact rule: attempt t of coefficient k is 64-bit word t * N + k, the first x < 2^64 - (2^64 mod q_l)
+ *     is kept as x mod q_l.  Q limbs only;
+ *   pt: the plaintext bits lumen_encrypt_values encrypts (slot scatter, INTT over Z_T, m * T^-1 mod q_l: Encoder.Encode);
+ *   s: the context's secret key, loaded or generated.
+ * The three calls agree: lumen_encrypt_sk_seeded returns the c0 halves of the very set lumen_encrypt_sk_values would
+ * return, and lumen_ct_expand_seeded rebuilds that set bit for bit on any context with the same moduli (the c0 words are
+ * taken as given, like lumen_set_upload; page-locked c0: one strided DMA, pageable: the bounce buffers).
+ * a_seed is public, secret_seed is key material: equal seeds are refused (the server could regenerate e).  A pair
+ * (a_seed, index) MUST NOT encrypt two messages under one key -- the same a twice leaks the difference of the
+ * plaintexts: take a fresh a_seed from the OS CSPRNG per call (or keep first_index moving) and use it for nothing else.
+ * The fresh noise is e itself, larger than the few units the public-key path leaves after its division by P
+ * (tools/noise_budget.py: every BASELINE shape tolerates it).
+ * Refused with a message, before any device work: NULL arguments; no secret key; no encoder tables; rows outside
+ * [1, N]; equal seeds.  count == 0 succeeds and touches nothing. */
+/* Encoder.Encode + Encryptor(sk).EncryptNew of `count` columns of `rows` slot values: full ciphertexts on the device */
+int lumen_encrypt_sk_values(lumen_ctx *ctx, const uint64_t *values, uint32_t rows, uint32_t count,
+                            const uint8_t secret_seed[32], const uint8_t a_seed[32], uint64_t first_index,
+                            lumen_set **out);
+/* the same ciphertexts in seeded form: only the c0 halves leave the device; c0: host, [count][L][N] */
+int lumen_encrypt_sk_seeded(lumen_ctx *ctx, const uint64_t *values, uint32_t rows, uint32_t count,
+                            const uint8_t secret_seed[32], const uint8_t a_seed[32], uint64_t first_index,
+                            uint64_t *c0);
+/* the server's side: c0 halves + public seed -> the full top-level set.  Needs no key of any kind. */
+int lumen_ct_expand_seeded(lumen_ctx *ctx, const uint64_t *c0, uint32_t count, const uint8_t a_seed[32],
+                           uint64_t first_index, lumen_set **out);
+
 /* ---- query loop of Prove (fhe/ligero.go:268-279): gather ciphertexts idx[i]
  * of a set into a new set (duplicates allowed). */
 int lumen_gather(lumen_ctx *ctx, const lumen_set *src, const uint32_t *idx, uint32_t n,

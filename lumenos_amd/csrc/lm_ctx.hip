@@ -638,6 +638,36 @@ int lm_h2d(lumen_ctx *ctx, void *dev, const void *host, size_t bytes) {
     return 0;
 }
 
+// the same for `height` rows of `width` bytes that lie spitch apart on the host and dpitch apart on the device
+// (the c0 halves of seeded ciphertexts into a full set): one strided DMA out of page-locked memory, whole rows
+// through the bounce buffers otherwise
+int lm_h2d_rows(lumen_ctx *ctx, void *dev, size_t dpitch, const void *host, size_t spitch, size_t width, size_t height) {
+    char *dst = (char *)dev;
+    const char *src = (const char *)host;
+    if (!width || !height) return 0;
+    if (width * height <= ((size_t)1 << 20) || lm_host_is_pinned(host)) {
+        LM_HIP(ctx, hipMemcpy2DAsync(dst, dpitch, src, spitch, width, height, hipMemcpyHostToDevice, ctx->stream));
+    } else {
+        LM_CHECK(ctx, width <= LM_IO_CHUNK, "lm_h2d_rows: a row of %zu bytes exceeds the bounce buffer", width);
+        if (int rc = io_buffers(ctx)) return rc;
+        const size_t per = LM_IO_CHUNK / width; // rows per bounce buffer
+        int i = 0;
+        for (size_t r = 0; r < height; r += per, i ^= 1) {
+            const size_t nr = std::min(per, height - r);
+            LM_HIP(ctx, hipEventSynchronize(ctx->ev_io[i])); // the copy that last read this bounce buffer
+            if (spitch == width)
+                par_memcpy(ctx->io_host[i], src + r * spitch, nr * width);
+            else
+                for (size_t k = 0; k < nr; k++) memcpy((char *)ctx->io_host[i] + k * width, src + (r + k) * spitch, width);
+            LM_HIP(ctx, hipMemcpy2DAsync(dst + r * dpitch, dpitch, ctx->io_host[i], width, width, nr, hipMemcpyHostToDevice,
+                                         ctx->stream));
+            LM_HIP(ctx, hipEventRecord(ctx->ev_io[i], ctx->stream));
+        }
+    }
+    LM_HIP(ctx, hipStreamSynchronize(ctx->stream)); // `host` is caller memory
+    return 0;
+}
+
 extern "C" int lumen_set_upload(lumen_ctx *ctx, lumen_set *set, uint32_t first, uint32_t n,
                                 const uint64_t *host) {
     LM_CHECK(nullptr, ctx && set && host, "lumen_set_upload: NULL argument");

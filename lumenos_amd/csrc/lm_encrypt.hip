@@ -18,7 +18,7 @@
 // the LDS-resident limb transform, the pk products and the sums fused into the stores).
 #include <cstring>
 
-#include "lm_ks_dev.h"
+#include "lm_enc_host.h"
 #include "lm_sample_dev.h"
 
 // small: [count][3][N] int8.  Per ciphertext N/16 blocks of stream 0 and N/8 blocks of streams 1, 2.
@@ -81,10 +81,6 @@ __global__ __launch_bounds__(256) void k_sample_small(int8_t *__restrict__ small
 //   k_enc_down   one workgroup per (ciphertext, w, Q limb): the lift fused into the load together with
 //                -e_w and, for w = 0, the message; NTT; combine with the product of k_enc_u in the store.
 // Without special primes (K = 0) there is nothing to divide by: c_w = U*pk_w + NTT(e_w).
-struct enc_tinv_t {
-    tw_t t[LM_MAX_LIMBS]; // message scale per Q limb: -P * T^-1 mod q_l (K > 0), T^-1 mod q_l (K = 0)
-};
-
 // pk: [2][LK][N] Shoup form (Q limbs times P^-1); out: [count][2][L][N]; upk: [count][2][K][N]
 template <int LOGN>
 __global__ LM_GEOM_BOUNDS(lm_geom_lds(LOGN)) void k_enc_u(const int8_t *__restrict__ small,
@@ -242,17 +238,7 @@ extern "C" int lumen_load_public_key(lumen_ctx *ctx, const uint64_t *pk) {
     return 0;
 }
 
-// ---- Encoder.Encode on the device ([LATTIGO-RECALL] bgv.Encoder: slot i of row 0 sits at the
-// evaluation point 5^i, row 1 at -5^i; slots -> INTT over Z_T -> scale by T^-1 mod q_l -> NTT)
-struct EncoderTables {
-    lm_dev<uint32_t> d_slot; // [N] slot -> coefficient position of the Z_T transform
-    lm_dev<tw_t> d_tw_inv;   // [N] inverse twiddles modulo T
-    lm_dev<tw_t> d_tw_fwd;   // [N] forward twiddles modulo T (Encoder.Decode)
-    mod_t modT;
-    tw_t ninvT;
-    enc_tinv_t tinv; // T^-1 mod q_l
-};
-
+// ---- Encoder.Encode on the device (EncoderTables, lm_enc_host.h)
 extern "C" int lumen_encoder_set(lumen_ctx *ctx, uint64_t psi_t) {
     LM_CHECK(nullptr, ctx, "lumen_encoder_set: NULL ctx");
     LM_ENTER(ctx);
@@ -293,6 +279,22 @@ __global__ void k_scatter_slots(const u64 *__restrict__ values, u64 *__restrict_
     const size_t c = g / rows;
     const uint32_t i = (uint32_t)(g % rows);
     m[(c << logN) + slot[i]] = lm_reduce(values[g], modT.q, modT.qinv64);
+}
+
+int lm_encode_coeffs(lumen_ctx *ctx, const EncoderTables *enc, const uint64_t *values, uint32_t rows, uint32_t n, u64 *dval,
+                     u64 *dm) {
+    const uint32_t N = ctx->N;
+    LM_HIP(ctx, hipMemcpyAsync(dval, values, (size_t)n * rows * sizeof(u64), hipMemcpyHostToDevice, ctx->stream));
+    LM_HIP(ctx, hipMemsetAsync(dm, 0, (size_t)n * N * sizeof(u64), ctx->stream));
+    const size_t total = (size_t)n * rows;
+    {
+        lm_prof_scope ps(ctx, "encode_scatter", n);
+        hipLaunchKernelGGL(k_scatter_slots, dim3((uint32_t)((total + 255) / 256)), dim3(256), 0, ctx->stream, dval, dm,
+                           enc->d_slot.get(), rows, ctx->logN, total, enc->modT);
+        LM_HIP(ctx, hipGetLastError());
+    }
+    lm_prof_scope ps(ctx, "encode_intt_T", n);
+    return lm_launch_ntt_subring(ctx, ctx->logN, enc->d_tw_inv.get(), enc->ninvT, dm, N, dm, N, n, 0, true, &enc->modT);
 }
 
 template <int LOGN>
@@ -391,21 +393,8 @@ static int encrypt_impl(lumen_ctx *ctx, const uint64_t *plaintexts, const uint64
         if (plaintexts)
             LM_HIP(ctx, hipMemcpyAsync(dpt, plaintexts + (size_t)first * L * N, (size_t)n * L * N * sizeof(u64),
                                        hipMemcpyHostToDevice, ctx->stream));
-        if (values) { // Encoder.Encode up to the coefficient vector modulo T
-            LM_HIP(ctx, hipMemcpyAsync(dval, values + (size_t)first * rows, (size_t)n * rows * sizeof(u64),
-                                       hipMemcpyHostToDevice, ctx->stream));
-            LM_HIP(ctx, hipMemsetAsync(dm, 0, (size_t)n * N * sizeof(u64), ctx->stream));
-            const size_t total = (size_t)n * rows;
-            {
-                lm_prof_scope ps(ctx, "encode_scatter", n);
-                hipLaunchKernelGGL(k_scatter_slots, dim3((uint32_t)((total + 255) / 256)), dim3(256), 0, ctx->stream, dval,
-                                   dm, enc->d_slot.get(), rows, ctx->logN, total, enc->modT);
-                LM_HIP(ctx, hipGetLastError());
-            }
-            lm_prof_scope ps(ctx, "encode_intt_T", n);
-            rc = lm_launch_ntt_subring(ctx, ctx->logN, enc->d_tw_inv.get(), enc->ninvT, dm, N, dm, N, n, 0, true, &enc->modT);
-            if (rc) break;
-        }
+        if (values)
+            if ((rc = lm_encode_coeffs(ctx, enc, values + (size_t)first * rows, rows, n, dval, dm))) break;
         {
             lm_prof_scope ps(ctx, "encrypt_pk_sample", n);
             const size_t threads = (size_t)n * (N >> 4) * 5;
@@ -443,11 +432,6 @@ extern "C" int lumen_encrypt_values(lumen_ctx *ctx, const uint64_t *values, uint
 // centred, reduced modulo T; NTT over Z_T; slot i read at the encoder's index; divided by the scale
 // the rescales left behind.  The secret key lives with the client: this entry point is for a client
 // that owns a GPU and for end-to-end tests, not for the proving server.
-struct SkTable {
-    lm_dev<tw_t> d_sk; // [L][N] Shoup form
-};
-
-// a secret generated on the device (lm_keygen.hip): [L][N] Shoup form
 void lm_install_secret_key_dev(lumen_ctx *ctx, lm_dev<tw_t> &&d_sk) {
     auto sp = std::make_shared<SkTable>();
     sp->d_sk = std::move(d_sk);

@@ -38,8 +38,7 @@
 #define LM_KG_ID_GALOIS 0x10000ull
 #define LM_KG_UNIFORM_STREAM 16u
 
-int lm_d2h(lumen_ctx *ctx, void *host, const void *dev, size_t bytes, bool wait); // lm_ctx.hip
-void lm_install_secret_key_dev(lumen_ctx *ctx, lm_dev<tw_t> &&d_sk);               // lm_encrypt.hip
+#include "lm_enc_host.h"
 
 struct kg_lim_t {
     u64 t[LM_MAX_LIMBS]; // 2^64 - (2^64 mod q_m): words below it are kept
@@ -63,10 +62,13 @@ __global__ __launch_bounds__(256) void k_keygen_small(int8_t *__restrict__ out, 
         *reinterpret_cast<uint2 *>(o + (size_t)blk * 8) = lm_gauss8(w, cdt);
 }
 
-// The `a` half of every entry: out is [nitems][b|a][LK][N].  blockIdx.y = item * LK + limb, one thread per block of 8
-// coefficients.  Attempt t of coefficients 8 blk .. 8 blk + 7 is words of block t * N/8 + blk.
-__global__ __launch_bounds__(256) void k_keygen_uniform(u64 *__restrict__ out, const u64 *__restrict__ index, uint32_t LK,
-                                                        uint32_t logN, lm_mods mods, kg_lim_t lim, enc_seed_t seed) {
+// The `a` half of every entry: a is the first of them, [LK][N] per item and item_stride words from one item to the next
+// (a key's [nitems][b|a][LK][N]: out + LK * N, 2 * LK * N apart; the secret-key encryptor's c1 halves alike, or a plain
+// [nitems][L][N] block).  blockIdx.y = item * LK + limb, one thread per block of 8 coefficients.  Attempt t of
+// coefficients 8 blk .. 8 blk + 7 is words of block t * N/8 + blk.
+__global__ __launch_bounds__(256) void k_keygen_uniform(u64 *__restrict__ a, size_t item_stride, const u64 *__restrict__ index,
+                                                        uint32_t LK, uint32_t logN, lm_mods mods, kg_lim_t lim,
+                                                        enc_seed_t seed) {
     const uint32_t N = 1u << logN, blk = blockIdx.x * blockDim.x + threadIdx.x;
     if (blk >= (N >> 3)) return;
     const uint32_t it = blockIdx.y / LK, m = blockIdx.y % LK;
@@ -85,7 +87,7 @@ __global__ __launch_bounds__(256) void k_keygen_uniform(u64 *__restrict__ out, c
             }
         }
     }
-    lm_store_run(out + (((size_t)it * 2 + 1) * LK + m) * N, blk * 8, r, 8);
+    lm_store_run(a + (size_t)it * item_stride + (size_t)m * N, blk * 8, r, 8);
 }
 
 // NTT of small polynomials over QP: slot j of `small` ([nslots][*] int8) -> mont[j][m] = NTT(.) * 2^64 mod q_m (the form
@@ -256,7 +258,7 @@ static uint64_t kg_p_mod(const lumen_ctx *ctx, uint64_t q) {
     return P;
 }
 
-static int kg_small(lumen_ctx *ctx, int8_t *out, const u64 *d_index, uint32_t nitems, uint32_t stream, const uint8_t seed[32]) {
+int lm_kg_small(lumen_ctx *ctx, int8_t *out, const u64 *d_index, uint32_t nitems, uint32_t stream, const uint8_t seed[32]) {
     const size_t threads = (size_t)nitems * (stream == 0 ? ctx->N >> 4 : ctx->N >> 3);
     hipLaunchKernelGGL(k_keygen_small, dim3((uint32_t)((threads + 255) / 256)), dim3(256), 0, ctx->stream, out, d_index, nitems,
                        stream, ctx->logN, kg_seed(seed), kg_cdt());
@@ -264,8 +266,23 @@ static int kg_small(lumen_ctx *ctx, int8_t *out, const u64 *d_index, uint32_t ni
     return 0;
 }
 
+// the uniform halves of nitems items over the first LK moduli (k_keygen_uniform's layout)
+int lm_kg_uniform(lumen_ctx *ctx, u64 *a, size_t item_stride, const u64 *d_index, uint32_t nitems, uint32_t LK,
+                  const uint8_t seed[32]) {
+    kg_lim_t lim;
+    for (uint32_t t = 0; t < LM_MAX_LIMBS; t++) {
+        const uint64_t q = ctx->mod[t < LK ? t : 0];
+        lim.t[t] = 0 - ((0 - q) % q); // 2^64 - (2^64 mod q)
+    }
+    const uint32_t nb = ctx->N >> 3, bs = nb < 256 ? nb : 256;
+    hipLaunchKernelGGL(k_keygen_uniform, dim3(nb / bs, nitems * LK), dim3(bs), 0, ctx->stream, a, item_stride, d_index, LK,
+                       ctx->logN, ctx->mods, lim, kg_seed(seed));
+    LM_HIP(ctx, hipGetLastError());
+    return 0;
+}
+
 // host words -> a device temporary, through the pinned staging buffer
-static int kg_upload(lumen_ctx *ctx, void *dev, const void *host, size_t bytes) {
+int lm_kg_upload(lumen_ctx *ctx, void *dev, const void *host, size_t bytes) {
     void *h = lm_stage(ctx, bytes);
     if (!h) return 1;
     memcpy(h, host, bytes);
@@ -305,23 +322,15 @@ static int kg_run(lumen_ctx *ctx, const uint8_t seed[32], const std::vector<u64>
     lm_dev<u64> d_tab, d_out;
     lm_dev<int8_t> d_e;
     if (kg_alloc(ctx, d_tab, tab.size(), false) || kg_alloc(ctx, d_out, out_words, false) || kg_alloc(ctx, d_e, (size_t)nitems * N, true)) return 1;
-    if (int rc = kg_upload(ctx, d_tab.get(), tab.data(), tab.size() * 8)) return rc;
+    if (int rc = lm_kg_upload(ctx, d_tab.get(), tab.data(), tab.size() * 8)) return rc;
     const u64 *d_index = d_tab.get(), *d_fac = fac ? d_index + nitems : nullptr;
     {
         lm_prof_scope ps(ctx, "keygen_sample", nitems);
-        if (int rc = kg_small(ctx, d_e.get(), d_index, nitems, 1, seed)) return rc;
+        if (int rc = lm_kg_small(ctx, d_e.get(), d_index, nitems, 1, seed)) return rc;
     }
     {
         lm_prof_scope ps(ctx, "keygen_uniform", (uint64_t)nitems * LK);
-        kg_lim_t lim;
-        for (uint32_t t = 0; t < LM_MAX_LIMBS; t++) {
-            const uint64_t q = ctx->mod[t < LK ? t : 0];
-            lim.t[t] = 0 - ((0 - q) % q); // 2^64 - (2^64 mod q)
-        }
-        const uint32_t nb = N >> 3, bs = nb < 256 ? nb : 256;
-        hipLaunchKernelGGL(k_keygen_uniform, dim3(nb / bs, nitems * LK), dim3(bs), 0, ctx->stream, d_out.get(), d_index, LK,
-                           ctx->logN, ctx->mods, lim, kg_seed(seed));
-        LM_HIP(ctx, hipGetLastError());
+        if (int rc = lm_kg_uniform(ctx, d_out.get() + (size_t)LK * N, (size_t)2 * LK * N, d_index, nitems, LK, seed)) return rc;
     }
     if (int rc = lm_for_logn(ctx, ctx->logN, [&](auto k) {
             return kg_evk_t<k>(ctx, d_e.get(), d_out.get(), s_out, sout_stride, s_in, d_fac, nitems, nent,
@@ -363,8 +372,8 @@ extern "C" int lumen_keygen_secret(lumen_ctx *ctx, const uint8_t seed[32], uint6
     if (sp->d_mont.alloc(ctx, words, "the generated secret") || d_sk.alloc(ctx, (size_t)L * N, "the secret key")) return 1;
     if (kg_alloc(ctx, d_idx, 1, false) || kg_alloc(ctx, d_small, N, true) || kg_alloc(ctx, d_std, words, true)) return 1;
     const u64 index = LM_KG_ID_SECRET * LM_KG_INDEX_STRIDE;
-    if (int rc = kg_upload(ctx, d_idx.get(), &index, 8)) return rc;
-    if (int rc = kg_small(ctx, d_small.get(), d_idx.get(), 1, 0, seed)) return rc;
+    if (int rc = lm_kg_upload(ctx, d_idx.get(), &index, 8)) return rc;
+    if (int rc = lm_kg_small(ctx, d_small.get(), d_idx.get(), 1, 0, seed)) return rc;
     if (int rc = lm_for_logn(ctx, ctx->logN, [&](auto k) {
             return kg_secret_ntt_t<k>(ctx, d_small.get(), sp->d_mont.get(), d_std.get(), 1, 0);
         }))
@@ -473,8 +482,8 @@ extern "C" int lumen_keygen_ringswitch(lumen_ctx *ctx, const uint8_t seed[32], u
     lm_dev<int8_t> d_small;
     if (kg_alloc(ctx, d_idx, 1, false) || kg_alloc(ctx, d_small, N, true) || kg_alloc(ctx, d_sout, words, true)) return 1;
     const u64 index = LM_KG_ID_RINGSWITCH * LM_KG_INDEX_STRIDE;
-    if (int rc = kg_upload(ctx, d_idx.get(), &index, 8)) return rc;
-    if (int rc = kg_small(ctx, d_small.get(), d_idx.get(), 1, 0, seed)) return rc;
+    if (int rc = lm_kg_upload(ctx, d_idx.get(), &index, 8)) return rc;
+    if (int rc = lm_kg_small(ctx, d_small.get(), d_idx.get(), 1, 0, seed)) return rc;
     // skNew(X^(N/n)) over QP
     if (int rc = lm_for_logn(ctx, ctx->logN, [&](auto k) {
             return kg_secret_ntt_t<k>(ctx, d_small.get(), d_sout.get(), nullptr, 1, ctx->logN - log_n_small);

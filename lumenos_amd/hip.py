@@ -127,6 +127,9 @@ SYMBOLS = {
     "lumen_keygen_galois": (C.c_int, [_vp, _u8p, _u64p, C.c_uint32, _u64p, C.c_uint32]),
     "lumen_keygen_relin": (C.c_int, [_vp, _u8p, _u64p, C.c_uint32]),
     "lumen_keygen_ringswitch": (C.c_int, [_vp, _u8p, C.c_uint32, C.c_uint32, _u64p, C.c_size_t, C.POINTER(C.c_int8)]),
+    "lumen_encrypt_sk_values": (C.c_int, [_vp, _u64p, C.c_uint32, C.c_uint32, _u8p, _u8p, C.c_uint64, C.POINTER(_vp)]),
+    "lumen_encrypt_sk_seeded": (C.c_int, [_vp, _u64p, C.c_uint32, C.c_uint32, _u8p, _u8p, C.c_uint64, _u64p]),
+    "lumen_ct_expand_seeded": (C.c_int, [_vp, _u64p, C.c_uint32, _u8p, C.c_uint64, C.POINTER(_vp)]),
     "lumen_group_create": (C.c_int, [_vpp, C.c_uint32, C.c_uint32, _vpp]),
     "lumen_group_unique_id": (C.c_int, [_u8p]),
     "lumen_group_create_rank": (C.c_int, [_vp, C.c_uint32, C.c_uint32, _u8p, _vpp]),
@@ -738,6 +741,38 @@ class Context:
         self._ck(self.lib.lumen_keygen_ringswitch(self.h, seed.ctypes.data_as(_u8p), log_n_small, w, _p64(key), key.size,
                                                   sk_small.ctypes.data_as(C.POINTER(C.c_int8))))
         return key, sk_small
+
+    # the client's encryptor (fhe/bfv.go:77): under the context's secret key; secret_seed is key material, a_seed public
+    def encrypt_sk_values(self, values, secret_seed, a_seed, first_index=0):
+        """Encoder.Encode + Encryptor(sk).EncryptNew of every row of `values` ([count][rows] slot values)"""
+        values = np.ascontiguousarray(values, dtype=np.uint64)
+        assert values.ndim == 2
+        ss, sa = self._seed(secret_seed), self._seed(a_seed)
+        h = C.c_void_p()
+        self._ck(self.lib.lumen_encrypt_sk_values(self.h, _p64(values), values.shape[1], values.shape[0],
+                                                  ss.ctypes.data_as(_u8p), sa.ctypes.data_as(_u8p), first_index, C.byref(h)))
+        return DeviceSet(self, h)
+
+    def encrypt_sk_seeded(self, values, secret_seed, a_seed, first_index=0, out=None):
+        """the same ciphertexts in seeded form: their c0 halves [count][L][N] (into `out` if given, e.g. page-locked)"""
+        values = np.ascontiguousarray(values, dtype=np.uint64)
+        assert values.ndim == 2
+        ss, sa = self._seed(secret_seed), self._seed(a_seed)
+        shape = (values.shape[0], self.L, self.N)
+        c0 = np.zeros(shape, dtype=np.uint64) if out is None else out
+        assert c0.shape == shape and c0.dtype == np.uint64 and c0.flags["C_CONTIGUOUS"]
+        self._ck(self.lib.lumen_encrypt_sk_seeded(self.h, _p64(values), values.shape[1], values.shape[0],
+                                                  ss.ctypes.data_as(_u8p), sa.ctypes.data_as(_u8p), first_index, _p64(c0)))
+        return c0
+
+    def expand_seeded(self, c0, a_seed, first_index=0):
+        """c0 halves [count][L][N] + the public seed -> the full set; needs no key"""
+        assert c0.dtype == np.uint64 and c0.flags["C_CONTIGUOUS"] and c0.shape[1:] == (self.L, self.N), c0.shape
+        sa = self._seed(a_seed)
+        h = C.c_void_p()
+        self._ck(self.lib.lumen_ct_expand_seeded(self.h, _p64(c0), c0.shape[0], sa.ctypes.data_as(_u8p), first_index,
+                                                 C.byref(h)))
+        return DeviceSet(self, h)
 
     def mul_counter(self):
         return int(self.lib.lumen_mul_counter(self.h))

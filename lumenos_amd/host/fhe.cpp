@@ -398,6 +398,8 @@ ClientBFV::ClientBFV(core::PrimeField *plaintextField, const Parameters &params,
     ctx_ = OwnedContext(params, device);
     check(lumen_encoder_set(Context(), encoder_root(params)), "lumen_encoder_set");
     check(lumen_load_secret_key(Context(), sk.data()), "lumen_load_secret_key");
+    encSeed_ = std::make_shared<KeySeedBytes>();
+    OsRandom(encSeed_->b, sizeof(encSeed_->b));
 }
 
 ClientBFV::ClientBFV(core::PrimeField *plaintextField, const Parameters &params, int device)
@@ -406,6 +408,8 @@ ClientBFV::ClientBFV(core::PrimeField *plaintextField, const Parameters &params,
     keySeed_ = std::make_shared<KeySeedBytes>();
     OsRandom(keySeed_->b, sizeof(keySeed_->b));
     check(lumen_keygen_secret(Context(), keySeed_->b, nullptr), "lumen_keygen_secret");
+    encSeed_ = std::make_shared<KeySeedBytes>(); // its own draw: a keygen seed keys nothing else
+    OsRandom(encSeed_->b, sizeof(encSeed_->b));
 }
 
 std::unique_ptr<ClientBFV> ClientBFV::NewWithGeneratedSecret(core::PrimeField *plaintextField, const Parameters &params,
@@ -425,11 +429,42 @@ std::vector<uint64_t> ClientBFV::SecretKeyForTest() {
 }
 
 ClientBFV::ClientBFV(ClientBFV &src, OwnedContext clone)
-    : ptField_(src.ptField_), params_(src.params_), ctx_(std::move(clone)), device_(src.device_), keySeed_(src.keySeed_) {}
+    : ptField_(src.ptField_), params_(src.params_), ctx_(std::move(clone)), device_(src.device_), keySeed_(src.keySeed_),
+      encSeed_(src.encSeed_) {}
 
 std::unique_ptr<ClientBFV> ClientBFV::CopyNew() { return std::unique_ptr<ClientBFV>(new ClientBFV(*this, ctx_.Clone())); }
 
 ClientBFV::~ClientBFV() = default;
+
+// Encryptor(sk).EncryptNew (fhe/bfv.go:77; vdec/batching_test.go:56) of whole columns on the device
+Ciphertexts ClientBFV::EncryptColumnsUnderSeedForTest(const std::vector<uint64_t> &values, int rows, int count,
+                                                      const std::array<uint8_t, 32> &aSeed, uint64_t firstIndex) {
+    if (rows < 0 || count < 0 || (size_t)rows * count != values.size()) throw std::invalid_argument("EncryptColumnsNew: size mismatch");
+    lumen_set *set = nullptr;
+    check(lumen_encrypt_sk_values(Context(), values.data(), (uint32_t)rows, (uint32_t)count, encSeed_->b, aSeed.data(), firstIndex,
+                                  &set),
+          "lumen_encrypt_sk_values");
+    return Ciphertexts(Context(), set, fresh_meta(params_));
+}
+
+Ciphertexts ClientBFV::EncryptColumnsNew(const std::vector<uint64_t> &values, int rows, int count) {
+    std::array<uint8_t, 32> aSeed;
+    OsRandom(aSeed.data(), aSeed.size()); // fresh per call: (seed, index) never meets two messages
+    return EncryptColumnsUnderSeedForTest(values, rows, count, aSeed, 0);
+}
+
+SeededCiphertexts ClientBFV::EncryptColumnsSeeded(const std::vector<uint64_t> &values, int rows, int count) {
+    if (rows < 0 || count < 0 || (size_t)rows * count != values.size())
+        throw std::invalid_argument("EncryptColumnsSeeded: size mismatch");
+    SeededCiphertexts out;
+    OsRandom(out.ASeed.data(), out.ASeed.size());
+    out.Count = count;
+    out.C0.resize((size_t)count * params_.Q.size() * (size_t)params_.N());
+    check(lumen_encrypt_sk_seeded(Context(), values.data(), (uint32_t)rows, (uint32_t)count, encSeed_->b, out.ASeed.data(),
+                                  out.FirstIndex, out.C0.data()),
+          "lumen_encrypt_sk_seeded");
+    return out;
+}
 
 // ------------------------------------------------------------------ KeyGenerator (cmd/client/main.go:74-81)
 static size_t evk_words(const Parameters &P) {
@@ -564,6 +599,15 @@ Ciphertexts ServerBFV::EncryptColumnsNew(const std::vector<uint64_t> &values, in
     check(lumen_encrypt_values(Context(), values.data(), (uint32_t)rows, (uint32_t)count, enc_->seed,
                                enc_->next.fetch_add((uint64_t)count), &set),
           "lumen_encrypt_values");
+    return Ciphertexts(Context(), set, fresh_meta(params_));
+}
+
+Ciphertexts ServerBFV::ExpandSeeded(const SeededCiphertexts &seeded) {
+    if (seeded.Count < 0 || seeded.C0.size() != (size_t)seeded.Count * params_.Q.size() * (size_t)params_.N())
+        throw std::invalid_argument("ExpandSeeded: C0 is not [Count][L][N]");
+    lumen_set *set = nullptr;
+    check(lumen_ct_expand_seeded(Context(), seeded.C0.data(), (uint32_t)seeded.Count, seeded.ASeed.data(), seeded.FirstIndex, &set),
+          "lumen_ct_expand_seeded");
     return Ciphertexts(Context(), set, fresh_meta(params_));
 }
 

@@ -5,6 +5,7 @@
 // test written against it reads like fhe/ligero_test.go; where the Go code hands []*rlwe.Ciphertext
 // around, this mirror hands `Ciphertexts` (an HBM-resident lumen_set) around.
 #pragma once
+#include <array>
 #include <atomic>
 #include <map>
 #include <memory>
@@ -147,6 +148,17 @@ struct ShardedCiphertexts {
     std::vector<uint64_t> Download() const; // the blocks in order: [Len][2][level+1][N]
 };
 
+// Ciphertexts under the secret key in seeded form (lumen_encrypt_sk_seeded): c1 of ciphertext i is pure randomness,
+// regenerated from the PUBLIC seed ASeed and the index FirstIndex + i, so only the c0 halves travel -- half the bytes of
+// the witness upload.  ServerBFV::ExpandSeeded rebuilds the full top-level set with no key.  An in-memory object: there
+// is no wire format for it yet.
+struct SeededCiphertexts {
+    std::array<uint8_t, 32> ASeed{};
+    uint64_t FirstIndex = 0;
+    int Count = 0;
+    std::vector<uint64_t> C0; // [Count][L][N], NTT domain
+};
+
 // Scale after `for ct.Level() > target { Rescale }` from level `from`: scale * prod q_l^-1 mod T
 uint64_t RescaledScale(const Parameters &params, uint64_t scale, int fromLevel, int toLevel);
 // The MetaData block rlwe.Ciphertext.WriteTo puts in front of the polynomials, as recalled
@@ -189,6 +201,9 @@ class ServerBFV {
     // "Evaluate polynomial".
     core::Element EvaluateColumns(const std::vector<uint64_t> &values, int rows, int count, int cols, core::Element z,
                                   uint64_t firstColumn = 0);
+    // the server's side of a client's seeded upload (lumen_ct_expand_seeded): c0 halves + public seed -> the full
+    // top-level ciphertexts, ready for LigeroCommitter::Commit.  Needs no key.
+    Ciphertexts ExpandSeeded(const SeededCiphertexts &seeded);
     void check(int rc, const char *what) const; // throws std::runtime_error with lumen_last_error
     void SetRingSwitchServer(RingSwitchServer *rs) { rs_ = rs; } // bfv.go:48-50
     RingSwitchServer *RingSwitch() const { return rs_; }          // bfv.go:52-54
@@ -246,6 +261,17 @@ class ClientBFV {
     // ClientBFV.CopyNew (bfv.go:96-98): the same key and tables, its own streams and scratch (lumen_ctx_clone); must
     // not outlive the client it was made from
     std::unique_ptr<ClientBFV> CopyNew();
+    // the rlwe.NewEncryptor(paramsFHE, sk) of fhe/bfv.go:77, on the device (lumen_encrypt_sk_*): Encoder.Encode +
+    // EncryptNew of `count` columns of `rows` values ([count][rows]) under the client's secret key.  The error seed is
+    // key material drawn once per client from getrandom(2) (CopyNews share it); every call draws a FRESH public seed for
+    // c1 from getrandom(2), so no (seed, index) pair ever encrypts two messages.
+    Ciphertexts EncryptColumnsNew(const std::vector<uint64_t> &values, int rows, int count);
+    // the same ciphertexts in seeded form: what the client uploads (c0 halves + the public seed)
+    SeededCiphertexts EncryptColumnsSeeded(const std::vector<uint64_t> &values, int rows, int count);
+    // test hook: the full ciphertexts under a GIVEN public seed and first index -- to compare a server's ExpandSeeded
+    // against, never to encrypt anything else
+    Ciphertexts EncryptColumnsUnderSeedForTest(const std::vector<uint64_t> &values, int rows, int count,
+                                               const std::array<uint8_t, 32> &aSeed, uint64_t firstIndex);
     bool HasGeneratedSecret() const { return (bool)keySeed_; }
     // the seed of a generated secret (what the KeyGenerator passes on); throws for a client that was handed its key
     const uint8_t *KeySeed() const;
@@ -264,6 +290,7 @@ class ClientBFV {
         uint8_t b[32];
     };
     std::shared_ptr<KeySeedBytes> keySeed_; // shared with every CopyNew
+    std::shared_ptr<KeySeedBytes> encSeed_; // the encryptor's error seed, shared with every CopyNew; keys nothing else
 };
 
 // rlwe.NewKeyGenerator(params) (cmd/client/main.go:74) bound to a client with a generated secret: every key is derived
