@@ -11,6 +11,7 @@
 #include <mutex>
 #include <set>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/lumenos_hip.h"
@@ -200,6 +201,14 @@ void lm_sync_all(lumen_ctx *ctx);
 // pinned host staging of at least `bytes`, safe to overwrite (the previous asynchronous copy out of it
 // has completed); record ctx->ev_stage on the stream after enqueuing the next copy
 void *lm_stage(lumen_ctx *ctx, size_t bytes);
+// host bytes -> device memory on the context's stream, through that staging buffer: `host` may change on return
+int lm_h2d_staged(lumen_ctx *ctx, void *dev, const void *host, size_t bytes);
+// device -> host bytes on the context's stream: a page-locked destination takes the DMA directly, a
+// pageable one goes through the two bounce buffers (lm_ctx.hip).  wait: return when `host` holds the data.
+int lm_d2h(lumen_ctx *ctx, void *host, const void *dev, size_t bytes, bool wait);
+// `height` rows of `width` bytes, spitch apart on the host, to rows dpitch apart on the device; returns when `host` may
+// be reused.  Page-locked memory: one DMA; pageable memory goes through the bounce buffers in whole rows.
+int lm_h2d_rows(lumen_ctx *ctx, void *dev, size_t dpitch, const void *host, size_t spitch, size_t width, size_t height);
 
 int lm_fail(lumen_ctx *ctx, const char *fmt, ...);
 extern thread_local std::string lm_global_err;
@@ -216,6 +225,14 @@ extern thread_local std::string lm_global_err;
     do {                                            \
         if (!(cond)) return lm_fail(ctx, __VA_ARGS__); \
     } while (0)
+
+// one thread per element: ceil(threads / 256) workgroups of 256 on the context's stream
+template <class... P, class... A>
+static inline int lm_launch_flat(lumen_ctx *ctx, void (*kernel)(P...), size_t threads, A &&...args) {
+    hipLaunchKernelGGL(kernel, dim3((uint32_t)((threads + 255) / 256)), dim3(256), 0, ctx->stream, std::forward<A>(args)...);
+    LM_HIP(ctx, hipGetLastError());
+    return 0;
+}
 
 // owns a freshly created set until the entry point hands it to the caller: every early return
 // (LM_HIP / LM_CHECK) gives the storage back instead of leaking it
@@ -275,6 +292,14 @@ static inline tw_t h_tw(uint64_t w, uint64_t q) {
     t.wp = (u64)((((u128)w) << 64) / q);
     return t;
 }
+// 2^64 mod q
+static inline uint64_t h_r64_mod(uint64_t q) { return (uint64_t)((((u128)1) << 64) % q); }
+// P mod q, P the product of the special primes (1 without any)
+static inline uint64_t h_p_mod(const lumen_ctx *ctx, uint64_t q) {
+    uint64_t P = 1 % q;
+    for (uint32_t a = 0; a < ctx->K; a++) P = h_mulmod(P, ctx->mod[ctx->L + a] % q, q);
+    return P;
+}
 static inline uint32_t h_bitrev(uint32_t x, int bits) {
     uint32_t r = 0;
     for (int i = 0; i < bits; i++) r = (r << 1) | ((x >> i) & 1);
@@ -306,19 +331,3 @@ lm_modmap lm_map_p(const lumen_ctx *ctx);
 int lm_encode_dev(lumen_ctx *ctx, const lumen_set *matrix, const u64 *dzero, uint32_t rho_inv, lumen_set **encoded);
 // pooled timing events of a context (lm_ctx.hip)
 hipEvent_t lm_ev_get(lumen_ctx *ctx);
-// ---- client-side decryption in stages (lm_encrypt.hip), shared by lumen_decrypt and lumen_verify_columns
-// what lumen_decrypt refuses about its set, scale and context (no device work)
-int lm_decrypt_check(lumen_ctx *ctx, const lumen_set *set, uint64_t scale, const char *what);
-// Decryptor.DecryptNew + the decoder's transform over Z_T, enqueued on the context's stream: t = [count][N] words
-// below T in the transform's output order, slot[i] = the position of slot value i in it.  `keep` holds the key and
-// encoder tables for as long as the caller's kernels read them.
-struct lm_decoded {
-    const u64 *t = nullptr;
-    const uint32_t *slot = nullptr;
-    std::shared_ptr<void> keep[2];
-};
-int lm_decrypt_decode(lumen_ctx *ctx, const lumen_set *set, lm_decoded *out);
-// values[c][i] = t[c][slot[i]] * scale^-1 mod T for i < nvalues, copied to the host buffer on the context's stream
-// (not waited for)
-int lm_decrypt_slots(lumen_ctx *ctx, const lm_decoded &dec, uint32_t count, uint64_t scale, uint32_t nvalues,
-                     uint64_t *values);

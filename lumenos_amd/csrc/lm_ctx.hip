@@ -59,6 +59,15 @@ void *lm_stage(lumen_ctx *ctx, size_t bytes) {
     return ctx->stage_host;
 }
 
+int lm_h2d_staged(lumen_ctx *ctx, void *dev, const void *host, size_t bytes) {
+    void *h = lm_stage(ctx, bytes);
+    if (!h) return 1;
+    memcpy(h, host, bytes);
+    LM_HIP(ctx, hipMemcpyAsync(dev, h, bytes, hipMemcpyHostToDevice, ctx->stream));
+    LM_HIP(ctx, hipEventRecord(ctx->ev_stage, ctx->stream));
+    return 0;
+}
+
 hipEvent_t lm_ev_get(lumen_ctx *ctx) {
     if (!ctx->ev_pool.empty()) {
         hipEvent_t e = ctx->ev_pool.back();
@@ -124,7 +133,7 @@ mod_t lm_make_mod(uint64_t q) {
     u64 inv = 1;
     for (int it = 0; it < 6; it++) inv *= 2 - (u64)q * inv;
     m.qneg = (u64)0 - inv;
-    u64 r = (u64)((((u128)1) << 64) % q);
+    u64 r = h_r64_mod(q);
     m.r2 = h_mulmod(r, r, q);
     return m;
 }

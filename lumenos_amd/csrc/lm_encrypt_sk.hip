@@ -9,12 +9,12 @@
 //     keystream(I, s) = ChaCha20(key, nonce = LE64(I) || LE32(s), counter = 0, 1, ...)           (lm_sample_dev.h)
 //     e   stream 3 of keystream(I, .) under secret_seed, the encryptor's CDT rule; one N-coefficient sample per
 //         ciphertext, extended to every limb (the public-key encryptor draws streams 0-2, key generation 16 + m)
-//     a_l stream 16 + l of keystream(I, .) under a_seed, key generation's rejection rule (k_keygen_uniform), Q limbs
+//     a_l stream 16 + l of keystream(I, .) under a_seed, key generation's rejection rule (k_sample_uniform), Q limbs
 //     pt  the plaintext bits of lumen_encrypt_values: slot scatter, INTT over Z_T, m * T^-1 mod q_l
 //
 // One kernel of its own, k_enc_sk (one workgroup per (ciphertext, Q limb): lift of e plus the scaled message in the
-// load, the limb transform, - a * s in the store); e comes from k_keygen_small, a from k_keygen_uniform, the message
-// from lm_encode_coeffs.
+// load, the limb transform, - a * s in the store); e and a come from the shared sampler (lm_sample.hip), the message
+// from lm_encode_coeffs (lm_encoder.hip), the key table from lm_decrypt.hip.
 #include <cstring>
 
 #include "lm_enc_host.h"
@@ -22,7 +22,7 @@
 #define LM_ENCSK_ERR_STREAM 3u
 
 // small [count][N] int8 errors; mcoef [count][N] plaintext coefficients modulo T (tinv: T^-1 mod q_l); sk [L][N] Shoup
-// form; a + c * a_stride and c0 + c * c0_stride: [L][N], the `a` halves filled by k_keygen_uniform.
+// form; a + c * a_stride and c0 + c * c0_stride: [L][N], the `a` halves filled by k_sample_uniform.
 //     c0 = NTT(e + m * T^-1) - a * s, canonical.
 // Dealt limb-major like k_enc_u: one twiddle table and one limb of s stay hot per XCD.
 template <int LOGN>
@@ -43,11 +43,9 @@ __global__ LM_GEOM_BOUNDS(lm_geom_lds(LOGN)) void k_enc_sk(const int8_t *__restr
     u64 *o = c0 + (size_t)c * c0_stride + (size_t)l * N;
     const tw_t ti = tinv.t[l];
     auto ld = [&](uint32_t i) {
-        const int8_t e = se[i];
-        u64 r = e >= 0 ? (u64)e : qc.q - (u64)(-(int)e);
-        r = lm_shoup3<true>(mc[i], ti.w, ti.wp, qc.nq, r); // e + m * T^-1, < 4q
-        r = lm_csub(lm_csub(r, 2 * qc.q), qc.q);
-        return lm_csub(r, qc.q);
+        u64 r = lm_lift_small(se[i], &qc.q);
+        lm_add_scaled_msg(r, mc[i], ti, qc); // e + m * T^-1
+        return r;
     };
     auto st = [&](uint32_t i0, const u64 *v, int n) {
         u64 av[8], b[8];
@@ -78,13 +76,6 @@ static int enc_sk_t(lumen_ctx *ctx, const int8_t *small, const u64 *mcoef, const
 // chunks bound the temporaries, as in the public-key encryptor
 #define LM_ENCSK_CHUNK 256u
 
-// sample indices first_index + first .. + n - 1 into d_idx
-static int enc_sk_indices(lumen_ctx *ctx, u64 *d_idx, uint64_t first_index, uint32_t n) {
-    u64 idx[LM_ENCSK_CHUNK];
-    for (uint32_t i = 0; i < n; i++) idx[i] = first_index + i;
-    return lm_kg_upload(ctx, d_idx, idx, (size_t)n * sizeof(u64));
-}
-
 // what the two encrypting entry points refuse, before any device work
 static int enc_sk_check(lumen_ctx *ctx, const char *what, uint32_t rows, const uint8_t secret_seed[32], const uint8_t a_seed[32]) {
     LM_CHECK(ctx, lm_ext_get<SkTable>(ctx, "secret_key"), "%s: no secret key on the context (lumen_load_secret_key, lumen_keygen_secret)",
@@ -107,27 +98,25 @@ static int enc_sk_impl(lumen_ctx *ctx, const uint64_t *values, uint32_t rows, ui
     const uint32_t chunk = std::min<uint32_t>(count, LM_ENCSK_CHUNK);
     lm_dev<int8_t> d_e; // the errors: zeroed on the stream before the block is given back
     if (d_e.release_on(ctx->stream, true).alloc(ctx, (size_t)chunk * N, "secret-key encryption")) return 1;
-    u64 *d_idx = (u64 *)lm_scratch(ctx, "encsk_index", (size_t)chunk * sizeof(u64));
     u64 *dval = (u64 *)lm_scratch(ctx, "enc_val", (size_t)chunk * rows * sizeof(u64));
     u64 *dm = (u64 *)lm_scratch(ctx, "enc_m", (size_t)chunk * N * sizeof(u64));
     u64 *da = dst ? nullptr : (u64 *)lm_scratch(ctx, "encsk_a", (size_t)chunk * limbs * sizeof(u64));
     u64 *dc0 = dst ? nullptr : (u64 *)lm_scratch(ctx, "encsk_c0", (size_t)chunk * limbs * sizeof(u64));
-    if (!d_idx || !dval || !dm || (!dst && (!da || !dc0))) return 1;
+    if (!dval || !dm || (!dst && (!da || !dc0))) return 1;
     for (uint32_t first = 0; first < count; first += chunk) {
         const uint32_t n = std::min(chunk, count - first);
         // the temporaries are reused: stream order puts these copies behind the previous chunk's kernels
         if (int rc = lm_encode_coeffs(ctx, enc_hold.get(), values + (size_t)first * rows, rows, n, dval, dm)) return rc;
-        if (int rc = enc_sk_indices(ctx, d_idx, first_index + first, n)) return rc;
         {
             lm_prof_scope ps(ctx, "encrypt_sk_sample", n);
-            if (int rc = lm_kg_small(ctx, d_e.get(), d_idx, n, LM_ENCSK_ERR_STREAM, secret_seed)) return rc;
+            if (int rc = lm_sample_small(ctx, d_e.get(), nullptr, first_index + first, n, LM_ENCSK_ERR_STREAM, 1, secret_seed)) return rc;
         }
         // full form: a is the c1 half of [ct][2][L][N]; seeded form: a scratch block, and only c0 is kept
         u64 *c0 = dst ? dst + (size_t)first * 2 * limbs : dc0, *a = dst ? c0 + limbs : da;
         const size_t stride = dst ? 2 * limbs : limbs;
         {
             lm_prof_scope ps(ctx, "encrypt_sk_uniform", (uint64_t)n * L);
-            if (int rc = lm_kg_uniform(ctx, a, stride, d_idx, n, L, a_seed)) return rc;
+            if (int rc = lm_sample_uniform(ctx, a, stride, nullptr, first_index + first, n, L, a_seed)) return rc;
         }
         if (int rc = lm_for_logn(ctx, ctx->logN, [&](auto k) {
                 return enc_sk_t<k>(ctx, d_e.get(), dm, enc_hold->tinv, sk_hold->d_sk.get(), a, stride, c0, stride, n);
@@ -181,13 +170,11 @@ extern "C" int lumen_ct_expand_seeded(lumen_ctx *ctx, const uint64_t *c0, uint32
     lm_set_guard og(ctx, o);
     if (count) {
         const uint32_t chunk = std::min<uint32_t>(count, LM_ENCSK_CHUNK);
-        u64 *d_idx = (u64 *)lm_scratch(ctx, "encsk_index", (size_t)chunk * sizeof(u64));
-        if (!d_idx) return 1;
         for (uint32_t first = 0; first < count; first += chunk) {
             const uint32_t n = std::min(chunk, count - first);
-            if (int rc = enc_sk_indices(ctx, d_idx, first_index + first, n)) return rc;
             lm_prof_scope ps(ctx, "encrypt_sk_uniform", (uint64_t)n * L);
-            if (int rc = lm_kg_uniform(ctx, o->d + (size_t)first * 2 * limbs + limbs, 2 * limbs, d_idx, n, L, a_seed)) return rc;
+            if (int rc = lm_sample_uniform(ctx, o->d + (size_t)first * 2 * limbs + limbs, 2 * limbs, nullptr, first_index + first, n, L, a_seed))
+                return rc;
         }
         lm_prof_scope ps(ctx, "expand_seeded_upload", count);
         if (int rc = lm_h2d_rows(ctx, o->d, 2 * limbs * sizeof(u64), c0, limbs * sizeof(u64), limbs * sizeof(u64), count)) return rc;

@@ -170,9 +170,6 @@ __global__ __launch_bounds__(256) void k_ct_wire(const u64 *__restrict__ set, ui
     for (u32 m = tid; m + 1 < N; m += 256) dst[m] = (src[m] >> (8 * lead)) | (src[m + 1] << (8 * a));
 }
 
-// device -> host bytes on the context's stream: a page-locked destination takes the DMA directly, a
-// pageable one goes through the two bounce buffers (lm_ctx.hip).  wait: return when `host` holds the data.
-int lm_d2h(lumen_ctx *ctx, void *host, const void *dev, size_t bytes, bool wait);
 bool lm_host_is_pinned(const void *p);
 
 #define LM_WIRE_CHUNK ((size_t)512 << 20) // wire bytes assembled per kernel launch (device scratch of that size)
@@ -637,11 +634,8 @@ extern "C" int lumen_gather(lumen_ctx *ctx, const lumen_set *src, const uint32_t
     lm_set_guard og(ctx, o);
     if (n) {
         uint32_t *didx = (uint32_t *)lm_scratch(ctx, "gather_idx", (size_t)n * 4);
-        uint32_t *hidx = (uint32_t *)lm_stage(ctx, (size_t)n * 4); // idx is caller memory: copy it before returning
-        if (!didx || !hidx) return 1;
-        memcpy(hidx, idx, (size_t)n * 4);
-        LM_HIP(ctx, hipMemcpyAsync(didx, hidx, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
-        LM_HIP(ctx, hipEventRecord(ctx->ev_stage, ctx->stream));
+        if (!didx) return 1;
+        if (int rc = lm_h2d_staged(ctx, didx, idx, (size_t)n * 4)) return rc; // idx is caller memory: copied before returning
         const size_t ctw2 = lm_ctw(ctx, src) / 2; // words of a ciphertext, in 16-byte units
         hipLaunchKernelGGL(k_gather, dim3(32, n), dim3(256), 0, ctx->stream, src->d, o->d, didx, ctw2);
         LM_HIP(ctx, hipGetLastError());

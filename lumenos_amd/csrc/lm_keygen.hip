@@ -6,7 +6,7 @@
 //
 // THE SAMPLING CONTRACT.  Everything is deterministic in (seed, key id, entry, limb, coefficient): keys generated one
 // at a time, in one batched call or on another GPU are the same bytes.
-//     keystream(I, s) = ChaCha20(key = seed, nonce = LE64(I) || LE32(s), counter = 0, 1, ...)   (lm_sample_dev.h)
+//     keystream(I, s) = ChaCha20(key = seed, nonce = LE64(I) || LE32(s), counter = 0, 1, ...)   (lm_sample.hip)
 //     sample index     I(key_id, e) = key_id * 4096 + e,   e = i * pw2 + j the gadget entry (RNS digit i, power-of-two
 //                      digit j; pw2 = 1 everywhere but the ring-switch key with K <= 1)
 //     key ids          secret 0, public 1, relinearisation 2, ring switch 3, Galois key of element g: 0x10000 + g
@@ -21,14 +21,10 @@
 // A keygen seed is key material (OS CSPRNG) and is used for nothing else: streams 0-2 of an index are the ones
 // lumen_encrypt_* would draw, so a keygen seed must never be passed to lumen_encrypt_*.
 //
-// Kernels: k_keygen_small (one thread per ChaCha20 block -> int8 coefficients), k_keygen_uniform (one thread per
-// block = 8 coefficients of attempt 0; attempt t of those coefficients is block t * N/8 + the same),
+// The samples come from the shared sampler (lm_sample.hip: k_sample_small, k_sample_uniform).  Kernels here:
 // k_keygen_secret_ntt (NTT(s) and NTT(skNew(X^(N/n))) over QP), k_keygen_gather / _square / _shoup (the secret's
 // images), k_keygen_evk (one workgroup per (key, entry, limb): lift + NTT of e, the products fused into the store).
-#include <cstring>
-
-#include "lm_ks_dev.h"
-#include "lm_sample_dev.h"
+#include "lm_enc_host.h"
 
 #define LM_KG_INDEX_STRIDE 4096ull
 #define LM_KG_ID_SECRET 0ull
@@ -36,59 +32,6 @@
 #define LM_KG_ID_RELIN 2ull
 #define LM_KG_ID_RINGSWITCH 3ull
 #define LM_KG_ID_GALOIS 0x10000ull
-#define LM_KG_UNIFORM_STREAM 16u
-
-#include "lm_enc_host.h"
-
-struct kg_lim_t {
-    u64 t[LM_MAX_LIMBS]; // 2^64 - (2^64 mod q_m): words below it are kept
-};
-
-// out: [nitems][N] int8; item i draws `stream` (0: ternary, else Gaussian) of sample index index[i]
-__global__ __launch_bounds__(256) void k_keygen_small(int8_t *__restrict__ out, const u64 *__restrict__ index,
-                                                      uint32_t nitems, uint32_t stream, uint32_t logN, enc_seed_t seed,
-                                                      enc_cdt_t cdt) {
-    const uint32_t N = 1u << logN, per = stream == 0 ? N >> 4 : N >> 3;
-    const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= (size_t)nitems * per) return;
-    const uint32_t it = (uint32_t)(g / per), blk = (uint32_t)(g % per);
-    const u64 I = index[it];
-    u32 w[16];
-    chacha20_block(seed, blk, (u32)I, (u32)(I >> 32), stream, w);
-    int8_t *o = out + (size_t)it * N;
-    if (stream == 0)
-        *reinterpret_cast<uint4 *>(o + (size_t)blk * 16) = lm_ternary16(w);
-    else
-        *reinterpret_cast<uint2 *>(o + (size_t)blk * 8) = lm_gauss8(w, cdt);
-}
-
-// The `a` half of every entry: a is the first of them, [LK][N] per item and item_stride words from one item to the next
-// (a key's [nitems][b|a][LK][N]: out + LK * N, 2 * LK * N apart; the secret-key encryptor's c1 halves alike, or a plain
-// [nitems][L][N] block).  blockIdx.y = item * LK + limb, one thread per block of 8 coefficients.  Attempt t of
-// coefficients 8 blk .. 8 blk + 7 is words of block t * N/8 + blk.
-__global__ __launch_bounds__(256) void k_keygen_uniform(u64 *__restrict__ a, size_t item_stride, const u64 *__restrict__ index,
-                                                        uint32_t LK, uint32_t logN, lm_mods mods, kg_lim_t lim,
-                                                        enc_seed_t seed) {
-    const uint32_t N = 1u << logN, blk = blockIdx.x * blockDim.x + threadIdx.x;
-    if (blk >= (N >> 3)) return;
-    const uint32_t it = blockIdx.y / LK, m = blockIdx.y % LK;
-    const u64 I = index[it], q = mods.m[m].q, qinv64 = mods.m[m].qinv64, bound = lim.t[m];
-    u64 r[8];
-    uint32_t pending = 0xFFu;
-    for (uint32_t t = 0; pending; t++) {
-        u32 w[16];
-        chacha20_block(seed, t * (N >> 3) + blk, (u32)I, (u32)(I >> 32), LM_KG_UNIFORM_STREAM + m, w);
-#pragma unroll
-        for (int i = 0; i < 8; i++) {
-            const u64 x = (u64)w[2 * i] | ((u64)w[2 * i + 1] << 32);
-            if (((pending >> i) & 1u) && x < bound) {
-                r[i] = lm_reduce(x, q, qinv64);
-                pending &= ~(1u << i);
-            }
-        }
-    }
-    lm_store_run(a + (size_t)it * item_stride + (size_t)m * N, blk * 8, r, 8);
-}
 
 // NTT of small polynomials over QP: slot j of `small` ([nslots][*] int8) -> mont[j][m] = NTT(.) * 2^64 mod q_m (the form
 // the storer of k_keygen_evk multiplies with) and, when given, std[j][m] = NTT(.).  loggap > 0: the polynomial is
@@ -108,8 +51,7 @@ __global__ LM_GEOM_BOUNDS(lm_geom_lds(LOGN)) void k_keygen_secret_ntt(const int8
     const uint32_t gmask = (1u << loggap) - 1;
     auto ld = [&](uint32_t i) -> u64 {
         if (i & gmask) return 0;
-        const int8_t v = s[i >> loggap];
-        return v >= 0 ? (u64)v : qc.q - (u64)(-(int)v);
+        return lm_lift_small(s[i >> loggap], &qc.q);
     };
     auto st = [&](uint32_t i0, const u64 *v, int n) {
         u64 a[8], b[8];
@@ -165,7 +107,7 @@ __global__ __launch_bounds__(256) void k_keygen_shoup(const u64 *__restrict__ st
 }
 
 // One workgroup per (key, entry, limb), dealt limb-major like k_enc_u: one twiddle table stays hot per XCD.
-//   small [nitems][N] int8 errors; out [nitems][b|a][LK][N] with the `a` halves filled by k_keygen_uniform;
+//   small [nitems][N] int8 errors; out [nitems][b|a][LK][N] with the `a` halves filled by k_sample_uniform;
 //   s_out + key * sout_stride and s_in: [LK][N] secrets in Montgomery form; fac [nent][LK]: P * 2^(w j) mod q_m on the
 //   Q limbs of the entry's RNS digit, 0 elsewhere (NULL: 0 everywhere, the public key).
 //   b = NTT(e) - a * s_out + fac * s_in, canonical; MONT: both halves leave multiplied by 2^64 mod q_m.
@@ -186,10 +128,7 @@ __global__ LM_GEOM_BOUNDS(lm_geom_lds(LOGN)) void k_keygen_evk(const int8_t *__r
     const u64 *so = s_out + (size_t)key * sout_stride + (size_t)m * N, *si = s_in ? s_in + (size_t)m * N : nullptr;
     const u64 f = fac ? fac[(size_t)e * LK + m] : 0;
     const tw_t R = rmont.t[m];
-    auto ld = [&](uint32_t i) -> u64 {
-        const int8_t v = se[i];
-        return v >= 0 ? (u64)v : qc.q - (u64)(-(int)v);
-    };
+    auto ld = [&](uint32_t i) -> u64 { return lm_lift_small(se[i], &qc.q); };
     auto st = [&](uint32_t i0, const u64 *v, int n) {
         u64 a[8], b[8], x[8], y[8];
         lm_load_run(oa, i0, a, n);
@@ -234,63 +173,14 @@ static int kg_alloc(lumen_ctx *ctx, lm_dev<T> &d, size_t count, bool secret) {
     return d.release_on(ctx->stream, secret).alloc(ctx, count, "key generation");
 }
 
-static enc_seed_t kg_seed(const uint8_t seed[32]) {
-    enc_seed_t k;
-    memcpy(k.k, seed, 32);
-    return k;
-}
-static enc_cdt_t kg_cdt() {
-    enc_cdt_t c;
-    memcpy(c.t, H_GAUSS_CDT, sizeof(c.t));
-    return c;
-}
 static lm_ninv_t kg_rmont(const lumen_ctx *ctx) { // 2^64 mod q_m
     lm_ninv_t r;
     for (uint32_t t = 0; t < LM_MAX_LIMBS; t++) {
         const uint64_t q = ctx->mod[t < ctx->L + ctx->K ? t : 0];
-        r.t[t] = h_tw((uint64_t)((((u128)1) << 64) % q), q);
+        r.t[t] = h_tw(h_r64_mod(q), q);
     }
     return r;
 }
-static uint64_t kg_p_mod(const lumen_ctx *ctx, uint64_t q) {
-    uint64_t P = 1 % q;
-    for (uint32_t a = 0; a < ctx->K; a++) P = h_mulmod(P, ctx->mod[ctx->L + a] % q, q);
-    return P;
-}
-
-int lm_kg_small(lumen_ctx *ctx, int8_t *out, const u64 *d_index, uint32_t nitems, uint32_t stream, const uint8_t seed[32]) {
-    const size_t threads = (size_t)nitems * (stream == 0 ? ctx->N >> 4 : ctx->N >> 3);
-    hipLaunchKernelGGL(k_keygen_small, dim3((uint32_t)((threads + 255) / 256)), dim3(256), 0, ctx->stream, out, d_index, nitems,
-                       stream, ctx->logN, kg_seed(seed), kg_cdt());
-    LM_HIP(ctx, hipGetLastError());
-    return 0;
-}
-
-// the uniform halves of nitems items over the first LK moduli (k_keygen_uniform's layout)
-int lm_kg_uniform(lumen_ctx *ctx, u64 *a, size_t item_stride, const u64 *d_index, uint32_t nitems, uint32_t LK,
-                  const uint8_t seed[32]) {
-    kg_lim_t lim;
-    for (uint32_t t = 0; t < LM_MAX_LIMBS; t++) {
-        const uint64_t q = ctx->mod[t < LK ? t : 0];
-        lim.t[t] = 0 - ((0 - q) % q); // 2^64 - (2^64 mod q)
-    }
-    const uint32_t nb = ctx->N >> 3, bs = nb < 256 ? nb : 256;
-    hipLaunchKernelGGL(k_keygen_uniform, dim3(nb / bs, nitems * LK), dim3(bs), 0, ctx->stream, a, item_stride, d_index, LK,
-                       ctx->logN, ctx->mods, lim, kg_seed(seed));
-    LM_HIP(ctx, hipGetLastError());
-    return 0;
-}
-
-// host words -> a device temporary, through the pinned staging buffer
-int lm_kg_upload(lumen_ctx *ctx, void *dev, const void *host, size_t bytes) {
-    void *h = lm_stage(ctx, bytes);
-    if (!h) return 1;
-    memcpy(h, host, bytes);
-    LM_HIP(ctx, hipMemcpyAsync(dev, h, bytes, hipMemcpyHostToDevice, ctx->stream));
-    LM_HIP(ctx, hipEventRecord(ctx->ev_stage, ctx->stream));
-    return 0;
-}
-
 template <int LOGN>
 static int kg_secret_ntt_t(lumen_ctx *ctx, const int8_t *small, u64 *mont, u64 *stdf, uint32_t nslots, uint32_t loggap) {
     const uint32_t LK = ctx->L + ctx->K;
@@ -322,15 +212,15 @@ static int kg_run(lumen_ctx *ctx, const uint8_t seed[32], const std::vector<u64>
     lm_dev<u64> d_tab, d_out;
     lm_dev<int8_t> d_e;
     if (kg_alloc(ctx, d_tab, tab.size(), false) || kg_alloc(ctx, d_out, out_words, false) || kg_alloc(ctx, d_e, (size_t)nitems * N, true)) return 1;
-    if (int rc = lm_kg_upload(ctx, d_tab.get(), tab.data(), tab.size() * 8)) return rc;
+    if (int rc = lm_h2d_staged(ctx, d_tab.get(), tab.data(), tab.size() * 8)) return rc;
     const u64 *d_index = d_tab.get(), *d_fac = fac ? d_index + nitems : nullptr;
     {
         lm_prof_scope ps(ctx, "keygen_sample", nitems);
-        if (int rc = lm_kg_small(ctx, d_e.get(), d_index, nitems, 1, seed)) return rc;
+        if (int rc = lm_sample_small(ctx, d_e.get(), d_index, 0, nitems, 1, 1, seed)) return rc;
     }
     {
         lm_prof_scope ps(ctx, "keygen_uniform", (uint64_t)nitems * LK);
-        if (int rc = lm_kg_uniform(ctx, d_out.get() + (size_t)LK * N, (size_t)2 * LK * N, d_index, nitems, LK, seed)) return rc;
+        if (int rc = lm_sample_uniform(ctx, d_out.get() + (size_t)LK * N, (size_t)2 * LK * N, d_index, 0, nitems, LK, seed)) return rc;
     }
     if (int rc = lm_for_logn(ctx, ctx->logN, [&](auto k) {
             return kg_evk_t<k>(ctx, d_e.get(), d_out.get(), s_out, sout_stride, s_in, d_fac, nitems, nent,
@@ -353,7 +243,7 @@ static std::vector<u64> kg_gadget(const lumen_ctx *ctx, uint32_t rns, uint32_t p
         for (uint32_t j = 0; j < pw2; j++)
             for (uint32_t m = i * alpha; m < L && m < (i + 1) * alpha; m++) {
                 const uint64_t q = ctx->mod[m];
-                fac[((size_t)i * pw2 + j) * LK + m] = h_mulmod(kg_p_mod(ctx, q), h_powmod(2, (uint64_t)w * j, q), q);
+                fac[((size_t)i * pw2 + j) * LK + m] = h_mulmod(h_p_mod(ctx, q), h_powmod(2, (uint64_t)w * j, q), q);
             }
     return fac;
 }
@@ -367,13 +257,11 @@ extern "C" int lumen_keygen_secret(lumen_ctx *ctx, const uint8_t seed[32], uint6
     auto sp = std::make_shared<KgSecret>();
     // d_sk, the decryptor's table: the first L limbs, exactly what lumen_load_secret_key would hold
     lm_dev<tw_t> d_sk;
-    lm_dev<u64> d_idx, d_std;
+    lm_dev<u64> d_std;
     lm_dev<int8_t> d_small;
     if (sp->d_mont.alloc(ctx, words, "the generated secret") || d_sk.alloc(ctx, (size_t)L * N, "the secret key")) return 1;
-    if (kg_alloc(ctx, d_idx, 1, false) || kg_alloc(ctx, d_small, N, true) || kg_alloc(ctx, d_std, words, true)) return 1;
-    const u64 index = LM_KG_ID_SECRET * LM_KG_INDEX_STRIDE;
-    if (int rc = lm_kg_upload(ctx, d_idx.get(), &index, 8)) return rc;
-    if (int rc = lm_kg_small(ctx, d_small.get(), d_idx.get(), 1, 0, seed)) return rc;
+    if (kg_alloc(ctx, d_small, N, true) || kg_alloc(ctx, d_std, words, true)) return 1;
+    if (int rc = lm_sample_small(ctx, d_small.get(), nullptr, LM_KG_ID_SECRET * LM_KG_INDEX_STRIDE, 1, 0, 1, seed)) return rc;
     if (int rc = lm_for_logn(ctx, ctx->logN, [&](auto k) {
             return kg_secret_ntt_t<k>(ctx, d_small.get(), sp->d_mont.get(), d_std.get(), 1, 0);
         }))
@@ -478,12 +366,10 @@ extern "C" int lumen_keygen_ringswitch(lumen_ctx *ctx, const uint8_t seed[32], u
     LM_CHECK(ctx, key_words == whole, "lumen_keygen_ringswitch: key of %zu words: expected %zu ([rns = %u][pw2 = %u][2][L+K = %u][N = %u])",
              key_words, whole, rns, pw2, LK, N);
     const size_t n = (size_t)1 << log_n_small, words = (size_t)LK * N;
-    lm_dev<u64> d_idx, d_sout;
+    lm_dev<u64> d_sout;
     lm_dev<int8_t> d_small;
-    if (kg_alloc(ctx, d_idx, 1, false) || kg_alloc(ctx, d_small, N, true) || kg_alloc(ctx, d_sout, words, true)) return 1;
-    const u64 index = LM_KG_ID_RINGSWITCH * LM_KG_INDEX_STRIDE;
-    if (int rc = lm_kg_upload(ctx, d_idx.get(), &index, 8)) return rc;
-    if (int rc = lm_kg_small(ctx, d_small.get(), d_idx.get(), 1, 0, seed)) return rc;
+    if (kg_alloc(ctx, d_small, N, true) || kg_alloc(ctx, d_sout, words, true)) return 1;
+    if (int rc = lm_sample_small(ctx, d_small.get(), nullptr, LM_KG_ID_RINGSWITCH * LM_KG_INDEX_STRIDE, 1, 0, 1, seed)) return rc;
     // skNew(X^(N/n)) over QP
     if (int rc = lm_for_logn(ctx, ctx->logN, [&](auto k) {
             return kg_secret_ntt_t<k>(ctx, d_small.get(), d_sout.get(), nullptr, 1, ctx->logN - log_n_small);

@@ -600,9 +600,8 @@ int get_tables(lumen_ctx *ctx, KsTables **out) {
     std::vector<tw_t> pinv(L);
     for (uint32_t t = 0; t < L; t++) {
         bxp[t] = make_bx(ctx->mod + L, K, ctx->mod[t]);
-        uint64_t q = ctx->mod[t], P = 1;
-        for (uint32_t a = 0; a < K; a++) P = h_mulmod(P, ctx->mod[L + a] % q, q);
-        pinv[t] = h_tw(h_invmod(P, q), q);
+        const uint64_t q = ctx->mod[t];
+        pinv[t] = h_tw(h_invmod(h_p_mod(ctx, q), q), q);
     }
     std::vector<uint16_t> pairs;
     for (uint32_t t = 0; t < LK; t++)

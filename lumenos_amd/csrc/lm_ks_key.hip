@@ -55,12 +55,8 @@ extern "C" int lumen_load_galois_key_ex(lumen_ctx *ctx, uint64_t gal_el, const u
     for (uint32_t t = 0; t < LM_MAX_LIMBS; t++) fac.t[t] = h_tw(1, ctx->mod[0] ? ctx->mod[0] : 3);
     for (uint32_t t = 0; t < LK; t++) {
         const uint64_t q = ctx->mod[t];
-        uint64_t r = (flags & LUMEN_KEY_MONTGOMERY) ? 1 : (uint64_t)((((u128)1) << 64) % q);
-        if (t < L) {
-            uint64_t P = 1;
-            for (uint32_t a = 0; a < K; a++) P = h_mulmod(P, ctx->mod[L + a] % q, q);
-            r = h_mulmod(r, h_invmod(P, q), q);
-        }
+        uint64_t r = (flags & LUMEN_KEY_MONTGOMERY) ? 1 : h_r64_mod(q);
+        if (t < L) r = h_mulmod(r, h_invmod(h_p_mod(ctx, q), q), q);
         fac.t[t] = h_tw(r, q);
     }
     lm_dev<u64> raw, d_new; // the staging copy of the host words, and the key in the gadget product's form

@@ -55,7 +55,7 @@ int upload_ptT(lumen_ctx *ctx, const uint64_t *pt, uint32_t nl, u64 **out) {
         for (uint32_t k = 0; k < N; k++) bad |= (uint64_t)(src[k] >= q);
         if (bad) return lm_fail(ctx, "plaintext residue out of range at limb %u", l);
         memcpy(h + (size_t)l * N, src, (size_t)N * sizeof(u64));
-        const uint64_t r = (uint64_t)((((u128)1) << 64) % q);
+        const uint64_t r = h_r64_mod(q);
         pc.c[l] = h_mulmod(ctx->T % q, h_mulmod(r, r, q), q);
     }
     LM_HIP(ctx, hipMemcpyAsync(draw, h, words * sizeof(u64), hipMemcpyHostToDevice, ctx->stream));

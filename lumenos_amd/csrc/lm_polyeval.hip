@@ -13,7 +13,7 @@
 //                     (8 per Montgomery reduction), the column's sum times z^(c0+j) -> one word per column
 //   k_poly_sum        the words of all columns -> one u64
 // A value >= T enters the products as it is: x * w^i and (x mod T) * w^i are the same residue, so the result is
-// that of the reduced witness lumen_encrypt_values commits to (lm_encrypt.hip, k_scatter_slots).
+// that of the reduced witness lumen_encrypt_values commits to (lm_encoder.hip, k_scatter_slots).
 #include <cstring>
 
 #include "lm_common.h"
@@ -42,7 +42,7 @@ __global__ __launch_bounds__(256) void k_poly_pow_table(u64 *__restrict__ out, u
 int lm_poly_pow_table(lumen_ctx *ctx, u64 *out, uint32_t n, uint64_t baseM, uint64_t e0) {
     const uint64_t T = ctx->T;
     hipLaunchKernelGGL(k_poly_pow_table, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, out, n, baseM, e0,
-                       (uint64_t)((((u128)1) << 64) % T), lm_make_mod(T));
+                       h_r64_mod(T), lm_make_mod(T));
     LM_HIP(ctx, hipGetLastError());
     return 0;
 }
@@ -138,7 +138,7 @@ int lm_poly_eval_enqueue(lumen_ctx *ctx, const uint64_t *values, uint32_t rows, 
         u64 *dpart = (u64 *)lm_scratch(ctx, "poly_part", (size_t)count * 8);
         if (!dval || !dw || !dz || !dpart) return 1;
         // Montgomery forms of z, w = z^cols and 1 (host: three scalars; the tables are built on the device)
-        const uint64_t R = (uint64_t)((((u128)1) << 64) % T), zr = z % T;
+        const uint64_t R = h_r64_mod(T), zr = z % T;
         const uint64_t zMont = h_mulmod(zr, R, T), wMont = h_mulmod(h_powmod(zr, cols, T), R, T);
         {
             lm_prof_scope ps(ctx, "poly_tables", (uint64_t)rows + count);

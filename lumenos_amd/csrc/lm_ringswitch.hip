@@ -20,8 +20,6 @@
 
 #include "lm_ks_dev.h"
 
-int lm_d2h(lumen_ctx *ctx, void *host, const void *dev, size_t bytes, bool wait);
-
 namespace {
 
 struct RsKey {
@@ -200,7 +198,7 @@ extern "C" int lumen_load_ringswitch_key(lumen_ctx *ctx, uint32_t log_n_small, u
             for (uint32_t t = 0; t < nt; t++) {
                 const uint32_t mi = t == 0 ? 0 : L + (t - 1);
                 const uint64_t q = ctx->mod[mi];
-                const uint64_t r = (uint64_t)((((u128)1) << 64) % q);
+                const uint64_t r = h_r64_mod(q);
                 const uint64_t *src = key + (((size_t)j * 2 + pw) * LK + mi) * N;
                 const size_t off = (((size_t)j * 2 + pw) * nt + t) * N;
                 for (uint32_t k = 0; k < N; k++) {

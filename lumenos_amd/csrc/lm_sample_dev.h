@@ -1,5 +1,5 @@
-// The ChaCha20 keystream and the Gaussian table of the deterministic samplers (lm_encrypt.hip, lm_keygen.hip), shared
-// bit for bit with the CPU checker (oracle/lo_encdet.c):
+// The ChaCha20 keystream, the Gaussian table and the two small-coefficient rules of the deterministic samplers
+// (lm_sample.hip), shared bit for bit with the CPU checker (oracle/lo_encdet.c):
 //     keystream(I, s) = ChaCha20(key = seed, nonce = LE64(I) || LE32(s), counter = block)
 #pragma once
 #include "lm_arith.h"

@@ -14,7 +14,7 @@
 // Only count * 24 bytes of verdicts come back.
 #include <cstring>
 
-#include "lm_common.h"
+#include "lm_enc_host.h"
 #include "lm_polyeval_dev.h"
 
 // lm_hash.hip
@@ -139,7 +139,7 @@ extern "C" int lumen_verify_columns(lumen_ctx *ctx, const lumen_set *opened, uin
         if (values)
             if (int rc = lm_decrypt_slots(ctx, dec, count, scale, rows, values)) return rc;
         const mod_t m = lm_make_mod(T);
-        const uint64_t R = (uint64_t)((((u128)1) << 64) % T), sinv = h_invmod(scale % T, T);
+        const uint64_t R = h_r64_mod(T), sinv = h_invmod(scale % T, T);
         const uint64_t sinvM = h_mulmod(sinv, R, T), sinvM2 = h_mulmod(sinvM, R, T);
         u64 *vr = dvec, *vb = dvec + N;
         {

@@ -241,6 +241,25 @@ def test_chunk_boundary(oracle):
 
 
 @pytest.mark.gpu
+def test_index_carries_into_the_second_nonce_word(oracle):
+    """three ciphertexts from sample index 2^32 - 2: the index crosses 2^32 inside one call.  Every word of the full
+    form equals the model, the seeded form is its c0 halves, and a key-less context rebuilds the set."""
+    shape, first = (8, 3, 2), (1 << 32) - 2
+    P, s, vals = _params(oracle, shape)
+    v, a_seed = vals[:3], A_SEEDS[1]
+    want, _, _ = em.encrypt(P, s, v, SECRET_SEED, a_seed, first)
+    ctx = _client(P, s)
+    full = ctx.encrypt_sk_values(v, SECRET_SEED, a_seed, first).download()
+    assert np.array_equal(full[:, 1], want[:, 1]), "c1"
+    assert np.array_equal(full[:, 0], want[:, 0]), "c0"
+    c0 = ctx.encrypt_sk_seeded(v, SECRET_SEED, a_seed, first)
+    assert np.array_equal(c0, full[:, 0])
+    server = make_context(P)  # no key, no encoder tables
+    assert np.array_equal(server.expand_seeded(c0, a_seed, first).download(), full)
+    server.close(), ctx.close()
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("generated", [False, True])
 def test_round_trip(oracle, generated):
     """lumen_decrypt returns the values under a loaded and under a generated key; the oracle's decryptor agrees"""

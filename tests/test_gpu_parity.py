@@ -853,6 +853,32 @@ def test_encrypt_values_matches_oracle_encode_then_encrypt(oracle, log_n, num_q,
     ctx.close()
 
 
+def test_encrypt_values_chunk_boundary_and_index_carry(oracle):
+    """257 columns from sample index 2^32 - 200 in ONE call: the 256-ciphertext chunk boundary (255 | 256) and the carry
+    of the index into the nonce's second word (199 | 200) both fall inside it.  The ciphertexts on either side of both
+    equal the oracle's deterministic encryption word for word, a single-column call at the last index gives the last
+    ciphertext, and all 257 decrypt.  (N = 2^8, two Q limbs: the sampler's index rule does not depend on the chain.)"""
+    from lumenos_amd import params as lp
+    P = make_params(oracle, 8, 2, num_p=0)
+    P.seed(257)
+    sk = P.keygen_secret()
+    pk = P.keygen_public(sk)
+    ctx = make_context(P)
+    ctx.load_public_key(pk)
+    ctx.load_secret_key(sk)
+    ctx.encoder_set(lp.encoder_psi(T_REF, 8))
+    seed = np.frombuffer(bytes(range(90, 122)), dtype=np.uint8)
+    n, first = 257, 2**32 - 200
+    vals = np.random.default_rng(n).integers(0, T_REF, size=(n, P.N), dtype=np.uint64)
+    cts = ctx.encrypt_values(vals, seed, first)
+    got = cts.download()
+    for i in (0, 199, 200, 255, 256):
+        assert np.array_equal(got[i], P.encrypt_det(pk, P.encode(vals[i]), seed, first + i)), i
+    assert np.array_equal(ctx.encrypt_values(vals[256:], seed, first + 256).download()[0], got[256])
+    assert np.array_equal(ctx.decrypt(cts, P.N), vals)
+    ctx.close()
+
+
 # ------------------------------------------------------------------ client-side decryption (SURVEY 8f-4)
 @pytest.mark.parametrize("log_n,num_q", [(10, 2), (10, 1), (12, 2), (14, 2)])
 def test_decrypt_matches_oracle(oracle, log_n, num_q):
