@@ -79,8 +79,9 @@ int lumen_ctx_wait(lumen_ctx *ctx, lumen_ctx *other);
  * "LUMEN_KS_FUSED_DIGITS" (value < 0: derived default), "LUMEN_DEBUG", "LUMEN_MODUP_TGROUP",
  * "LUMEN_MODDOWN_TGROUP" (work-list order of the key switch's two transform kernels), "LUMEN_KS_PLACEMENT" (candidate
  * blocks per key-switch scratch buffer among which a context's first key switch picks by measurement, 0 = none:
- * takes effect when the buffers are next allocated, e.g. after lumen_ctx_trim).  An unknown name or a value out of a
- * switch's range is an error and changes nothing. */
+ * takes effect when the buffers are next allocated, e.g. after lumen_ctx_trim), "LUMEN_BATCH_CHUNKS" (chunks of columns
+ * per limb in lumen_batch_ciphertexts, 0 .. 4096, 0 = derived from the CU count; the residues do not depend on it).  An
+ * unknown name or a value out of a switch's range is an error and changes nothing. */
 int lumen_ctx_set_tuning(lumen_ctx *ctx, const char *name, long value);
 /* TEST HOOK (not a tuning switch, never read from the environment): lumen_group_create then lets LUMEN_TRANSPORT_RCCL
  * through although ranks share a device, so that the library's RCCL call sequence can be run with W > 1 on a one-GPU
@@ -452,6 +453,45 @@ int lumen_encrypt_sk_seeded(lumen_ctx *ctx, const uint64_t *values, uint32_t row
 /* the server's side: c0 halves + public seed -> the full top-level set.  Needs no key of any kind. */
 int lumen_ct_expand_seeded(lumen_ctx *ctx, const uint64_t *c0, uint32_t count, const uint8_t a_seed[32],
                            uint64_t first_index, lumen_set **out);
+
+/* ---- the front end of the proof of decryption (cmd/client/main.go:203-208: Proof.ProveDecrypt ->
+ * vdec.ProveBfvDecBatched, vdec/prover.go:50-98, vdec/batching.go): what the client computes on its own ciphertexts
+ * before the call into lazer.  lazer itself is out of scope: these two calls produce the arguments of ProveVdecLnpTbox.
+ *
+ * lumen_batch_ciphertexts = vdec.BatchCiphertexts: each row alpha_j of `alphas` (host [count][rows], count = the set's)
+ * is encoded as a plaintext at scale pt_scale (Encoder.Encode: alpha_j * pt_scale mod T into the slots, inverse transform
+ * over Z_T -- the scale is applied modulo T, ahead of the transform) and the result is ONE ciphertext of the set's limb
+ * count,
+ *     out = sum_j MulNew(ct_j, pt(alpha_j))                                   (canonical residues)
+ * A word of `alphas` >= T counts as its residue (the transcript samples raw 64-bit words).  The result's scale is the
+ * ciphertexts' scale * pt_scale mod T: the caller tracks it (the reference copies the ciphertexts' MetaData into the
+ * plaintexts, so pt_scale is the ciphertexts' scale there).  lumen_mul_counter grows by count.
+ * THE BUDGET.  Multiplying by a full-size plaintext costs about N * T in noise, so the batch only decrypts where
+ *     T * count * N * T * (B + 1) < Q_level / 2,
+ * B the noise of the inputs in the form phase = m * T^-1 + e.  The reference's vdec tests use T = 0x3ee0001 for exactly
+ * that reason; with the 57-bit T of cmd/server its own -vdec path overflows at level 1.  The library computes what it is
+ * asked to compute: tools/noise_budget.py --vdec COUNT says whether a shape fits.
+ * Refused with a message, before any device work: NULL arguments; count == 0; rows outside [1, N]; a lane-sharded set;
+ * a limb count outside [1, L]; no encoder tables; pt_scale == 0 mod T; T >= 2^60.
+ *
+ * lumen_vdec_witness = the witness generation of prover.go:104-119 (core/utils.go:12-33) on ONE ciphertext of ONE limb
+ * (run lumen_rescale(., 1) first), N centred coefficients each, host arrays:
+ *     sk       the secret key, in {-1, 0, 1} (anything else is an error)
+ *     c0, c1   the ciphertext's halves, coefficient domain, in (-q_0/2, q_0/2]
+ *     m_delta  the message m (host [rows] slot values) at `scale`: Encode(m * scale mod T) * T^-1 mod q_0, coefficient
+ *              domain, centred
+ *     err      (or NULL) c0 + c1 * sk - m_delta mod q_0, centred: the e whose smallness lazer proves.  The decryption
+ *              is right exactly when |err| * 2T < q_0.
+ * Recorded deviation: prover.go:119 passes isNTT = false for an NTT-domain plaintext, i.e. it hands lazer limb 0's
+ * NTT-domain words as if they were coefficients.  That is not reproduced: m_delta is in the coefficient domain, like
+ * c0 and c1.  The reference takes only the first `degree` (2048) coefficients (prover.go:92,138-143); here all N are
+ * returned and the caller slices.
+ * Refused in addition: a set of other than one ciphertext or other than one limb; no secret key; scale == 0 mod T. */
+int lumen_batch_ciphertexts(lumen_ctx *ctx, const lumen_set *cts, const uint64_t *alphas /* host [count][rows] */,
+                            uint32_t rows, uint64_t pt_scale, lumen_set **out /* 1 ciphertext, cts' limb count */);
+int lumen_vdec_witness(lumen_ctx *ctx, const lumen_set *ct, const uint64_t *m /* host [rows] */, uint32_t rows,
+                       uint64_t scale, int8_t *sk /* [N] */, int64_t *c0, int64_t *c1, int64_t *m_delta,
+                       int64_t *err /* or NULL */);
 
 /* ---- query loop of Prove (fhe/ligero.go:268-279): gather ciphertexts idx[i]
  * of a set into a new set (duplicates allowed). */

@@ -89,6 +89,8 @@ struct lm_tuning {
     // LUMEN_KS_PLACEMENT: candidate blocks per key-switch scratch buffer among which the first key switch of a context
     // picks by measurement (lm_ks_scratch.hip, lm_placement.h); 0 or 1 = take what hipMalloc returns
     uint32_t ks_placement = 6;
+    // LUMEN_BATCH_CHUNKS: chunks of columns per Q limb in k_batch_mac (lm_vdec.hip); 0 = limbs * chunks at about the CU count
+    uint32_t batch_chunks = 0;
     // lumen_test_allow_shared_device_rccl (tests only; not reachable through lumen_ctx_set_tuning or the environment):
     // LUMEN_TRANSPORT_RCCL accepts ranks that share a device, for the test double tests/cpp/fake_rccl.cpp
     uint32_t rccl_shared_device = 0;

@@ -202,6 +202,9 @@ static int tuning_set(lm_tuning &t, const char *name, long v) {
     } else if (n == "LUMEN_KS_PLACEMENT") {
         if (!in(0, 32)) return 2;
         t.ks_placement = (uint32_t)v;
+    } else if (n == "LUMEN_BATCH_CHUNKS") { // 0: the derived default
+        if (!in(0, 4096)) return 2;
+        t.batch_chunks = (uint32_t)v;
     } else {
         return 1;
     }
@@ -209,7 +212,7 @@ static int tuning_set(lm_tuning &t, const char *name, long v) {
 }
 static void tuning_from_env(lm_tuning &t) {
     for (const char *n : {"LUMEN_KS_BATCH", "LUMEN_KS_LANES", "LUMEN_KS_FUSED_DIGITS", "LUMEN_DEBUG",
-                          "LUMEN_MODUP_TGROUP", "LUMEN_MODDOWN_TGROUP", "LUMEN_KS_PLACEMENT"}) {
+                          "LUMEN_MODUP_TGROUP", "LUMEN_MODDOWN_TGROUP", "LUMEN_KS_PLACEMENT", "LUMEN_BATCH_CHUNKS"}) {
         const char *e = getenv(n);
         // an empty override counts as unset; a value out of range is reported and leaves the default
         if (e && *e && tuning_set(t, n, atol(e)))

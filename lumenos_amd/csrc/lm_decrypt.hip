@@ -149,6 +149,15 @@ static int decrypt_phase_t(lumen_ctx *ctx, const u64 *ct, const tw_t *sk, u64 *p
                      ctx->sh->tw_inv.get());
 }
 
+int lm_decrypt_phase(lumen_ctx *ctx, const u64 *ct, uint32_t count, uint32_t nl, const SkTable *sk, u64 *phase, bool times_T) {
+    dec_scale_t sc;
+    for (uint32_t l = 0; l < LM_MAX_LIMBS; l++) {
+        const uint64_t q = ctx->mod[l < nl ? l : 0];
+        sc.t[l] = h_tw(h_mulmod(ctx->ninv[l < nl ? l : 0].w, times_T ? ctx->T % q : 1, q), q);
+    }
+    return lm_for_logn(ctx, ctx->logN, [&](auto k) { return decrypt_phase_t<k>(ctx, ct, sk->d_sk.get(), phase, count, nl, sc); });
+}
+
 int lm_decrypt_check(lumen_ctx *ctx, const lumen_set *set, uint64_t scale, const char *what) {
     LM_FULL_WIDTH(ctx, set, what);
     LM_CHECK(ctx, set->nl >= 1 && set->nl <= ctx->L, "%s: %u limbs out of range [1, %u]", what, set->nl, ctx->L);
@@ -169,13 +178,7 @@ int lm_decrypt_decode(lumen_ctx *ctx, const lumen_set *set, lm_decoded *out) {
     u64 *phase = (u64 *)lm_scratch(ctx, "dec_phase", (size_t)count * nl * N * sizeof(u64));
     u64 *m = (u64 *)lm_scratch(ctx, "dec_m", (size_t)count * N * sizeof(u64));
     if (!phase || !m) return 1;
-    dec_scale_t sc;
-    for (uint32_t l = 0; l < LM_MAX_LIMBS; l++) {
-        const uint64_t q = ctx->mod[l < nl ? l : 0];
-        sc.t[l] = h_tw(h_mulmod(ctx->ninv[l < nl ? l : 0].w, T % q, q), q);
-    }
-    if (int rc = lm_for_logn(ctx, ctx->logN, [&](auto k) { return decrypt_phase_t<k>(ctx, set->d, sk->d_sk.get(), phase, count, nl, sc); }))
-        return rc;
+    if (int rc = lm_decrypt_phase(ctx, set->d, count, nl, sk, phase, true)) return rc;
     if (nl > 2) { // deeper than what Prove returns: exact CRT by mixed radix
         std::vector<garner_t> hg(1);
         garner_t &G = hg[0];

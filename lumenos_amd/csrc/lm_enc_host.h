@@ -32,8 +32,9 @@ struct EncoderTables {
 };
 // Encoder.Encode up to the coefficient vector modulo T, enqueued on the context's stream: n columns of `rows` host
 // values -> dm [n][N] (dval: device staging of n * rows words).  The caller waits for the stream before `values` changes.
+// scale: the plaintext's scale, applied to the values modulo T ahead of the transform (1: Encode of a fresh plaintext).
 int lm_encode_coeffs(lumen_ctx *ctx, const EncoderTables *enc, const uint64_t *values, uint32_t rows, uint32_t n, u64 *dval,
-                     u64 *dm);
+                     u64 *dm, uint64_t scale = 1);
 
 // ---- the secret-key table and client-side decryption in stages (lm_decrypt.hip), shared by lumen_decrypt and
 // lumen_verify_columns
@@ -53,6 +54,9 @@ struct lm_decoded {
     std::shared_ptr<void> keep[2];
 };
 int lm_decrypt_decode(lumen_ctx *ctx, const lumen_set *set, lm_decoded *out);
+// The decryptor's first kernel alone (k_decrypt_phase: c0 + c1 * s formed in the load of the inverse transform):
+// phase [count][nl][N] = INTT(c0 + c1 * s), times T when times_T (what Decode goes on from), canonical.
+int lm_decrypt_phase(lumen_ctx *ctx, const u64 *ct, uint32_t count, uint32_t nl, const SkTable *sk, u64 *phase, bool times_T);
 // values[c][i] = t[c][slot[i]] * scale^-1 mod T for i < nvalues, copied to the host buffer on the context's stream
 // (not waited for)
 int lm_decrypt_slots(lumen_ctx *ctx, const lm_decoded &dec, uint32_t count, uint64_t scale, uint32_t nvalues,

@@ -44,15 +44,30 @@ __global__ void k_scatter_slots(const u64 *__restrict__ values, u64 *__restrict_
     m[(c << logN) + slot[i]] = lm_reduce(values[g], modT.q, modT.qinv64);
 }
 
+// the same with the plaintext's scale: m[c][slot[i]] = values[c][i] * scale mod T.  Encoder.Encode multiplies the VALUES
+// by pt.Scale modulo T, ahead of the transform over Z_T [LATTIGO-RECALL] -- modulo T, not modulo q_l.
+__global__ void k_scatter_slots_scaled(const u64 *__restrict__ values, u64 *__restrict__ m, const uint32_t *__restrict__ slot,
+                                       uint32_t rows, uint32_t logN, size_t total, mod_t modT, tw_t scale) {
+    const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= total) return;
+    const size_t c = g / rows;
+    const uint32_t i = (uint32_t)(g % rows);
+    m[(c << logN) + slot[i]] = lm_shoup(lm_reduce(values[g], modT.q, modT.qinv64), scale, modT.q);
+}
+
 int lm_encode_coeffs(lumen_ctx *ctx, const EncoderTables *enc, const uint64_t *values, uint32_t rows, uint32_t n, u64 *dval,
-                     u64 *dm) {
+                     u64 *dm, uint64_t scale) {
     const uint32_t N = ctx->N;
     LM_HIP(ctx, hipMemcpyAsync(dval, values, (size_t)n * rows * sizeof(u64), hipMemcpyHostToDevice, ctx->stream));
     LM_HIP(ctx, hipMemsetAsync(dm, 0, (size_t)n * N * sizeof(u64), ctx->stream));
     const size_t total = (size_t)n * rows;
     {
         lm_prof_scope ps(ctx, "encode_scatter", n);
-        if (int rc = lm_launch_flat(ctx, k_scatter_slots, total, dval, dm, enc->d_slot.get(), rows, ctx->logN, total, enc->modT))
+        const uint64_t T = enc->modT.q;
+        if (int rc = scale % T == 1 % T
+                         ? lm_launch_flat(ctx, k_scatter_slots, total, dval, dm, enc->d_slot.get(), rows, ctx->logN, total, enc->modT)
+                         : lm_launch_flat(ctx, k_scatter_slots_scaled, total, dval, dm, enc->d_slot.get(), rows, ctx->logN, total,
+                                          enc->modT, h_tw(scale % T, T)))
             return rc;
     }
     lm_prof_scope ps(ctx, "encode_intt_T", n);

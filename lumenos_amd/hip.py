@@ -130,6 +130,8 @@ SYMBOLS = {
     "lumen_encrypt_sk_values": (C.c_int, [_vp, _u64p, C.c_uint32, C.c_uint32, _u8p, _u8p, C.c_uint64, C.POINTER(_vp)]),
     "lumen_encrypt_sk_seeded": (C.c_int, [_vp, _u64p, C.c_uint32, C.c_uint32, _u8p, _u8p, C.c_uint64, _u64p]),
     "lumen_ct_expand_seeded": (C.c_int, [_vp, _u64p, C.c_uint32, _u8p, C.c_uint64, C.POINTER(_vp)]),
+    "lumen_batch_ciphertexts": (C.c_int, [_vp, _vp, _u64p, C.c_uint32, C.c_uint64, C.POINTER(_vp)]),
+    "lumen_vdec_witness": (C.c_int, [_vp, _vp, _u64p, C.c_uint32, C.c_uint64, C.POINTER(C.c_int8)] + [C.POINTER(C.c_int64)] * 4),
     "lumen_group_create": (C.c_int, [_vpp, C.c_uint32, C.c_uint32, _vpp]),
     "lumen_group_unique_id": (C.c_int, [_u8p]),
     "lumen_group_create_rank": (C.c_int, [_vp, C.c_uint32, C.c_uint32, _u8p, _vpp]),
@@ -773,6 +775,30 @@ class Context:
         self._ck(self.lib.lumen_ct_expand_seeded(self.h, _p64(c0), c0.shape[0], sa.ctypes.data_as(_u8p), first_index,
                                                  C.byref(h)))
         return DeviceSet(self, h)
+
+    # the front end of the proof of decryption (vdec/batching.go, vdec/prover.go:104-119)
+    def batch_ciphertexts(self, s, alphas, pt_scale=1):
+        """vdec.BatchCiphertexts: sum_j ct_j * pt(alphas[j]) as ONE ciphertext of s's limb count; alphas [count][rows]
+        raw 64-bit words, encoded at scale pt_scale.  The result's scale is s's scale * pt_scale mod T."""
+        alphas = np.ascontiguousarray(alphas, dtype=np.uint64)
+        assert alphas.ndim == 2 and alphas.shape[0] == s.count, (alphas.shape, s.count)
+        h = C.c_void_p()
+        self._ck(self.lib.lumen_batch_ciphertexts(self.h, s.h, _p64(alphas), alphas.shape[1], pt_scale, C.byref(h)))
+        return DeviceSet(self, h)
+
+    def vdec_witness(self, s, m, scale, want_err=True):
+        """Witness of the proof of decryption on ONE one-limb ciphertext: dict of sk (int8), c0, c1, m_delta and err
+        (int64), N centred coefficients each; m: the slot values the ciphertext decrypts to at `scale`."""
+        m = np.ascontiguousarray(m, dtype=np.uint64).reshape(-1)
+        sk = np.zeros(self.N, dtype=np.int8)
+        w = {k: np.zeros(self.N, dtype=np.int64) for k in ("c0", "c1", "m_delta", "err")}
+        p = lambda a: a.ctypes.data_as(C.POINTER(C.c_int64))
+        self._ck(self.lib.lumen_vdec_witness(self.h, s.h, _p64(m), m.size, scale, sk.ctypes.data_as(C.POINTER(C.c_int8)),
+                                             p(w["c0"]), p(w["c1"]), p(w["m_delta"]), p(w["err"]) if want_err else None))
+        if not want_err:
+            del w["err"]
+        w["sk"] = sk
+        return w
 
     def mul_counter(self):
         return int(self.lib.lumen_mul_counter(self.h))

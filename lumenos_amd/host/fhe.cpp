@@ -1364,6 +1364,60 @@ void Proof::Verify(core::Element point, core::Element value, core::PrimeField &f
     if (claim != value) throw std::runtime_error(" claimed value does not match the evaluation of the committed polynomial");
 }
 
+vdec::Witness Proof::ProveDecrypt(ClientBFV &client, core::Span *ctx) const {
+    (void)ctx; // ligero.go:505 starts the span at the top level whatever the caller's span is
+    core::ScopedSpan span("Verifiable decrypt", nullptr, "Verifiable decrypt...");
+    core::Transcript transcript("vdec");
+    if (!QueriedCts || QueriedCts->Len() == 0)
+        throw std::runtime_error("ProveDecrypt: the proof holds no opened ciphertexts (QueriedCts is empty: Decrypt fills it)");
+    if ((size_t)QueriedCts->Len() != QueriedCols.size())
+        throw std::runtime_error("ProveDecrypt: " + std::to_string(QueriedCols.size()) + " decrypted columns for " +
+                                 std::to_string(QueriedCts->Len()) + " opened ciphertexts");
+    const Parameters &params = client.GetParameters();
+    lumen_ctx *h = client.Context();
+
+    core::ScopedSpan colSpan("Batching decrypted columns", span.get());
+    auto batched = vdec::BatchColumns(QueriedCols, *client.Field(), transcript);
+    const std::vector<core::Element> &m = batched.first;
+    colSpan.End();
+
+    core::ScopedSpan ctSpan("Batching ciphertexts", span.get());
+    Ciphertexts batchCt = vdec::BatchCiphertexts(*QueriedCts, batched.second, client);
+    ctSpan.End();
+
+    // for batchCt.LevelQ() > 0 { Rescale } (prover.go:84-87)
+    if (batchCt.Level() > 0) {
+        lumen_set *low = nullptr;
+        client.check(lumen_rescale(h, batchCt.Handle(), 1, &low), "lumen_rescale");
+        MetaData md = batchCt.Meta;
+        md.Scale = RescaledScale(params, md.Scale, batchCt.Level(), 0);
+        batchCt = Ciphertexts(h, low, md);
+    }
+
+    core::ScopedSpan witSpan("Witness generation", span.get());
+    const size_t N = (size_t)params.N();
+    vdec::Witness w;
+    w.sk.resize(N), w.ct0.resize(N), w.ct1.resize(N), w.mDelta.resize(N), w.err.resize(N);
+    w.Degree = (int)std::min<size_t>(2048, N); // `degree` of prover.go:92
+    client.check(lumen_vdec_witness(h, batchCt.Handle(), m.data(), (uint32_t)m.size(), batchCt.Scale(), w.sk.data(), w.ct0.data(),
+                                    w.ct1.data(), w.mDelta.data(), w.err.data()),
+                 "lumen_vdec_witness");
+    witSpan.End();
+
+    // the decryption relation: m is what the batch ciphertext decrypts to iff |err| * 2T < q_0
+    uint64_t emax = 0;
+    for (int64_t e : w.err) emax = std::max<uint64_t>(emax, (uint64_t)(e < 0 ? -e : e));
+    const unsigned __int128 lhs = (unsigned __int128)emax * 2 * params.T;
+    if (lhs >= params.Q[0])
+        throw std::runtime_error("ProveDecrypt: the batch of " + std::to_string(QueriedCts->Len()) +
+                                 " ciphertexts does not decrypt to the batched columns (max |err| = " + std::to_string(emax) +
+                                 ", |err| * 2T >= q_0): outside the noise budget T * count * N * T * (B + 1) < Q_level / 2 "
+                                 "of a full-size plaintext product -- see tools/noise_budget.py --vdec");
+    // Here vdec.CallVdecProver (prover.go:121-) fills lazer's polyvecs from the five arrays and calls ProveVdecLnpTbox.
+    // lazer is not part of this project ("Proof of decryption"): the witness is the result.
+    return w;
+}
+
 std::vector<uint8_t> EncryptedProof::MarshalBinary() const {
     std::vector<uint8_t> buf(MarshaledSize());
     MarshalInto(buf.data(), buf.size(), false);
@@ -1377,4 +1431,46 @@ WireBuffer EncryptedProof::MarshalBinaryPinned() const {
 }
 
 } // namespace fhe
+
+namespace vdec {
+std::pair<std::vector<core::Element>, std::vector<std::vector<uint64_t>>>
+BatchColumns(const std::vector<std::vector<core::Element>> &matrixColMajor, core::PrimeField &field, core::Transcript &transcript) {
+    if (matrixColMajor.empty()) throw std::invalid_argument("BatchColumns: no columns");
+    const size_t rows = matrixColMajor[0].size(), cols = matrixColMajor.size();
+    const uint64_t T = field.Modulus();
+    std::vector<std::vector<uint64_t>> alphas(cols);
+    for (auto &a : alphas) {
+        a.assign(rows, 0);
+        transcript.SampleUints("pod_alpha", a);
+    }
+    std::vector<core::Element> batchCol(rows, 0);
+    for (size_t j = 0; j < cols; j++) {
+        if (matrixColMajor[j].size() != rows) throw std::invalid_argument("BatchColumns: columns of unequal length");
+        for (size_t i = 0; i < rows; i++)
+            batchCol[i] = field.Add(batchCol[i], field.Mul(matrixColMajor[j][i] % T, alphas[j][i] % T));
+    }
+    return {std::move(batchCol), std::move(alphas)};
+}
+
+fhe::Ciphertexts BatchCiphertexts(const fhe::Ciphertexts &cts, const std::vector<std::vector<uint64_t>> &alphasColMajor,
+                                  fhe::ClientBFV &client) {
+    if (alphasColMajor.empty() || (int)alphasColMajor.size() != cts.Len())
+        throw std::invalid_argument("BatchCiphertexts: " + std::to_string(alphasColMajor.size()) + " challenge columns for " +
+                                    std::to_string(cts.Len()) + " ciphertexts");
+    const size_t rows = alphasColMajor[0].size();
+    std::vector<uint64_t> flat;
+    flat.reserve(alphasColMajor.size() * rows);
+    for (const auto &a : alphasColMajor) {
+        if (a.size() != rows) throw std::invalid_argument("BatchCiphertexts: challenge columns of unequal length");
+        flat.insert(flat.end(), a.begin(), a.end());
+    }
+    lumen_set *out = nullptr;
+    client.check(lumen_batch_ciphertexts(client.Context(), cts.Handle(), flat.data(), (uint32_t)rows, cts.Scale(), &out),
+                 "lumen_batch_ciphertexts");
+    fhe::MetaData md = cts.Meta;
+    const uint64_t T = client.GetParameters().T;
+    md.Scale = core::MulMod(cts.Scale() % T, cts.Scale() % T, T); // MulNew: Scale_ct * Scale_pt
+    return fhe::Ciphertexts(client.Context(), out, md);
+}
+} // namespace vdec
 } // namespace lumenos

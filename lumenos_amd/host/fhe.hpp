@@ -16,6 +16,21 @@
 #include "core.hpp"
 
 namespace lumenos {
+namespace vdec {
+// The arguments of lazer's ProveVdecLnpTbox as vdec.CallVdecProver prepares them (vdec/prover.go:104-119,
+// core/utils.go:12-33): centred coefficient vectors of the level-0 batch ciphertext, of the secret key and of the
+// batched message at the ciphertext's scale, N entries each.  The reference hands lazer the first Degree of them
+// (prover.go:92,138-143); the caller slices.  err = ct0 + ct1 * sk - mDelta mod q_0, centred: the e whose smallness
+// lazer proves (the decryption is right exactly when |err| * 2T < q_0).
+// Recorded deviation: prover.go:119 reads the NTT-domain words of the plaintext as if they were coefficients
+// (isNTT = false); mDelta here is in the coefficient domain, like ct0 and ct1.
+struct Witness {
+    std::vector<int8_t> sk;
+    std::vector<int64_t> ct0, ct1, mDelta, err;
+    int Degree = 2048;
+};
+} // namespace vdec
+
 namespace fhe {
 
 // bgv.ParametersLiteral as produced by GenerateBGVParamsForNTT
@@ -503,6 +518,16 @@ struct Proof {
     // depth, or fewer paths than queries, are the Merkle failure of the first such query.
     void Verify(core::Element point, core::Element value, core::PrimeField &field, core::Transcript &transcript,
                 ClientBFV &client) const;
+    // Proof.ProveDecrypt (ligero.go:504-515) -> vdec.ProveBfvDecBatched (vdec/prover.go:50-98) up to the call into lazer,
+    // under the reference's spans "Verifiable decrypt", "Batching decrypted columns", "Batching ciphertexts" and
+    // "Witness generation", with the transcript "vdec": folds QueriedCols with the transcript's challenges on the host,
+    // batches QueriedCts on the client's device (lumen_batch_ciphertexts), rescales to level 0 and returns the witness
+    // (lumen_vdec_witness).  Stops where CallVdecProver would call ProveVdecLnpTbox: lazer is not part of this project.
+    // THE BUDGET: a full-size plaintext costs about N * T in noise, so the batch only decrypts where
+    // T * count * N * T * (B + 1) < Q_level / 2 (include/lumenos_hip.h; tools/noise_budget.py --vdec): the reference's
+    // vdec tests use T = 0x3ee0001 for that reason.  The decryption relation is checked on the device: throws
+    // std::runtime_error naming the budget when |err| * 2T >= q_0, and when QueriedCts is empty.
+    vdec::Witness ProveDecrypt(ClientBFV &client, core::Span *ctx) const;
 };
 // the error Proof.Verify's loop returns for one column's status word of lumen_verify_columns (ligero.go:556, 561, 565:
 // PATH before R before B); empty when the column passed
@@ -523,4 +548,18 @@ Ciphertexts matrixInnerSumEval(const Ciphertexts &matrix, const Plaintext &plain
 std::vector<int> sampleQueryIndices(core::Transcript &transcript, int queries, int extCols); // ligero.go:638-644
 
 } // namespace fhe
+
+// the front end of the reference's `vdec` package (vdec/batching.go) above the C ABI
+namespace vdec {
+// vdec.BatchColumns (batching.go:43-64), on the host: one SampleUints("pod_alpha", rows words) per column, in column
+// order; batchCol[i] = sum_j matrixColMajor[j][i] * alphas[j][i] mod T (a challenge word >= T counts as its residue).
+// Returns (batchCol, alphasColMajor).
+std::pair<std::vector<core::Element>, std::vector<std::vector<uint64_t>>>
+BatchColumns(const std::vector<std::vector<core::Element>> &matrixColMajor, core::PrimeField &field, core::Transcript &transcript);
+// vdec.BatchCiphertexts (batching.go:9-41) on the client's device (lumen_batch_ciphertexts): sum_j cts[j] * pt(alphas[j]),
+// the plaintexts at the ciphertexts' scale (alphaPts[i].MetaData = cts[0].MetaData).  ONE ciphertext at the level of
+// `cts`; its Scale is the square of theirs modulo T.
+fhe::Ciphertexts BatchCiphertexts(const fhe::Ciphertexts &cts, const std::vector<std::vector<uint64_t>> &alphasColMajor,
+                                  fhe::ClientBFV &client);
+} // namespace vdec
 } // namespace lumenos

@@ -9,6 +9,14 @@ all hold the same Enc(0), so their coefficients add up before they meet its nois
 replays nttInner's control flow on the rows of A (float64: only magnitudes matter) and prints, per
 shape, log2 of the largest per-column noise gain against the budget, for a given fresh-noise sigma.
 
+--vdec COUNT [cols logN [T]]: the batch of the proof of decryption (lumen_batch_ciphertexts, vdec/batching.go).  Every
+opened column is multiplied by a FULL-SIZE plaintext (N coefficients up to T), which costs about N * T in noise, and
+COUNT of them are added: the batch decrypts only where
+    T * COUNT * N * T * (B + 1) < Q_level / 2,
+B the noise of the opened columns in the form phase = m * T^-1 + e.  One line per plaintext modulus (the prover's
+57-bit T and the 0x3ee0001 of the reference's vdec tests, or the one given) says whether the shape fits at level 1
+(two limbs, where the batch is formed) and at level 0 (one limb, where the witness is read after the rescale).
+
 It is how DESIGN.md section 4 decides whether a reference shape fits its own LogQ heuristic and how
 much the fresh encryption noise of the restated encryptor matters.  Not a test; not product code.
 """
@@ -133,7 +141,35 @@ def chain_bits(cols):
     return 58 + 56 * (k - 1), k
 
 
+T_VDEC = 0x3EE0001  # the reference's vdec tests (vdec/batching_test.go, ring_switch_test.go:17)
+
+
+def vdec_line(count, cols, logn, t, log_b=None):
+    """one line: does a batch of `count` opened columns fit at level 1 and at level 0 under plaintext modulus t"""
+    N = 1 << logn
+    if log_b is None:
+        # the opened columns: Encode's gain on a fresh noise of sigma 3.2, divided by the dropped limbs, plus the
+        # rescale's own rounding (about sqrt(N) with a ternary secret); the walk is over the prover's T -- for another
+        # T only the magnitude of the twiddles changes, and the level-1 noise is dominated by the rounding term
+        log_b = math.log2(math.sqrt(N) + 19)
+    lt = math.log2(t)
+    need = lt + math.log2(count) + logn + lt + math.log2(2 ** log_b + 1)  # log2 of T * count * N * T * (B + 1)
+    lvl1, lvl0 = 58 + 56 - 1, 58 - 1  # log2(Q_level / 2) of the chain [58, 56, ...]
+    # after the rescale the noise is the level-1 noise over q_1 plus the rounding term again
+    need0 = lt + math.log2(2 ** (need - lt - 56) + 2 ** log_b + 1)
+    fit = lambda a, b: "fits" if a < b else "DOES NOT FIT"
+    return (f"vdec count={count} cols={cols} LogN={logn} T=2^{lt:.1f}: log2(T*count*N*T*(B+1)) = {need:.1f} with B = 2^{log_b:.1f}; "
+            f"level 1 (Q/2 = 2^{lvl1}): {fit(need, lvl1)} by {lvl1 - need:+.1f} bits; "
+            f"level 0 (q_0/2 = 2^{lvl0}): T*|e| = 2^{need0:.1f}, {fit(need0, lvl0)} by {lvl0 - need0:+.1f} bits")
+
+
 if __name__ == "__main__":
+    if len(sys.argv) > 2 and sys.argv[1] == "--vdec":
+        count = int(sys.argv[2])
+        cols, logn = (int(sys.argv[3]), int(sys.argv[4])) if len(sys.argv) > 4 else (4096, 14)
+        for t in ([int(sys.argv[5], 0)] if len(sys.argv) > 5 else [T, T_VDEC]):
+            print(vdec_line(count, cols, logn, t))
+        sys.exit(0)
     shapes = [(1024, 12), (1024, 13), (2048, 12), (4096, 13), (4096, 14)]
     if len(sys.argv) > 2:
         shapes = [(int(sys.argv[1]), int(sys.argv[2]))]
