@@ -419,8 +419,11 @@ __global__ __launch_bounds__(256) void k_ks_mac(const u64 *__restrict__ ext, con
 // parked in LDS; then every wave writes one block of the new accumulator limb linearly,
 // acc_out[j] = acc_in[j] + d[index[j]], the automorphism being a gather out of the wave's own LDS block.  (acc is
 // ping-ponged: an output needs the old accumulator at two positions, j and index[j].)
+// N = 2^14: the limb stays in registers (lm_ntt_forward_w14, 512 threads, two workgroups per CU); the last pass only
+// parks its raw outputs in the wave's slot, and d is formed there, half a wave's block at a time, right before that
+// half is gathered (see the LOGN == 14 branch).
 template <int LOGN>
-__global__ LM_GEOM_BOUNDS(lm_geom_lds(LOGN)) void k_moddown_ntt(const u64 *__restrict__ u, const u64 *__restrict__ acc_in,
+__global__ LM_GEOM_BOUNDS(lm_geom_fwd(LOGN)) void k_moddown_ntt(const u64 *__restrict__ u, const u64 *__restrict__ acc_in,
                                                      u64 *__restrict__ acc_out, const bx_t *__restrict__ bxp,
                                                      const tw_t *__restrict__ pinv,
                                                      const uint32_t *__restrict__ index,
@@ -449,74 +452,142 @@ __global__ LM_GEOM_BOUNDS(lm_geom_lds(LOGN)) void k_moddown_ntt(const u64 *__res
     tw_t pi = pinv[t];
     pi.w = qc.q - pi.w, pi.wp = ~pi.wp;
     auto ld = [&](uint32_t i) { return bx_apply(c, up0[i], up1[i], qc); };
-    // the store phase combines every finished run of 8 with the gadget product u (and c0 for w == 0): both
-    // are requested by pre() before the run's butterflies, not after them
-    constexpr int RUN = lm_fwd_run<LOGN>();
-    static_assert(RUN <= 8, "lm_load_run moves at most 8 coefficients");
-    struct storer_t {
-        const u64 *uq, *ain;
-        u64 *sm;
-        const lm_qc &qc;
-        tw_t pi;
-        uint32_t w;
-        u64 uv[RUN], cv[RUN];
-        __device__ __forceinline__ void pre(uint32_t i0) {
-            lm_load_run(uq, i0, uv, RUN);
-            if (w == 0) lm_load_run(ain, i0, cv, RUN);
-        }
-        __device__ __forceinline__ void operator()(uint32_t i0, const u64 *v, int count) {
+    if constexpr (LOGN == 14) {
+        // Limb in registers, two workgroups per CU.  The storer is the extension kernel's (lm_w14_runs: the raw outputs
+        // of the last butterflies, any u64, go to the wave's slot; no pre(), no arithmetic), which is what leaves the
+        // last pass its registers.  `after` runs once per half h = i0h >> 10 of the wave's block, on the wave's own slot:
+        //  (a) combine, in place.  Lane pairs on consecutive words (the addressing of lm_w14_linear_out): coefficients
+        //      i, i + 1 with i = wave << 11 | i0h | 2 lane + 128 k get slot = slot * (-P^-1) + u' (+ c0 for w == 0) -- the
+        //      multiply-add of the LDS form's storer below on the same operands, so d < 6q as there; u' and c0 arrive as
+        //      16-byte words, one contiguous kilobyte per load instruction;
+        //  (b) gather.  In the bit-reversed order of the NTT domain an automorphism X -> X^g permutes BLOCKS onto blocks:
+        //      position i evaluates at psi^e, e = 2 bitrev(i) + 1; the low b + 1 bits of g e mod 2N only depend on the
+        //      low b + 1 bits of e, i.e. on the TOP b bits of i -- so the top b bits of index[i] are a function (a
+        //      bijection) of the top b bits of i, for every b.  With b = 4 the unit is 1024 coefficients, and in the w14
+        //      layout half h of wave `wave` is exactly the aligned block sb = 2 wave + h (bits 13..11 = wave, bit 10 = h):
+        //      the output block jb = inv_index[sb * 1024] >> 10 gathers from this half and from nothing else,
+        //      acc_out[j] = acc_in[j] + slot[index[j] & 1023] for the 1024 j of block jb.
+        // Both block numbers are fetched before the transform, so that no dependent load sits in `after`.  (The half's
+        // index words requested before its combine instead of after it: measured, no difference -- EXPERIMENTS R10.)
+        const uint32_t wave = tid >> 6, lane = tid & 63;
+        const uint32_t jb0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)(inv_index[(2 * wave) << 10] >> 10));
+        const uint32_t jb1 = (uint32_t)__builtin_amdgcn_readfirstlane((int)(inv_index[(2 * wave + 1) << 10] >> 10));
+        lm_w14_runs st{sm};
+        auto after = [&](uint32_t i0h, uint32_t) {
+            const uint32_t pb = LM_PAD((wave << 10) | (2 * lane));
+            // (in chunks of CH pairs, fenced: the 16 words of a whole half's u' and c0 beside e[16..31], still live for
+            // h = 0, and the scheduler's hoisting of phase (b)'s loads over them spill 9 VGPRs)
+            constexpr uint32_t CH = 4;
+            const uint32_t i = (wave << 11) | i0h | (2 * lane);
+            const uint32_t jb = i0h ? jb1 : jb0, sbase = wave << 10;
 #pragma unroll
-            for (int k = 0; k < RUN; k++)
-                if (k < count) {
-                    // u' - lift * P^-1 = u' + lift * (-P^-1) (u' = u * P^-1 < q comes out of the gadget product, see
-                    // lumen_load_galois_key); the multiplication takes the unreduced lift and leaves [0, 3q) on top
-                    // of its addend: u' (+ c0 < 2q for w == 0).  NOTHING is reduced here -- d < 6q goes to LDS as it
-                    // is, and the one reduction of a rotation happens where the accumulator word is formed (below).
-                    const u64 add = w == 0 ? uv[k] + cv[k] : uv[k];
-                    sm[LM_PAD(i0 + k)] = lm_shoup3<true>(v[k], pi.w, pi.wp, qc.nq, add); // the slots this work item just consumed
+            for (uint32_t k0 = 0; k0 < 8; k0 += CH) {
+                ulonglong2 uv[CH], cv[CH];
+#pragma unroll
+                for (uint32_t k = 0; k < CH; k++) {
+                    uv[k] = *reinterpret_cast<const ulonglong2 *>(uq + i + 128 * (k0 + k));
+                    if (w == 0) cv[k] = *reinterpret_cast<const ulonglong2 *>(ain + i + 128 * (k0 + k));
                 }
-        }
-    } st{uq, ain, sm, qc, pi, w, {}, {}};
-    // acc_out[j] = acc_in[j] + d[index[j]]: the automorphism is applied as a gather out of LDS, so the
-    // accumulator itself streams through HBM linearly in 16-byte vectors.
-    // NO workgroup barrier (round 5).  In the bit-reversed order of the NTT domain an automorphism X -> X^g permutes
-    // BLOCKS onto blocks: position i evaluates at psi^e, e = 2 bitrev(i) + 1; the low b + 1 bits of g e mod 2N only
-    // depend on the low b + 1 bits of e, i.e. on the TOP b bits of i -- so the top b bits of index[i] are a function
-    // (a bijection) of the top b bits of i, for every b.  With b = log2(waves): every output block of N / waves
-    // coefficients gathers from exactly ONE source block, the one a single wave has just left in LDS.  Wave w
-    // therefore serves output block jb = inv_index[w * BLK] / BLK as soon as ITS OWN last pass is done (a wave's LDS
-    // operations execute in order) and goes home; the waves of a workgroup finish up to 12 us apart
-    // (profiles/r02_ubench_phases.txt), and the barrier this replaces made the early ones wait for the last.
-    // Every lane handles 8 pairs; only the block number jb is fetched early -- the pairs' index and accumulator words are
-    // requested in `after`, once the wave's last pass is done (ahead of it they cost 48 VGPRs the last pass needs).
-    constexpr uint32_t NW = lm_nthreads(LOGN) / 64, BLK = N / NW, IT = BLK / 128;
-    const uint32_t wave = tid >> 6, lane = tid & 63;
-    const uint32_t jb = NW > 1 ? (uint32_t)__builtin_amdgcn_readfirstlane((int)(inv_index[wave * BLK] / BLK)) : 0u;
-    auto after = [&](uint32_t, uint32_t) {
-        uint2 p[IT];
-        ulonglong2 x[IT];
 #pragma unroll
-        for (uint32_t k = 0; k < IT; k++) {
-            const uint32_t j = jb * BLK + 2 * lane + k * 128;
-            p[k] = *reinterpret_cast<const uint2 *>(index + j);
-            x[k] = *reinterpret_cast<const ulonglong2 *>(ain + j);
-        }
-        lm_wave_sync();
+                for (uint32_t k = 0; k < CH; k++) {
+                    // u' - lift * P^-1 = u' + lift * (-P^-1), nothing reduced: see the storer of the LDS form
+                    const uint32_t p = lm_w14_at(pb, 128 * (k0 + k));
+                    const u64 a0 = w == 0 ? uv[k].x + cv[k].x : uv[k].x, a1 = w == 0 ? uv[k].y + cv[k].y : uv[k].y;
+                    sm[p] = lm_shoup3<true>(sm[p], pi.w, pi.wp, qc.nq, a0);
+                    sm[p + 1] = lm_shoup3<true>(sm[p + 1], pi.w, pi.wp, qc.nq, a1);
+                }
+                LM_W14_FENCE();
+            }
+            lm_wave_sync();
+            uint2 p[8];
+            ulonglong2 x[8];
 #pragma unroll
-        for (uint32_t k = 0; k < IT; k++) {
-            const uint32_t j = jb * BLK + 2 * lane + k * 128;
-            // the accumulator is LAZY across the rotations of an InnerSum: words in [0, 2q).  acc (< 2q) + d (< 6q)
-            // < 8q comes back under 2q with two conditional subtractions -- the only ones of the kernel (the
-            // canonical form cost four per coefficient of c0 and three of c1: d to [0, q), + c0, + acc).  Its
-            // readers take [0, 2q): the inverse transform's loader (< 3q), the gadget product's own-digit operand
-            // (any u64), this kernel, and the rescale that ends matrixInnerSumEval (lm_rescale.hip).
-            ulonglong2 y;
-            y.x = lm_csub(lm_csub(x[k].x + sm[LM_PAD(p[k].x)], 4 * qc.q), 2 * qc.q);
-            y.y = lm_csub(lm_csub(x[k].y + sm[LM_PAD(p[k].y)], 4 * qc.q), 2 * qc.q);
-            *reinterpret_cast<ulonglong2 *>(aout + j) = y;
-        }
-    };
-    lm_ntt_forward<LOGN>(sm, tw_all + (size_t)t * N, qc, tid, ld, st, after);
+            for (uint32_t k = 0; k < 8; k++) {
+                const uint32_t j = (jb << 10) + 2 * lane + k * 128;
+                p[k] = *reinterpret_cast<const uint2 *>(index + j);
+                x[k] = *reinterpret_cast<const ulonglong2 *>(ain + j);
+            }
+#pragma unroll
+            for (uint32_t k = 0; k < 8; k++) {
+                const uint32_t j = (jb << 10) + 2 * lane + k * 128;
+                // lazy accumulator: acc (< 2q) + d (< 6q) < 8q back under 2q, as in the LDS form below
+                ulonglong2 y;
+                y.x = lm_csub(lm_csub(x[k].x + sm[LM_PAD(sbase | (p[k].x & 1023u))], 4 * qc.q), 2 * qc.q);
+                y.y = lm_csub(lm_csub(x[k].y + sm[LM_PAD(sbase | (p[k].y & 1023u))], 4 * qc.q), 2 * qc.q);
+                *reinterpret_cast<ulonglong2 *>(aout + j) = y;
+            }
+        };
+        lm_ntt_forward_w14(sm, tw_all + (size_t)t * N, qc, tid, ld, st, after);
+    } else {
+        // the store phase combines every finished run of 8 with the gadget product u (and c0 for w == 0): both
+        // are requested by pre() before the run's butterflies, not after them
+        constexpr int RUN = lm_fwd_run<LOGN>();
+        static_assert(RUN <= 8, "lm_load_run moves at most 8 coefficients");
+        struct storer_t {
+            const u64 *uq, *ain;
+            u64 *sm;
+            const lm_qc &qc;
+            tw_t pi;
+            uint32_t w;
+            u64 uv[RUN], cv[RUN];
+            __device__ __forceinline__ void pre(uint32_t i0) {
+                lm_load_run(uq, i0, uv, RUN);
+                if (w == 0) lm_load_run(ain, i0, cv, RUN);
+            }
+            __device__ __forceinline__ void operator()(uint32_t i0, const u64 *v, int count) {
+#pragma unroll
+                for (int k = 0; k < RUN; k++)
+                    if (k < count) {
+                        // u' - lift * P^-1 = u' + lift * (-P^-1) (u' = u * P^-1 < q comes out of the gadget product, see
+                        // lumen_load_galois_key); the multiplication takes the unreduced lift and leaves [0, 3q) on top
+                        // of its addend: u' (+ c0 < 2q for w == 0).  NOTHING is reduced here -- d < 6q goes to LDS as it
+                        // is, and the one reduction of a rotation happens where the accumulator word is formed (below).
+                        const u64 add = w == 0 ? uv[k] + cv[k] : uv[k];
+                        sm[LM_PAD(i0 + k)] = lm_shoup3<true>(v[k], pi.w, pi.wp, qc.nq, add); // the slots this work item just consumed
+                    }
+            }
+        } st{uq, ain, sm, qc, pi, w, {}, {}};
+        // acc_out[j] = acc_in[j] + d[index[j]]: the automorphism is applied as a gather out of LDS, so the
+        // accumulator itself streams through HBM linearly in 16-byte vectors.
+        // NO workgroup barrier (round 5).  In the bit-reversed order of the NTT domain an automorphism X -> X^g permutes
+        // BLOCKS onto blocks: position i evaluates at psi^e, e = 2 bitrev(i) + 1; the low b + 1 bits of g e mod 2N only
+        // depend on the low b + 1 bits of e, i.e. on the TOP b bits of i -- so the top b bits of index[i] are a function
+        // (a bijection) of the top b bits of i, for every b.  With b = log2(waves): every output block of N / waves
+        // coefficients gathers from exactly ONE source block, the one a single wave has just left in LDS.  Wave w
+        // therefore serves output block jb = inv_index[w * BLK] / BLK as soon as ITS OWN last pass is done (a wave's LDS
+        // operations execute in order) and goes home; the waves of a workgroup finish up to 12 us apart
+        // (profiles/r02_ubench_phases.txt), and the barrier this replaces made the early ones wait for the last.
+        // Every lane handles 8 pairs; only the block number jb is fetched early -- the pairs' index and accumulator words are
+        // requested in `after`, once the wave's last pass is done (ahead of it they cost 48 VGPRs the last pass needs).
+        constexpr uint32_t NW = lm_nthreads(LOGN) / 64, BLK = N / NW, IT = BLK / 128;
+        const uint32_t wave = tid >> 6, lane = tid & 63;
+        const uint32_t jb = NW > 1 ? (uint32_t)__builtin_amdgcn_readfirstlane((int)(inv_index[wave * BLK] / BLK)) : 0u;
+        auto after = [&](uint32_t, uint32_t) {
+            uint2 p[IT];
+            ulonglong2 x[IT];
+#pragma unroll
+            for (uint32_t k = 0; k < IT; k++) {
+                const uint32_t j = jb * BLK + 2 * lane + k * 128;
+                p[k] = *reinterpret_cast<const uint2 *>(index + j);
+                x[k] = *reinterpret_cast<const ulonglong2 *>(ain + j);
+            }
+            lm_wave_sync();
+#pragma unroll
+            for (uint32_t k = 0; k < IT; k++) {
+                const uint32_t j = jb * BLK + 2 * lane + k * 128;
+                // the accumulator is LAZY across the rotations of an InnerSum: words in [0, 2q).  acc (< 2q) + d (< 6q)
+                // < 8q comes back under 2q with two conditional subtractions -- the only ones of the kernel (the
+                // canonical form cost four per coefficient of c0 and three of c1: d to [0, q), + c0, + acc).  Its
+                // readers take [0, 2q): the inverse transform's loader (< 3q), the gadget product's own-digit operand
+                // (any u64), this kernel, and the rescale that ends matrixInnerSumEval (lm_rescale.hip).
+                ulonglong2 y;
+                y.x = lm_csub(lm_csub(x[k].x + sm[LM_PAD(p[k].x)], 4 * qc.q), 2 * qc.q);
+                y.y = lm_csub(lm_csub(x[k].y + sm[LM_PAD(p[k].y)], 4 * qc.q), 2 * qc.q);
+                *reinterpret_cast<ulonglong2 *>(aout + j) = y;
+            }
+        };
+        lm_ntt_forward<LOGN>(sm, tw_all + (size_t)t * N, qc, tid, ld, st, after);
+    }
 }
 
 // words of a lazy accumulator ([0, 2q), see k_moddown_ntt) to canonical form: for the callers that hand the
@@ -720,7 +791,8 @@ static int moddown_work_list(lumen_ctx *ctx, KsTables *tb, uint32_t B, const uin
 // lanes: 2048x1024 0.0850 / 0.0743, 4096x2048 0.193 / 0.163, 8192x4096 0.864 / 0.799, 16384x4096 1.86 / 1.92).
 // Up to 2^13 a limb needs at most half of a CU's LDS, so workgroups of two kernels are resident side by side and
 // one batch's memory-bound steps run under the other's transforms; at 2^14 a transform workgroup owns the whole
-// LDS and two transform kernels only evict each other's L2 sets.  LUMEN_KS_LANES = 1 / 2 overrides.  (With two
+// LDS and two transform kernels only evict each other's L2 sets (still so with the forward kernels of a rotation two
+// workgroups per CU and the inverse ones owning it: 1.677 / 1.718 s, round 10).  LUMEN_KS_LANES = 1 / 2 overrides.  (With two
 // lanes a kernel's HIP-event time includes its neighbour's: the roofline is read at N = 2^14, one lane.)
 static uint32_t ks_lanes(const lumen_ctx *ctx) {
     return ctx->tune.ks_lanes ? ctx->tune.ks_lanes : (ctx->logN <= 13 ? 2 : 1);
@@ -845,7 +917,7 @@ int rotate_accumulate(lumen_ctx *ctx, const u64 *acc, u64 *acc_out, uint32_t B, 
         if (int rc = moddown_work_list(ctx, tb, B, &work_down)) return rc;
         lm_prof_scope ps(ctx, "ks_moddown_ntt", (uint64_t)B * 2 * L);
         return lm_for_logn(ctx, ctx->logN, [&](auto n) {
-            return lm_launch(ctx, k_moddown_ntt<n>, lm_geom_lds(n), B * 2 * L, s.u, acc, acc_out, tb->d_bxp.get(), tb->d_pinv.get(),
+            return lm_launch(ctx, k_moddown_ntt<n>, lm_geom_fwd(n), B * 2 * L, s.u, acc, acc_out, tb->d_bxp.get(), tb->d_pinv.get(),
                              gk.d_index.get(), gk.d_inv_index.get(), work_down, B, L, K, ctx->mods, ctx->sh->tw_fwd.get());
         });
     }

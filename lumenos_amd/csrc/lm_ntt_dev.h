@@ -804,9 +804,9 @@ __device__ __forceinline__ void lm_ntt_forward_w14(u64 *sm, const tw_t *tw, cons
         }
     }
 }
-// Storer of lm_ntt_forward_w14 that parks the runs in the wave's slot, and the coalesced output of one half from
-// there (the counterparts of lm_lds_runs / lm_linear_out): f(j, v0, v1) gets coefficients j, j + 1 of the limb,
-// lanes on consecutive pairs, one contiguous kilobyte per store instruction.
+// Storer of lm_ntt_forward_w14 that parks the runs in the wave's slot (the extension kernel's and ModDown's), and the
+// coalesced output of one half from there (the counterparts of lm_lds_runs / lm_linear_out): f(j, v0, v1) gets
+// coefficients j, j + 1 of the limb, lanes on consecutive pairs, one contiguous kilobyte per store instruction.
 struct lm_w14_runs {
     u64 *sm;
     __device__ __forceinline__ void operator()(uint32_t i0, const u64 *v, int count) const {
@@ -827,7 +827,8 @@ __device__ __forceinline__ void lm_w14_linear_out(const u64 *sm, uint32_t tid, u
     }
 }
 
-// Geometry of the forward kernels that run lm_ntt_forward_w14 at N = 2^14 (k_limb_ntt<14, false>, k_modup_ntt<14>)
+// Geometry of the forward kernels that run lm_ntt_forward_w14 at N = 2^14 (k_limb_ntt<14, false>, k_modup_ntt<14>,
+// k_moddown_ntt<14>)
 // and lm_ntt_forward below it.  4 waves per SIMD caps the N = 2^14 kernels at 128 VGPRs, so that two workgroups of
 // 8 waves fit on a CU.
 __host__ __device__ constexpr lm_geom lm_geom_fwd(int logN) {

@@ -2,7 +2,7 @@
 # A/B builds of the HIP library: tools/build_variant.sh NAME [--patch tools/exp_X.patch ...] [-DFLAG ...] compiles every
 # translation unit with the extra flags into lumenos_amd/csrc/variants/NAME/ and links liblumenos_hip.so there (select it at run
 # time with LUMEN_HIP_LIB=<path>; the .so files are git-ignored but travel with gpurun).  --patch: the experiment patches under
-# tools/ (code that was measured and is NOT part of the product, e.g. exp_no_butterflies.patch, exp_moddown_r4.patch) are applied to
+# tools/ (code that was measured and is NOT part of the product, e.g. exp_no_butterflies.patch, exp_sub_batch.patch) are applied to
 # a COPY of the sources inside the variant's directory; the product tree is never touched.
 set -e
 name=$1; shift
