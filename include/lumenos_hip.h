@@ -344,6 +344,19 @@ int lumen_matrix_inner_sum(lumen_ctx *ctx, const lumen_set *matrix, const uint64
 int lumen_mul_plain(lumen_ctx *ctx, const lumen_set *in, const uint64_t *pt, lumen_set **out);
 int lumen_inner_sum(lumen_ctx *ctx, const lumen_set *in, uint32_t n, lumen_set **out);
 
+/* ---- the same at every level of the modulus chain.  The two entry points above serve the top level, where the path
+ * calls them, and refuse any other set; these take a set with 1 <= nl <= L limbs.  The hybrid key switch then runs on
+ * the ceil(nl / K) digits of that level over its nl Q limbs and the K limbs modulo P, with the Galois keys as they
+ * are loaded (lumen_load_galois_key[_ex]: the RNS gadget does not depend on the level).  Preconditions as above: n /
+ * rows a power of two <= N, 1 or 2 special primes, a full-width set. */
+/* Evaluator.InnerSum(ct, 1, n) at the level of `in`: 1 <= in->nl <= L.  With in->nl == L the result equals
+   lumen_inner_sum's word for word. */
+int lumen_inner_sum_at_level(lumen_ctx *ctx, const lumen_set *in, uint32_t n, lumen_set **out);
+/* matrixInnerSumEval (ligero.go:299-370) at the level of `matrix`: pt is [matrix->nl][N]; out has
+   min(matrix->nl, 2) limbs.  With matrix->nl == L: lumen_matrix_inner_sum's words. */
+int lumen_matrix_inner_sum_at_level(lumen_ctx *ctx, const lumen_set *matrix, const uint64_t *pt,
+                                    uint32_t rows, lumen_set **out);
+
 /* ---- fhe.RingSwitchServer (fhe/ring_switch.go:93-113): Evaluator.ApplyEvaluationKey of every
  * ciphertext of `in` into the ring of degree 2^log_n_small with the single modulus q_0, at level 0.
  * key: the rlwe.EvaluationKey of NewRingSwitchClient (ring_switch.go:43-56) as the client posts it

@@ -187,10 +187,13 @@ __global__ LM_GEOM_BOUNDS(lm_geom_lds(LOGN)) void k_intt_pack(const u64 *__restr
 
 // ---- step 2: digit extension + NTT.  One workgroup per (column b, digit d, target t).
 // coef: [B][L][N] coefficient-domain c1; acc: [B][2][L][N] (c1 NTT values for own limbs); ext: [L+K][B][beta][N] (ks_ext_at)
+// L is the level the rotation runs at (KsTables::nl) and a target t a POSITION in [0, L + K): the Q limbs of the level,
+// then the limbs modulo P, whose moduli and twiddle tables sit `pshift` = (the context's L) - L entries further on
+// (ks_mod_at; 0 at the top level).
 template <int LOGN>
 __global__ LM_GEOM_BOUNDS(lm_geom_fwd(LOGN)) void k_modup_ntt(const u64 *__restrict__ coef, const u64 *__restrict__ acc,
                                                     u64 *__restrict__ ext, const bx_t *__restrict__ bx,
-                                                    uint32_t B, uint32_t L, uint32_t K, uint32_t beta,
+                                                    uint32_t B, uint32_t L, uint32_t K, uint32_t beta, uint32_t pshift,
                                                     const uint32_t *__restrict__ work, lm_mods mods,
                                                     const tw_t *__restrict__ tw_all) {
     extern __shared__ __attribute__((aligned(16))) u64 sm[];
@@ -200,10 +203,11 @@ __global__ LM_GEOM_BOUNDS(lm_geom_fwd(LOGN)) void k_modup_ntt(const u64 *__restr
     // limbs reuse the NTT-domain c1), in the order of a host-built work list (modup_work_list): XCD-
     // aware, so that the targets of one digit run back to back on one XCD and share its L2.
     const uint32_t wk = work[blockIdx.x];
-    const uint32_t b = wk & 0xFFFF, d = (wk >> 16) & 0xFF, t = wk >> 24; // t: modulus index (Q limbs then P limbs)
+    const uint32_t b = wk & 0xFFFF, d = (wk >> 16) & 0xFF, t = wk >> 24; // t: target position (Q limbs then P limbs)
+    const uint32_t mt = ks_mod_at(t, L, pshift);                         // its modulus: wave-uniform, as t is
     const bx_t c = bx[d * LK + t];
     u64 *o = ext + ks_ext_at(b, d, t, B, beta) * N;
-    const lm_qc qc = lm_make_qc(mods.m[t]);
+    const lm_qc qc = lm_make_qc(mods.m[mt]);
     const u64 *s0 = coef + ((size_t)b * L + d * K) * N;
     const u64 *s1 = c.ns == 2 ? s0 + N : s0; // second limb of the digit
     auto ld = [&](uint32_t i) { return bx_apply(c, s0[i], s1[i], qc); };
@@ -220,16 +224,18 @@ __global__ LM_GEOM_BOUNDS(lm_geom_fwd(LOGN)) void k_modup_ntt(const u64 *__restr
     if constexpr (LOGN == 14) { // limb in registers, two workgroups per CU: the runs go through the wave's slot, half by half
         lm_w14_runs st{sm};
         auto after = [&](uint32_t i0, uint32_t) { lm_w14_linear_out(sm, tid, i0, out); };
-        lm_ntt_forward_w14(sm, tw_all + (size_t)t * N, qc, tid, ld, st, after);
+        lm_ntt_forward_w14(sm, tw_all + (size_t)mt * N, qc, tid, ld, st, after);
     } else {
         lm_lds_runs st{sm};
         auto after = [&](uint32_t, uint32_t) { lm_linear_out<LOGN>(sm, tid, out); };
-        lm_ntt_forward<LOGN>(sm, tw_all + (size_t)t * N, qc, tid, ld, st, after);
+        lm_ntt_forward<LOGN>(sm, tw_all + (size_t)mt * N, qc, tid, ld, st, after);
     }
 }
 
 // ---- step 3: gadget product.  u[b][w][t][i] = sum_d ext[b][d][t][i] * key[d][w][t][i]  (storage: ks_u_at, ks_ext_at, ks_key_at)
 // key in Montgomery form (k * 2^64 mod q): 128-bit accumulation, one Montgomery reduction.
+// L, beta: of the level the rotation runs at; the key is the stored one, [ctx L + K][key_beta][2] with the top level's
+// digit count, of which a lower level reads digits d < beta at the moduli of its positions (ks_mod_at).
 // COLS columns share one read of the key limb (the key is re-read B/COLS times per launch, out of
 // L2 / Infinity Cache); VEC consecutive coefficients per thread move as one VEC*8-byte access.
 #ifndef LM_MAC_COLS
@@ -323,8 +329,8 @@ __device__ __forceinline__ void mac2(mac_acc &p, mac_acc &q, u64 x, u64 k0, u64 
 
 __global__ __launch_bounds__(256) void k_ks_mac(const u64 *__restrict__ ext, const u64 *__restrict__ acc,
                                                 const u64 *__restrict__ key, u64 *__restrict__ u, uint32_t B,
-                                                uint32_t L, uint32_t K, uint32_t beta, uint32_t logN,
-                                                lm_mods mods) {
+                                                uint32_t L, uint32_t K, uint32_t beta, uint32_t pshift,
+                                                uint32_t key_beta, uint32_t logN, lm_mods mods) {
     typedef mac_vec<LM_MAC_VEC> vec;
     const uint32_t N = 1u << logN, LK = L + K;
     // 1-D grid, XCD-aware: workgroup k runs on XCD k % 8 (round-robin dispatch) and each XCD has its own
@@ -347,10 +353,11 @@ __global__ __launch_bounds__(256) void k_ks_mac(const u64 *__restrict__ ext, con
     // (walking the Q limbs first and the limbs modulo P last, so that what the next three kernels read is what was written
     // last -- with the extension kernel writing its P-limb targets first -- was measured: this kernel -2 %, the extension
     // kernel +1.2 %, the step +0.3 %: profiles/r06_exp_ks_p_last_interleaved.txt)
-    const uint32_t t = LK - 1 - slice / per_limb;                             // modulus index
+    const uint32_t t = LK - 1 - slice / per_limb;                             // target position
+    const uint32_t mt = ks_mod_at(t, L, pshift);                              // its modulus and key limb
     const uint32_t b0 = z * LM_MAC_COLS;
     if (i >= N) return;
-    const mod_t md = mods.m[t];
+    const mod_t md = mods.m[mt];
     const uint32_t own = t < L ? t / K : 0xFFFFFFFFu; // digit whose limbs include t: its "extension" is c1 itself
     mac_acc a0[LM_MAC_COLS][LM_MAC_VEC], a1[LM_MAC_COLS][LM_MAC_VEC];
 #pragma unroll
@@ -364,8 +371,8 @@ __global__ __launch_bounds__(256) void k_ks_mac(const u64 *__restrict__ ext, con
     };
     auto fetch = [&](uint32_t d) {
         digit_t g;
-        g.k0 = vec::load(key + ks_key_at(d, 0, t, beta) * N + i);
-        g.k1 = vec::load(key + ks_key_at(d, 1, t, beta) * N + i);
+        g.k0 = vec::load(key + ks_key_at(d, 0, mt, key_beta) * N + i);
+        g.k1 = vec::load(key + ks_key_at(d, 1, mt, key_beta) * N + i);
 #pragma unroll
         for (int c = 0; c < LM_MAC_COLS; c++) {
             const uint32_t bc = b0 + c < B ? b0 + c : B - 1;
@@ -634,28 +641,38 @@ uint64_t hat_inv(const uint64_t *src, uint32_t ns, uint32_t a) {
 
 } // namespace
 
-int get_tables(lumen_ctx *ctx, KsTables **out) {
+int get_tables(lumen_ctx *ctx, KsTables **out) { return get_tables_at(ctx, ctx->L, out); }
+
+// Level nl of the chain: digits d = limbs [dK, min(dK + K, nl)) -- for K = 2 and odd nl the last one is the single
+// limb nl - 1, which a higher level pairs with limb nl, so its constants are the level's own -- extended to the
+// positions [0, nl + K) of ks_mod_at.  The tables of the top level stay under the name (and with the contents) they
+// always had; a lower level's are "ks_tables:<nl>".
+int get_tables_at(lumen_ctx *ctx, uint32_t nl, KsTables **out) {
     LM_SHARED_LOCK(ctx);
-    auto it = ctx->ext.find("ks_tables");
+    LM_CHECK(ctx, nl >= 1 && nl <= ctx->L, "key switch at %u limbs: the chain has %u", nl, ctx->L);
+    const std::string name = nl == ctx->L ? std::string("ks_tables") : "ks_tables:" + std::to_string(nl);
+    auto it = ctx->ext.find(name);
     if (it != ctx->ext.end()) {
         *out = static_cast<KsTables *>(it->second.get());
         return 0;
     }
-    const uint32_t L = ctx->L, K = ctx->K, LK = L + K;
+    const uint32_t L = nl, K = ctx->K, LK = L + K, pshift = ctx->L - nl, ctxLK = ctx->L + K;
     LM_CHECK(ctx, K >= 1 && K <= 2, "key switching supports 1 or 2 special primes (have %u)", K);
     auto sp = std::make_shared<KsTables>();
     KsTables &tb = *sp;
+    tb.nl = L;
     tb.beta = (L + K - 1) / K;
     std::vector<bx_t> bx((size_t)tb.beta * LK);
     for (uint32_t d = 0; d < tb.beta; d++) {
         const uint32_t lo = d * K, hi = std::min(lo + K, L), ns = hi - lo;
         for (uint32_t t = 0; t < LK; t++) {
-            bx_t c = make_bx(ctx->mod + lo, ns, ctx->mod[t]);
+            bx_t c = make_bx(ctx->mod + lo, ns, ctx->mod[ks_mod_at(t, L, pshift)]);
             c.own = (t >= lo && t < hi) ? 1 : 0;
             bx[(size_t)d * LK + t] = c;
         }
     }
-    for (uint32_t i = 0; i < LM_MAX_LIMBS; i++) tb.yscale.t[i] = ctx->ninv[i < LK ? i : 0];
+    // (by modulus index, as the inverse transforms read it: the limbs modulo P at the context's L + a)
+    for (uint32_t i = 0; i < LM_MAX_LIMBS; i++) tb.yscale.t[i] = ctx->ninv[i < ctxLK ? i : 0];
     for (uint32_t d = 0; d < tb.beta; d++) {
         const uint32_t lo = d * K, hi = std::min(lo + K, L), ns = hi - lo;
         for (uint32_t a = 0; a < ns; a++) {
@@ -664,13 +681,13 @@ int get_tables(lumen_ctx *ctx, KsTables **out) {
         }
     }
     for (uint32_t a = 0; a < K; a++) {
-        const uint64_t m = ctx->mod[L + a];
-        tb.yscale.t[L + a] = h_tw(h_mulmod(ctx->ninv[L + a].w, hat_inv(ctx->mod + L, K, a), m), m);
+        const uint64_t m = ctx->mod[ctx->L + a];
+        tb.yscale.t[ctx->L + a] = h_tw(h_mulmod(ctx->ninv[ctx->L + a].w, hat_inv(ctx->mod + ctx->L, K, a), m), m);
     }
     std::vector<bx_t> bxp(L);
     std::vector<tw_t> pinv(L);
     for (uint32_t t = 0; t < L; t++) {
-        bxp[t] = make_bx(ctx->mod + L, K, ctx->mod[t]);
+        bxp[t] = make_bx(ctx->mod + ctx->L, K, ctx->mod[t]);
         const uint64_t q = ctx->mod[t];
         pinv[t] = h_tw(h_invmod(h_p_mod(ctx, q), q), q);
     }
@@ -682,7 +699,7 @@ int get_tables(lumen_ctx *ctx, KsTables **out) {
     if (tb.d_bx.upload(ctx, bx, "the key switch's extension constants") || tb.d_bxp.upload(ctx, bxp, "the key switch's lift constants") ||
         tb.d_pinv.upload(ctx, pinv, "the key switch's P^-1 table"))
         return 1;
-    ctx->ext["ks_tables"] = sp;
+    ctx->ext[name] = sp;
     *out = sp.get();
     return 0;
 }
@@ -740,8 +757,8 @@ static int interleave_work_lists(lumen_ctx *ctx, const std::vector<std::vector<u
 static int modup_work_list(lumen_ctx *ctx, KsTables *tb, uint32_t B, const uint32_t **out) {
     const uint32_t LM_MODUP_TGROUP = ctx->tune.modup_tgroup;
     LM_SHARED_LOCK(ctx); // the cached lists are shared with the context's clones
-    // packed as column (16 bits) | digit (8) | target modulus (8): refuse what does not fit
-    LM_CHECK(ctx, B >= 1 && B <= 65535 && tb->beta <= 255 && ctx->L + ctx->K <= 255,
+    // packed as column (16 bits) | digit (8) | target position (8): refuse what does not fit
+    LM_CHECK(ctx, B >= 1 && B <= 65535 && tb->beta <= 255 && tb->nl + ctx->K <= 255,
              "key-switch batch of %u columns (beta %u) does not fit the packed work list", B, tb->beta);
     const uint32_t cache_key = B | (LM_MODUP_TGROUP << 16);
     auto it = tb->d_work.find(cache_key);
@@ -749,7 +766,7 @@ static int modup_work_list(lumen_ctx *ctx, KsTables *tb, uint32_t B, const uint3
         *out = it->second.get();
         return 0;
     }
-    const uint32_t LK = ctx->L + ctx->K, beta = tb->beta;
+    const uint32_t LK = tb->nl + ctx->K, beta = tb->beta;
     std::vector<std::vector<uint8_t>> need(beta); // digit -> targets that need an extension
     for (uint16_t pr : tb->pairs) need[pr & 0xFF].push_back((uint8_t)(pr >> 8));
     std::vector<std::vector<uint32_t>> lists(8);
@@ -775,7 +792,7 @@ static int moddown_work_list(lumen_ctx *ctx, KsTables *tb, uint32_t B, const uin
         *out = it->second.get();
         return 0;
     }
-    const uint32_t L = ctx->L;
+    const uint32_t L = tb->nl;
     std::vector<std::vector<uint32_t>> lists(8);
     for (uint32_t x = 0; x < 8; x++)
         for (uint32_t t0 = 0; t0 < L; t0 += LM_MODDOWN_TGROUP)
@@ -845,17 +862,20 @@ struct LaneGuard {
     ~LaneGuard() { ctx->stream = saved; }
 };
 
-// grid of k_ks_mac for a batch of B columns
-static dim3 ks_mac_grid(const lumen_ctx *ctx, uint32_t B) {
-    return dim3(((ctx->N / LM_MAC_VEC + 255) / 256) * (ctx->L + ctx->K) * ((B + LM_MAC_COLS - 1) / LM_MAC_COLS));
+// grid of k_ks_mac for a batch of B columns at the level of L limbs
+static dim3 ks_mac_grid(const lumen_ctx *ctx, uint32_t B, uint32_t L) {
+    return dim3(((ctx->N / LM_MAC_VEC + 255) / 256) * (L + ctx->K) * ((B + LM_MAC_COLS - 1) / LM_MAC_COLS));
 }
 
 } // namespace
 
-// acc, acc_out: [B][2][L][N] at top level; acc_out = acc + Rot_galEl(acc) for every column
+// acc, acc_out: [B][2][L][N], L = the level of `tb`; acc_out = acc + Rot_galEl(acc) for every column
 int rotate_accumulate(lumen_ctx *ctx, const u64 *acc, u64 *acc_out, uint32_t B, const lm_galois_key &gk,
                       KsTables *tb, const KsScratch &s) {
-    const uint32_t N = ctx->N, L = ctx->L, K = ctx->K, beta = tb->beta;
+    const uint32_t N = ctx->N, L = tb->nl, K = ctx->K, beta = tb->beta;
+    // the limbs modulo P sit behind the context's L Q limbs: in the moduli, the twiddles and the stored key, which is
+    // [ctx L + K][key_beta][2] whatever the level (the RNS gadget does not depend on it)
+    const uint32_t pshift = ctx->L - L, key_beta = (ctx->L + K - 1) / K;
     // 1. c1 -> coefficient domain, scaled for the basis extension, and the (hi, lo) packing of the two-limb
     // digits: fused into the transform for the first nf digits, k_pack_v for the others
     const uint32_t nf = K == 2 ? ks_fused_digits(ctx, B, L) : 0;
@@ -886,15 +906,15 @@ int rotate_accumulate(lumen_ctx *ctx, const u64 *acc, u64 *acc_out, uint32_t B, 
         lm_prof_scope ps(ctx, "ks_modup_ntt", nb);
         if (int rc = lm_for_logn(ctx, ctx->logN, [&](auto n) {
                 return lm_launch(ctx, k_modup_ntt<n>, lm_geom_fwd(n), (uint32_t)nb, s.coef, acc, s.ext, tb->d_bx.get(), B, L, K, beta,
-                                 work, ctx->mods, ctx->sh->tw_fwd.get());
+                                 pshift, work, ctx->mods, ctx->sh->tw_fwd.get());
             }))
             return rc;
     }
     // 3. gadget product
     {
         lm_prof_scope ps(ctx, "ks_mac", (uint64_t)B);
-        hipLaunchKernelGGL(k_ks_mac, ks_mac_grid(ctx, B), dim3(256), 0, ctx->stream, s.ext, acc, gk.d_key.get(), s.u, B, L, K,
-                           beta, ctx->logN, ctx->mods);
+        hipLaunchKernelGGL(k_ks_mac, ks_mac_grid(ctx, B, L), dim3(256), 0, ctx->stream, s.ext, acc, gk.d_key.get(), s.u, B, L, K,
+                           beta, pshift, key_beta, ctx->logN, ctx->mods);
         LM_HIP(ctx, hipGetLastError());
     }
     // 4a. P limbs of u -> coefficient domain (in place)
@@ -906,7 +926,7 @@ int rotate_accumulate(lumen_ctx *ctx, const u64 *acc, u64 *acc_out, uint32_t B, 
             return rc;
         if (K == 2) {
             lm_prof_scope ps(ctx, "ks_pack_v", (uint64_t)B);
-            hipLaunchKernelGGL(k_pack_v, dim3(2048), dim3(256), 0, ctx->stream, up, pstride, B * 2, 1u, K, L, K,
+            hipLaunchKernelGGL(k_pack_v, dim3(2048), dim3(256), 0, ctx->stream, up, pstride, B * 2, 1u, K, ctx->L, K,
                                ctx->logN, ctx->mods);
             LM_HIP(ctx, hipGetLastError());
         }
@@ -942,7 +962,7 @@ int inner_sum_batch(lumen_ctx *ctx, u64 *acc, uint32_t B, uint32_t n, KsTables *
         if (int rc = rotate_accumulate(ctx, src, dst, B, *gk, tb, s)) return rc;
     }
     if (cnt & 1)
-        LM_HIP(ctx, hipMemcpyAsync(acc, s.acc2, (size_t)B * 2 * ctx->L * ctx->N * 8, hipMemcpyDeviceToDevice,
+        LM_HIP(ctx, hipMemcpyAsync(acc, s.acc2, (size_t)B * 2 * tb->nl * ctx->N * 8, hipMemcpyDeviceToDevice,
                                    ctx->stream));
     return 0;
 }
@@ -972,10 +992,10 @@ extern "C" int lumen_ks_mac_probe(lumen_ctx *ctx, uint32_t batch, const void *ex
     }
     const u64 *pe = ext ? (const u64 *)ext : s.ext;
     u64 *pu = u ? (u64 *)u : s.u;
-    const dim3 grid = ks_mac_grid(ctx, B);
+    const dim3 grid = ks_mac_grid(ctx, B, L);
     auto launch = [&] {
         hipLaunchKernelGGL(k_ks_mac, grid, dim3(256), 0, ctx->stream, pe, (const u64 *)acc, (const u64 *)key, pu, B, L, K,
-                           tb->beta, ctx->logN, ctx->mods);
+                           tb->beta, 0u, tb->beta, ctx->logN, ctx->mods);
     };
     for (int i = 0; i < 3; i++) launch();
     LM_HIP(ctx, hipGetLastError());
@@ -992,21 +1012,31 @@ extern "C" int lumen_ks_mac_probe(lumen_ctx *ctx, uint32_t batch, const void *ex
 
 static int check_inner_sum_level(lumen_ctx *ctx, const lumen_set *in, const char *what) {
     LM_FULL_WIDTH(ctx, in, what);
-    // the hybrid key switch is tabulated for the top level (digits of K limbs over all L limbs): the
-    // path only ever calls InnerSum there (fhe/ligero.go:319-325 -- MulNew and InnerSum precede the
-    // rescale).  A lower-level set is refused, never silently mis-evaluated.
+    // lumen_inner_sum and lumen_matrix_inner_sum serve the top level, where the path calls InnerSum
+    // (fhe/ligero.go:319-325 -- MulNew and InnerSum precede the rescale), and refuse anything else: their callers
+    // rely on that.  The *_at_level entry points take a set at any level of the chain.
     LM_CHECK(ctx, in->nl == ctx->L, "%s is implemented at the top level only (set has %u of %u limbs)", what,
              in->nl, ctx->L);
     return 0;
 }
 
-extern "C" int lumen_inner_sum(lumen_ctx *ctx, const lumen_set *in, uint32_t n, lumen_set **out) {
-    LM_CHECK(nullptr, ctx && in && out, "lumen_inner_sum: NULL argument");
-    LM_ENTER(ctx);
-    if (int rc = check_inner_sum_level(ctx, in, "InnerSum")) return rc;
+// A set at a level of the chain: full width, 1 <= nl <= L (a set of another context may have more).
+static int check_level_of_chain(lumen_ctx *ctx, const lumen_set *in, const char *what) {
+    LM_FULL_WIDTH(ctx, in, what);
+    LM_CHECK(ctx, in->nl >= 1 && in->nl <= ctx->L, "%s: set has %u limbs, the chain has %u", what, in->nl, ctx->L);
+    return 0;
+}
+
+namespace {
+
+// InnerSum(ct, 1, n) at the level of `in` (checked by the caller).  The scratch is the top level's whatever the level:
+// a first call low in the chain must not run the placement selection on small blocks that the first call at the top
+// would regrow.
+int inner_sum_at(lumen_ctx *ctx, const lumen_set *in, uint32_t n, lumen_set **out) {
     LM_CHECK(ctx, n && !(n & (n - 1)) && n <= ctx->N, "InnerSum length %u is not a power of two <= N", n);
-    KsTables *tb = nullptr;
-    if (int rc = get_tables(ctx, &tb)) return rc;
+    KsTables *top = nullptr, *tb = nullptr;
+    if (int rc = get_tables(ctx, &top)) return rc;
+    if (int rc = get_tables_at(ctx, in->nl, &tb)) return rc;
     lumen_set *o = nullptr;
     if (int rc = lumen_set_create(ctx, in->count, in->nl, &o)) return rc;
     lm_set_guard og(ctx, o);
@@ -1014,7 +1044,7 @@ extern "C" int lumen_inner_sum(lumen_ctx *ctx, const lumen_set *in, uint32_t n, 
         LM_HIP(ctx, hipMemcpyAsync(o->d, in->d, in->words * 8, hipMemcpyDeviceToDevice, ctx->stream));
     const uint32_t Bmax = std::min<uint32_t>(ks_batch(ctx), std::max(in->count, 1u));
     KsScratch s;
-    if (int rc = get_scratch(ctx, Bmax, tb, &s)) return rc;
+    if (int rc = get_scratch(ctx, Bmax, top, &s)) return rc;
     const size_t ctw = (size_t)2 * in->nl * ctx->N;
     for (uint32_t first = 0; first < in->count; first += Bmax) {
         const uint32_t B = std::min(Bmax, in->count - first);
@@ -1025,17 +1055,15 @@ extern "C" int lumen_inner_sum(lumen_ctx *ctx, const lumen_set *in, uint32_t n, 
     return 0;
 }
 
-extern "C" int lumen_matrix_inner_sum(lumen_ctx *ctx, const lumen_set *matrix, const uint64_t *pt,
-                                      uint32_t rows, lumen_set **out) {
-    LM_CHECK(nullptr, ctx && matrix && pt && out, "lumen_matrix_inner_sum: NULL argument");
-    LM_ENTER(ctx);
-    if (int rc = check_inner_sum_level(ctx, matrix, "matrixInnerSumEval")) return rc;
+// matrixInnerSumEval at the level of `matrix` (checked by the caller): nl limbs in, min(nl, 2) out
+int matrix_inner_sum_at(lumen_ctx *ctx, const lumen_set *matrix, const uint64_t *pt, uint32_t rows, lumen_set **out) {
     LM_CHECK(ctx, rows && !(rows & (rows - 1)) && rows <= ctx->N, "rows=%u is not a power of two <= N", rows);
-    KsTables *tb = nullptr;
-    if (int rc = get_tables(ctx, &tb)) return rc;
+    KsTables *top = nullptr, *tb = nullptr;
+    if (int rc = get_tables(ctx, &top)) return rc;
+    if (int rc = get_tables_at(ctx, matrix->nl, &tb)) return rc;
     u64 *ptT = nullptr;
     if (int rc = upload_ptT(ctx, pt, matrix->nl, &ptT)) return rc;
-    const uint32_t N = ctx->N, L = ctx->L;
+    const uint32_t N = ctx->N, L = matrix->nl;
     const uint32_t target = std::min<uint32_t>(2, L);
     lumen_set *o = nullptr;
     if (int rc = lumen_set_create(ctx, matrix->count, target, &o)) return rc;
@@ -1046,10 +1074,11 @@ extern "C" int lumen_matrix_inner_sum(lumen_ctx *ctx, const lumen_set *matrix, c
     const uint32_t group = std::min<uint32_t>(8 * Bmax, std::max(matrix->count, 1u));
     KsScratch s[2];
     const size_t ctw = (size_t)2 * L * N, octw = (size_t)2 * target * N;
+    const size_t group_bytes = (size_t)group * 2 * ctx->L * N * 8; // sized for the top level, as the key switch's scratch
     u64 *acc = nullptr; // the group's accumulators: placed together with the key switch's scratch (get_scratch)
-    if (get_scratch(ctx, Bmax, tb, &s[0], 0, &acc, (size_t)group * ctw * 8) || (ks_lanes(ctx) > 1 && get_scratch(ctx, Bmax, tb, &s[1], 1)))
+    if (get_scratch(ctx, Bmax, top, &s[0], 0, &acc, group_bytes) || (ks_lanes(ctx) > 1 && get_scratch(ctx, Bmax, top, &s[1], 1)))
         return 1;
-    u64 *work = (u64 *)lm_scratch(ctx, "rescale_work", (size_t)group * ctw * 8);
+    u64 *work = (u64 *)lm_scratch(ctx, "rescale_work", group_bytes);
     u64 *tbuf = (u64 *)lm_scratch(ctx, "rescale_t", (size_t)group * 2 * N * 8);
     if (!acc || !work || !tbuf) return 1;
     for (uint32_t g0 = 0; g0 < matrix->count; g0 += group) {
@@ -1084,4 +1113,36 @@ extern "C" int lumen_matrix_inner_sum(lumen_ctx *ctx, const lumen_set *matrix, c
     }
     *out = og.release();
     return 0;
+}
+
+} // namespace
+
+extern "C" int lumen_inner_sum(lumen_ctx *ctx, const lumen_set *in, uint32_t n, lumen_set **out) {
+    LM_CHECK(nullptr, ctx && in && out, "lumen_inner_sum: NULL argument");
+    LM_ENTER(ctx);
+    if (int rc = check_inner_sum_level(ctx, in, "InnerSum")) return rc;
+    return inner_sum_at(ctx, in, n, out);
+}
+
+extern "C" int lumen_inner_sum_at_level(lumen_ctx *ctx, const lumen_set *in, uint32_t n, lumen_set **out) {
+    LM_CHECK(nullptr, ctx && in && out, "lumen_inner_sum_at_level: NULL argument");
+    LM_ENTER(ctx);
+    if (int rc = check_level_of_chain(ctx, in, "InnerSum")) return rc;
+    return inner_sum_at(ctx, in, n, out);
+}
+
+extern "C" int lumen_matrix_inner_sum(lumen_ctx *ctx, const lumen_set *matrix, const uint64_t *pt,
+                                      uint32_t rows, lumen_set **out) {
+    LM_CHECK(nullptr, ctx && matrix && pt && out, "lumen_matrix_inner_sum: NULL argument");
+    LM_ENTER(ctx);
+    if (int rc = check_inner_sum_level(ctx, matrix, "matrixInnerSumEval")) return rc;
+    return matrix_inner_sum_at(ctx, matrix, pt, rows, out);
+}
+
+extern "C" int lumen_matrix_inner_sum_at_level(lumen_ctx *ctx, const lumen_set *matrix, const uint64_t *pt,
+                                               uint32_t rows, lumen_set **out) {
+    LM_CHECK(nullptr, ctx && matrix && pt && out, "lumen_matrix_inner_sum_at_level: NULL argument");
+    LM_ENTER(ctx);
+    if (int rc = check_level_of_chain(ctx, matrix, "matrixInnerSumEval")) return rc;
+    return matrix_inner_sum_at(ctx, matrix, pt, rows, out);
 }

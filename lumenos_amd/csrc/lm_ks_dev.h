@@ -47,6 +47,14 @@ __host__ __device__ __forceinline__ size_t ks_key_at(uint32_t d, uint32_t w, uin
     return ((size_t)t * beta + d) * 2 + w;
 }
 
+// The key switch at a level of nl <= L limbs works on nl + K POSITIONS: the level's Q limbs, then the K limbs modulo P.
+// The context's tables (moduli, twiddles, inverse-transform scales, key limbs) hold the limbs modulo P behind ALL L
+// Q limbs, so position t is modulus t for t < nl and t + (L - nl) behind them; pshift = L - nl is 0 at the top level,
+// where the map is the identity.
+__host__ __device__ __forceinline__ uint32_t ks_mod_at(uint32_t t, uint32_t nl, uint32_t pshift) {
+    return t < nl ? t : t + pshift;
+}
+
 // 64 x 64 -> 128-bit product as four 32x32+64 multiply-adds (the compiler's __int128 multiply goes
 // through v_mul_lo/hi_u32, twice as slow each)
 __device__ __forceinline__ void mul128(u64 a, u64 b, u64 &lo, u64 &hi) {

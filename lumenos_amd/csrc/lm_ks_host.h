@@ -3,28 +3,34 @@
 #pragma once
 #include "lm_ks_dev.h"
 
-// per-context constants of the key switch and its cached work lists (lm_keyswitch.hip)
+// per-context constants of the key switch at one level of the modulus chain (nl of the context's L limbs; below, L
+// stands for nl) and its cached work lists (lm_keyswitch.hip)
 struct KsTables {
-    lm_dev<bx_t> d_bx;   // [beta][L+K]
+    lm_dev<bx_t> d_bx;   // [beta][L+K], targets by position (ks_mod_at)
     lm_dev<bx_t> d_bxp;  // [L]  (P -> q_t)
     lm_dev<tw_t> d_pinv; // [L]  P^-1 mod q_t
-    uint32_t beta = 0;
+    uint32_t nl = 0;     // the level: Q limbs of the ciphertexts it switches
+    uint32_t beta = 0;   // ceil(nl / K) digits
     lm_ninv_t yscale; // per modulus: N^-1 * (M/m)^-1 mod m of the source group the modulus sits in
     std::vector<uint16_t> pairs; // (digit | target << 8) of every extension the key switch needs, target-major
     std::map<uint32_t, lm_dev<uint32_t>> d_work; // per batch size: the workgroup order of the extension kernel
     std::map<uint32_t, lm_dev<uint32_t>> d_work_down; // ... and of the ModDown kernel
 };
-int get_tables(lumen_ctx *ctx, KsTables **out);
+int get_tables(lumen_ctx *ctx, KsTables **out); // the top level's
+// the tables of the level with nl limbs, 1 <= nl <= L, built at its first use and cached (nl == L: get_tables)
+int get_tables_at(lumen_ctx *ctx, uint32_t nl, KsTables **out);
 
 // the scratch buffers of one lane
 struct KsScratch {
     u64 *coef, *ext, *u, *acc2;
 };
 
-// acc, acc_out: [B][2][L][N] at top level; acc_out = acc + Rot_galEl(acc) for every column (lm_keyswitch.hip)
+// acc, acc_out: [B][2][nl][N] at the level of `tb`; acc_out = acc + Rot_galEl(acc) for every column (lm_keyswitch.hip).
+// s: scratch of a batch of B columns at the TOP level, of which a lower level uses a prefix of every block.
 int rotate_accumulate(lumen_ctx *ctx, const u64 *acc, u64 *acc_out, uint32_t B, const lm_galois_key &gk,
                       KsTables *tb, const KsScratch &s);
-// the scratch of a batch of B columns on `lane`, placed by measurement at a context's first key switch (lm_ks_scratch.hip)
+// the scratch of a batch of B columns on `lane`, placed by measurement at a context's first key switch (lm_ks_scratch.hip).
+// tb: always the TOP level's tables, whatever level asks -- the blocks are sized, and the candidates timed, once.
 int get_scratch(lumen_ctx *ctx, uint32_t B, KsTables *tb, KsScratch *s, int lane = 0, u64 **group_acc = nullptr,
                 size_t group_acc_bytes = 0);
 

@@ -113,6 +113,8 @@ SYMBOLS = {
     "lumen_matrix_inner_sum": (C.c_int, [_vp, _vp, _u64p, C.c_uint32, _vpp]),
     "lumen_mul_plain": (C.c_int, [_vp, _vp, _u64p, _vpp]),
     "lumen_inner_sum": (C.c_int, [_vp, _vp, C.c_uint32, _vpp]),
+    "lumen_inner_sum_at_level": (C.c_int, [_vp, _vp, C.c_uint32, _vpp]),
+    "lumen_matrix_inner_sum_at_level": (C.c_int, [_vp, _vp, _u64p, C.c_uint32, _vpp]),
     "lumen_gather": (C.c_int, [_vp, _vp, _u32p, C.c_uint32, _vpp]),
     "lumen_plain_inner_products": (C.c_int, [_vp, _vp, _u64p, _u64p]),
     "lumen_poly_eval_columns": (C.c_int, [_vp, _u64p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint64, _u64p]),
@@ -618,6 +620,20 @@ class Context:
         pt = np.ascontiguousarray(pt, dtype=np.uint64)
         h = C.c_void_p()
         self._ck(self.lib.lumen_matrix_inner_sum(self.h, matrix.h, _p64(pt), rows, C.byref(h)))
+        return DeviceSet(self, h)
+
+    def inner_sum_at_level(self, s, n):
+        """InnerSum(ct, 1, n) at the level of `s` (1 <= limbs <= L); at the top level, inner_sum's words"""
+        h = C.c_void_p()
+        self._ck(self.lib.lumen_inner_sum_at_level(self.h, s.h, n, C.byref(h)))
+        return DeviceSet(self, h)
+
+    def matrix_inner_sum_at_level(self, matrix, pt, rows):
+        """matrixInnerSumEval at the level of `matrix`: pt is [limbs][N], the result has min(limbs, 2) limbs"""
+        pt = np.ascontiguousarray(pt, dtype=np.uint64)
+        assert pt.shape == (matrix.nl, self.N), pt.shape
+        h = C.c_void_p()
+        self._ck(self.lib.lumen_matrix_inner_sum_at_level(self.h, matrix.h, _p64(pt), rows, C.byref(h)))
         return DeviceSet(self, h)
 
     def plain_inner_products(self, s, vec):

@@ -827,8 +827,16 @@ std::pair<LigeroProver, std::vector<uint8_t>> LigeroCommitter::Commit(const Shar
 
 Ciphertexts matrixInnerSumEval(const Ciphertexts &matrix, const Plaintext &plaintext, int rows, ServerBFV &backend) {
     lumen_set *out = nullptr;
-    backend.check(lumen_matrix_inner_sum(backend.Context(), matrix.Handle(), plaintext.Value.data(), (uint32_t)rows, &out),
-                  "lumen_matrix_inner_sum");
+    // Evaluator.InnerSum works at ct.Level(): a matrix below the top level (one rescaled first) takes the entry point
+    // that does, with the plaintext at the matrix's level; a top-level one the call it always took
+    if (matrix.Level() == backend.GetParameters().MaxLevel()) {
+        backend.check(lumen_matrix_inner_sum(backend.Context(), matrix.Handle(), plaintext.Value.data(), (uint32_t)rows, &out),
+                      "lumen_matrix_inner_sum");
+    } else {
+        if (plaintext.Level != matrix.Level()) throw std::invalid_argument("matrixInnerSumEval: plaintext and matrix at different levels");
+        backend.check(lumen_matrix_inner_sum_at_level(backend.Context(), matrix.Handle(), plaintext.Value.data(), (uint32_t)rows, &out),
+                      "lumen_matrix_inner_sum_at_level");
+    }
     // MulNew: Scale_ct * Scale_pt (Encoder.Encode leaves 1); InnerSum keeps it; the Rescale loop to level 1
     MetaData md = matrix.Meta;
     md.Scale = RescaledScale(backend.GetParameters(), md.Scale, matrix.Level(), 1);

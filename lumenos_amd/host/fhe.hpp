@@ -543,7 +543,8 @@ std::vector<std::vector<core::Element>> EncodeRows(const std::vector<std::vector
 Proof LigeroProveReference(const LigeroCommitter &c, const std::vector<uint64_t> &matrix, core::Element point,
                            core::PrimeField &field, core::Transcript &transcript, int device = 0);
 
-// matrixInnerSumEval (ligero.go:299-370), without the ring switch
+// matrixInnerSumEval (ligero.go:299-370), without the ring switch, at the level of `matrix` (the plaintext at the same
+// level: the first Level + 1 limbs of an Encode)
 Ciphertexts matrixInnerSumEval(const Ciphertexts &matrix, const Plaintext &plaintext, int rows, ServerBFV &backend);
 std::vector<int> sampleQueryIndices(core::Transcript &transcript, int queries, int extCols); // ligero.go:638-644
 
