@@ -357,6 +357,32 @@ int lumen_inner_sum_at_level(lumen_ctx *ctx, const lumen_set *in, uint32_t n, lu
 int lumen_matrix_inner_sum_at_level(lumen_ctx *ctx, const lumen_set *matrix, const uint64_t *pt,
                                     uint32_t rows, lumen_set **out);
 
+/* ---- ciphertext x ciphertext: Evaluator.MulRelinNew(ct, ct) -- ServerBFV.MulNew / Mul take an rlwe.Operand, which may
+ * be a ciphertext (fhe/bfv.go:34-42) -- with the relinearisation key the client generates and posts in the /keys body
+ * (cmd/client/main.go:74-81; lumen_keygen_relin).  For two degree-1 ciphertexts a = (a0, a1), b = (b0, b1) of the same
+ * nl limbs, 1 <= nl <= L, for every Q limb i < nl, coefficient-wise mod q_i:
+ *     d0 = T a0 b0      d1 = T (a0 b1 + a1 b0)      d2 = T a1 b1
+ *     (k0, k1) = the hybrid key switch (gadget product + ModDown at level nl) of d2 under the relinearisation key
+ *     out = (d0 + k0, d1 + k1)                                               (canonical residues)
+ * T mod q_i is the factor lumen_mul_plain gives its plaintext: ciphertexts encrypt m * T^-1 + e, and the product of two
+ * keeps that form with one T.  The result's scale is scale_a * scale_b mod T: the caller tracks it.  The noise of a
+ * product is about T^2 * N * B (B: the operands' noise), so it only decrypts where that stays under Q_level / 2
+ * (T = 0x3ee0001: from two limbs; the 57-bit T of cmd/server: three).
+ * lumen_load_relin_key: evk in lumen_keygen_relin's layout, [digit(beta)][b|a][limb(L+K)][N], NTT domain, standard form or,
+ * with LUMEN_KEY_MONTGOMERY, Lattigo's; converted on the device like a Galois key and shared read-only with clones;
+ * loading again replaces it.  It is no Galois key: lumen_load_galois_key(1, .) and it do not see each other.
+ * lumen_mul_relin: b has as many ciphertexts as a (pairwise) or one (every ciphertext of a times it); a == b (squares)
+ * is allowed.  out: a new set of a's count and level.  lumen_mul_counter grows by a's count.
+ * lumen_mul_tensor: the degree-2 triple (d0, d1, d2) before relinearisation, for parity tests, like lumen_mul_plain: host,
+ * [count][3][nl][N]; needs no key; leaves lumen_mul_counter as it is.
+ * Where lumen_mul_relin is a context's first key switch, the key-switch scratch is placed by timed rotations under the
+ * relinearisation key, as a first InnerSum places it under a Galois key: the order of the calls does not matter.
+ * Refused with a message: NULL arguments; unknown flags; no special primes (K = 0) or more than two; no relinearisation
+ * key loaded; operands of different levels; a count mismatch; a lane-sharded set; a limb count outside [1, L]. */
+int lumen_load_relin_key(lumen_ctx *ctx, const uint64_t *evk, uint32_t flags);
+int lumen_mul_relin(lumen_ctx *ctx, const lumen_set *a, const lumen_set *b, lumen_set **out);
+int lumen_mul_tensor(lumen_ctx *ctx, const lumen_set *a, const lumen_set *b, uint64_t *host_out /* [count][3][nl][N] */);
+
 /* ---- fhe.RingSwitchServer (fhe/ring_switch.go:93-113): Evaluator.ApplyEvaluationKey of every
  * ciphertext of `in` into the ring of degree 2^log_n_small with the single modulus q_0, at level 0.
  * key: the rlwe.EvaluationKey of NewRingSwitchClient (ring_switch.go:43-56) as the client posts it

@@ -27,7 +27,7 @@
 //
 // This file is the rotation: its six kernels, the per-context tables and work lists, rotate_accumulate and the InnerSum
 // entry points.  The other subjects of the key switch live beside it: where the scratch buffers sit in HBM in
-// lm_ks_scratch.hip (mechanism) and lm_placement.h (policy), Galois-key loading in lm_ks_key.hip, the ciphertext x
+// lm_ks_scratch.hip (mechanism) and lm_placement.h (policy), Galois- and relinearisation-key loading in lm_ks_key.hip, the ciphertext x
 // plaintext product (step 0, MulNew) in lm_mulplain.hip, the stream layouts and mul128 in lm_ks_dev.h, and what these
 // units share on the host in lm_ks_host.h.
 #include <cstdlib>
@@ -35,9 +35,30 @@
 
 #include "lm_ks_host.h"
 
+// ---- what the relinearisation (lm_mulrelin.hip) shares with InnerSum, declared in lm_ks_host.h
 // columns processed together (scratch ~ 172 limbs per column): 64 by default, LUMEN_KS_BATCH at context
 // creation (lm_tuning)
-static uint32_t ks_batch(const lumen_ctx *ctx) { return ctx->tune.ks_batch; }
+uint32_t ks_batch(const lumen_ctx *ctx) { return ctx->tune.ks_batch; }
+
+// Lanes: independent column batches alternate between the context's two streams (LaneGuard, lm_ks_host.h) so that the
+// HBM-bound steps of one batch (gadget product, correction-bit pass) overlap the VALU-bound transforms of the other.
+// Two lanes up to N = 2^13, one at N = 2^14 (round 4, measured on one MI355X, seconds per prover step with 1 / 2
+// lanes: 2048x1024 0.0850 / 0.0743, 4096x2048 0.193 / 0.163, 8192x4096 0.864 / 0.799, 16384x4096 1.86 / 1.92).
+// Up to 2^13 a limb needs at most half of a CU's LDS, so workgroups of two kernels are resident side by side and
+// one batch's memory-bound steps run under the other's transforms; at 2^14 a transform workgroup owns the whole
+// LDS and two transform kernels only evict each other's L2 sets (still so with the forward kernels of a rotation two
+// workgroups per CU and the inverse ones owning it: 1.677 / 1.718 s, round 10).  LUMEN_KS_LANES = 1 / 2 overrides.  (With two
+// lanes a kernel's HIP-event time includes its neighbour's: the roofline is read at N = 2^14, one lane.)
+uint32_t ks_lanes(const lumen_ctx *ctx) {
+    return ctx->tune.ks_lanes ? ctx->tune.ks_lanes : (ctx->logN <= 13 ? 2 : 1);
+}
+
+// A set at a level of the chain: full width, 1 <= nl <= L (a set of another context may have more).
+int check_level_of_chain(lumen_ctx *ctx, const lumen_set *in, const char *what) {
+    LM_FULL_WIDTH(ctx, in, what);
+    LM_CHECK(ctx, in->nl >= 1 && in->nl <= ctx->L, "%s: set has %u limbs, the chain has %u", what, in->nl, ctx->L);
+    return 0;
+}
 
 // v = uint64(float64(y0)/float64(m0) + float64(y1)/float64(m1))  ([LATTIGO-RECALL] reconstructRNS).
 // The double expression is within 2^-49 of S = A / M, A = y0*m1 + y1*m0, M = m0*m1, and S < 2: unless
@@ -801,19 +822,6 @@ static int moddown_work_list(lumen_ctx *ctx, KsTables *tb, uint32_t B, const uin
     return interleave_work_lists(ctx, lists, (size_t)2 * B * L, "ModDown", tb->d_work_down, cache_key, out);
 }
 
-// Enqueue on the context's second stream for the lifetime of the guard.  Independent column
-// batches alternate between the two streams so that the HBM-bound steps of one batch (gadget
-// product, correction-bit pass) overlap the VALU-bound transforms of the other.
-// Two lanes up to N = 2^13, one at N = 2^14 (round 4, measured on one MI355X, seconds per prover step with 1 / 2
-// lanes: 2048x1024 0.0850 / 0.0743, 4096x2048 0.193 / 0.163, 8192x4096 0.864 / 0.799, 16384x4096 1.86 / 1.92).
-// Up to 2^13 a limb needs at most half of a CU's LDS, so workgroups of two kernels are resident side by side and
-// one batch's memory-bound steps run under the other's transforms; at 2^14 a transform workgroup owns the whole
-// LDS and two transform kernels only evict each other's L2 sets (still so with the forward kernels of a rotation two
-// workgroups per CU and the inverse ones owning it: 1.677 / 1.718 s, round 10).  LUMEN_KS_LANES = 1 / 2 overrides.  (With two
-// lanes a kernel's HIP-event time includes its neighbour's: the roofline is read at N = 2^14, one lane.)
-static uint32_t ks_lanes(const lumen_ctx *ctx) {
-    return ctx->tune.ks_lanes ? ctx->tune.ks_lanes : (ctx->logN <= 13 ? 2 : 1);
-}
 // digits whose packing is fused into the c1 inverse transform (k_intt_pack): the largest count whose
 // B * nf two-transform workgroups are whole rounds of the device's workgroup slots (CUs x resident
 // workgroups per CU: 256 x 1 at N = 2^14, so 4 of 6 digits at B = 64), so that no slot waits for a
@@ -852,15 +860,6 @@ static uint32_t ks_fused_digits(lumen_ctx *ctx, uint32_t B, uint32_t L) {
         if (((uint64_t)B * nf) % slots == 0) return nf;
     return 0;
 }
-
-struct LaneGuard {
-    lumen_ctx *ctx;
-    hipStream_t saved;
-    LaneGuard(lumen_ctx *c, int lane) : ctx(c), saved(c->stream) {
-        if (lane) ctx->stream = ctx->stream2;
-    }
-    ~LaneGuard() { ctx->stream = saved; }
-};
 
 // grid of k_ks_mac for a batch of B columns at the level of L limbs
 static dim3 ks_mac_grid(const lumen_ctx *ctx, uint32_t B, uint32_t L) {
@@ -1017,13 +1016,6 @@ static int check_inner_sum_level(lumen_ctx *ctx, const lumen_set *in, const char
     // rely on that.  The *_at_level entry points take a set at any level of the chain.
     LM_CHECK(ctx, in->nl == ctx->L, "%s is implemented at the top level only (set has %u of %u limbs)", what,
              in->nl, ctx->L);
-    return 0;
-}
-
-// A set at a level of the chain: full width, 1 <= nl <= L (a set of another context may have more).
-static int check_level_of_chain(lumen_ctx *ctx, const lumen_set *in, const char *what) {
-    LM_FULL_WIDTH(ctx, in, what);
-    LM_CHECK(ctx, in->nl >= 1 && in->nl <= ctx->L, "%s: set has %u limbs, the chain has %u", what, in->nl, ctx->L);
     return 0;
 }
 

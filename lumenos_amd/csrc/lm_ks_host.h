@@ -1,5 +1,6 @@
 // Host-side declarations shared by the units of the Galois key switch: the rotation (lm_keyswitch.hip), the placement of
-// its scratch buffers (lm_ks_scratch.hip) and the ciphertext x plaintext product that precedes it (lm_mulplain.hip).
+// its scratch buffers (lm_ks_scratch.hip), the ciphertext x plaintext product that precedes it (lm_mulplain.hip) and the
+// ciphertext x ciphertext product that ends in one (lm_mulrelin.hip).
 #pragma once
 #include "lm_ks_dev.h"
 
@@ -38,3 +39,20 @@ int get_scratch(lumen_ctx *ctx, uint32_t B, KsTables *tb, KsScratch *s, int lane
 int upload_ptT(lumen_ctx *ctx, const uint64_t *pt, uint32_t nl, u64 **out);
 int launch_mul_plain(lumen_ctx *ctx, const u64 *ct, u64 *out, const u64 *ptT, size_t words, uint32_t nl,
                      uint32_t ncts);
+
+// the relinearisation key as a switching key with identity gather tables (lm_ks_key.hip); empty before lumen_load_relin_key
+std::shared_ptr<lm_galois_key> lm_relin_key(lumen_ctx *ctx);
+// a set at a level of the chain: full width, 1 <= nl <= L (lm_keyswitch.hip)
+int check_level_of_chain(lumen_ctx *ctx, const lumen_set *in, const char *what);
+// the batching of a key switch, shared by InnerSum and the relinearisation (lm_keyswitch.hip)
+uint32_t ks_batch(const lumen_ctx *ctx);
+uint32_t ks_lanes(const lumen_ctx *ctx);
+// enqueue on the context's second stream for the lifetime of the guard
+struct LaneGuard {
+    lumen_ctx *ctx;
+    hipStream_t saved;
+    LaneGuard(lumen_ctx *c, int lane) : ctx(c), saved(c->stream) {
+        if (lane) ctx->stream = ctx->stream2;
+    }
+    ~LaneGuard() { ctx->stream = saved; }
+};

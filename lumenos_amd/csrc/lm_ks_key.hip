@@ -1,6 +1,7 @@
-// Galois keys of the hybrid key switch (lm_keyswitch.hip): which elements an InnerSum needs, and a key's way to the
-// device -- range check, Montgomery form with P^-1 folded in, the gadget product's limb-major layout (ks_key_at) -- with
-// the automorphism's gather tables.
+// The switching keys of the hybrid key switch (lm_keyswitch.hip), Galois keys and the relinearisation key: which
+// elements an InnerSum needs, and a key's way to the device -- range check, Montgomery form with P^-1 folded in, the
+// gadget product's limb-major layout (ks_key_at) -- with the gather tables of its automorphism (the identity for the
+// relinearisation key).  key_to_device and key_install are shared by the two loaders.
 #include "lm_ks_dev.h"
 
 extern "C" uint32_t lumen_inner_sum_galois_elements(const lumen_ctx *ctx, uint32_t n, uint64_t *gal_els) {
@@ -36,14 +37,11 @@ __global__ __launch_bounds__(256) void k_key_prepare(const u64 *__restrict__ src
 
 int lm_h2d(lumen_ctx *ctx, void *dev, const void *host, size_t bytes);
 
-extern "C" int lumen_load_galois_key_ex(lumen_ctx *ctx, uint64_t gal_el, const uint64_t *evk, uint32_t flags) {
-    LM_CHECK(nullptr, ctx && evk, "lumen_load_galois_key: NULL argument");
-    LM_ENTER(ctx);
+namespace {
+
+// host words [beta][b|a][L+K][N] -> the key in the gadget product's form, on the device; returns with the stream idle
+int key_to_device(lumen_ctx *ctx, const uint64_t *evk, uint32_t flags, const char *what, lm_dev<u64> &d_new) {
     const uint32_t N = ctx->N, L = ctx->L, K = ctx->K, LK = L + K;
-    LM_CHECK(ctx, K >= 1, "parameters have no special primes: key switching unavailable");
-    LM_CHECK(ctx, (gal_el & 1) && gal_el < 2ull * N, "Galois element %llu is not an odd residue mod 2N",
-             (unsigned long long)gal_el);
-    LM_CHECK(ctx, !(flags & ~(uint32_t)LUMEN_KEY_MONTGOMERY), "lumen_load_galois_key_ex: unknown flags 0x%x", flags);
     const uint32_t beta = (L + K - 1) / K;
     const size_t words = (size_t)beta * 2 * LK * N;
     // To Montgomery form (one-off per key), on the device since round 4: the host loop of 128-bit divisions cost
@@ -59,12 +57,12 @@ extern "C" int lumen_load_galois_key_ex(lumen_ctx *ctx, uint64_t gal_el, const u
         if (t < L) r = h_mulmod(r, h_invmod(h_p_mod(ctx, q), q), q);
         fac.t[t] = h_tw(r, q);
     }
-    lm_dev<u64> raw, d_new; // the staging copy of the host words, and the key in the gadget product's form
+    lm_dev<u64> raw; // the staging copy of the host words
     uint32_t *bad = (uint32_t *)lm_scratch(ctx, "key_bad", 4);
-    if (!bad || raw.alloc(ctx, words, "the staging copy of a Galois key")) return 1;
+    if (!bad || raw.alloc(ctx, words, ("the staging copy of " + std::string(what)).c_str())) return 1;
     LM_HIP(ctx, hipMemsetAsync(bad, 0xFF, 4, ctx->stream));
     if (int rc = lm_h2d(ctx, raw.get(), evk, words * 8)) return rc; // returns when evk may be reused
-    if (int rc = d_new.alloc(ctx, words, "a Galois key")) return rc;
+    if (int rc = d_new.alloc(ctx, words, what)) return rc;
     hipLaunchKernelGGL(k_key_prepare, dim3(2048), dim3(256), 0, ctx->stream, raw.get(), d_new.get(), ctx->logN, LK, words, ctx->mods, fac,
                        bad);
     uint32_t first_bad = 0;
@@ -74,6 +72,44 @@ extern "C" int lumen_load_galois_key_ex(lumen_ctx *ctx, uint64_t gal_el, const u
     if (e != hipSuccess) return lm_fail(ctx, "key conversion failed: %s", hipGetErrorString(e));
     if (first_bad != 0xFFFFFFFFu)
         return lm_fail(ctx, "key residue out of range (digit %u limb %u)", first_bad / (2 * LK), first_bad % LK);
+    return 0; // (the staging copy goes with `raw`: the stream is idle)
+}
+
+// gk takes the new words and, once, the gather tables of its automorphism.  Call under LM_SHARED_LOCK.
+int key_install(lumen_ctx *ctx, lm_galois_key &gk, lm_dev<u64> &d_new, const std::vector<uint32_t> &index, const char *what) {
+    if (gk.d_key) {
+        // a key loaded again.  The table is shared with every clone (group ranks on one GPU, CopyNew): its device
+        // pointer must stay what a clone may have read a moment ago, so the new words are copied INTO the old
+        // block (same size: it only depends on the parameters).  A clone computing at this very moment sees old or
+        // new words -- the documented "do not reconfigure under a running clone" -- but never freed memory.
+        lm_sync_all(ctx);
+        hipError_t ce = hipMemcpyAsync(gk.d_key.get(), d_new.get(), d_new.count() * 8, hipMemcpyDeviceToDevice, ctx->stream);
+        if (ce == hipSuccess) ce = hipStreamSynchronize(ctx->stream);
+        d_new.reset();
+        LM_CHECK(ctx, ce == hipSuccess, "replacing %s failed: %s", what, hipGetErrorString(ce));
+    } else {
+        gk.d_key = std::move(d_new);
+    }
+    // the gather tables depend on the element alone: a key loaded again keeps them
+    std::vector<uint32_t> inv_index(index.size());
+    for (uint32_t i = 0; i < index.size(); i++) inv_index[index[i]] = i;
+    if (!gk.d_inv_index && gk.d_inv_index.upload(ctx, inv_index, "an automorphism's index table")) return 1;
+    if (!gk.d_index && gk.d_index.upload(ctx, index, "an automorphism's index table")) return 1;
+    return 0;
+}
+
+} // namespace
+
+extern "C" int lumen_load_galois_key_ex(lumen_ctx *ctx, uint64_t gal_el, const uint64_t *evk, uint32_t flags) {
+    LM_CHECK(nullptr, ctx && evk, "lumen_load_galois_key: NULL argument");
+    LM_ENTER(ctx);
+    const uint32_t N = ctx->N;
+    LM_CHECK(ctx, ctx->K >= 1, "parameters have no special primes: key switching unavailable");
+    LM_CHECK(ctx, (gal_el & 1) && gal_el < 2ull * N, "Galois element %llu is not an odd residue mod 2N",
+             (unsigned long long)gal_el);
+    LM_CHECK(ctx, !(flags & ~(uint32_t)LUMEN_KEY_MONTGOMERY), "lumen_load_galois_key_ex: unknown flags 0x%x", flags);
+    lm_dev<u64> d_new;
+    if (int rc = key_to_device(ctx, evk, flags, "a Galois key", d_new)) return rc;
     std::vector<uint32_t> index(N);
     const uint64_t mask = 2ull * N - 1;
     for (uint32_t i = 0; i < N; i++) { // [LATTIGO-RECALL] ring.AutomorphismNTTIndex
@@ -81,29 +117,38 @@ extern "C" int lumen_load_galois_key_ex(lumen_ctx *ctx, uint64_t gal_el, const u
         const uint64_t t2 = ((gal_el * t1 & mask) - 1) >> 1;
         index[i] = h_bitrev((uint32_t)t2, (int)ctx->logN);
     }
-    raw.reset(); // the staging copy has served (the stream is idle)
     LM_SHARED_LOCK(ctx);
-    lm_galois_key &gk = ctx->gkeys[gal_el];
-    if (gk.d_key) {
-        // a key loaded again.  The table is shared with every clone (group ranks on one GPU, CopyNew): its device
-        // pointer must stay what a clone may have read a moment ago, so the new words are copied INTO the old
-        // block (same size: it only depends on the parameters).  A clone computing at this very moment sees old or
-        // new words -- the documented "do not reconfigure under a running clone" -- but never freed memory.
-        lm_sync_all(ctx);
-        hipError_t ce = hipMemcpyAsync(gk.d_key.get(), d_new.get(), words * 8, hipMemcpyDeviceToDevice, ctx->stream);
-        if (ce == hipSuccess) ce = hipStreamSynchronize(ctx->stream);
-        d_new.reset();
-        LM_CHECK(ctx, ce == hipSuccess, "replacing Galois key %llu failed: %s", (unsigned long long)gal_el, hipGetErrorString(ce));
-    } else {
-        gk.d_key = std::move(d_new);
-    }
-    // the gather tables depend on the element alone: a key loaded again keeps them
-    std::vector<uint32_t> inv_index(N);
-    for (uint32_t i = 0; i < N; i++) inv_index[index[i]] = i;
-    if (!gk.d_inv_index && gk.d_inv_index.upload(ctx, inv_index, "an automorphism's index table")) return 1;
-    if (!gk.d_index && gk.d_index.upload(ctx, index, "an automorphism's index table")) return 1;
-    return 0;
+    const std::string what = "Galois key " + std::to_string(gal_el);
+    return key_install(ctx, ctx->gkeys[gal_el], d_new, index, what.c_str());
 }
+
+// The relinearisation key (s^2 -> s; lumen_keygen_relin, kgen.GenRelinearizationKeyNew): a switching key like a Galois
+// key's, in the same form, whose "automorphism" is the identity -- lm_mulrelin.hip runs it through rotate_accumulate.
+// It lives beside the Galois keys, not among them: element 1 of ctx->gkeys stays whatever lumen_load_galois_key(1, .)
+// made of it.
+static const char *const RELIN_KEY = "relin_key";
+
+extern "C" int lumen_load_relin_key(lumen_ctx *ctx, const uint64_t *evk, uint32_t flags) {
+    LM_CHECK(nullptr, ctx && evk, "lumen_load_relin_key: NULL argument");
+    LM_ENTER(ctx);
+    LM_CHECK(ctx, ctx->K >= 1, "parameters have no special primes: key switching unavailable");
+    LM_CHECK(ctx, !(flags & ~(uint32_t)LUMEN_KEY_MONTGOMERY), "lumen_load_relin_key: unknown flags 0x%x", flags);
+    lm_dev<u64> d_new;
+    if (int rc = key_to_device(ctx, evk, flags, "the relinearisation key", d_new)) return rc;
+    std::vector<uint32_t> index(ctx->N);
+    for (uint32_t i = 0; i < ctx->N; i++) index[i] = i;
+    LM_SHARED_LOCK(ctx);
+    auto gk = lm_ext_get<lm_galois_key>(ctx, RELIN_KEY);
+    if (!gk) {
+        gk = std::make_shared<lm_galois_key>();
+        if (int rc = key_install(ctx, *gk, d_new, index, "the relinearisation key")) return rc;
+        lm_ext_put(ctx, RELIN_KEY, gk); // only a complete key becomes visible
+        return 0;
+    }
+    return key_install(ctx, *gk, d_new, index, "the relinearisation key");
+}
+
+std::shared_ptr<lm_galois_key> lm_relin_key(lumen_ctx *ctx) { return lm_ext_get<lm_galois_key>(ctx, RELIN_KEY); }
 
 extern "C" int lumen_load_galois_key(lumen_ctx *ctx, uint64_t gal_el, const uint64_t *evk) {
     return lumen_load_galois_key_ex(ctx, gal_el, evk, 0);

@@ -58,11 +58,15 @@ int get_scratch(lumen_ctx *ctx, uint32_t B, KsTables *tb, KsScratch *s, int lane
         bufs.push_back({bytes[c], there ? it->second.get() : nullptr, c == 4 ? 4u : Kc}); // (the group accumulator is the big one: four draws)
         have = have && there;
     }
+    // the key the timed rotations run under: any Galois key, or the relinearisation key where a context's first key
+    // switch is a ciphertext x ciphertext product (its placement then serves the InnerSums that follow as well)
     const lm_galois_key *gk = nullptr;
     {
         LM_SHARED_LOCK(ctx);
         if (!ctx->gkeys.empty()) gk = &ctx->gkeys.begin()->second;
     }
+    const std::shared_ptr<lm_galois_key> rlk = gk ? nullptr : lm_relin_key(ctx); // kept alive for the selection
+    if (!gk) gk = rlk.get();
     auto plain = [&]() -> int {
         bool ok = true;
         for (int c = 0; c < NB; c++) ok = (*slot[c] = (u64 *)lm_scratch(ctx, names[lane][c], bytes[c])) != nullptr && ok;

@@ -115,6 +115,9 @@ SYMBOLS = {
     "lumen_inner_sum": (C.c_int, [_vp, _vp, C.c_uint32, _vpp]),
     "lumen_inner_sum_at_level": (C.c_int, [_vp, _vp, C.c_uint32, _vpp]),
     "lumen_matrix_inner_sum_at_level": (C.c_int, [_vp, _vp, _u64p, C.c_uint32, _vpp]),
+    "lumen_load_relin_key": (C.c_int, [_vp, _u64p, C.c_uint32]),
+    "lumen_mul_relin": (C.c_int, [_vp, _vp, _vp, _vpp]),
+    "lumen_mul_tensor": (C.c_int, [_vp, _vp, _vp, _u64p]),
     "lumen_gather": (C.c_int, [_vp, _vp, _u32p, C.c_uint32, _vpp]),
     "lumen_plain_inner_products": (C.c_int, [_vp, _vp, _u64p, _u64p]),
     "lumen_poly_eval_columns": (C.c_int, [_vp, _u64p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint64, _u64p]),
@@ -635,6 +638,25 @@ class Context:
         h = C.c_void_p()
         self._ck(self.lib.lumen_matrix_inner_sum_at_level(self.h, matrix.h, _p64(pt), rows, C.byref(h)))
         return DeviceSet(self, h)
+
+    def load_relin_key(self, evk, montgomery=False):
+        """evk: [beta][2][L+K][N], what keygen_relin returns (rlwe.RelinearizationKey, s^2 -> s)"""
+        evk = np.ascontiguousarray(evk, dtype=np.uint64)
+        assert evk.shape == self.evk_shape(), evk.shape
+        self._ck(self.lib.lumen_load_relin_key(self.h, _p64(evk), LUMEN_KEY_MONTGOMERY if montgomery else 0))
+
+    def mul_relin(self, a, b):
+        """MulRelinNew(a, b) for two sets of one level: pairwise, or every ciphertext of `a` times the one of `b`;
+        the result's scale is the product of the operands' scales mod T"""
+        h = C.c_void_p()
+        self._ck(self.lib.lumen_mul_relin(self.h, a.h, b.h, C.byref(h)))
+        return DeviceSet(self, h)
+
+    def mul_tensor(self, a, b):
+        """the degree-2 ciphertexts (d0, d1, d2) of a x b before relinearisation: [count][3][limbs][N]"""
+        out = np.zeros((a.count, 3, a.nl, self.N), dtype=np.uint64)
+        self._ck(self.lib.lumen_mul_tensor(self.h, a.h, b.h, _p64(out)))
+        return out
 
     def plain_inner_products(self, s, vec):
         """out[j] = sum_i s[j][i] * vec[i] mod q_0 for a one-limb set (the plain prover, ligero.go:886-918)"""

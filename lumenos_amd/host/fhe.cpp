@@ -504,8 +504,9 @@ std::map<uint64_t, std::vector<uint64_t>> KeyGenerator::GenGaloisKeysNew(const s
     return out;
 }
 
-KeySet KeyGenerator::GenKeySetNew(int rows, uint32_t flags) {
+KeySet KeyGenerator::GenKeySetNew(int rows, uint32_t flags, bool withRelin) {
     KeySet ks;
+    if (withRelin) ks.Rlk = GenRelinearizationKeyNew(flags);
     ks.Flags = flags;
     ks.Pk = GenKeyPairNew();
     ks.GaloisElements = client_.GetParameters().GaloisElementsForInnerSum(1, rows);
@@ -543,7 +544,24 @@ std::unique_ptr<ServerBFV> ServerBFV::NewFromKeySet(core::PrimeField *plaintextF
     for (size_t i = 0; i < keys.GaloisKeys.size(); i++)
         s->check(lumen_load_galois_key_ex(s->Context(), keys.GaloisElements[i], keys.GaloisKeys[i].data(), keys.Flags),
                  "lumen_load_galois_key_ex");
+    if (!keys.Rlk.empty()) s->SetRelinearizationKey(keys.Rlk, keys.Flags);
     return s;
+}
+
+void ServerBFV::SetRelinearizationKey(const std::vector<uint64_t> &rlk, uint32_t flags) {
+    if (rlk.size() != evk_words(params_) || rlk.empty())
+        throw std::invalid_argument("SetRelinearizationKey: the key is not [beta][b|a][L+K][N]");
+    check(lumen_load_relin_key(Context(), rlk.data(), flags), "lumen_load_relin_key");
+}
+
+Ciphertexts ServerBFV::MulRelinNew(const Ciphertexts &a, const Ciphertexts &b) {
+    if (!a.Handle() || !b.Handle()) throw std::invalid_argument("MulRelinNew: an operand holds no ciphertexts");
+    lumen_set *set = nullptr;
+    check(lumen_mul_relin(Context(), a.Handle(), b.Handle(), &set), "lumen_mul_relin");
+    MetaData md = a.Meta;
+    const uint64_t T = params_.T;
+    md.Scale = MulMod(a.Scale() % T, b.Scale() % T, T); // bgv: Scale_a * Scale_b
+    return Ciphertexts(Context(), set, md);
 }
 
 Plaintext ServerBFV::Encode(const std::vector<uint64_t> &values) const {

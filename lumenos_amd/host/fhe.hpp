@@ -79,11 +79,13 @@ struct Proof;
 // What a client posts to /keys (cmd/client/main.go:74-81, 124-131) before it is marshalled: the public key and one
 // Galois key per entry of params.GaloisElementsForInnerSum(1, rows), in that order (rotations by N/2 and by N both
 // map to the element 1, so an element may appear twice, with the same key).  Flags: 0 = standard-form words,
-// LUMEN_KEY_MONTGOMERY = Lattigo's storage form (x * 2^64 mod q_i), what rlwe.GaloisKey holds.
+// LUMEN_KEY_MONTGOMERY = Lattigo's storage form (x * 2^64 mod q_i), what rlwe.GaloisKey holds.  Rlk: the
+// relinearisation key of the same body (kgen.GenRelinearizationKeyNew, main.go:78), empty when the set carries none.
 struct KeySet {
     std::vector<uint64_t> Pk;                      // [2][L+K][N]
     std::vector<uint64_t> GaloisElements;          // GaloisElementsForInnerSum(1, rows)
     std::vector<std::vector<uint64_t>> GaloisKeys; // [beta][b|a][L+K][N] each
+    std::vector<uint64_t> Rlk;                     // [beta][b|a][L+K][N], or empty
     uint32_t Flags = 0;
 };
 
@@ -192,7 +194,8 @@ class ServerBFV {
     ServerBFV(core::PrimeField *plaintextField, const Parameters &params, std::vector<uint64_t> pk,
               const std::map<uint64_t, std::vector<uint64_t>> &evk, int device = 0);
     // the same from a posted key set (cmd/server/main.go:100-140 after unmarshalling): keys.GaloisElements must be
-    // params.GaloisElementsForInnerSum(1, rows); the keys go to the device in keys.Flags' form (lumen_load_galois_key_ex)
+    // params.GaloisElementsForInnerSum(1, rows); the keys go to the device in keys.Flags' form (lumen_load_galois_key_ex),
+    // the relinearisation key too when the set carries one (SetRelinearizationKey)
     static std::unique_ptr<ServerBFV> NewFromKeySet(core::PrimeField *plaintextField, const Parameters &params, int rows,
                                                     const KeySet &keys, int device = 0);
     ~ServerBFV();
@@ -200,6 +203,14 @@ class ServerBFV {
     const Parameters &GetParameters() const { return params_; }
     int MulCounter() const; // bfv.go:44-46
     lumen_ctx *Context() const { return ctx_.get(); }
+    // the rlwe.RelinearizationKey of the evaluation key set (bfv.go:23-28: NewMemEvaluationKeySet(rlk, galoisKeys...)),
+    // [beta][b|a][L+K][N] as KeyGenerator::GenRelinearizationKeyNew(flags) returns it; CopyNews share it; setting it again
+    // replaces it (lumen_load_relin_key)
+    void SetRelinearizationKey(const std::vector<uint64_t> &rlk, uint32_t flags = 0);
+    // Evaluator.MulRelinNew over an rlwe.Operand that is a ciphertext (bfv.go:34-42): a[i] * b[i], or a[i] * b[0] when b
+    // holds one ciphertext; a and b of one level (a and b may be the same object: squares).  The result's Scale() is
+    // a.Scale() * b.Scale() mod T; MulCounter() grows by a.Len().  Needs the relinearisation key.
+    Ciphertexts MulRelinNew(const Ciphertexts &a, const Ciphertexts &b);
     // Encoder.Encode(values, pt) at MaxLevel ([LATTIGO-RECALL] m * T^-1 form, slot index matrix)
     Plaintext Encode(const std::vector<uint64_t> &values) const;
     // Encryptor.EncryptNew(pt) under pk, host layout [2][L][N]
@@ -321,7 +332,8 @@ class KeyGenerator {
     // GenGaloisKeysNew(galEls, sk): one launch of each kernel and one transfer for all the (distinct) elements
     std::map<uint64_t, std::vector<uint64_t>> GenGaloisKeysNew(const std::vector<uint64_t> &galEls, uint32_t flags = 0);
     // pk + the Galois keys of params.GaloisElementsForInnerSum(1, rows) in that order: the body of POST /keys
-    KeySet GenKeySetNew(int rows, uint32_t flags = 0);
+    // withRelin: the set carries the relinearisation key as well, as the reference's /keys body does
+    KeySet GenKeySetNew(int rows, uint32_t flags = 0, bool withRelin = false);
 
   private:
     ClientBFV &client_;
