@@ -82,6 +82,9 @@ struct lm_tuning {
     uint32_t ks_batch = 64;      // LUMEN_KS_BATCH: columns per key-switch batch
     uint32_t ks_lanes = 0;       // LUMEN_KS_LANES: 1 / 2 streams for the column batches of a key switch; 0 = by ring degree
     int32_t ks_fused_digits = -1; // LUMEN_KS_FUSED_DIGITS: digits packed inside k_intt_pack (-1: derive)
+    // LUMEN_KS_CLOSE_FUSED: 1 = the last rotation of matrixInnerSumEval's InnerSum ends in k_ks_close (lm_ks_close.hip), the
+    // rescale's inverse transform with the last ModDown folded in; 0 = k_moddown_ntt and the whole rescale.  Same residues.
+    uint32_t ks_close_fused = 1;
     uint32_t debug = 0;          // LUMEN_DEBUG
     // LUMEN_MODUP_TGROUP / LUMEN_MODDOWN_TGROUP: target limbs one XCD walks back to back in the work lists of the
     // two transform kernels of a key switch (lm_keyswitch.hip); 1 .. 31
@@ -326,6 +329,11 @@ mod_t lm_make_mod(uint64_t q);
 void lm_build_tw(uint64_t q, uint64_t psi, uint32_t logN, std::vector<tw_t> &fwd, std::vector<tw_t> &inv);
 int lm_rescale_polys(lumen_ctx *ctx, const u64 *src, uint32_t nl, u64 *dst, uint32_t target,
                      uint32_t npoly, u64 *work, u64 *tbuf);
+// The same from coefficient-form limbs: coef, [npoly][nl][N] in [0, 4q), is what the rescale's inverse transform leaves in
+// its work buffer (the closing rotation of matrixInnerSumEval writes it itself, lm_ks_close.hip).  lm_rescale_coef_ready:
+// 0 when the modulus chain has the tables this form needs, 2 when it has not (then lm_rescale_polys is the only way).
+int lm_rescale_coef_ready(lumen_ctx *ctx);
+int lm_rescale_polys_from_coef(lumen_ctx *ctx, const u64 *coef, uint32_t nl, u64 *dst, uint32_t target, uint32_t npoly);
 lm_modmap lm_map_q(uint32_t nl);
 // the K limbs modulo P of a [K]-periodic buffer: moduli L .. L+K-1
 lm_modmap lm_map_p(const lumen_ctx *ctx);

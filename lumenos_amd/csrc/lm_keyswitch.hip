@@ -27,7 +27,8 @@
 //
 // This file is the rotation: its six kernels, the per-context tables and work lists, rotate_accumulate and the InnerSum
 // entry points.  The other subjects of the key switch live beside it: where the scratch buffers sit in HBM in
-// lm_ks_scratch.hip (mechanism) and lm_placement.h (policy), Galois- and relinearisation-key loading in lm_ks_key.hip, the ciphertext x
+// lm_ks_scratch.hip (mechanism) and lm_placement.h (policy), the end of the last rotation before a rescale -- the rescale's inverse
+// transform with that rotation's ModDown folded in -- in lm_ks_close.hip, Galois- and relinearisation-key loading in lm_ks_key.hip, the ciphertext x
 // plaintext product (step 0, MulNew) in lm_mulplain.hip, the stream layouts and mul128 in lm_ks_dev.h, and what these
 // units share on the host in lm_ks_host.h.
 #include <cstdlib>
@@ -868,9 +869,11 @@ static dim3 ks_mac_grid(const lumen_ctx *ctx, uint32_t B, uint32_t L) {
 
 } // namespace
 
-// acc, acc_out: [B][2][L][N], L = the level of `tb`; acc_out = acc + Rot_galEl(acc) for every column
-int rotate_accumulate(lumen_ctx *ctx, const u64 *acc, u64 *acc_out, uint32_t B, const lm_galois_key &gk,
-                      KsTables *tb, const KsScratch &s) {
+// Steps 1-4a of a rotation of acc, [B][2][L][N], L = the level of `tb`: the gadget product u in s.u, its limbs modulo P
+// in the coefficient domain and packed.  What follows is the seam between the two ways a rotation ends: ModDown
+// (rotate_accumulate) or, for the last rotation before a rescale, the closing inverse transform (rotate_close).
+static int rotate_front(lumen_ctx *ctx, const u64 *acc, uint32_t B, const lm_galois_key &gk, KsTables *tb,
+                        const KsScratch &s) {
     const uint32_t N = ctx->N, L = tb->nl, K = ctx->K, beta = tb->beta;
     // the limbs modulo P sit behind the context's L Q limbs: in the moduli, the twiddles and the stored key, which is
     // [ctx L + K][key_beta][2] whatever the level (the RNS gadget does not depend on it)
@@ -930,6 +933,14 @@ int rotate_accumulate(lumen_ctx *ctx, const u64 *acc, u64 *acc_out, uint32_t B, 
             LM_HIP(ctx, hipGetLastError());
         }
     }
+    return 0;
+}
+
+// acc, acc_out: [B][2][L][N], L = the level of `tb`; acc_out = acc + Rot_galEl(acc) for every column
+int rotate_accumulate(lumen_ctx *ctx, const u64 *acc, u64 *acc_out, uint32_t B, const lm_galois_key &gk,
+                      KsTables *tb, const KsScratch &s) {
+    if (int rc = rotate_front(ctx, acc, B, gk, tb, s)) return rc;
+    const uint32_t L = tb->nl, K = ctx->K;
     // 4b + 5. lift to Q, NTT, combine, automorphism, accumulate
     {
         const uint32_t *work_down = nullptr;
@@ -944,9 +955,22 @@ int rotate_accumulate(lumen_ctx *ctx, const u64 *acc, u64 *acc_out, uint32_t B, 
 
 namespace {
 
-int inner_sum_batch(lumen_ctx *ctx, u64 *acc, uint32_t B, uint32_t n, KsTables *tb, const KsScratch &s) {
+// coef_out = the coefficient form of acc + Rot_galEl(acc), [B][2][L][N]: the last rotation before a rescale (lm_ks_close.hip)
+int rotate_close(lumen_ctx *ctx, const u64 *acc, u64 *coef_out, uint32_t B, const lm_galois_key &gk, uint64_t gal_el,
+                 KsTables *tb, const KsScratch &s) {
+    if (int rc = rotate_front(ctx, acc, B, gk, tb, s)) return rc;
+    const uint32_t *work_down = nullptr;
+    if (int rc = moddown_work_list(ctx, tb, B, &work_down)) return rc;
+    return ks_close_launch(ctx, acc, coef_out, B, gk, gal_el, tb, s, work_down);
+}
+
+// InnerSum(., 1, n) of the B columns of acc, in place.  With close_out (a rescale follows and n > 1) the last rotation
+// leaves its result there in coefficient form instead, and acc holds nothing the caller may use.
+int inner_sum_batch(lumen_ctx *ctx, u64 *acc, uint32_t B, uint32_t n, KsTables *tb, const KsScratch &s,
+                    u64 *close_out = nullptr) {
     uint64_t gal[64];
     const uint32_t cnt = lumen_inner_sum_galois_elements(ctx, n, gal);
+    LM_CHECK(ctx, !close_out || cnt, "InnerSum(%u) has no rotation to close", n);
     for (uint32_t r = 0; r < cnt; r++) {
         const lm_galois_key *gk; // (an entry of the map never moves or goes, and a key loaded again keeps its blocks)
         {
@@ -958,6 +982,8 @@ int inner_sum_batch(lumen_ctx *ctx, u64 *acc, uint32_t B, uint32_t n, KsTables *
         }
         // ping-pong: the automorphism reads two positions of the old accumulator per output
         u64 *src = (r & 1) ? s.acc2 : acc, *dst = (r & 1) ? acc : s.acc2;
+        if (close_out && r + 1 == cnt) // whichever of the two blocks the rotations so far have left the accumulator in
+            return rotate_close(ctx, src, close_out, B, *gk, gal[r], tb, s);
         if (int rc = rotate_accumulate(ctx, src, dst, B, *gk, tb, s)) return rc;
     }
     if (cnt & 1)
@@ -1073,6 +1099,15 @@ int matrix_inner_sum_at(lumen_ctx *ctx, const lumen_set *matrix, const uint64_t 
     u64 *work = (u64 *)lm_scratch(ctx, "rescale_work", group_bytes);
     u64 *tbuf = (u64 *)lm_scratch(ctx, "rescale_t", (size_t)group * 2 * N * 8);
     if (!acc || !work || !tbuf) return 1;
+    // The last rotation of a batch writes the rescale's coefficient-form input itself, at the batch's place in `work`
+    // (LUMEN_KS_CLOSE_FUSED, lm_ks_close.hip): when a rescale follows, there is a rotation (rows > 1) and the chain has
+    // the coefficient form's tables.
+    bool close = false;
+    if (L > target && rows > 1 && ctx->tune.ks_close_fused) {
+        const int rc = lm_rescale_coef_ready(ctx);
+        if (rc && rc != 2) return rc;
+        close = rc == 0;
+    }
     for (uint32_t g0 = 0; g0 < matrix->count; g0 += group) {
         const uint32_t gn = std::min(group, matrix->count - g0);
         // fork: the second lane starts after everything already enqueued on the main stream
@@ -1087,7 +1122,8 @@ int matrix_inner_sum_at(lumen_ctx *ctx, const lumen_set *matrix, const uint64_t 
             LaneGuard guard(ctx, (int)lane);
             if (int rc = launch_mul_plain(ctx, matrix->d + (size_t)(g0 + first) * ctw, a, ptT, (size_t)B * ctw, L, B)) // ligero.go:319
                 return rc;
-            if (int rc = inner_sum_batch(ctx, a, B, rows, tb, s[lane])) return rc; // ligero.go:325
+            if (int rc = inner_sum_batch(ctx, a, B, rows, tb, s[lane], close ? work + (size_t)first * ctw : nullptr)) // ligero.go:325
+                return rc;
         }
         // join: the rescale of the group needs both lanes
         if (ks_lanes(ctx) > 1) {
@@ -1095,7 +1131,9 @@ int matrix_inner_sum_at(lumen_ctx *ctx, const lumen_set *matrix, const uint64_t 
             LM_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));
         }
         // ligero.go:331-333
-        if (L > target) {
+        if (close) { // the inverse transforms are done
+            if (int rc = lm_rescale_polys_from_coef(ctx, work, L, o->d + (size_t)g0 * octw, target, gn * 2)) return rc;
+        } else if (L > target) {
             if (int rc = lm_rescale_polys(ctx, acc, L, o->d + (size_t)g0 * octw, target, gn * 2, work, tbuf)) return rc;
         } else {
             if (int rc = acc_canon(ctx, acc, (size_t)gn * ctw, L)) return rc; // no rescale to absorb the lazy range

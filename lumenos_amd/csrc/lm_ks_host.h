@@ -30,6 +30,11 @@ struct KsScratch {
 // s: scratch of a batch of B columns at the TOP level, of which a lower level uses a prefix of every block.
 int rotate_accumulate(lumen_ctx *ctx, const u64 *acc, u64 *acc_out, uint32_t B, const lm_galois_key &gk,
                       KsTables *tb, const KsScratch &s);
+// the last rotation of an InnerSum that a rescale follows, after its steps 1-4a (lm_ks_close.hip): out, [B][2][nl][N], gets
+// the COEFFICIENT form of acc + Rot_galEl(acc), canonical -- what the rescale's inverse transform would have made of it.
+// work_down: ModDown's work list for B columns at the level of `tb`.
+int ks_close_launch(lumen_ctx *ctx, const u64 *acc, u64 *out, uint32_t B, const lm_galois_key &gk, uint64_t gal_el,
+                    KsTables *tb, const KsScratch &s, const uint32_t *work_down);
 // the scratch of a batch of B columns on `lane`, placed by measurement at a context's first key switch (lm_ks_scratch.hip).
 // tb: always the TOP level's tables, whatever level asks -- the blocks are sized, and the candidates timed, once.
 int get_scratch(lumen_ctx *ctx, uint32_t B, KsTables *tb, KsScratch *s, int lane = 0, u64 **group_acc = nullptr,

@@ -154,14 +154,16 @@ __global__ __launch_bounds__(256) void k_rescale_coef(const u64 *__restrict__ co
         }
 }
 
-static int rescale_polys_coef(lumen_ctx *ctx, const u64 *src, uint32_t nl, u64 *dst, uint32_t target, uint32_t npoly,
-                              u64 *work) {
+int lm_rescale_coef_ready(lumen_ctx *ctx) {
+    RescaleTables *tb = nullptr;
+    return get_rescale_tables(ctx, &tb);
+}
+
+// the coefficient form behind its inverse transforms: the l-loop per coefficient, then the surviving limbs back
+int lm_rescale_polys_from_coef(lumen_ctx *ctx, const u64 *work, uint32_t nl, u64 *dst, uint32_t target, uint32_t npoly) {
     RescaleTables *tb = nullptr;
     if (int rc = get_rescale_tables(ctx, &tb)) return rc;
     const uint32_t N = ctx->N;
-    if (int rc = lm_launch_ntt_strided(ctx, src, (size_t)nl * N, work, (size_t)nl * N, npoly, lm_map_q(nl), true,
-                                       "rescale_intt", nullptr))
-        return rc;
     {
         lm_prof_scope ps(ctx, "rescale_coef", npoly);
         const size_t total = (size_t)npoly * N;
@@ -172,6 +174,16 @@ static int rescale_polys_coef(lumen_ctx *ctx, const u64 *src, uint32_t nl, u64 *
     }
     return lm_launch_ntt_strided(ctx, dst, (size_t)target * N, dst, (size_t)target * N, npoly, lm_map_q(target), false,
                                  "rescale_ntt", nullptr);
+}
+
+static int rescale_polys_coef(lumen_ctx *ctx, const u64 *src, uint32_t nl, u64 *dst, uint32_t target, uint32_t npoly,
+                              u64 *work) {
+    if (int rc = lm_rescale_coef_ready(ctx)) return rc;
+    const uint32_t N = ctx->N;
+    if (int rc = lm_launch_ntt_strided(ctx, src, (size_t)nl * N, work, (size_t)nl * N, npoly, lm_map_q(nl), true,
+                                       "rescale_intt", nullptr))
+        return rc;
+    return lm_rescale_polys_from_coef(ctx, work, nl, dst, target, npoly);
 }
 
 template <int LOGN>
