@@ -385,6 +385,30 @@ int lumen_load_relin_key(lumen_ctx *ctx, const uint64_t *evk, uint32_t flags);
 int lumen_mul_relin(lumen_ctx *ctx, const lumen_set *a, const lumen_set *b, lumen_set **out);
 int lumen_mul_tensor(lumen_ctx *ctx, const lumen_set *a, const lumen_set *b, uint64_t *host_out /* [count][3][nl][N] */);
 
+/* ---- rotations: Evaluator.Automorphism, RotateColumnsNew, RotateRowsNew and RotateHoistedNew of the *bgv.Evaluator that
+ * ServerBFV embeds (fhe/bfv.go:13-21), with the Galois keys lumen_load_galois_key[_ex] loaded (lumen_keygen_galois makes
+ * one for any odd element).  `in`: a set of `count` ciphertexts at one level, 1 <= nl <= L; it is not modified.  With
+ * (k0, k1) the hybrid key switch of c1 at that level under the key of g and index_g the NTT-domain table of X -> X^g
+ * ([LATTIGO-RECALL] ring.AutomorphismNTTIndex), for d = (c0 + k0, k1):
+ *     out[w][l][j] = d[w][l][index_g[j]]                                     (canonical residues)
+ * in a new set of the same count and level.  On the slots of a BGV plaintext (two rows of N/2): g = 5^k rotates both rows
+ * by k to the left (slot i takes the value of slot i + k mod N/2), g = 2N - 1 swaps the rows.
+ * lumen_galois_element: 5^(k mod N/2) mod 2N (rlwe.Parameters.GaloisElement; k may be negative; 0 and N/2 give 1); the row
+ * swap is 2N - 1 (GaloisElementForRowRotation).  0 for a NULL context.
+ * lumen_rotate_columns(k) = lumen_automorphism(lumen_galois_element(k)); lumen_rotate_rows = lumen_automorphism(2N - 1).
+ * lumen_rotate_hoisted: outs[i] = lumen_automorphism(in, gal_els[i]) word for word, i < n_els <= 64, with the
+ * decomposition of c1 (inverse transform, digit extension) done once and shared by the elements.  An element equal to 1 and
+ * repeated elements are allowed; each gets its own set.  n_els == 0 does nothing.  On failure every outs[i] is NULL.
+ * gal_el == 1 is a copy and needs no key.  count == 0 gives an empty set.  lumen_mul_counter does not move.
+ * Refused with a message, before any device work: NULL arguments; an even element or one >= 2N; no key loaded for the
+ * element; no special primes (K = 0) or more than two; a lane-sharded set; a limb count outside [1, L]; n_els > 64. */
+uint64_t lumen_galois_element(const lumen_ctx *ctx, int64_t k);
+int lumen_automorphism(lumen_ctx *ctx, const lumen_set *in, uint64_t gal_el, lumen_set **out);
+int lumen_rotate_columns(lumen_ctx *ctx, const lumen_set *in, int64_t k, lumen_set **out);
+int lumen_rotate_rows(lumen_ctx *ctx, const lumen_set *in, lumen_set **out);
+int lumen_rotate_hoisted(lumen_ctx *ctx, const lumen_set *in, const uint64_t *gal_els, uint32_t n_els,
+                         lumen_set **outs /* [n_els] new sets */);
+
 /* ---- fhe.RingSwitchServer (fhe/ring_switch.go:93-113): Evaluator.ApplyEvaluationKey of every
  * ciphertext of `in` into the ring of degree 2^log_n_small with the single modulus q_0, at level 0.
  * key: the rlwe.EvaluationKey of NewRingSwitchClient (ring_switch.go:43-56) as the client posts it

@@ -25,8 +25,8 @@
 // share an L2; the gadget product keeps key material in Montgomery form and
 // accumulates the beta products of a coefficient in 128 bits, one reduction per output.
 //
-// This file is the rotation: its six kernels, the per-context tables and work lists, rotate_accumulate and the InnerSum
-// entry points.  The other subjects of the key switch live beside it: where the scratch buffers sit in HBM in
+// This file is the rotation: its seven kernels, the per-context tables and work lists, rotate_accumulate, the InnerSum
+// entry points and the rotation on its own (lumen_automorphism, lumen_rotate_columns / _rows / _hoisted).  The other subjects of the key switch live beside it: where the scratch buffers sit in HBM in
 // lm_ks_scratch.hip (mechanism) and lm_placement.h (policy), the end of the last rotation before a rescale -- the rescale's inverse
 // transform with that rotation's ModDown folded in -- in lm_ks_close.hip, Galois- and relinearisation-key loading in lm_ks_key.hip, the ciphertext x
 // plaintext product (step 0, MulNew) in lm_mulplain.hip, the stream layouts and mul128 in lm_ks_dev.h, and what these
@@ -451,15 +451,19 @@ __global__ __launch_bounds__(256) void k_ks_mac(const u64 *__restrict__ ext, con
 // N = 2^14: the limb stays in registers (lm_ntt_forward_w14, 512 threads, two workgroups per CU); the last pass only
 // parks its raw outputs in the wave's slot, and d is formed there, half a wave's block at a time, right before that
 // half is gathered (see the LOGN == 14 branch).
-template <int LOGN>
-__global__ LM_GEOM_BOUNDS(lm_geom_fwd(LOGN)) void k_moddown_ntt(const u64 *__restrict__ u, const u64 *__restrict__ acc_in,
-                                                     u64 *__restrict__ acc_out, const bx_t *__restrict__ bxp,
-                                                     const tw_t *__restrict__ pinv,
-                                                     const uint32_t *__restrict__ index,
-                                                     const uint32_t *__restrict__ inv_index,
-                                                     const uint32_t *__restrict__ work, uint32_t B,
-                                                     uint32_t L, uint32_t K, lm_mods mods,
-                                                     const tw_t *__restrict__ tw_all) {
+// The two kernels below share this body.  ACCUMULATE (k_moddown_ntt): as described, acc_out = acc_in + d o index, lazy.
+// Without it (k_rotdown_ntt, the rotation alone: lumen_automorphism) acc_in is the ciphertext itself, read once, linearly,
+// for the c0 that goes into d, and the gather store is acc_out[j] = d[index[j]] in canonical form: d < 6q comes under q
+// with three conditional subtractions (4q, 2q, q), and no second read of acc_in at the output positions stands beside it.
+template <int LOGN, bool ACCUMULATE>
+__device__ __forceinline__ void moddown_body(const u64 *__restrict__ u, const u64 *__restrict__ acc_in,
+                                             u64 *__restrict__ acc_out, const bx_t *__restrict__ bxp,
+                                             const tw_t *__restrict__ pinv,
+                                             const uint32_t *__restrict__ index,
+                                             const uint32_t *__restrict__ inv_index,
+                                             const uint32_t *__restrict__ work, uint32_t B,
+                                             uint32_t L, uint32_t K, const lm_mods &mods,
+                                             const tw_t *__restrict__ tw_all) {
     extern __shared__ __attribute__((aligned(16))) u64 sm[];
     constexpr uint32_t N = 1u << LOGN;
     const uint32_t tid = threadIdx.x;
@@ -534,15 +538,20 @@ __global__ LM_GEOM_BOUNDS(lm_geom_fwd(LOGN)) void k_moddown_ntt(const u64 *__res
             for (uint32_t k = 0; k < 8; k++) {
                 const uint32_t j = (jb << 10) + 2 * lane + k * 128;
                 p[k] = *reinterpret_cast<const uint2 *>(index + j);
-                x[k] = *reinterpret_cast<const ulonglong2 *>(ain + j);
+                if constexpr (ACCUMULATE) x[k] = *reinterpret_cast<const ulonglong2 *>(ain + j);
             }
 #pragma unroll
             for (uint32_t k = 0; k < 8; k++) {
                 const uint32_t j = (jb << 10) + 2 * lane + k * 128;
-                // lazy accumulator: acc (< 2q) + d (< 6q) < 8q back under 2q, as in the LDS form below
                 ulonglong2 y;
-                y.x = lm_csub(lm_csub(x[k].x + sm[LM_PAD(sbase | (p[k].x & 1023u))], 4 * qc.q), 2 * qc.q);
-                y.y = lm_csub(lm_csub(x[k].y + sm[LM_PAD(sbase | (p[k].y & 1023u))], 4 * qc.q), 2 * qc.q);
+                if constexpr (ACCUMULATE) {
+                    // lazy accumulator: acc (< 2q) + d (< 6q) < 8q back under 2q, as in the LDS form below
+                    y.x = lm_csub(lm_csub(x[k].x + sm[LM_PAD(sbase | (p[k].x & 1023u))], 4 * qc.q), 2 * qc.q);
+                    y.y = lm_csub(lm_csub(x[k].y + sm[LM_PAD(sbase | (p[k].y & 1023u))], 4 * qc.q), 2 * qc.q);
+                } else { // d < 6q alone, canonical
+                    y.x = lm_csub(lm_csub(lm_csub(sm[LM_PAD(sbase | (p[k].x & 1023u))], 4 * qc.q), 2 * qc.q), qc.q);
+                    y.y = lm_csub(lm_csub(lm_csub(sm[LM_PAD(sbase | (p[k].y & 1023u))], 4 * qc.q), 2 * qc.q), qc.q);
+                }
                 *reinterpret_cast<ulonglong2 *>(aout + j) = y;
             }
         };
@@ -598,7 +607,7 @@ __global__ LM_GEOM_BOUNDS(lm_geom_fwd(LOGN)) void k_moddown_ntt(const u64 *__res
             for (uint32_t k = 0; k < IT; k++) {
                 const uint32_t j = jb * BLK + 2 * lane + k * 128;
                 p[k] = *reinterpret_cast<const uint2 *>(index + j);
-                x[k] = *reinterpret_cast<const ulonglong2 *>(ain + j);
+                if constexpr (ACCUMULATE) x[k] = *reinterpret_cast<const ulonglong2 *>(ain + j);
             }
             lm_wave_sync();
 #pragma unroll
@@ -610,13 +619,33 @@ __global__ LM_GEOM_BOUNDS(lm_geom_fwd(LOGN)) void k_moddown_ntt(const u64 *__res
                 // readers take [0, 2q): the inverse transform's loader (< 3q), the gadget product's own-digit operand
                 // (any u64), this kernel, and the rescale that ends matrixInnerSumEval (lm_rescale.hip).
                 ulonglong2 y;
-                y.x = lm_csub(lm_csub(x[k].x + sm[LM_PAD(p[k].x)], 4 * qc.q), 2 * qc.q);
-                y.y = lm_csub(lm_csub(x[k].y + sm[LM_PAD(p[k].y)], 4 * qc.q), 2 * qc.q);
+                if constexpr (ACCUMULATE) {
+                    y.x = lm_csub(lm_csub(x[k].x + sm[LM_PAD(p[k].x)], 4 * qc.q), 2 * qc.q);
+                    y.y = lm_csub(lm_csub(x[k].y + sm[LM_PAD(p[k].y)], 4 * qc.q), 2 * qc.q);
+                } else { // the rotation alone: d < 6q, canonical -- no k_acc_canon pass follows
+                    y.x = lm_csub(lm_csub(lm_csub(sm[LM_PAD(p[k].x)], 4 * qc.q), 2 * qc.q), qc.q);
+                    y.y = lm_csub(lm_csub(lm_csub(sm[LM_PAD(p[k].y)], 4 * qc.q), 2 * qc.q), qc.q);
+                }
                 *reinterpret_cast<ulonglong2 *>(aout + j) = y;
             }
         };
         lm_ntt_forward<LOGN>(sm, tw_all + (size_t)t * N, qc, tid, ld, st, after);
     }
+}
+
+#define LM_MODDOWN_PARAMS                                                                                                      \
+    const u64 *__restrict__ u, const u64 *__restrict__ acc_in, u64 *__restrict__ acc_out, const bx_t *__restrict__ bxp,        \
+        const tw_t *__restrict__ pinv, const uint32_t *__restrict__ index, const uint32_t *__restrict__ inv_index,             \
+        const uint32_t *__restrict__ work, uint32_t B, uint32_t L, uint32_t K, lm_mods mods, const tw_t *__restrict__ tw_all
+template <int LOGN>
+__global__ LM_GEOM_BOUNDS(lm_geom_fwd(LOGN)) void k_moddown_ntt(LM_MODDOWN_PARAMS) {
+    moddown_body<LOGN, true>(u, acc_in, acc_out, bxp, pinv, index, inv_index, work, B, L, K, mods, tw_all);
+}
+// ModDown that ends in a plain gather: out = sigma_g(c0 + k0, k1), canonical; acc_in = the input ciphertexts, acc_out = the
+// output set (another block: a workgroup's output block is another workgroup's c0)
+template <int LOGN>
+__global__ LM_GEOM_BOUNDS(lm_geom_fwd(LOGN)) void k_rotdown_ntt(LM_MODDOWN_PARAMS) {
+    moddown_body<LOGN, false>(u, acc_in, acc_out, bxp, pinv, index, inv_index, work, B, L, K, mods, tw_all);
 }
 
 // words of a lazy accumulator ([0, 2q), see k_moddown_ntt) to canonical form: for the callers that hand the
@@ -869,15 +898,13 @@ static dim3 ks_mac_grid(const lumen_ctx *ctx, uint32_t B, uint32_t L) {
 
 } // namespace
 
-// Steps 1-4a of a rotation of acc, [B][2][L][N], L = the level of `tb`: the gadget product u in s.u, its limbs modulo P
-// in the coefficient domain and packed.  What follows is the seam between the two ways a rotation ends: ModDown
-// (rotate_accumulate) or, for the last rotation before a rescale, the closing inverse transform (rotate_close).
-static int rotate_front(lumen_ctx *ctx, const u64 *acc, uint32_t B, const lm_galois_key &gk, KsTables *tb,
-                        const KsScratch &s) {
+// Steps 1-4a of a rotation of acc, [B][2][L][N], L = the level of `tb`, in two halves.
+// rotate_decompose, steps 1-2: the digits of c1 extended to every limb, in s.coef and s.ext.  It depends on the ciphertext
+// alone -- not on the key, not on the Galois element -- so several rotations of one ciphertext share it
+// (lumen_rotate_hoisted: [LATTIGO-RECALL] Evaluator.DecomposeNTT before AutomorphismHoisted).
+static int rotate_decompose(lumen_ctx *ctx, const u64 *acc, uint32_t B, KsTables *tb, const KsScratch &s) {
     const uint32_t N = ctx->N, L = tb->nl, K = ctx->K, beta = tb->beta;
-    // the limbs modulo P sit behind the context's L Q limbs: in the moduli, the twiddles and the stored key, which is
-    // [ctx L + K][key_beta][2] whatever the level (the RNS gadget does not depend on it)
-    const uint32_t pshift = ctx->L - L, key_beta = (ctx->L + K - 1) / K;
+    const uint32_t pshift = ctx->L - L; // the limbs modulo P sit behind the context's L Q limbs (moduli, twiddles)
     // 1. c1 -> coefficient domain, scaled for the basis extension, and the (hi, lo) packing of the two-limb
     // digits: fused into the transform for the first nf digits, k_pack_v for the others
     const uint32_t nf = K == 2 ? ks_fused_digits(ctx, B, L) : 0;
@@ -912,6 +939,19 @@ static int rotate_front(lumen_ctx *ctx, const u64 *acc, uint32_t B, const lm_gal
             }))
             return rc;
     }
+    return 0;
+}
+
+// rotate_product, steps 3-4a, under one key: reads s.ext and acc, leaves the gadget product u in s.u, its limbs modulo P
+// in the coefficient domain and packed.  What follows is the seam between the ways a rotation ends: ModDown into an
+// accumulator (rotate_accumulate), ModDown into a plain gather (rotate_store) or, for the last rotation before a rescale,
+// the closing inverse transform (rotate_close).
+static int rotate_product(lumen_ctx *ctx, const u64 *acc, uint32_t B, const lm_galois_key &gk, KsTables *tb,
+                          const KsScratch &s) {
+    const uint32_t N = ctx->N, L = tb->nl, K = ctx->K, beta = tb->beta;
+    // the limbs modulo P sit behind the context's L Q limbs: in the moduli, the twiddles and the stored key, which is
+    // [ctx L + K][key_beta][2] whatever the level (the RNS gadget does not depend on it)
+    const uint32_t pshift = ctx->L - L, key_beta = (ctx->L + K - 1) / K;
     // 3. gadget product
     {
         lm_prof_scope ps(ctx, "ks_mac", (uint64_t)B);
@@ -939,7 +979,8 @@ static int rotate_front(lumen_ctx *ctx, const u64 *acc, uint32_t B, const lm_gal
 // acc, acc_out: [B][2][L][N], L = the level of `tb`; acc_out = acc + Rot_galEl(acc) for every column
 int rotate_accumulate(lumen_ctx *ctx, const u64 *acc, u64 *acc_out, uint32_t B, const lm_galois_key &gk,
                       KsTables *tb, const KsScratch &s) {
-    if (int rc = rotate_front(ctx, acc, B, gk, tb, s)) return rc;
+    if (int rc = rotate_decompose(ctx, acc, B, tb, s)) return rc;
+    if (int rc = rotate_product(ctx, acc, B, gk, tb, s)) return rc;
     const uint32_t L = tb->nl, K = ctx->K;
     // 4b + 5. lift to Q, NTT, combine, automorphism, accumulate
     {
@@ -955,10 +996,23 @@ int rotate_accumulate(lumen_ctx *ctx, const u64 *acc, u64 *acc_out, uint32_t B, 
 
 namespace {
 
+// After rotate_product: out = Rot_galEl(in) for every column, canonical, [B][2][L][N] both; `out` is another block than `in`.
+int rotate_store(lumen_ctx *ctx, const u64 *in, u64 *out, uint32_t B, const lm_galois_key &gk, KsTables *tb, const KsScratch &s) {
+    const uint32_t L = tb->nl, K = ctx->K;
+    const uint32_t *work_down = nullptr;
+    if (int rc = moddown_work_list(ctx, tb, B, &work_down)) return rc;
+    lm_prof_scope ps(ctx, "ks_rotdown_ntt", (uint64_t)B * 2 * L);
+    return lm_for_logn(ctx, ctx->logN, [&](auto n) {
+        return lm_launch(ctx, k_rotdown_ntt<n>, lm_geom_fwd(n), B * 2 * L, s.u, in, out, tb->d_bxp.get(), tb->d_pinv.get(),
+                         gk.d_index.get(), gk.d_inv_index.get(), work_down, B, L, K, ctx->mods, ctx->sh->tw_fwd.get());
+    });
+}
+
 // coef_out = the coefficient form of acc + Rot_galEl(acc), [B][2][L][N]: the last rotation before a rescale (lm_ks_close.hip)
 int rotate_close(lumen_ctx *ctx, const u64 *acc, u64 *coef_out, uint32_t B, const lm_galois_key &gk, uint64_t gal_el,
                  KsTables *tb, const KsScratch &s) {
-    if (int rc = rotate_front(ctx, acc, B, gk, tb, s)) return rc;
+    if (int rc = rotate_decompose(ctx, acc, B, tb, s)) return rc;
+    if (int rc = rotate_product(ctx, acc, B, gk, tb, s)) return rc;
     const uint32_t *work_down = nullptr;
     if (int rc = moddown_work_list(ctx, tb, B, &work_down)) return rc;
     return ks_close_launch(ctx, acc, coef_out, B, gk, gal_el, tb, s, work_down);
@@ -1175,4 +1229,134 @@ extern "C" int lumen_matrix_inner_sum_at_level(lumen_ctx *ctx, const lumen_set *
     LM_ENTER(ctx);
     if (int rc = check_level_of_chain(ctx, matrix, "matrixInnerSumEval")) return rc;
     return matrix_inner_sum_at(ctx, matrix, pt, rows, out);
+}
+
+// ---- the rotation alone: Evaluator.Automorphism / RotateColumnsNew / RotateRowsNew / RotateHoistedNew (the evaluator that
+// ServerBFV embeds, fhe/bfv.go:13-21).  out = sigma_g(c0 + k0(c1), k1(c1)): decompose, product, and a ModDown that ends in
+// a plain gather (k_rotdown_ntt).  The input set is read in place and the output set is the destination: no accumulator,
+// no ping-pong, no copy, no canonicalising pass.  Batching, lanes, per-level tables and the scratch sized and placed for the
+// top level are lumen_mul_relin's.
+extern "C" uint64_t lumen_galois_element(const lumen_ctx *ctx, int64_t k) {
+    if (!ctx || ctx->N < 2) return 0;
+    // [LATTIGO-RECALL] rlwe.Parameters.GaloisElement: 5 generates the column rotations, its order mod 2N is N / 2
+    const int64_t order = (int64_t)(ctx->N >> 1);
+    int64_t e = k % order;
+    if (e < 0) e += order;
+    const uint64_t mask = 2ull * ctx->N - 1;
+    uint64_t g = 1, b = 5;
+    for (; e; e >>= 1, b = (b * b) & mask)
+        if (e & 1) g = (g * b) & mask;
+    return g;
+}
+
+namespace {
+
+// new sets that go back to the pool unless the call succeeds
+struct NewSets {
+    lumen_ctx *ctx;
+    std::vector<lumen_set *> v;
+    explicit NewSets(lumen_ctx *c) : ctx(c) {}
+    ~NewSets() {
+        for (lumen_set *s : v)
+            if (s) lumen_set_destroy(ctx, s);
+    }
+    NewSets(const NewSets &) = delete;
+    NewSets &operator=(const NewSets &) = delete;
+};
+
+#define LM_MAX_HOISTED 64u
+
+// outs[i] = Automorphism(in, gal_els[i]) for the n_els elements; the decomposition of a batch runs once, whatever n_els
+int rotate_sets(lumen_ctx *ctx, const lumen_set *in, const uint64_t *gal_els, uint32_t n_els, lumen_set **outs, const char *what) {
+    for (uint32_t i = 0; i < n_els; i++) outs[i] = nullptr;
+    if (int rc = check_level_of_chain(ctx, in, what)) return rc;
+    LM_CHECK(ctx, n_els <= LM_MAX_HOISTED, "%s: %u Galois elements, at most %u in one call", what, n_els, LM_MAX_HOISTED);
+    bool keyed = false;
+    for (uint32_t i = 0; i < n_els; i++) {
+        LM_CHECK(ctx, (gal_els[i] & 1) && gal_els[i] < 2ull * ctx->N, "%s: Galois element %llu is not an odd residue mod 2N", what,
+                 (unsigned long long)gal_els[i]);
+        keyed = keyed || gal_els[i] != 1;
+    }
+    // the identity is a copy and needs no key ([LATTIGO-RECALL] Evaluator.Automorphism returns the input for galEl == 1)
+    KsTables *top = nullptr, *tb = nullptr;
+    std::vector<const lm_galois_key *> keys(n_els, nullptr);
+    if (keyed) {
+        LM_CHECK(ctx, ctx->K >= 1, "parameters have no special primes: key switching unavailable");
+        if (int rc = get_tables(ctx, &top)) return rc; // (refuses K > 2, as InnerSum does)
+        if (int rc = get_tables_at(ctx, in->nl, &tb)) return rc;
+        LM_SHARED_LOCK(ctx); // (an entry of the map never moves or goes, and a key loaded again keeps its blocks)
+        for (uint32_t i = 0; i < n_els; i++) {
+            if (gal_els[i] == 1) continue;
+            auto it = ctx->gkeys.find(gal_els[i]);
+            LM_CHECK(ctx, it != ctx->gkeys.end() && it->second.d_key && it->second.d_index && it->second.d_inv_index,
+                     "Galois key for element %llu not loaded", (unsigned long long)gal_els[i]);
+            keys[i] = &it->second;
+        }
+    }
+    const uint32_t count = in->count, nl = in->nl;
+    NewSets made(ctx);
+    made.v.assign(n_els, nullptr);
+    for (uint32_t i = 0; i < n_els; i++)
+        if (int rc = lumen_set_create(ctx, count, nl, &made.v[i])) return rc;
+    if (count) {
+        for (uint32_t i = 0; i < n_els; i++)
+            if (gal_els[i] == 1)
+                LM_HIP(ctx, hipMemcpyAsync(made.v[i]->d, in->d, in->words * 8, hipMemcpyDeviceToDevice, ctx->stream));
+    }
+    if (count && keyed) {
+        const uint32_t Bmax = std::min<uint32_t>(ks_batch(ctx), count), lanes = ks_lanes(ctx);
+        const size_t ctw = (size_t)2 * nl * ctx->N;
+        KsScratch s[2];
+        if (get_scratch(ctx, Bmax, top, &s[0], 0) || (lanes > 1 && get_scratch(ctx, Bmax, top, &s[1], 1))) return 1;
+        if (lanes > 1) { // fork: the second lane starts after everything already enqueued on the main stream
+            LM_HIP(ctx, hipEventRecord(ctx->ev_fork, ctx->stream));
+            LM_HIP(ctx, hipStreamWaitEvent(ctx->stream2, ctx->ev_fork, 0));
+        }
+        uint32_t lane = 0;
+        for (uint32_t first = 0; first < count; first += Bmax, lane = (lane + 1) % lanes) {
+            const uint32_t B = std::min(Bmax, count - first);
+            const u64 *src = in->d + (size_t)first * ctw;
+            LaneGuard guard(ctx, (int)lane);
+            if (int rc = rotate_decompose(ctx, src, B, tb, s[lane])) return rc; // once per batch: s.ext survives the loop
+            for (uint32_t i = 0; i < n_els; i++) {
+                if (!keys[i]) continue;
+                if (int rc = rotate_product(ctx, src, B, *keys[i], tb, s[lane])) return rc; // s.u, rewritten per element
+                if (int rc = rotate_store(ctx, src, made.v[i]->d + (size_t)first * ctw, B, *keys[i], tb, s[lane])) return rc;
+            }
+        }
+        if (lanes > 1) { // join: the caller reads the sets on the main stream
+            LM_HIP(ctx, hipEventRecord(ctx->ev_join, ctx->stream2));
+            LM_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));
+        }
+    }
+    for (uint32_t i = 0; i < n_els; i++) outs[i] = made.v[i], made.v[i] = nullptr;
+    return 0;
+}
+
+} // namespace
+
+extern "C" int lumen_automorphism(lumen_ctx *ctx, const lumen_set *in, uint64_t gal_el, lumen_set **out) {
+    LM_CHECK(nullptr, ctx && in && out, "lumen_automorphism: NULL argument");
+    LM_ENTER(ctx);
+    return rotate_sets(ctx, in, &gal_el, 1, out, "lumen_automorphism");
+}
+
+extern "C" int lumen_rotate_columns(lumen_ctx *ctx, const lumen_set *in, int64_t k, lumen_set **out) {
+    LM_CHECK(nullptr, ctx && in && out, "lumen_rotate_columns: NULL argument");
+    LM_ENTER(ctx);
+    const uint64_t g = lumen_galois_element(ctx, k);
+    return rotate_sets(ctx, in, &g, 1, out, "lumen_rotate_columns");
+}
+
+extern "C" int lumen_rotate_rows(lumen_ctx *ctx, const lumen_set *in, lumen_set **out) {
+    LM_CHECK(nullptr, ctx && in && out, "lumen_rotate_rows: NULL argument");
+    LM_ENTER(ctx);
+    const uint64_t g = 2ull * ctx->N - 1; // [LATTIGO-RECALL] GaloisElementForRowRotation
+    return rotate_sets(ctx, in, &g, 1, out, "lumen_rotate_rows");
+}
+
+extern "C" int lumen_rotate_hoisted(lumen_ctx *ctx, const lumen_set *in, const uint64_t *gal_els, uint32_t n_els, lumen_set **outs) {
+    LM_CHECK(nullptr, ctx && in && gal_els && outs, "lumen_rotate_hoisted: NULL argument");
+    LM_ENTER(ctx);
+    return rotate_sets(ctx, in, gal_els, n_els, outs, "lumen_rotate_hoisted");
 }

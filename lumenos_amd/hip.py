@@ -117,6 +117,11 @@ SYMBOLS = {
     "lumen_matrix_inner_sum_at_level": (C.c_int, [_vp, _vp, _u64p, C.c_uint32, _vpp]),
     "lumen_load_relin_key": (C.c_int, [_vp, _u64p, C.c_uint32]),
     "lumen_mul_relin": (C.c_int, [_vp, _vp, _vp, _vpp]),
+    "lumen_galois_element": (C.c_uint64, [_vp, C.c_int64]),
+    "lumen_automorphism": (C.c_int, [_vp, _vp, C.c_uint64, _vpp]),
+    "lumen_rotate_columns": (C.c_int, [_vp, _vp, C.c_int64, _vpp]),
+    "lumen_rotate_rows": (C.c_int, [_vp, _vp, _vpp]),
+    "lumen_rotate_hoisted": (C.c_int, [_vp, _vp, _u64p, C.c_uint32, _vpp]),
     "lumen_mul_tensor": (C.c_int, [_vp, _vp, _vp, _u64p]),
     "lumen_gather": (C.c_int, [_vp, _vp, _u32p, C.c_uint32, _vpp]),
     "lumen_plain_inner_products": (C.c_int, [_vp, _vp, _u64p, _u64p]),
@@ -651,6 +656,35 @@ class Context:
         h = C.c_void_p()
         self._ck(self.lib.lumen_mul_relin(self.h, a.h, b.h, C.byref(h)))
         return DeviceSet(self, h)
+
+    def galois_element(self, k):
+        """5^(k mod N/2) mod 2N: the element of a column rotation by k; the row swap is 2N - 1"""
+        return int(self.lib.lumen_galois_element(self.h, k))
+
+    def automorphism(self, s, gal_el):
+        """Evaluator.Automorphism(ct, galEl) of every ciphertext of `s`, at its level, under the loaded Galois key"""
+        h = C.c_void_p()
+        self._ck(self.lib.lumen_automorphism(self.h, s.h, gal_el, C.byref(h)))
+        return DeviceSet(self, h)
+
+    def rotate_columns(self, s, k):
+        """RotateColumnsNew(ct, k): slot i of each row takes the value of slot i + k"""
+        h = C.c_void_p()
+        self._ck(self.lib.lumen_rotate_columns(self.h, s.h, k, C.byref(h)))
+        return DeviceSet(self, h)
+
+    def rotate_rows(self, s):
+        """RotateRowsNew(ct): the two rows of N/2 slots change places"""
+        h = C.c_void_p()
+        self._ck(self.lib.lumen_rotate_rows(self.h, s.h, C.byref(h)))
+        return DeviceSet(self, h)
+
+    def rotate_hoisted(self, s, gal_els):
+        """RotateHoistedNew: one set per element of gal_els (at most 64), the decomposition of c1 shared by all"""
+        g = np.ascontiguousarray(gal_els, dtype=np.uint64).reshape(-1)
+        hs = (C.c_void_p * max(g.size, 1))()
+        self._ck(self.lib.lumen_rotate_hoisted(self.h, s.h, _p64(g) if g.size else _p64(np.zeros(1, dtype=np.uint64)), g.size, hs))
+        return [DeviceSet(self, C.c_void_p(hs[i])) for i in range(g.size)]
 
     def mul_tensor(self, a, b):
         """the degree-2 ciphertexts (d0, d1, d2) of a x b before relinearisation: [count][3][limbs][N]"""

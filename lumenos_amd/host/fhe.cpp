@@ -564,6 +564,50 @@ Ciphertexts ServerBFV::MulRelinNew(const Ciphertexts &a, const Ciphertexts &b) {
     return Ciphertexts(Context(), set, md);
 }
 
+void ServerBFV::LoadGaloisKeys(const std::map<uint64_t, std::vector<uint64_t>> &keys, uint32_t flags) {
+    for (const auto &kv : keys)
+        if (kv.second.size() != evk_words(params_) || kv.second.empty())
+            throw std::invalid_argument("LoadGaloisKeys: a Galois key is not [beta][b|a][L+K][N]");
+    for (const auto &kv : keys)
+        check(lumen_load_galois_key_ex(Context(), kv.first, kv.second.data(), flags), "lumen_load_galois_key_ex");
+}
+
+Ciphertexts ServerBFV::AutomorphismNew(const Ciphertexts &ct, uint64_t galEl) {
+    if (!ct.Handle()) throw std::invalid_argument("AutomorphismNew: the operand holds no ciphertexts");
+    lumen_set *set = nullptr;
+    check(lumen_automorphism(Context(), ct.Handle(), galEl, &set), "lumen_automorphism");
+    return Ciphertexts(Context(), set, ct.Meta);
+}
+
+Ciphertexts ServerBFV::RotateColumnsNew(const Ciphertexts &ct, int k) {
+    if (!ct.Handle()) throw std::invalid_argument("RotateColumnsNew: the operand holds no ciphertexts");
+    lumen_set *set = nullptr;
+    check(lumen_rotate_columns(Context(), ct.Handle(), k, &set), "lumen_rotate_columns");
+    return Ciphertexts(Context(), set, ct.Meta);
+}
+
+Ciphertexts ServerBFV::RotateRowsNew(const Ciphertexts &ct) {
+    if (!ct.Handle()) throw std::invalid_argument("RotateRowsNew: the operand holds no ciphertexts");
+    lumen_set *set = nullptr;
+    check(lumen_rotate_rows(Context(), ct.Handle(), &set), "lumen_rotate_rows");
+    return Ciphertexts(Context(), set, ct.Meta);
+}
+
+std::map<int, Ciphertexts> ServerBFV::RotateHoistedNew(const Ciphertexts &ct, const std::vector<int> &rotations) {
+    if (!ct.Handle()) throw std::invalid_argument("RotateHoistedNew: the operand holds no ciphertexts");
+    const std::set<int> distinct(rotations.begin(), rotations.end()); // the reference fills a map: one entry per rotation
+    const std::vector<int> rots(distinct.begin(), distinct.end());
+    std::vector<uint64_t> els;
+    for (int r : rots) els.push_back(lumen_galois_element(Context(), r));
+    std::vector<lumen_set *> sets(std::max<size_t>(rots.size(), 1), nullptr);
+    const uint64_t none = 1; // (the list pointer is never NULL, even for no rotation at all)
+    check(lumen_rotate_hoisted(Context(), ct.Handle(), els.empty() ? &none : els.data(), (uint32_t)els.size(), sets.data()),
+          "lumen_rotate_hoisted");
+    std::map<int, Ciphertexts> out;
+    for (size_t i = 0; i < rots.size(); i++) out.emplace(rots[i], Ciphertexts(Context(), sets[i], ct.Meta));
+    return out;
+}
+
 Plaintext ServerBFV::Encode(const std::vector<uint64_t> &values) const {
     const int N = params_.N(), nl = (int)params_.Q.size();
     if ((int)values.size() > N) throw std::invalid_argument("cannot Encode: too many values for the ring degree");

@@ -58,6 +58,7 @@ struct Parameters {
     // explicit moduli (what a Go host passes: Lattigo's own)
     static Parameters FromModuli(int logN, std::vector<uint64_t> q, std::vector<uint64_t> p, uint64_t T);
     uint64_t GaloisElement(int k) const; // 5^k mod 2N
+    uint64_t GaloisElementForRowRotation() const { return (2ull << LogN) - 1; }
     // params.GaloisElementsForInnerSum(batch, n) (fhe/ligero_test.go:53, cmd/client/main.go:81): the elements
     // the CLIENT generates keys for -- rotations {1, 2, ..., n/2, n}*batch plus the row swap iff n > N/2
     // (12 / 14 / 15 / 16 keys at the four reference configurations, as their key-size logs show)
@@ -211,6 +212,22 @@ class ServerBFV {
     // holds one ciphertext; a and b of one level (a and b may be the same object: squares).  The result's Scale() is
     // a.Scale() * b.Scale() mod T; MulCounter() grows by a.Len().  Needs the relinearisation key.
     Ciphertexts MulRelinNew(const Ciphertexts &a, const Ciphertexts &b);
+    // Galois keys for arbitrary elements, beside whatever the constructor loaded (evk.GaloisKeys of an
+    // rlwe.MemEvaluationKeySet holds any element the client generated): element -> [beta][b|a][L+K][N] as
+    // KeyGenerator::GenGaloisKeysNew returns them, in `flags`' form.  CopyNews share them; loading an element again replaces its key.
+    void LoadGaloisKeys(const std::map<uint64_t, std::vector<uint64_t>> &keys, uint32_t flags = 0);
+    // The rotations of the embedded *bgv.Evaluator (bfv.go:13-21), on every ciphertext of `ct` at its level; the result
+    // keeps ct's MetaData (a rotation leaves the scale alone) and MulCounter() does not move.  Each needs the Galois key of
+    // its element (the identity needs none and copies).
+    // Evaluator.Automorphism(ct, galEl, opOut) into a new set
+    Ciphertexts AutomorphismNew(const Ciphertexts &ct, uint64_t galEl);
+    // Evaluator.RotateColumnsNew(ct, k): slot i of both rows takes the value of slot i + k (mod N/2)
+    Ciphertexts RotateColumnsNew(const Ciphertexts &ct, int k);
+    // Evaluator.RotateRowsNew(ct): the two rows of N/2 slots change places
+    Ciphertexts RotateRowsNew(const Ciphertexts &ct);
+    // Evaluator.RotateHoistedNew(ct, rotations): rotation -> RotateColumnsNew(ct, rotation), the decomposition of c1 done
+    // once (lumen_rotate_hoisted); at most 64 distinct rotations
+    std::map<int, Ciphertexts> RotateHoistedNew(const Ciphertexts &ct, const std::vector<int> &rotations);
     // Encoder.Encode(values, pt) at MaxLevel ([LATTIGO-RECALL] m * T^-1 form, slot index matrix)
     Plaintext Encode(const std::vector<uint64_t> &values) const;
     // Encryptor.EncryptNew(pt) under pk, host layout [2][L][N]
