@@ -253,7 +253,7 @@ struct lm_set_guard {
         s = nullptr;
         return r;
     }
-    lm_set_guard(const lm_set_guard &) = delete;
+    lm_set_guard(lm_set_guard &&o) : ctx(o.ctx), s(o.release()) {} // (movable: a call that makes several sets keeps a vector)
     lm_set_guard &operator=(const lm_set_guard &) = delete;
 };
 

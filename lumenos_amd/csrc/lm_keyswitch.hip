@@ -25,41 +25,20 @@
 // share an L2; the gadget product keeps key material in Montgomery form and
 // accumulates the beta products of a coefficient in 128 bits, one reduction per output.
 //
-// This file is the rotation: its seven kernels, the per-context tables and work lists, rotate_accumulate, the InnerSum
-// entry points and the rotation on its own (lumen_automorphism, lumen_rotate_columns / _rows / _hoisted).  The other subjects of the key switch live beside it: where the scratch buffers sit in HBM in
+// This file is one rotation of a batch of columns: its six transform and product kernels, the per-context tables and
+// work lists, and the steps a caller composes -- rotate_decompose, rotate_product and the three ways a rotation ends,
+// rotate_accumulate, rotate_store, rotate_close -- with lumen_ks_mac_probe, which times the gadget product alone.  The
+// other subjects of the key switch live beside it: the batching of its callers (batches, lanes, groups) in
+// lm_ks_batch.hip; the callers in lm_innersum.hip (InnerSum, matrixInnerSumEval), lm_rotate.hip (lumen_automorphism,
+// lumen_rotate_columns / _rows / _hoisted) and lm_mulrelin.hip (the relinearisation); where the scratch buffers sit in HBM in
 // lm_ks_scratch.hip (mechanism) and lm_placement.h (policy), the end of the last rotation before a rescale -- the rescale's inverse
-// transform with that rotation's ModDown folded in -- in lm_ks_close.hip, Galois- and relinearisation-key loading in lm_ks_key.hip, the ciphertext x
+// transform with that rotation's ModDown folded in -- in lm_ks_close.hip, Galois- and relinearisation-key loading and lookup in lm_ks_key.hip, the ciphertext x
 // plaintext product (step 0, MulNew) in lm_mulplain.hip, the stream layouts and mul128 in lm_ks_dev.h, and what these
 // units share on the host in lm_ks_host.h.
 #include <cstdlib>
 #include <cstring>
 
 #include "lm_ks_host.h"
-
-// ---- what the relinearisation (lm_mulrelin.hip) shares with InnerSum, declared in lm_ks_host.h
-// columns processed together (scratch ~ 172 limbs per column): 64 by default, LUMEN_KS_BATCH at context
-// creation (lm_tuning)
-uint32_t ks_batch(const lumen_ctx *ctx) { return ctx->tune.ks_batch; }
-
-// Lanes: independent column batches alternate between the context's two streams (LaneGuard, lm_ks_host.h) so that the
-// HBM-bound steps of one batch (gadget product, correction-bit pass) overlap the VALU-bound transforms of the other.
-// Two lanes up to N = 2^13, one at N = 2^14 (round 4, measured on one MI355X, seconds per prover step with 1 / 2
-// lanes: 2048x1024 0.0850 / 0.0743, 4096x2048 0.193 / 0.163, 8192x4096 0.864 / 0.799, 16384x4096 1.86 / 1.92).
-// Up to 2^13 a limb needs at most half of a CU's LDS, so workgroups of two kernels are resident side by side and
-// one batch's memory-bound steps run under the other's transforms; at 2^14 a transform workgroup owns the whole
-// LDS and two transform kernels only evict each other's L2 sets (still so with the forward kernels of a rotation two
-// workgroups per CU and the inverse ones owning it: 1.677 / 1.718 s, round 10).  LUMEN_KS_LANES = 1 / 2 overrides.  (With two
-// lanes a kernel's HIP-event time includes its neighbour's: the roofline is read at N = 2^14, one lane.)
-uint32_t ks_lanes(const lumen_ctx *ctx) {
-    return ctx->tune.ks_lanes ? ctx->tune.ks_lanes : (ctx->logN <= 13 ? 2 : 1);
-}
-
-// A set at a level of the chain: full width, 1 <= nl <= L (a set of another context may have more).
-int check_level_of_chain(lumen_ctx *ctx, const lumen_set *in, const char *what) {
-    LM_FULL_WIDTH(ctx, in, what);
-    LM_CHECK(ctx, in->nl >= 1 && in->nl <= ctx->L, "%s: set has %u limbs, the chain has %u", what, in->nl, ctx->L);
-    return 0;
-}
 
 // v = uint64(float64(y0)/float64(m0) + float64(y1)/float64(m1))  ([LATTIGO-RECALL] reconstructRNS).
 // The double expression is within 2^-49 of S = A / M, A = y0*m1 + y1*m0, M = m0*m1, and S < 2: unless
@@ -648,28 +627,8 @@ __global__ LM_GEOM_BOUNDS(lm_geom_fwd(LOGN)) void k_rotdown_ntt(LM_MODDOWN_PARAM
     moddown_body<LOGN, false>(u, acc_in, acc_out, bxp, pinv, index, inv_index, work, B, L, K, mods, tw_all);
 }
 
-// words of a lazy accumulator ([0, 2q), see k_moddown_ntt) to canonical form: for the callers that hand the
-// accumulator out as it is (lumen_inner_sum; matrixInnerSumEval when there is no limb to drop).  Elementwise,
-// [count][2][L][N], 16-byte accesses.
-__global__ __launch_bounds__(256) void k_acc_canon(u64 *__restrict__ acc, size_t pairs, uint32_t logN, uint32_t L, lm_mods mods) {
-    const size_t stride = (size_t)gridDim.x * blockDim.x;
-    for (size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x; g < pairs; g += stride) {
-        const u64 q = mods.m[(uint32_t)((g >> (logN - 1)) % L)].q;
-        ulonglong2 v = *reinterpret_cast<ulonglong2 *>(acc + 2 * g);
-        v.x = lm_csub(v.x, q), v.y = lm_csub(v.y, q);
-        *reinterpret_cast<ulonglong2 *>(acc + 2 * g) = v;
-    }
-}
-
 // -------------------------------------------------------------------- host side
 namespace {
-
-int acc_canon(lumen_ctx *ctx, u64 *acc, size_t words, uint32_t L) {
-    if (!words) return 0;
-    hipLaunchKernelGGL(k_acc_canon, dim3(2048), dim3(256), 0, ctx->stream, acc, words / 2, ctx->logN, L, ctx->mods);
-    LM_HIP(ctx, hipGetLastError());
-    return 0;
-}
 
 bx_t make_bx(const uint64_t *src, uint32_t ns, uint64_t t) {
     bx_t c;
@@ -891,9 +850,32 @@ static uint32_t ks_fused_digits(lumen_ctx *ctx, uint32_t B, uint32_t L) {
     return 0;
 }
 
-// grid of k_ks_mac for a batch of B columns at the level of L limbs
-static dim3 ks_mac_grid(const lumen_ctx *ctx, uint32_t B, uint32_t L) {
-    return dim3(((ctx->N / LM_MAC_VEC + 255) / 256) * (L + ctx->K) * ((B + LM_MAC_COLS - 1) / LM_MAC_COLS));
+// 3. the gadget product of a batch of B columns at the level of `tb` under `key`, [ctx L + K][key_beta][2] whatever the
+// level (the RNS gadget does not depend on it): the limbs modulo P sit behind the context's L Q limbs, in the moduli
+// and in the stored key
+static int launch_ks_mac(lumen_ctx *ctx, const u64 *ext, const u64 *acc, const u64 *key, u64 *u, uint32_t B, KsTables *tb) {
+    const uint32_t L = tb->nl, K = ctx->K, pshift = ctx->L - L, key_beta = (ctx->L + K - 1) / K;
+    const dim3 grid(((ctx->N / LM_MAC_VEC + 255) / 256) * (L + K) * ((B + LM_MAC_COLS - 1) / LM_MAC_COLS));
+    hipLaunchKernelGGL(k_ks_mac, grid, dim3(256), 0, ctx->stream, ext, acc, key, u, B, L, K, tb->beta, pshift, key_beta, ctx->logN,
+                       ctx->mods);
+    LM_HIP(ctx, hipGetLastError());
+    return 0;
+}
+
+// 4b + 5. lift to Q, NTT, combine, automorphism: accumulated into out = in + ... (ACCUMULATE, k_moddown_ntt) or stored as a
+// plain gather (k_rotdown_ntt)
+template <bool ACCUMULATE>
+static int launch_moddown(lumen_ctx *ctx, const u64 *in, u64 *out, uint32_t B, const lm_galois_key &gk, KsTables *tb,
+                          const KsScratch &s) {
+    const uint32_t L = tb->nl, K = ctx->K;
+    const uint32_t *work_down = nullptr;
+    if (int rc = moddown_work_list(ctx, tb, B, &work_down)) return rc;
+    lm_prof_scope ps(ctx, ACCUMULATE ? "ks_moddown_ntt" : "ks_rotdown_ntt", (uint64_t)B * 2 * L);
+    return lm_for_logn(ctx, ctx->logN, [&](auto n) {
+        return lm_launch(ctx, ACCUMULATE ? k_moddown_ntt<n> : k_rotdown_ntt<n>, lm_geom_fwd(n), B * 2 * L, s.u, in, out,
+                         tb->d_bxp.get(), tb->d_pinv.get(), gk.d_index.get(), gk.d_inv_index.get(), work_down, B, L, K, ctx->mods,
+                         ctx->sh->tw_fwd.get());
+    });
 }
 
 } // namespace
@@ -902,7 +884,7 @@ static dim3 ks_mac_grid(const lumen_ctx *ctx, uint32_t B, uint32_t L) {
 // rotate_decompose, steps 1-2: the digits of c1 extended to every limb, in s.coef and s.ext.  It depends on the ciphertext
 // alone -- not on the key, not on the Galois element -- so several rotations of one ciphertext share it
 // (lumen_rotate_hoisted: [LATTIGO-RECALL] Evaluator.DecomposeNTT before AutomorphismHoisted).
-static int rotate_decompose(lumen_ctx *ctx, const u64 *acc, uint32_t B, KsTables *tb, const KsScratch &s) {
+int rotate_decompose(lumen_ctx *ctx, const u64 *acc, uint32_t B, KsTables *tb, const KsScratch &s) {
     const uint32_t N = ctx->N, L = tb->nl, K = ctx->K, beta = tb->beta;
     const uint32_t pshift = ctx->L - L; // the limbs modulo P sit behind the context's L Q limbs (moduli, twiddles)
     // 1. c1 -> coefficient domain, scaled for the basis extension, and the (hi, lo) packing of the two-limb
@@ -923,9 +905,7 @@ static int rotate_decompose(lumen_ctx *ctx, const u64 *acc, uint32_t B, KsTables
     }
     if (K == 2 && nf < beta) { // the digits the transform did not pack
         lm_prof_scope ps(ctx, "ks_pack_v", (uint64_t)B);
-        hipLaunchKernelGGL(k_pack_v, dim3(2048), dim3(256), 0, ctx->stream, s.coef + (size_t)2 * nf * N, (size_t)L * N,
-                           B, beta - nf, K, 2 * nf, L - 2 * nf, ctx->logN, ctx->mods);
-        LM_HIP(ctx, hipGetLastError());
+        if (int rc = lm_launch_pack_v(ctx, s.coef + (size_t)2 * nf * N, (size_t)L * N, B, beta - nf, K, 2 * nf, L - 2 * nf)) return rc;
     }
     // 2. digit extension + NTT
     {
@@ -946,18 +926,12 @@ static int rotate_decompose(lumen_ctx *ctx, const u64 *acc, uint32_t B, KsTables
 // in the coefficient domain and packed.  What follows is the seam between the ways a rotation ends: ModDown into an
 // accumulator (rotate_accumulate), ModDown into a plain gather (rotate_store) or, for the last rotation before a rescale,
 // the closing inverse transform (rotate_close).
-static int rotate_product(lumen_ctx *ctx, const u64 *acc, uint32_t B, const lm_galois_key &gk, KsTables *tb,
-                          const KsScratch &s) {
-    const uint32_t N = ctx->N, L = tb->nl, K = ctx->K, beta = tb->beta;
-    // the limbs modulo P sit behind the context's L Q limbs: in the moduli, the twiddles and the stored key, which is
-    // [ctx L + K][key_beta][2] whatever the level (the RNS gadget does not depend on it)
-    const uint32_t pshift = ctx->L - L, key_beta = (ctx->L + K - 1) / K;
+int rotate_product(lumen_ctx *ctx, const u64 *acc, uint32_t B, const lm_galois_key &gk, KsTables *tb, const KsScratch &s) {
+    const uint32_t N = ctx->N, L = tb->nl, K = ctx->K;
     // 3. gadget product
     {
         lm_prof_scope ps(ctx, "ks_mac", (uint64_t)B);
-        hipLaunchKernelGGL(k_ks_mac, ks_mac_grid(ctx, B, L), dim3(256), 0, ctx->stream, s.ext, acc, gk.d_key.get(), s.u, B, L, K,
-                           beta, pshift, key_beta, ctx->logN, ctx->mods);
-        LM_HIP(ctx, hipGetLastError());
+        if (int rc = launch_ks_mac(ctx, s.ext, acc, gk.d_key.get(), s.u, B, tb)) return rc;
     }
     // 4a. P limbs of u -> coefficient domain (in place)
     {
@@ -968,9 +942,7 @@ static int rotate_product(lumen_ctx *ctx, const u64 *acc, uint32_t B, const lm_g
             return rc;
         if (K == 2) {
             lm_prof_scope ps(ctx, "ks_pack_v", (uint64_t)B);
-            hipLaunchKernelGGL(k_pack_v, dim3(2048), dim3(256), 0, ctx->stream, up, pstride, B * 2, 1u, K, ctx->L, K,
-                               ctx->logN, ctx->mods);
-            LM_HIP(ctx, hipGetLastError());
+            if (int rc = lm_launch_pack_v(ctx, up, pstride, B * 2, 1u, K, ctx->L, K)) return rc;
         }
     }
     return 0;
@@ -981,31 +953,12 @@ int rotate_accumulate(lumen_ctx *ctx, const u64 *acc, u64 *acc_out, uint32_t B, 
                       KsTables *tb, const KsScratch &s) {
     if (int rc = rotate_decompose(ctx, acc, B, tb, s)) return rc;
     if (int rc = rotate_product(ctx, acc, B, gk, tb, s)) return rc;
-    const uint32_t L = tb->nl, K = ctx->K;
-    // 4b + 5. lift to Q, NTT, combine, automorphism, accumulate
-    {
-        const uint32_t *work_down = nullptr;
-        if (int rc = moddown_work_list(ctx, tb, B, &work_down)) return rc;
-        lm_prof_scope ps(ctx, "ks_moddown_ntt", (uint64_t)B * 2 * L);
-        return lm_for_logn(ctx, ctx->logN, [&](auto n) {
-            return lm_launch(ctx, k_moddown_ntt<n>, lm_geom_fwd(n), B * 2 * L, s.u, acc, acc_out, tb->d_bxp.get(), tb->d_pinv.get(),
-                             gk.d_index.get(), gk.d_inv_index.get(), work_down, B, L, K, ctx->mods, ctx->sh->tw_fwd.get());
-        });
-    }
+    return launch_moddown<true>(ctx, acc, acc_out, B, gk, tb, s);
 }
-
-namespace {
 
 // After rotate_product: out = Rot_galEl(in) for every column, canonical, [B][2][L][N] both; `out` is another block than `in`.
 int rotate_store(lumen_ctx *ctx, const u64 *in, u64 *out, uint32_t B, const lm_galois_key &gk, KsTables *tb, const KsScratch &s) {
-    const uint32_t L = tb->nl, K = ctx->K;
-    const uint32_t *work_down = nullptr;
-    if (int rc = moddown_work_list(ctx, tb, B, &work_down)) return rc;
-    lm_prof_scope ps(ctx, "ks_rotdown_ntt", (uint64_t)B * 2 * L);
-    return lm_for_logn(ctx, ctx->logN, [&](auto n) {
-        return lm_launch(ctx, k_rotdown_ntt<n>, lm_geom_fwd(n), B * 2 * L, s.u, in, out, tb->d_bxp.get(), tb->d_pinv.get(),
-                         gk.d_index.get(), gk.d_inv_index.get(), work_down, B, L, K, ctx->mods, ctx->sh->tw_fwd.get());
-    });
+    return launch_moddown<false>(ctx, in, out, B, gk, tb, s);
 }
 
 // coef_out = the coefficient form of acc + Rot_galEl(acc), [B][2][L][N]: the last rotation before a rescale (lm_ks_close.hip)
@@ -1018,36 +971,6 @@ int rotate_close(lumen_ctx *ctx, const u64 *acc, u64 *coef_out, uint32_t B, cons
     return ks_close_launch(ctx, acc, coef_out, B, gk, gal_el, tb, s, work_down);
 }
 
-// InnerSum(., 1, n) of the B columns of acc, in place.  With close_out (a rescale follows and n > 1) the last rotation
-// leaves its result there in coefficient form instead, and acc holds nothing the caller may use.
-int inner_sum_batch(lumen_ctx *ctx, u64 *acc, uint32_t B, uint32_t n, KsTables *tb, const KsScratch &s,
-                    u64 *close_out = nullptr) {
-    uint64_t gal[64];
-    const uint32_t cnt = lumen_inner_sum_galois_elements(ctx, n, gal);
-    LM_CHECK(ctx, !close_out || cnt, "InnerSum(%u) has no rotation to close", n);
-    for (uint32_t r = 0; r < cnt; r++) {
-        const lm_galois_key *gk; // (an entry of the map never moves or goes, and a key loaded again keeps its blocks)
-        {
-            LM_SHARED_LOCK(ctx);
-            auto it = ctx->gkeys.find(gal[r]);
-            LM_CHECK(ctx, it != ctx->gkeys.end(), "Galois key for element %llu not loaded",
-                     (unsigned long long)gal[r]);
-            gk = &it->second;
-        }
-        // ping-pong: the automorphism reads two positions of the old accumulator per output
-        u64 *src = (r & 1) ? s.acc2 : acc, *dst = (r & 1) ? acc : s.acc2;
-        if (close_out && r + 1 == cnt) // whichever of the two blocks the rotations so far have left the accumulator in
-            return rotate_close(ctx, src, close_out, B, *gk, gal[r], tb, s);
-        if (int rc = rotate_accumulate(ctx, src, dst, B, *gk, tb, s)) return rc;
-    }
-    if (cnt & 1)
-        LM_HIP(ctx, hipMemcpyAsync(acc, s.acc2, (size_t)B * 2 * tb->nl * ctx->N * 8, hipMemcpyDeviceToDevice,
-                                   ctx->stream));
-    return 0;
-}
-
-} // namespace
-
 // Times the gadget product alone on caller-chosen device blocks: how its speed depends on WHERE in HBM its
 // three streams sit (tools/ks_mac_placement.py).  A NULL block = the one the product itself uses (the key
 // switch's scratch, the first Galois key loaded).  The blocks' contents are whatever they hold: the kernel's
@@ -1058,7 +981,7 @@ extern "C" int lumen_ks_mac_probe(lumen_ctx *ctx, uint32_t batch, const void *ex
     LM_ENTER(ctx);
     KsTables *tb = nullptr;
     if (int rc = get_tables(ctx, &tb)) return rc;
-    const uint32_t N = ctx->N, L = ctx->L, K = ctx->K, B = batch ? batch : ks_batch(ctx);
+    const uint32_t N = ctx->N, L = ctx->L, B = batch ? batch : ks_batch(ctx);
     LM_CHECK(ctx, B <= 65535 && reps >= 1 && reps <= 100000, "lumen_ks_mac_probe: batch %u / reps %u out of range", B, reps);
     KsScratch s;
     if (int rc = get_scratch(ctx, B, tb, &s)) return rc;
@@ -1071,292 +994,16 @@ extern "C" int lumen_ks_mac_probe(lumen_ctx *ctx, uint32_t batch, const void *ex
     }
     const u64 *pe = ext ? (const u64 *)ext : s.ext;
     u64 *pu = u ? (u64 *)u : s.u;
-    const dim3 grid = ks_mac_grid(ctx, B, L);
-    auto launch = [&] {
-        hipLaunchKernelGGL(k_ks_mac, grid, dim3(256), 0, ctx->stream, pe, (const u64 *)acc, (const u64 *)key, pu, B, L, K,
-                           tb->beta, 0u, tb->beta, ctx->logN, ctx->mods);
-    };
-    for (int i = 0; i < 3; i++) launch();
-    LM_HIP(ctx, hipGetLastError());
+    auto launch = [&] { return launch_ks_mac(ctx, pe, (const u64 *)acc, (const u64 *)key, pu, B, tb); }; // the top level's
+    for (int i = 0; i < 3; i++)
+        if (int rc = launch()) return rc;
     LM_HIP(ctx, hipEventRecord(ctx->tm0, ctx->stream));
-    for (uint32_t i = 0; i < reps; i++) launch();
-    LM_HIP(ctx, hipGetLastError());
+    for (uint32_t i = 0; i < reps; i++)
+        if (int rc = launch()) return rc;
     LM_HIP(ctx, hipEventRecord(ctx->tm1, ctx->stream));
     LM_HIP(ctx, hipEventSynchronize(ctx->tm1));
     float ms = 0;
     LM_HIP(ctx, hipEventElapsedTime(&ms, ctx->tm0, ctx->tm1));
     *ms_per_launch = ms / (float)reps;
     return 0;
-}
-
-static int check_inner_sum_level(lumen_ctx *ctx, const lumen_set *in, const char *what) {
-    LM_FULL_WIDTH(ctx, in, what);
-    // lumen_inner_sum and lumen_matrix_inner_sum serve the top level, where the path calls InnerSum
-    // (fhe/ligero.go:319-325 -- MulNew and InnerSum precede the rescale), and refuse anything else: their callers
-    // rely on that.  The *_at_level entry points take a set at any level of the chain.
-    LM_CHECK(ctx, in->nl == ctx->L, "%s is implemented at the top level only (set has %u of %u limbs)", what,
-             in->nl, ctx->L);
-    return 0;
-}
-
-namespace {
-
-// InnerSum(ct, 1, n) at the level of `in` (checked by the caller).  The scratch is the top level's whatever the level:
-// a first call low in the chain must not run the placement selection on small blocks that the first call at the top
-// would regrow.
-int inner_sum_at(lumen_ctx *ctx, const lumen_set *in, uint32_t n, lumen_set **out) {
-    LM_CHECK(ctx, n && !(n & (n - 1)) && n <= ctx->N, "InnerSum length %u is not a power of two <= N", n);
-    KsTables *top = nullptr, *tb = nullptr;
-    if (int rc = get_tables(ctx, &top)) return rc;
-    if (int rc = get_tables_at(ctx, in->nl, &tb)) return rc;
-    lumen_set *o = nullptr;
-    if (int rc = lumen_set_create(ctx, in->count, in->nl, &o)) return rc;
-    lm_set_guard og(ctx, o);
-    if (in->words)
-        LM_HIP(ctx, hipMemcpyAsync(o->d, in->d, in->words * 8, hipMemcpyDeviceToDevice, ctx->stream));
-    const uint32_t Bmax = std::min<uint32_t>(ks_batch(ctx), std::max(in->count, 1u));
-    KsScratch s;
-    if (int rc = get_scratch(ctx, Bmax, top, &s)) return rc;
-    const size_t ctw = (size_t)2 * in->nl * ctx->N;
-    for (uint32_t first = 0; first < in->count; first += Bmax) {
-        const uint32_t B = std::min(Bmax, in->count - first);
-        if (int rc = inner_sum_batch(ctx, o->d + (size_t)first * ctw, B, n, tb, s)) return rc;
-    }
-    if (int rc = acc_canon(ctx, o->d, o->words, in->nl)) return rc; // the rotations leave [0, 2q)
-    *out = og.release();
-    return 0;
-}
-
-// matrixInnerSumEval at the level of `matrix` (checked by the caller): nl limbs in, min(nl, 2) out
-int matrix_inner_sum_at(lumen_ctx *ctx, const lumen_set *matrix, const uint64_t *pt, uint32_t rows, lumen_set **out) {
-    LM_CHECK(ctx, rows && !(rows & (rows - 1)) && rows <= ctx->N, "rows=%u is not a power of two <= N", rows);
-    KsTables *top = nullptr, *tb = nullptr;
-    if (int rc = get_tables(ctx, &top)) return rc;
-    if (int rc = get_tables_at(ctx, matrix->nl, &tb)) return rc;
-    u64 *ptT = nullptr;
-    if (int rc = upload_ptT(ctx, pt, matrix->nl, &ptT)) return rc;
-    const uint32_t N = ctx->N, L = matrix->nl;
-    const uint32_t target = std::min<uint32_t>(2, L);
-    lumen_set *o = nullptr;
-    if (int rc = lumen_set_create(ctx, matrix->count, target, &o)) return rc;
-    lm_set_guard og(ctx, o);
-    const uint32_t Bmax = std::min<uint32_t>(ks_batch(ctx), std::max(matrix->count, 1u));
-    // the rescale to level 1 runs on groups of batches: one batch alone (2*B polynomials) does not
-    // fill the 256 CUs in the kernels that take one workgroup per polynomial
-    const uint32_t group = std::min<uint32_t>(8 * Bmax, std::max(matrix->count, 1u));
-    KsScratch s[2];
-    const size_t ctw = (size_t)2 * L * N, octw = (size_t)2 * target * N;
-    const size_t group_bytes = (size_t)group * 2 * ctx->L * N * 8; // sized for the top level, as the key switch's scratch
-    u64 *acc = nullptr; // the group's accumulators: placed together with the key switch's scratch (get_scratch)
-    if (get_scratch(ctx, Bmax, top, &s[0], 0, &acc, group_bytes) || (ks_lanes(ctx) > 1 && get_scratch(ctx, Bmax, top, &s[1], 1)))
-        return 1;
-    u64 *work = (u64 *)lm_scratch(ctx, "rescale_work", group_bytes);
-    u64 *tbuf = (u64 *)lm_scratch(ctx, "rescale_t", (size_t)group * 2 * N * 8);
-    if (!acc || !work || !tbuf) return 1;
-    // The last rotation of a batch writes the rescale's coefficient-form input itself, at the batch's place in `work`
-    // (LUMEN_KS_CLOSE_FUSED, lm_ks_close.hip): when a rescale follows, there is a rotation (rows > 1) and the chain has
-    // the coefficient form's tables.
-    bool close = false;
-    if (L > target && rows > 1 && ctx->tune.ks_close_fused) {
-        const int rc = lm_rescale_coef_ready(ctx);
-        if (rc && rc != 2) return rc;
-        close = rc == 0;
-    }
-    for (uint32_t g0 = 0; g0 < matrix->count; g0 += group) {
-        const uint32_t gn = std::min(group, matrix->count - g0);
-        // fork: the second lane starts after everything already enqueued on the main stream
-        if (ks_lanes(ctx) > 1) {
-            LM_HIP(ctx, hipEventRecord(ctx->ev_fork, ctx->stream));
-            LM_HIP(ctx, hipStreamWaitEvent(ctx->stream2, ctx->ev_fork, 0));
-        }
-        uint32_t lane = 0;
-        for (uint32_t first = 0; first < gn; first += Bmax, lane = (lane + 1) % ks_lanes(ctx)) {
-            const uint32_t B = std::min(Bmax, gn - first);
-            u64 *a = acc + (size_t)first * ctw;
-            LaneGuard guard(ctx, (int)lane);
-            if (int rc = launch_mul_plain(ctx, matrix->d + (size_t)(g0 + first) * ctw, a, ptT, (size_t)B * ctw, L, B)) // ligero.go:319
-                return rc;
-            if (int rc = inner_sum_batch(ctx, a, B, rows, tb, s[lane], close ? work + (size_t)first * ctw : nullptr)) // ligero.go:325
-                return rc;
-        }
-        // join: the rescale of the group needs both lanes
-        if (ks_lanes(ctx) > 1) {
-            LM_HIP(ctx, hipEventRecord(ctx->ev_join, ctx->stream2));
-            LM_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));
-        }
-        // ligero.go:331-333
-        if (close) { // the inverse transforms are done
-            if (int rc = lm_rescale_polys_from_coef(ctx, work, L, o->d + (size_t)g0 * octw, target, gn * 2)) return rc;
-        } else if (L > target) {
-            if (int rc = lm_rescale_polys(ctx, acc, L, o->d + (size_t)g0 * octw, target, gn * 2, work, tbuf)) return rc;
-        } else {
-            if (int rc = acc_canon(ctx, acc, (size_t)gn * ctw, L)) return rc; // no rescale to absorb the lazy range
-            LM_HIP(ctx, hipMemcpyAsync(o->d + (size_t)g0 * octw, acc, (size_t)gn * ctw * 8, hipMemcpyDeviceToDevice,
-                                       ctx->stream));
-        }
-    }
-    *out = og.release();
-    return 0;
-}
-
-} // namespace
-
-extern "C" int lumen_inner_sum(lumen_ctx *ctx, const lumen_set *in, uint32_t n, lumen_set **out) {
-    LM_CHECK(nullptr, ctx && in && out, "lumen_inner_sum: NULL argument");
-    LM_ENTER(ctx);
-    if (int rc = check_inner_sum_level(ctx, in, "InnerSum")) return rc;
-    return inner_sum_at(ctx, in, n, out);
-}
-
-extern "C" int lumen_inner_sum_at_level(lumen_ctx *ctx, const lumen_set *in, uint32_t n, lumen_set **out) {
-    LM_CHECK(nullptr, ctx && in && out, "lumen_inner_sum_at_level: NULL argument");
-    LM_ENTER(ctx);
-    if (int rc = check_level_of_chain(ctx, in, "InnerSum")) return rc;
-    return inner_sum_at(ctx, in, n, out);
-}
-
-extern "C" int lumen_matrix_inner_sum(lumen_ctx *ctx, const lumen_set *matrix, const uint64_t *pt,
-                                      uint32_t rows, lumen_set **out) {
-    LM_CHECK(nullptr, ctx && matrix && pt && out, "lumen_matrix_inner_sum: NULL argument");
-    LM_ENTER(ctx);
-    if (int rc = check_inner_sum_level(ctx, matrix, "matrixInnerSumEval")) return rc;
-    return matrix_inner_sum_at(ctx, matrix, pt, rows, out);
-}
-
-extern "C" int lumen_matrix_inner_sum_at_level(lumen_ctx *ctx, const lumen_set *matrix, const uint64_t *pt,
-                                               uint32_t rows, lumen_set **out) {
-    LM_CHECK(nullptr, ctx && matrix && pt && out, "lumen_matrix_inner_sum_at_level: NULL argument");
-    LM_ENTER(ctx);
-    if (int rc = check_level_of_chain(ctx, matrix, "matrixInnerSumEval")) return rc;
-    return matrix_inner_sum_at(ctx, matrix, pt, rows, out);
-}
-
-// ---- the rotation alone: Evaluator.Automorphism / RotateColumnsNew / RotateRowsNew / RotateHoistedNew (the evaluator that
-// ServerBFV embeds, fhe/bfv.go:13-21).  out = sigma_g(c0 + k0(c1), k1(c1)): decompose, product, and a ModDown that ends in
-// a plain gather (k_rotdown_ntt).  The input set is read in place and the output set is the destination: no accumulator,
-// no ping-pong, no copy, no canonicalising pass.  Batching, lanes, per-level tables and the scratch sized and placed for the
-// top level are lumen_mul_relin's.
-extern "C" uint64_t lumen_galois_element(const lumen_ctx *ctx, int64_t k) {
-    if (!ctx || ctx->N < 2) return 0;
-    // [LATTIGO-RECALL] rlwe.Parameters.GaloisElement: 5 generates the column rotations, its order mod 2N is N / 2
-    const int64_t order = (int64_t)(ctx->N >> 1);
-    int64_t e = k % order;
-    if (e < 0) e += order;
-    const uint64_t mask = 2ull * ctx->N - 1;
-    uint64_t g = 1, b = 5;
-    for (; e; e >>= 1, b = (b * b) & mask)
-        if (e & 1) g = (g * b) & mask;
-    return g;
-}
-
-namespace {
-
-// new sets that go back to the pool unless the call succeeds
-struct NewSets {
-    lumen_ctx *ctx;
-    std::vector<lumen_set *> v;
-    explicit NewSets(lumen_ctx *c) : ctx(c) {}
-    ~NewSets() {
-        for (lumen_set *s : v)
-            if (s) lumen_set_destroy(ctx, s);
-    }
-    NewSets(const NewSets &) = delete;
-    NewSets &operator=(const NewSets &) = delete;
-};
-
-#define LM_MAX_HOISTED 64u
-
-// outs[i] = Automorphism(in, gal_els[i]) for the n_els elements; the decomposition of a batch runs once, whatever n_els
-int rotate_sets(lumen_ctx *ctx, const lumen_set *in, const uint64_t *gal_els, uint32_t n_els, lumen_set **outs, const char *what) {
-    for (uint32_t i = 0; i < n_els; i++) outs[i] = nullptr;
-    if (int rc = check_level_of_chain(ctx, in, what)) return rc;
-    LM_CHECK(ctx, n_els <= LM_MAX_HOISTED, "%s: %u Galois elements, at most %u in one call", what, n_els, LM_MAX_HOISTED);
-    bool keyed = false;
-    for (uint32_t i = 0; i < n_els; i++) {
-        LM_CHECK(ctx, (gal_els[i] & 1) && gal_els[i] < 2ull * ctx->N, "%s: Galois element %llu is not an odd residue mod 2N", what,
-                 (unsigned long long)gal_els[i]);
-        keyed = keyed || gal_els[i] != 1;
-    }
-    // the identity is a copy and needs no key ([LATTIGO-RECALL] Evaluator.Automorphism returns the input for galEl == 1)
-    KsTables *top = nullptr, *tb = nullptr;
-    std::vector<const lm_galois_key *> keys(n_els, nullptr);
-    if (keyed) {
-        LM_CHECK(ctx, ctx->K >= 1, "parameters have no special primes: key switching unavailable");
-        if (int rc = get_tables(ctx, &top)) return rc; // (refuses K > 2, as InnerSum does)
-        if (int rc = get_tables_at(ctx, in->nl, &tb)) return rc;
-        LM_SHARED_LOCK(ctx); // (an entry of the map never moves or goes, and a key loaded again keeps its blocks)
-        for (uint32_t i = 0; i < n_els; i++) {
-            if (gal_els[i] == 1) continue;
-            auto it = ctx->gkeys.find(gal_els[i]);
-            LM_CHECK(ctx, it != ctx->gkeys.end() && it->second.d_key && it->second.d_index && it->second.d_inv_index,
-                     "Galois key for element %llu not loaded", (unsigned long long)gal_els[i]);
-            keys[i] = &it->second;
-        }
-    }
-    const uint32_t count = in->count, nl = in->nl;
-    NewSets made(ctx);
-    made.v.assign(n_els, nullptr);
-    for (uint32_t i = 0; i < n_els; i++)
-        if (int rc = lumen_set_create(ctx, count, nl, &made.v[i])) return rc;
-    if (count) {
-        for (uint32_t i = 0; i < n_els; i++)
-            if (gal_els[i] == 1)
-                LM_HIP(ctx, hipMemcpyAsync(made.v[i]->d, in->d, in->words * 8, hipMemcpyDeviceToDevice, ctx->stream));
-    }
-    if (count && keyed) {
-        const uint32_t Bmax = std::min<uint32_t>(ks_batch(ctx), count), lanes = ks_lanes(ctx);
-        const size_t ctw = (size_t)2 * nl * ctx->N;
-        KsScratch s[2];
-        if (get_scratch(ctx, Bmax, top, &s[0], 0) || (lanes > 1 && get_scratch(ctx, Bmax, top, &s[1], 1))) return 1;
-        if (lanes > 1) { // fork: the second lane starts after everything already enqueued on the main stream
-            LM_HIP(ctx, hipEventRecord(ctx->ev_fork, ctx->stream));
-            LM_HIP(ctx, hipStreamWaitEvent(ctx->stream2, ctx->ev_fork, 0));
-        }
-        uint32_t lane = 0;
-        for (uint32_t first = 0; first < count; first += Bmax, lane = (lane + 1) % lanes) {
-            const uint32_t B = std::min(Bmax, count - first);
-            const u64 *src = in->d + (size_t)first * ctw;
-            LaneGuard guard(ctx, (int)lane);
-            if (int rc = rotate_decompose(ctx, src, B, tb, s[lane])) return rc; // once per batch: s.ext survives the loop
-            for (uint32_t i = 0; i < n_els; i++) {
-                if (!keys[i]) continue;
-                if (int rc = rotate_product(ctx, src, B, *keys[i], tb, s[lane])) return rc; // s.u, rewritten per element
-                if (int rc = rotate_store(ctx, src, made.v[i]->d + (size_t)first * ctw, B, *keys[i], tb, s[lane])) return rc;
-            }
-        }
-        if (lanes > 1) { // join: the caller reads the sets on the main stream
-            LM_HIP(ctx, hipEventRecord(ctx->ev_join, ctx->stream2));
-            LM_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));
-        }
-    }
-    for (uint32_t i = 0; i < n_els; i++) outs[i] = made.v[i], made.v[i] = nullptr;
-    return 0;
-}
-
-} // namespace
-
-extern "C" int lumen_automorphism(lumen_ctx *ctx, const lumen_set *in, uint64_t gal_el, lumen_set **out) {
-    LM_CHECK(nullptr, ctx && in && out, "lumen_automorphism: NULL argument");
-    LM_ENTER(ctx);
-    return rotate_sets(ctx, in, &gal_el, 1, out, "lumen_automorphism");
-}
-
-extern "C" int lumen_rotate_columns(lumen_ctx *ctx, const lumen_set *in, int64_t k, lumen_set **out) {
-    LM_CHECK(nullptr, ctx && in && out, "lumen_rotate_columns: NULL argument");
-    LM_ENTER(ctx);
-    const uint64_t g = lumen_galois_element(ctx, k);
-    return rotate_sets(ctx, in, &g, 1, out, "lumen_rotate_columns");
-}
-
-extern "C" int lumen_rotate_rows(lumen_ctx *ctx, const lumen_set *in, lumen_set **out) {
-    LM_CHECK(nullptr, ctx && in && out, "lumen_rotate_rows: NULL argument");
-    LM_ENTER(ctx);
-    const uint64_t g = 2ull * ctx->N - 1; // [LATTIGO-RECALL] GaloisElementForRowRotation
-    return rotate_sets(ctx, in, &g, 1, out, "lumen_rotate_rows");
-}
-
-extern "C" int lumen_rotate_hoisted(lumen_ctx *ctx, const lumen_set *in, const uint64_t *gal_els, uint32_t n_els, lumen_set **outs) {
-    LM_CHECK(nullptr, ctx && in && gal_els && outs, "lumen_rotate_hoisted: NULL argument");
-    LM_ENTER(ctx);
-    return rotate_sets(ctx, in, gal_els, n_els, outs, "lumen_rotate_hoisted");
 }

@@ -1,4 +1,4 @@
-// The closing rotation of an InnerSum that a rescale follows (matrixInnerSumEval, lm_keyswitch.hip).
+// The closing rotation of an InnerSum that a rescale follows (matrixInnerSumEval, lm_innersum.hip).
 //
 // A rotation ends in k_moddown_ntt: per (column, polynomial, Q limb t) it lifts the P limbs of the gadget product into
 // q_t, runs a FORWARD transform of that lift and forms

@@ -1,6 +1,9 @@
-// Host-side declarations shared by the units of the Galois key switch: the rotation (lm_keyswitch.hip), the placement of
-// its scratch buffers (lm_ks_scratch.hip), the ciphertext x plaintext product that precedes it (lm_mulplain.hip) and the
-// ciphertext x ciphertext product that ends in one (lm_mulrelin.hip).
+// Host-side declarations shared by the units of the hybrid key switch: the rotation's kernels and steps
+// (lm_keyswitch.hip), the batch driver of its callers (lm_ks_batch.hip), the callers themselves -- InnerSum and
+// matrixInnerSumEval (lm_innersum.hip), the rotation on its own (lm_rotate.hip), the ciphertext x ciphertext product
+// that ends in a key switch (lm_mulrelin.hip) --, the placement of the scratch buffers (lm_ks_scratch.hip), the closing
+// rotation before a rescale (lm_ks_close.hip), the switching keys (lm_ks_key.hip) and the ciphertext x plaintext
+// product that precedes an InnerSum (lm_mulplain.hip).
 #pragma once
 #include "lm_ks_dev.h"
 
@@ -26,10 +29,20 @@ struct KsScratch {
     u64 *coef, *ext, *u, *acc2;
 };
 
-// acc, acc_out: [B][2][nl][N] at the level of `tb`; acc_out = acc + Rot_galEl(acc) for every column (lm_keyswitch.hip).
+// ---- the steps of a rotation of B columns (lm_keyswitch.hip).  acc, in, out: [B][2][nl][N] at the level of `tb`.
 // s: scratch of a batch of B columns at the TOP level, of which a lower level uses a prefix of every block.
+// steps 1-2: the digits of c1 extended to every limb, in s.coef and s.ext; depends on the ciphertext alone
+int rotate_decompose(lumen_ctx *ctx, const u64 *acc, uint32_t B, KsTables *tb, const KsScratch &s);
+// steps 3-4a under one key: the gadget product in s.u, its limbs modulo P in the coefficient domain and packed
+int rotate_product(lumen_ctx *ctx, const u64 *acc, uint32_t B, const lm_galois_key &gk, KsTables *tb, const KsScratch &s);
+// all steps: acc_out = acc + Rot_galEl(acc) for every column, lazy ([0, 2q))
 int rotate_accumulate(lumen_ctx *ctx, const u64 *acc, u64 *acc_out, uint32_t B, const lm_galois_key &gk,
                       KsTables *tb, const KsScratch &s);
+// after rotate_product: out = Rot_galEl(in) for every column, canonical; `out` is another block than `in`
+int rotate_store(lumen_ctx *ctx, const u64 *in, u64 *out, uint32_t B, const lm_galois_key &gk, KsTables *tb, const KsScratch &s);
+// all steps, the last rotation before a rescale: coef_out = the coefficient form of acc + Rot_galEl(acc)
+int rotate_close(lumen_ctx *ctx, const u64 *acc, u64 *coef_out, uint32_t B, const lm_galois_key &gk, uint64_t gal_el,
+                 KsTables *tb, const KsScratch &s);
 // the last rotation of an InnerSum that a rescale follows, after its steps 1-4a (lm_ks_close.hip): out, [B][2][nl][N], gets
 // the COEFFICIENT form of acc + Rot_galEl(acc), canonical -- what the rescale's inverse transform would have made of it.
 // work_down: ModDown's work list for B columns at the level of `tb`.
@@ -47,9 +60,12 @@ int launch_mul_plain(lumen_ctx *ctx, const u64 *ct, u64 *out, const u64 *ptT, si
 
 // the relinearisation key as a switching key with identity gather tables (lm_ks_key.hip); empty before lumen_load_relin_key
 std::shared_ptr<lm_galois_key> lm_relin_key(lumen_ctx *ctx);
-// a set at a level of the chain: full width, 1 <= nl <= L (lm_keyswitch.hip)
+// the loaded Galois key of an element, complete (key, gather table and its inverse), or a refusal (lm_ks_key.hip).  An
+// entry of the map never moves or goes, and a key loaded again keeps its blocks: the pointer outlives the lock.
+int ks_find_key(lumen_ctx *ctx, uint64_t gal_el, const lm_galois_key **gk);
+// a set at a level of the chain: full width, 1 <= nl <= L (lm_ks_batch.hip)
 int check_level_of_chain(lumen_ctx *ctx, const lumen_set *in, const char *what);
-// the batching of a key switch, shared by InnerSum and the relinearisation (lm_keyswitch.hip)
+// the batching of a key switch: columns per batch and lanes of the context (lm_ks_batch.hip)
 uint32_t ks_batch(const lumen_ctx *ctx);
 uint32_t ks_lanes(const lumen_ctx *ctx);
 // enqueue on the context's second stream for the lifetime of the guard
@@ -61,3 +77,50 @@ struct LaneGuard {
     }
     ~LaneGuard() { ctx->stream = saved; }
 };
+
+// ---- the batch driver of the key switch's callers (lm_ks_batch.hip): `count` ciphertexts at the level of nl limbs go
+// through the key switch in BATCHES of at most Bmax columns, which alternate between the LANES; a caller with an
+// accumulator for a GROUP of batches (matrixInnerSumEval, lumen_mul_relin: every batch works in its own slice of it)
+// takes groups of 8 batches, the others one group of everything.
+struct KsRun {
+    KsTables *top = nullptr, *tb = nullptr; // the top level's tables (they size the scratch) and the level's
+    uint32_t Bmax = 0, group = 0, lanes = 1;
+    bool grouped = false;
+    size_t group_bytes = 0; // a group's accumulators at the TOP level
+    KsScratch s[2] = {};    // per lane
+    u64 *acc = nullptr;     // the group's accumulators (grouped runs)
+};
+// Opens a run in two steps, because a caller's own refusals and allocations stand between them.  ks_run_open: both table
+// sets (it refuses what the key switch cannot serve) and the batching; allocates no scratch.  max_lanes: 1 keeps the run
+// on the main stream, 2 gives it the context's lanes.  ks_run_scratch: the lanes' scratch and the group's accumulators.
+int ks_run_open(lumen_ctx *ctx, uint32_t count, uint32_t nl, uint32_t max_lanes, bool group_acc, KsRun *run);
+int ks_run_scratch(lumen_ctx *ctx, KsRun *run);
+// The loop: per group fork, batch(g0, first, B, s, acc) for every batch -- ciphertexts [g0 + first, g0 + first + B) of the
+// caller's, on the batch's lane, s that lane's scratch, acc the batch's slice of the group's accumulators (words of ctw per
+// ciphertext; NULL without) --, join, then end_of_group(g0, gn) on the main stream.  The first non-zero status ends the run.
+template <class Batch, class Group>
+int ks_run(lumen_ctx *ctx, const KsRun &run, uint32_t count, size_t ctw, Batch &&batch, Group &&end_of_group) {
+    for (uint32_t g0 = 0; g0 < count; g0 += run.group) {
+        const uint32_t gn = std::min(run.group, count - g0);
+        if (run.lanes > 1) { // fork: the second lane starts after everything already enqueued on the main stream
+            LM_HIP(ctx, hipEventRecord(ctx->ev_fork, ctx->stream));
+            LM_HIP(ctx, hipStreamWaitEvent(ctx->stream2, ctx->ev_fork, 0));
+        }
+        uint32_t lane = 0;
+        for (uint32_t first = 0; first < gn; first += run.Bmax, lane = (lane + 1) % run.lanes) {
+            const uint32_t B = std::min(run.Bmax, gn - first);
+            LaneGuard guard(ctx, (int)lane);
+            if (int rc = batch(g0, first, B, run.s[lane], run.acc ? run.acc + (size_t)first * ctw : nullptr)) return rc;
+        }
+        if (run.lanes > 1) { // join: the next group reuses the accumulators, and what follows reads on the main stream
+            LM_HIP(ctx, hipEventRecord(ctx->ev_join, ctx->stream2));
+            LM_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));
+        }
+        if (int rc = end_of_group(g0, gn)) return rc;
+    }
+    return 0;
+}
+template <class Batch>
+int ks_run(lumen_ctx *ctx, const KsRun &run, uint32_t count, size_t ctw, Batch &&batch) {
+    return ks_run(ctx, run, count, ctw, batch, [](uint32_t, uint32_t) { return 0; });
+}

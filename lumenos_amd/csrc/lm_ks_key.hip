@@ -2,7 +2,7 @@
 // elements an InnerSum needs, and a key's way to the device -- range check, Montgomery form with P^-1 folded in, the
 // gadget product's limb-major layout (ks_key_at) -- with the gather tables of its automorphism (the identity for the
 // relinearisation key).  key_to_device and key_install are shared by the two loaders.
-#include "lm_ks_dev.h"
+#include "lm_ks_host.h"
 
 extern "C" uint32_t lumen_inner_sum_galois_elements(const lumen_ctx *ctx, uint32_t n, uint64_t *gal_els) {
     // InnerSum(ct, 1, n), n a power of two: rotations by 2^i; when n == N the
@@ -149,6 +149,15 @@ extern "C" int lumen_load_relin_key(lumen_ctx *ctx, const uint64_t *evk, uint32_
 }
 
 std::shared_ptr<lm_galois_key> lm_relin_key(lumen_ctx *ctx) { return lm_ext_get<lm_galois_key>(ctx, RELIN_KEY); }
+
+int ks_find_key(lumen_ctx *ctx, uint64_t gal_el, const lm_galois_key **gk) {
+    LM_SHARED_LOCK(ctx);
+    auto it = ctx->gkeys.find(gal_el);
+    LM_CHECK(ctx, it != ctx->gkeys.end() && it->second.d_key && it->second.d_index && it->second.d_inv_index,
+             "Galois key for element %llu not loaded", (unsigned long long)gal_el);
+    *gk = &it->second;
+    return 0;
+}
 
 extern "C" int lumen_load_galois_key(lumen_ctx *ctx, uint64_t gal_el, const uint64_t *evk) {
     return lumen_load_galois_key_ex(ctx, gal_el, evk, 0);

@@ -1,5 +1,5 @@
 // Ciphertext x plaintext product, MulNew(ct, pt) (fhe/ligero.go:319): lumen_mul_plain, and step 0 of
-// matrixInnerSumEval (lm_keyswitch.hip, through lm_ks_host.h).
+// matrixInnerSumEval (lm_innersum.hip, through lm_ks_host.h).
 #include <cstring>
 
 #include "lm_ks_host.h"

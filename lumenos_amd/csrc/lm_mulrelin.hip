@@ -10,7 +10,7 @@
 // (k0, d2 + k1) in the lazy range [0, 2q); the tensor kernel therefore writes (0, d2) as the batch's accumulator and
 // (d0, d1 - d2) into the output set, and one closing elementwise pass adds the two and canonicalises (it stands where
 // k_acc_canon stands after an InnerSum).  Batching, lanes, per-level tables and the scratch sized and placed for the top
-// level are matrixInnerSumEval's.
+// level are the batch driver's (lm_ks_batch.hip), grouped as matrixInnerSumEval's.
 #include "lm_ks_host.h"
 
 // Block order of the two elementwise kernels: LIMB-MAJOR, blockIdx.x = (limb * count + ciphertext) * nblk + k, a block
@@ -183,50 +183,30 @@ extern "C" int lumen_mul_relin(lumen_ctx *ctx, const lumen_set *a, const lumen_s
     LM_ENTER(ctx);
     LM_CHECK(ctx, ctx->K >= 1, "parameters have no special primes: key switching unavailable");
     if (int rc = check_operands(ctx, a, b, "lumen_mul_relin")) return rc;
-    KsTables *top = nullptr, *tb = nullptr;
-    if (int rc = get_tables(ctx, &top)) return rc; // (refuses K > 2, as InnerSum does)
-    if (int rc = get_tables_at(ctx, a->nl, &tb)) return rc;
+    KsRun run;
+    if (int rc = ks_run_open(ctx, a->count, a->nl, 2, true, &run)) return rc; // (refuses K > 2, as InnerSum does)
     const std::shared_ptr<lm_galois_key> rlk = lm_relin_key(ctx); // kept alive for the call
     LM_CHECK(ctx, rlk && rlk->d_key, "lumen_mul_relin: no relinearisation key loaded (lumen_load_relin_key)");
-    const uint32_t N = ctx->N, nl = a->nl, count = a->count;
+    const uint32_t nl = a->nl, count = a->count;
     const bool bcast = b->count != count;
     lumen_set *o = nullptr;
     if (int rc = lumen_set_create(ctx, count, nl, &o)) return rc;
     lm_set_guard og(ctx, o);
+    const size_t ctw = (size_t)2 * nl * ctx->N;
+    if (int rc = ks_run_scratch(ctx, &run)) return rc;
     // batches of a group alternate between the lanes, each in its own slice of the group's accumulators, as in
     // matrixInnerSumEval; everything of a batch -- tensor, key switch, closing pass -- stays on its lane
-    const uint32_t Bmax = std::min<uint32_t>(ks_batch(ctx), std::max(count, 1u));
-    const uint32_t group = std::min<uint32_t>(8 * Bmax, std::max(count, 1u)), lanes = ks_lanes(ctx);
-    const size_t ctw = (size_t)2 * nl * N;
-    const size_t group_bytes = (size_t)group * 2 * ctx->L * N * 8; // sized for the top level, as the key switch's scratch
-    KsScratch s[2];
-    u64 *acc = nullptr;
-    if (get_scratch(ctx, Bmax, top, &s[0], 0, &acc, group_bytes) || (lanes > 1 && get_scratch(ctx, Bmax, top, &s[1], 1))) return 1;
-    if (!acc) return 1;
-    for (uint32_t g0 = 0; g0 < count; g0 += group) {
-        const uint32_t gn = std::min(group, count - g0);
-        if (lanes > 1) { // fork: the second lane starts after everything already enqueued on the main stream
-            LM_HIP(ctx, hipEventRecord(ctx->ev_fork, ctx->stream));
-            LM_HIP(ctx, hipStreamWaitEvent(ctx->stream2, ctx->ev_fork, 0));
-        }
-        uint32_t lane = 0;
-        for (uint32_t first = 0; first < gn; first += Bmax, lane = (lane + 1) % lanes) {
-            const uint32_t B = std::min(Bmax, gn - first);
-            const size_t at = (size_t)(g0 + first) * ctw;
-            u64 *d2 = acc + (size_t)first * ctw;
-            LaneGuard guard(ctx, (int)lane);
-            if (int rc = launch_tensor<true>(ctx, a->d + at, bcast ? b->d : b->d + at, bcast, o->d + at, d2, B, nl)) return rc;
-            if (int rc = rotate_accumulate(ctx, d2, s[lane].acc2, B, *rlk, tb, s[lane])) return rc;
-            lm_prof_scope ps(ctx, "relin_close", B);
-            hipLaunchKernelGGL(k_relin_close, dim3(mr_grid(ctx, B, nl)), dim3(256), 0, ctx->stream, o->d + at, s[lane].acc2, B, nl,
-                               ctx->logN, ctx->mods);
-            LM_HIP(ctx, hipGetLastError());
-        }
-        if (lanes > 1) { // join: the next group reuses the accumulators, and the caller reads the set on the main stream
-            LM_HIP(ctx, hipEventRecord(ctx->ev_join, ctx->stream2));
-            LM_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));
-        }
-    }
+    auto batch = [&](uint32_t g0, uint32_t first, uint32_t B, const KsScratch &s, u64 *d2) {
+        const size_t at = (size_t)(g0 + first) * ctw;
+        if (int rc = launch_tensor<true>(ctx, a->d + at, bcast ? b->d : b->d + at, bcast, o->d + at, d2, B, nl)) return rc;
+        if (int rc = rotate_accumulate(ctx, d2, s.acc2, B, *rlk, run.tb, s)) return rc;
+        lm_prof_scope ps(ctx, "relin_close", B);
+        hipLaunchKernelGGL(k_relin_close, dim3(mr_grid(ctx, B, nl)), dim3(256), 0, ctx->stream, o->d + at, s.acc2, B, nl, ctx->logN,
+                           ctx->mods);
+        LM_HIP(ctx, hipGetLastError());
+        return 0;
+    };
+    if (int rc = ks_run(ctx, run, count, ctw, batch)) return rc;
     ctx->mul_counter += count; // as lumen_mul_plain counts its products; lumen_mul_tensor, a parity hook, does not
     *out = og.release();
     return 0;

@@ -10,7 +10,7 @@ off.  The shapes are the smallest that can still go wrong:
                      end in a general Galois element (5, 25: strided source coefficients);
   1 and 3 columns  : one workgroup per (column, polynomial, limb), the work list of a batch that is no multiple of 8;
   LUMEN_KS_BATCH   : a batch edge inside a group (each batch writes at its own offset of the rescale's work block), and
-                     more batches than a group holds, on one and on two streams;
+                     more batches than a group holds, at the top level and below it, on one and on two streams;
   levels 3 and 4 of a five-limb chain (a single-limb last digit; one limb to drop, where the rescale otherwise keeps
   its per-step form), K = 1 (single-limb lift), moduli at the context's bound (the loader's lazy sums), and one column
   of the headline configuration."""
@@ -197,21 +197,24 @@ def test_the_switch_selects_the_route_and_the_scopes_count_it(cells):
 
 @gpu
 @pytest.mark.parametrize("lanes", [1, 2])
-@pytest.mark.parametrize("batch,cols", [(2, 3), (1, 9)])
-def test_batch_edge_and_group_offset(cells, batch, cols, lanes):
+@pytest.mark.parametrize("batch,cols,nl", [(2, 3, 5), (1, 9, 5), (1, 11, 3)], ids=["2-3", "1-9", "1-11-nl3"])
+def test_batch_edge_and_group_offset(cells, batch, cols, nl, lanes):
     """Batches of 2 + 1 columns in one group, and nine batches of one column in groups of eight and one: every batch
-    writes its coefficient-form limbs at its own place in the group's work block, on one stream or on two."""
+    writes its coefficient-form limbs at its own place in the group's work block, on one stream or on two.  The same
+    below the top level (lumen_matrix_inner_sum_at_level at nl = 3): eleven batches of one column, a group of eight and
+    a group of three in blocks that are sized for the top level."""
     cell = cells(10)
     P, ctx = cell.P, cell.ctx
     rows = 4
-    cts = random_cts(P, cols, 5, seed=97 + cols)
-    pt, _ = cell.want(5, rows)
+    cts = np.ascontiguousarray(random_cts(P, cols, 5, seed=97 + cols)[:, :, :nl])
+    pt, _ = cell.want(nl, rows)
     want = P.matrix_inner_sum(cts, pt, rows, cell.evks(rows))
     try:
         ctx.set_tuning("LUMEN_KS_BATCH", batch)
         ctx.set_tuning("LUMEN_KS_LANES", lanes)
         dev = ctx.upload(cts)
-        fused, plain = _both_routes(ctx, lambda: ctx.matrix_inner_sum(dev, pt, rows).download())
+        call = ctx.matrix_inner_sum if nl == P.L else ctx.matrix_inner_sum_at_level
+        fused, plain = _both_routes(ctx, lambda: call(dev, pt, rows).download())
     finally:
         ctx.set_tuning("LUMEN_KS_BATCH", 64)
         ctx.set_tuning("LUMEN_KS_LANES", 0)
