@@ -208,6 +208,11 @@ void lm_sync_all(lumen_ctx *ctx);
 void *lm_stage(lumen_ctx *ctx, size_t bytes);
 // host bytes -> device memory on the context's stream, through that staging buffer: `host` may change on return
 int lm_h2d_staged(lumen_ctx *ctx, void *dev, const void *host, size_t bytes);
+// whether `p` is page-locked host memory (lumen_host_alloc, hipHostMalloc / hipHostRegister): the DMA engines take it as it is
+bool lm_host_is_pinned(const void *p);
+// host -> device on the context's stream; returns when `host` may be reused.  A page-locked source is handed to the
+// DMA engine as it is, a pageable one goes through the two bounce buffers (lm_ctx.hip).
+int lm_h2d(lumen_ctx *ctx, void *dev, const void *host, size_t bytes);
 // device -> host bytes on the context's stream: a page-locked destination takes the DMA directly, a
 // pageable one goes through the two bounce buffers (lm_ctx.hip).  wait: return when `host` holds the data.
 int lm_d2h(lumen_ctx *ctx, void *host, const void *dev, size_t bytes, bool wait);
@@ -339,5 +344,13 @@ lm_modmap lm_map_q(uint32_t nl);
 lm_modmap lm_map_p(const lumen_ctx *ctx);
 // fhe.Encode with Enc(0) resident on the device; never blocks the host (lm_ctntt.hip)
 int lm_encode_dev(lumen_ctx *ctx, const lumen_set *matrix, const u64 *dzero, uint32_t rho_inv, lumen_set **encoded);
+// P(z) over one block of columns in three steps, so that a group can enqueue every rank's block before it waits for any
+// (lm_polyeval.hip): the argument checks alone; the evaluation enqueued on the context's stream (page-locked `values`
+// must stay alive until _finish); the wait for the block's partial
+int lm_poly_eval_check(lumen_ctx *ctx, const uint64_t *values, uint32_t rows, uint32_t count, uint64_t first_column,
+                       uint32_t cols, const char *what);
+int lm_poly_eval_enqueue(lumen_ctx *ctx, const uint64_t *values, uint32_t rows, uint32_t count, uint64_t first_column,
+                         uint32_t cols, uint64_t z, const char *what);
+int lm_poly_eval_finish(lumen_ctx *ctx, uint64_t *partial);
 // pooled timing events of a context (lm_ctx.hip)
 hipEvent_t lm_ev_get(lumen_ctx *ctx);

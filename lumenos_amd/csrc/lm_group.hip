@@ -12,6 +12,12 @@
 // ncclAllGather on the contexts' own streams.  RCCL is loaded at run time (dlopen): the library has no
 // link-time dependency on it, a one-GPU host never loads it, and a process that already carries an RCCL
 // (PyTorch's) shares that copy (same soname).
+//
+// Where things live: every exchange -- the all-to-all, the all-gather of the digests, the gather to the root and the
+// agreement step -- is a `collective` handed to run_collective(), which owns the skeleton (refusal of a poisoned group,
+// timing bracket, RCCL group, the copy transport's event protocol); a caller supplies what it moves.  agree() is the
+// one agreement step of the one-process-per-GPU form; group_make() is the body both constructors share.  An entry
+// point that enqueues on, or waits for, the ranks' streams begins with G_USABLE.
 #include <dlfcn.h>
 #include <rccl/rccl.h>
 
@@ -188,36 +194,6 @@ int use(lumen_group *g, uint32_t i) {
     return 0;
 }
 
-// timing bracket of one collective on local rank i's stream
-void stats_resolve(lumen_group *g, bool only_done);
-// (the caller has made rank i's device current: events are created on, and recorded from, the current device)
-void time_begin(lumen_group *g, const char *name, uint32_t i, uint64_t bytes) {
-    if (g->pend.size() > 512) stats_resolve(g, true); // a long run that never reads its statistics
-    lumen_group::pending p;
-    p.name = name, p.call = g->call_seq, p.local = i, p.bytes = bytes;
-    p.a = lm_ev_get(g->ctx[i]);
-    p.b = nullptr;
-    if (!p.a || hipEventRecord(p.a, g->ctx[i]->stream) != hipSuccess) { // no measurement rather than a bad event in the pool
-        (void)hipGetLastError();
-        if (p.a) hipEventDestroy(p.a);
-        return;
-    }
-    g->pend.push_back(p);
-}
-void time_end(lumen_group *g, uint32_t i) {
-    for (auto it = g->pend.rbegin(); it != g->pend.rend(); ++it)
-        if (it->local == i && it->call == g->call_seq && !it->b) {
-            hipEvent_t b = lm_ev_get(g->ctx[i]);
-            if (!b || hipEventRecord(b, g->ctx[i]->stream) != hipSuccess) {
-                (void)hipGetLastError();
-                if (b) hipEventDestroy(b);
-                return; // stats_resolve drops a measurement without an end
-            }
-            it->b = b;
-            return;
-        }
-}
-
 // folds finished measurements into the statistics: per call the slowest local rank's time, bytes as sent by one
 // rank.  only_done: leave what is still running on the device for later (no host block)
 void stats_resolve(lumen_group *g, bool only_done = false) {
@@ -269,27 +245,33 @@ void stats_resolve(lumen_group *g, bool only_done = false) {
     if (g->pend.empty()) g->call_ms.clear();
 }
 
-// "everything enqueued so far on every local rank" -> ev_ready; then dst's stream waits for all of them
-int ready_all(lumen_group *g) {
-    for (uint32_t i = 0; i < g->ctx.size(); i++) {
-        if (use(g, i)) return 1;
-        G_HIP(hipEventRecord(g->ev_ready[i], g->ctx[i]->stream));
+// timing bracket of one collective on local rank i's stream
+// (the caller has made rank i's device current: events are created on, and recorded from, the current device)
+void time_begin(lumen_group *g, const char *name, uint32_t i, uint64_t bytes) {
+    if (g->pend.size() > 512) stats_resolve(g, true); // a long run that never reads its statistics
+    lumen_group::pending p;
+    p.name = name, p.call = g->call_seq, p.local = i, p.bytes = bytes;
+    p.a = lm_ev_get(g->ctx[i]);
+    p.b = nullptr;
+    if (!p.a || hipEventRecord(p.a, g->ctx[i]->stream) != hipSuccess) { // no measurement rather than a bad event in the pool
+        (void)hipGetLastError();
+        if (p.a) hipEventDestroy(p.a);
+        return;
     }
-    return 0;
+    g->pend.push_back(p);
 }
-int wait_ready(lumen_group *g, uint32_t j) {
-    for (uint32_t i = 0; i < g->ctx.size(); i++)
-        if (i != j) G_HIP(hipStreamWaitEvent(g->ctx[j]->stream, g->ev_ready[i], 0));
-    return 0;
-}
-// the sources may reuse what was read once every destination has pulled its part
-int done_all(lumen_group *g, const std::vector<uint32_t> &dsts) {
-    for (uint32_t i = 0; i < g->ctx.size(); i++) {
-        if (use(g, i)) return 1;
-        for (uint32_t j : dsts)
-            if (i != j) G_HIP(hipStreamWaitEvent(g->ctx[i]->stream, g->ev_done[j], 0));
-    }
-    return 0;
+void time_end(lumen_group *g, uint32_t i) {
+    for (auto it = g->pend.rbegin(); it != g->pend.rend(); ++it)
+        if (it->local == i && it->call == g->call_seq && !it->b) {
+            hipEvent_t b = lm_ev_get(g->ctx[i]);
+            if (!b || hipEventRecord(b, g->ctx[i]->stream) != hipSuccess) {
+                (void)hipGetLastError();
+                if (b) hipEventDestroy(b);
+                return; // stats_resolve drops a measurement without an end
+            }
+            it->b = b;
+            return;
+        }
 }
 
 int copy_between(lumen_group *g, uint32_t dst_local, void *dst, uint32_t src_local, const void *src, size_t bytes) {
@@ -302,20 +284,76 @@ int copy_between(lumen_group *g, uint32_t dst_local, void *dst, uint32_t src_loc
     return 0;
 }
 
+// ---- one collective: what a caller moves.  The callbacks run with their rank's device current.
+struct collective {
+    const char *what;               // the entry point, named when a poisoned group refuses the call
+    const char *stat = nullptr;     // its name in lumen_group_stats; nullptr: untimed and uncounted (agree())
+    std::vector<uint64_t> sent;     // with `stat`: the bytes local rank i sends
+    // RCCL: post(i) posts local rank i's sends and receives inside the RCCL group; `first`, if any, runs on local
+    // rank 0 before the group opens
+    std::function<int()> first;
+    std::function<int(uint32_t)> post;
+    // copies (every rank is local: local index == rank): each destination of `dsts` pulls its parts on its own stream
+    std::vector<uint32_t> dsts;
+    std::function<int(uint32_t)> pull;
+};
+
+// The skeleton every exchange shares.  A poisoned group is refused; each local rank's stream gets the timing bracket
+// around its part.  RCCL: one ncclGroupStart ... ncclGroupEnd around all local ranks' posts; leaving in between poisons
+// the group (rccl_group_scope).  Copies: "everything enqueued so far on every local rank" -> ev_ready; a destination's
+// stream waits for all of them, pulls, records ev_done; the sources may reuse what was read once every destination
+// has pulled its part, so every stream waits for every destination's ev_done.
+int run_collective(lumen_group *g, const collective &c) {
+    const uint32_t n = (uint32_t)g->ctx.size();
+    G_USABLE(g, c.what);
+    g->call_seq++;
+    auto each_rank = [&](const std::function<int(uint32_t)> &f) {
+        for (uint32_t i = 0; i < n; i++)
+            if (use(g, i) || f(i)) return 1;
+        return 0;
+    };
+    if (c.stat && each_rank([&](uint32_t i) { return time_begin(g, c.stat, i, c.sent[i]), 0; })) return 1;
+    if (g->transport == LUMEN_TRANSPORT_RCCL) {
+        if (c.first && (use(g, 0) || c.first())) return 1;
+        rccl_group_scope grp(g);
+        if (grp.begin() || each_rank(c.post) || grp.end()) return 1;
+    } else {
+        if (each_rank([&](uint32_t i) {
+                G_HIP(hipEventRecord(g->ev_ready[i], g->ctx[i]->stream));
+                return 0;
+            }))
+            return 1;
+        for (uint32_t j : c.dsts) {
+            if (use(g, j)) return 1;
+            for (uint32_t i = 0; i < n; i++)
+                if (i != j) G_HIP(hipStreamWaitEvent(g->ctx[j]->stream, g->ev_ready[i], 0));
+            if (c.pull(j)) return 1;
+            G_HIP(hipEventRecord(g->ev_done[j], g->ctx[j]->stream));
+        }
+        if (each_rank([&](uint32_t i) {
+                for (uint32_t j : c.dsts)
+                    if (i != j) G_HIP(hipStreamWaitEvent(g->ctx[i]->stream, g->ev_done[j], 0));
+                return 0;
+            }))
+            return 1;
+    }
+    return c.stat ? each_rank([&](uint32_t i) { return time_end(g, i), 0; }) : 0;
+}
+
 bool same_params(const lumen_ctx *a, const lumen_ctx *b) {
     return a->logN == b->logN && a->L == b->L && a->K == b->K && a->T == b->T &&
            !memcmp(a->mod, b->mod, sizeof(uint64_t) * (a->L + a->K));
 }
 
-int group_finish_create(lumen_group *g) {
-    const uint32_t n = (uint32_t)g->ctx.size();
-    g->ev_ready.assign(n, nullptr), g->ev_done.assign(n, nullptr), g->d_digests.assign(n, nullptr);
-    for (uint32_t i = 0; i < n; i++) {
-        if (use(g, i)) return 1;
-        G_HIP(hipEventCreateWithFlags(&g->ev_ready[i], hipEventDisableTiming));
-        G_HIP(hipEventCreateWithFlags(&g->ev_done[i], hipEventDisableTiming));
-    }
-    return 0;
+// destroys the communicators made so far (a poisoned group's are aborted: that is what releases kernels blocked on a peer)
+void rccl_drop(lumen_group *g) {
+    for (uint32_t i = 0; i < g->comm.size(); i++)
+        if (g->comm[i]) {
+            (void)hipSetDevice(g->ctx[i]->device);
+            if (g->poisoned && g->rccl->CommAbort) g->rccl->CommAbort(g->comm[i]);
+            else g->rccl->CommDestroy(g->comm[i]);
+        }
+    g->comm.clear();
 }
 
 } // namespace
@@ -332,19 +370,14 @@ extern "C" void lumen_group_destroy(lumen_group *g) {
             stats_resolve(g);
         } else {
             // half a collective sits on the ranks' streams: waiting for them may never return.  Abort the communicators
-            // (that is what releases kernels blocked on a peer) and drop the timing events unread.
+            // and drop the timing events unread.
             for (auto &p : g->pend) {
                 if (p.a) hipEventDestroy(p.a);
                 if (p.b) hipEventDestroy(p.b);
             }
             g->pend.clear();
         }
-        for (uint32_t i = 0; i < g->comm.size(); i++)
-            if (g->comm[i]) {
-                (void)hipSetDevice(g->ctx[i]->device);
-                if (g->poisoned && g->rccl->CommAbort) g->rccl->CommAbort(g->comm[i]);
-                else g->rccl->CommDestroy(g->comm[i]);
-            }
+        rccl_drop(g);
         for (hipEvent_t e : g->ev_ready)
             if (e) hipEventDestroy(e);
         for (hipEvent_t e : g->ev_done)
@@ -353,8 +386,28 @@ extern "C" void lumen_group_destroy(lumen_group *g) {
     delete g;
 }
 
+namespace {
+
+#define RCCL_IPC_HINT                                                                                                       \
+    "hosts whose driver only does dmabuf IPC need HSA_ENABLE_IPC_MODE_LEGACY=0 in the process environment; NCCL_DEBUG=WARN " \
+    "prints RCCL's own reason"
+
+// The communicators of every local rank exist (`made`: how): all of them must span the W ranks, and the group's note
+// names the library that serves it.  Returns what is wrong, or nothing.
+std::string rccl_connected(lumen_group *g, const std::string &made) {
+    int cnt = 0;
+    const ncclResult_t rc = g->rccl->CommCount(g->comm[0], &cnt);
+    if (rc != ncclSuccess || (uint32_t)cnt != g->W)
+        return "the RCCL communicator reports " + std::to_string(cnt) + " ranks, expected " + std::to_string(g->W);
+    g->rccl_ranks = (uint32_t)cnt;
+    int ver = 0;
+    (void)g->rccl->GetVersion(&ver);
+    g->note = "rccl: librccl version " + std::to_string(ver) + ", " + made;
+    return "";
+}
+
 // RCCL communicators for every rank of a one-process group; on failure `why` says what refused and nothing is left behind
-static bool rccl_init_all(lumen_group *g, std::string &why) {
+bool rccl_init_all(lumen_group *g, std::string &why) {
     g->rccl = rccl_load();
     if (!g->rccl) {
         why = g_rccl.why;
@@ -366,35 +419,19 @@ static bool rccl_init_all(lumen_group *g, std::string &why) {
     g->comm.assign(W, nullptr);
     const ncclResult_t r = g->rccl->CommInitAll(g->comm.data(), (int)W, devs.data());
     if (r != ncclSuccess) {
-        why = std::string("ncclCommInitAll over ") + std::to_string(W) + " devices failed: " + g->rccl->GetErrorString(r) +
-              " (hosts whose driver only does dmabuf IPC need HSA_ENABLE_IPC_MODE_LEGACY=0 in the process environment; "
-              "NCCL_DEBUG=WARN prints RCCL's own reason)";
+        why = std::string("ncclCommInitAll over ") + std::to_string(W) + " devices failed: " + g->rccl->GetErrorString(r) + " (" RCCL_IPC_HINT ")";
         g->comm.clear();
         return false;
     }
-    int cnt = 0;
-    const ncclResult_t rc = g->rccl->CommCount(g->comm[0], &cnt);
-    if (rc != ncclSuccess || (uint32_t)cnt != W) {
-        why = "the RCCL communicator reports " + std::to_string(cnt) + " ranks, expected " + std::to_string(W);
-        for (uint32_t i = 0; i < W; i++)
-            if (g->comm[i]) {
-                (void)hipSetDevice(g->ctx[i]->device);
-                g->rccl->CommDestroy(g->comm[i]);
-            }
-        g->comm.clear();
-        return false;
-    }
-    g->rccl_ranks = (uint32_t)cnt;
-    int ver = 0;
-    (void)g->rccl->GetVersion(&ver);
-    g->note = "rccl: librccl version " + std::to_string(ver) + ", ncclCommInitAll over " + std::to_string(W) + " devices";
-    return true;
+    why = rccl_connected(g, "ncclCommInitAll over " + std::to_string(W) + " devices");
+    if (!why.empty()) rccl_drop(g);
+    return why.empty();
 }
 
 // copy transport across several devices: peer access where the hardware offers it (xGMI: hipMemcpyPeerAsync then moves
 // device to device); a pair without it still works -- the runtime stages such copies through host memory -- but the
 // group says so ("copy-staged") instead of passing for a device-to-device exchange
-static int peer_setup(lumen_group *g) {
+int peer_setup(lumen_group *g) {
     uint32_t pairs = 0, direct = 0;
     for (uint32_t i = 0; i < g->ctx.size(); i++)
         for (uint32_t j = 0; j < g->ctx.size(); j++) {
@@ -417,6 +454,35 @@ static int peer_setup(lumen_group *g) {
     return 0;
 }
 
+// The body both constructors share.  `who` has checked the arguments of its own; ctxs are the n local contexts, global
+// ranks first_rank .. first_rank + n - 1 of 2^log_world.  connect() sets up the transport on the locked group; whatever
+// fails, the half-made group is destroyed (communicators included) on the way out.
+int group_make(const char *who, lumen_ctx *const *ctxs, uint32_t n, uint32_t first_rank, uint32_t log_world, uint32_t transport,
+               const std::function<int(lumen_group *)> &connect, lumen_group **out) {
+    const uint32_t W = 1u << log_world;
+    LM_CHECK(nullptr, W == 1 || (ctxs[0]->N >> log_world) >= 64, "%s: a lane shard of 1/%u of N = %u is narrower than 64 coefficients",
+             who, W, ctxs[0]->N);
+    std::unique_ptr<lumen_group, void (*)(lumen_group *)> guard(new lumen_group(), lumen_group_destroy);
+    lumen_group *g = guard.get();
+    g->logw = log_world, g->W = W, g->transport = (int)transport;
+    for (uint32_t i = 0; i < n; i++) {
+        g->ctx.push_back(ctxs[i]), g->rank.push_back(first_rank + i);
+        g->multi_device |= ctxs[i]->device != ctxs[0]->device;
+    }
+    group_lock lk(g);
+    g->ev_ready.assign(n, nullptr), g->ev_done.assign(n, nullptr), g->d_digests.assign(n, nullptr);
+    for (uint32_t i = 0; i < n; i++) {
+        if (use(g, i)) return 1;
+        G_HIP(hipEventCreateWithFlags(&g->ev_ready[i], hipEventDisableTiming));
+        G_HIP(hipEventCreateWithFlags(&g->ev_done[i], hipEventDisableTiming));
+    }
+    if (connect(g)) return 1;
+    *out = guard.release();
+    return 0;
+}
+
+} // namespace
+
 extern "C" int lumen_group_create(lumen_ctx *const *ctxs, uint32_t log_world, uint32_t transport, lumen_group **out) {
     LM_CHECK(nullptr, ctxs && out, "lumen_group_create: NULL argument");
     *out = nullptr;
@@ -430,24 +496,15 @@ extern "C" int lumen_group_create(lumen_ctx *const *ctxs, uint32_t log_world, ui
         LM_CHECK(nullptr, same_params(ctxs[0], ctxs[r]), "lumen_group_create: rank %u has other parameters than rank 0", r);
         devices.insert(ctxs[r]->device);
     }
-    LM_CHECK(nullptr, W == 1 || (ctxs[0]->N >> log_world) >= 64,
-             "lumen_group_create: a lane shard of 1/%u of N = %u is narrower than 64 coefficients", W, ctxs[0]->N);
-    const bool distinct = devices.size() == W;
     const bool automatic = transport == LUMEN_TRANSPORT_AUTO;
     // (the shared-device exception is a test switch: real RCCL refuses such a communicator itself)
-    const bool rccl_possible = distinct || ctxs[0]->tune.rccl_shared_device;
+    const bool rccl_possible = devices.size() == W || ctxs[0]->tune.rccl_shared_device;
     if (automatic) transport = (rccl_possible && W > 1) ? LUMEN_TRANSPORT_RCCL : LUMEN_TRANSPORT_COPY;
     LM_CHECK(nullptr, transport != LUMEN_TRANSPORT_RCCL || rccl_possible,
              "lumen_group_create: RCCL needs every rank on its own device (%zu devices for %u ranks); use LUMEN_TRANSPORT_COPY", devices.size(), W);
-    std::unique_ptr<lumen_group, void (*)(lumen_group *)> guard(new lumen_group(), lumen_group_destroy);
-    lumen_group *g = guard.get();
-    g->logw = log_world, g->W = W, g->transport = (int)transport, g->multi_device = devices.size() > 1;
-    for (uint32_t r = 0; r < W; r++) g->ctx.push_back(ctxs[r]), g->rank.push_back(r);
-    group_lock lk(g);
-    if (group_finish_create(g)) return 1;
-    if (transport == LUMEN_TRANSPORT_RCCL) {
+    return group_make("lumen_group_create", ctxs, W, 0, log_world, transport, [&](lumen_group *g) {
         std::string why;
-        if (!rccl_init_all(g, why)) {
+        if (g->transport == LUMEN_TRANSPORT_RCCL && !rccl_init_all(g, why)) {
             // asked for by name: an error.  Chosen by LUMEN_TRANSPORT_AUTO: the W devices of one process can always
             // exchange by (peer) copies -- a host without librccl, or whose RCCL refuses to initialise, still runs
             LM_CHECK(nullptr, automatic, "lumen_group_create: RCCL transport unavailable: %s", why.c_str());
@@ -455,11 +512,10 @@ extern "C" int lumen_group_create(lumen_ctx *const *ctxs, uint32_t log_world, ui
             g->transport = LUMEN_TRANSPORT_COPY, g->rccl = nullptr, g->rccl_ranks = 0;
             g->note = "auto: fell back to device copies, RCCL unavailable: " + why;
         }
-    }
-    if (g->transport == LUMEN_TRANSPORT_COPY && g->multi_device && peer_setup(g)) return 1;
-    if (g->note.empty()) g->note = g->transport == LUMEN_TRANSPORT_COPY ? "stream-ordered copies on one device" : "";
-    *out = guard.release();
-    return 0;
+        if (g->transport == LUMEN_TRANSPORT_COPY && g->multi_device && peer_setup(g)) return 1;
+        if (g->note.empty()) g->note = g->transport == LUMEN_TRANSPORT_COPY ? "stream-ordered copies on one device" : "";
+        return 0;
+    }, out);
 }
 
 extern "C" int lumen_group_unique_id(uint8_t id[128]) {
@@ -479,38 +535,20 @@ extern "C" int lumen_group_create_rank(lumen_ctx *ctx, uint32_t rank, uint32_t l
     LM_CHECK(nullptr, ctx && id && out, "lumen_group_create_rank: NULL argument");
     *out = nullptr;
     LM_CHECK(nullptr, log_world <= 6 && rank < (1u << log_world), "lumen_group_create_rank: rank %u of 2^%u", rank, log_world);
-    const uint32_t W = 1u << log_world;
-    LM_CHECK(nullptr, W == 1 || (ctx->N >> log_world) >= 64,
-             "lumen_group_create_rank: a lane shard of 1/%u of N = %u is narrower than 64 coefficients", W, ctx->N);
-    std::unique_ptr<lumen_group, void (*)(lumen_group *)> guard(new lumen_group(), lumen_group_destroy);
-    lumen_group *g = guard.get();
-    g->logw = log_world, g->W = W, g->transport = LUMEN_TRANSPORT_RCCL;
-    g->ctx.push_back(ctx), g->rank.push_back(rank);
-    group_lock lk(g);
-    if (group_finish_create(g)) return 1;
-    g->rccl = rccl_load();
-    LM_CHECK(nullptr, g->rccl, "lumen_group_create_rank: RCCL unavailable: %s", g_rccl.why.c_str());
-    ncclUniqueId u;
-    memcpy(&u, id, 128);
-    g->comm.assign(1, nullptr);
-    if (use(g, 0)) return 1;
-    {
-        const ncclResult_t r = g->rccl->CommInitRank(&g->comm[0], (int)W, u, (int)rank);
-        LM_CHECK(nullptr, r == ncclSuccess,
-                 "ncclCommInitRank (rank %u of %u on device %d) failed: %s -- RCCL needs every rank on its own device, and "
-                 "on hosts whose driver only does dmabuf IPC the process environment must carry "
-                 "HSA_ENABLE_IPC_MODE_LEGACY=0; NCCL_DEBUG=WARN prints RCCL's own reason", rank, W, ctx->device,
-                 g->rccl->GetErrorString(r));
-    }
-    int cnt = 0;
-    G_NCCL(g, g->rccl->CommCount(g->comm[0], &cnt));
-    g->rccl_ranks = (uint32_t)cnt;
-    LM_CHECK(nullptr, g->rccl_ranks == W, "lumen_group_create_rank: the RCCL communicator reports %u ranks, expected %u", g->rccl_ranks, W);
-    int ver = 0;
-    (void)g->rccl->GetVersion(&ver);
-    g->note = "rccl: librccl version " + std::to_string(ver) + ", ncclCommInitRank " + std::to_string(rank) + " of " + std::to_string(W);
-    *out = guard.release();
-    return 0;
+    return group_make("lumen_group_create_rank", &ctx, 1, rank, log_world, LUMEN_TRANSPORT_RCCL, [&](lumen_group *g) {
+        g->rccl = rccl_load();
+        LM_CHECK(nullptr, g->rccl, "lumen_group_create_rank: RCCL unavailable: %s", g_rccl.why.c_str());
+        ncclUniqueId u;
+        memcpy(&u, id, 128);
+        g->comm.assign(1, nullptr);
+        if (use(g, 0)) return 1;
+        const ncclResult_t r = g->rccl->CommInitRank(&g->comm[0], (int)g->W, u, (int)rank);
+        LM_CHECK(nullptr, r == ncclSuccess, "ncclCommInitRank (rank %u of %u on device %d) failed: %s -- RCCL needs every rank on its own "
+                 "device; " RCCL_IPC_HINT, rank, g->W, ctx->device, g->rccl->GetErrorString(r));
+        const std::string why = rccl_connected(g, "ncclCommInitRank " + std::to_string(rank) + " of " + std::to_string(g->W));
+        LM_CHECK(nullptr, why.empty(), "lumen_group_create_rank: %s", why.c_str());
+        return 0;
+    }, out);
 }
 
 extern "C" uint32_t lumen_group_world(const lumen_group *g) { return g ? g->W : 0; }
@@ -534,63 +572,9 @@ extern "C" int lumen_group_sync(lumen_group *g) {
     return 0;
 }
 
-// ---- all-to-all on contiguous blocks.  send_ptr[i] / recv_ptr[i]: base of local rank i's W blocks of blk bytes.
-static int all_to_all_raw(lumen_group *g, const std::vector<const u64 *> &send, const std::vector<u64 *> &recv, size_t blk_words,
-                          const char *stat_name) {
-    const uint32_t n = (uint32_t)g->ctx.size(), W = g->W;
-    G_USABLE(g, stat_name);
-    g->call_seq++;
-    const uint64_t sent = (uint64_t)blk_words * 8 * (W - 1);
-    if (g->transport == LUMEN_TRANSPORT_RCCL) {
-        for (uint32_t i = 0; i < n; i++) {
-            if (use(g, i)) return 1;
-            time_begin(g, stat_name, i, sent);
-        }
-        rccl_group_scope grp(g);
-        if (grp.begin()) return 1;
-        for (uint32_t i = 0; i < n; i++) {
-            if (use(g, i)) return 1;
-            for (uint32_t p = 0; p < W; p++) {
-                G_NCCL(g, g->rccl->Send(send[i] + (size_t)p * blk_words, blk_words, ncclUint64, (int)p, g->comm[i], g->ctx[i]->stream));
-                G_NCCL(g, g->rccl->Recv(recv[i] + (size_t)p * blk_words, blk_words, ncclUint64, (int)p, g->comm[i], g->ctx[i]->stream));
-            }
-        }
-        if (grp.end()) return 1;
-        for (uint32_t i = 0; i < n; i++) {
-            if (use(g, i)) return 1;
-            time_end(g, i);
-        }
-        return 0;
-    }
-    // copy transport: every rank is local (n == W, local index == rank)
-    for (uint32_t i = 0; i < n; i++) {
-        if (use(g, i)) return 1;
-        time_begin(g, stat_name, i, sent);
-    }
-    if (ready_all(g)) return 1;
-    std::vector<uint32_t> all;
-    for (uint32_t j = 0; j < n; j++) {
-        if (use(g, j) || wait_ready(g, j)) return 1;
-        for (uint32_t k = 0; k < n; k++) {
-            const uint32_t i = (j + k) % n; // start with the rank's own block, then spread over the peers
-            if (copy_between(g, j, recv[j] + (size_t)i * blk_words, i, send[i] + (size_t)j * blk_words, blk_words * 8)) return 1;
-        }
-        G_HIP(hipEventRecord(g->ev_done[j], g->ctx[j]->stream));
-        all.push_back(j);
-    }
-    if (done_all(g, all)) return 1;
-    for (uint32_t i = 0; i < n; i++) {
-        if (use(g, i)) return 1;
-        time_end(g, i);
-    }
-    return 0;
-}
-
+// ---- all-to-all on contiguous blocks: local rank i sends block p of send[i] to rank p and receives block p of recv[i] from it
 static int all_to_all_sets(lumen_group *g, const lumen_set *const *send, lumen_set *const *recv, const char *stat_name) {
-    group_lock lk(g);
     const uint32_t n = (uint32_t)g->ctx.size(), W = g->W;
-    std::vector<const u64 *> sp;
-    std::vector<u64 *> rp;
     for (uint32_t i = 0; i < n; i++) {
         LM_CHECK(nullptr, send[i] && recv[i], "lumen_group_all_to_all: set %u is NULL", i);
         LM_CHECK(nullptr, send[i]->words == recv[i]->words && send[i]->words == send[0]->words,
@@ -599,14 +583,34 @@ static int all_to_all_sets(lumen_group *g, const lumen_set *const *send, lumen_s
         LM_CHECK(nullptr, send[i]->count % W == 0 && recv[i]->count % W == 0,
                  "lumen_group_all_to_all: %u / %u ciphertexts are not %u equal blocks", send[i]->count, recv[i]->count, W);
         LM_CHECK(nullptr, (const void *)send[i]->d != (const void *)recv[i]->d, "lumen_group_all_to_all: in-place exchange");
-        sp.push_back(send[i]->d), rp.push_back(recv[i]->d);
     }
     if (!send[0]->words) return 0;
-    return all_to_all_raw(g, sp, rp, send[0]->words / W, stat_name);
+    const size_t blk = send[0]->words / W; // words
+    collective c;
+    c.what = c.stat = stat_name;
+    c.sent.assign(n, (uint64_t)blk * 8 * (W - 1));
+    c.post = [&](uint32_t i) {
+        for (uint32_t p = 0; p < W; p++) {
+            G_NCCL(g, g->rccl->Send(send[i]->d + (size_t)p * blk, blk, ncclUint64, (int)p, g->comm[i], g->ctx[i]->stream));
+            G_NCCL(g, g->rccl->Recv(recv[i]->d + (size_t)p * blk, blk, ncclUint64, (int)p, g->comm[i], g->ctx[i]->stream));
+        }
+        return 0;
+    };
+    for (uint32_t j = 0; j < n; j++) c.dsts.push_back(j);
+    c.pull = [&](uint32_t j) {
+        for (uint32_t k = 0; k < n; k++) {
+            const uint32_t i = (j + k) % n; // start with the rank's own block, then spread over the peers
+            if (copy_between(g, j, recv[j]->d + (size_t)i * blk, i, send[i]->d + (size_t)j * blk, blk * 8)) return 1;
+        }
+        return 0;
+    };
+    return run_collective(g, c);
 }
 
 extern "C" int lumen_group_all_to_all(lumen_group *g, const lumen_set *const *send, lumen_set *const *recv) {
     LM_CHECK(nullptr, g && send && recv, "lumen_group_all_to_all: NULL argument");
+    group_lock lk(g);
+    G_USABLE(g, "lumen_group_all_to_all");
     return all_to_all_sets(g, send, recv, "all_to_all");
 }
 
@@ -616,9 +620,9 @@ namespace {
 // owning context's pool behind an event on its stream (lm_set_release_async), so the call returns with its work
 // enqueued and the host goes on to enqueue the rescale and the leaf hashing of every rank (lumen_set_destroy would
 // wait for every rank's Encode here).  Other ranks' reads of a temporary are ordered before that event: the
-// copy transport makes the source's stream wait for every destination (done_all), RCCL sends from the owner's stream.
+// copy transport makes the source's stream wait for every destination (run_collective), RCCL sends from the owner's stream.
 // ONLY when the call marks itself successful (commit()): on an error path the exchange may have stopped between some
-// destinations' copies and done_all(), and then the owner's stream has NOT waited for the other ranks' reads -- an
+// destinations' copies and those closing waits, and then the owner's stream has NOT waited for the other ranks' reads -- an
 // event on it would not cover them and the next taker of the block could overwrite it mid-copy.  There every local
 // rank is drained first and the blocks go back the blocking way.
 struct set_bin {
@@ -658,6 +662,7 @@ extern "C" int lumen_group_encode(lumen_group *g, const lumen_set *const *matrix
                                   uint32_t rho_inv, lumen_set **encoded) {
     LM_CHECK(nullptr, g && matrix && zero_ct && encoded, "lumen_group_encode: NULL argument");
     group_lock lk(g);
+    G_USABLE(g, "lumen_group_encode");
     const uint32_t n = (uint32_t)g->ctx.size(), W = g->W, logw = g->logw;
     for (uint32_t i = 0; i < n; i++) {
         encoded[i] = nullptr;
@@ -733,7 +738,6 @@ extern "C" int lumen_group_all_gather_digests(lumen_group *g) {
         if (i == 0) per = c->aux_digests;
         LM_CHECK(nullptr, c->aux_digests == per, "lumen_group_all_gather_digests: local rank %u hashed %u leaves, rank 0 %u", i, c->aux_digests, per);
     }
-    g->call_seq++;
     const size_t part = (size_t)per * 32;
     for (uint32_t i = 0; i < n; i++) {
         lumen_ctx *c = g->ctx[i];
@@ -748,39 +752,28 @@ extern "C" int lumen_group_all_gather_digests(lumen_group *g) {
         c->aux_lo = c->aux_hi = nullptr;
         G_HIP(hipEventRecord(c->ev_aux, c->stream_aux));
         G_HIP(hipStreamWaitEvent(c->stream, c->ev_aux, 0));
-        time_begin(g, "all_gather", i, (uint64_t)part * (W - 1));
     }
     g->n_per_rank = per;
-    if (g->transport == LUMEN_TRANSPORT_RCCL) {
-        rccl_group_scope grp(g);
-        if (grp.begin()) return 1;
-        for (uint32_t i = 0; i < n; i++) {
-            if (use(g, i)) return 1;
-            G_NCCL(g, g->rccl->AllGather(src[i], g->d_digests[i], part, ncclUint8, g->comm[i], g->ctx[i]->stream));
-        }
-        if (grp.end()) return 1;
-    } else {
-        if (ready_all(g)) return 1;
-        std::vector<uint32_t> all;
-        for (uint32_t j = 0; j < n; j++) {
-            if (use(g, j) || wait_ready(g, j)) return 1;
-            for (uint32_t i = 0; i < n; i++)
-                if (copy_between(g, j, g->d_digests[j] + (size_t)i * part, i, src[i], part)) return 1;
-            G_HIP(hipEventRecord(g->ev_done[j], g->ctx[j]->stream));
-            all.push_back(j);
-        }
-        if (done_all(g, all)) return 1;
-    }
-    for (uint32_t i = 0; i < n; i++) {
-        if (use(g, i)) return 1;
-        time_end(g, i);
-    }
-    return 0;
+    collective c;
+    c.what = "lumen_group_all_gather_digests", c.stat = "all_gather";
+    c.sent.assign(n, (uint64_t)part * (W - 1));
+    c.post = [&](uint32_t i) {
+        G_NCCL(g, g->rccl->AllGather(src[i], g->d_digests[i], part, ncclUint8, g->comm[i], g->ctx[i]->stream));
+        return 0;
+    };
+    for (uint32_t j = 0; j < n; j++) c.dsts.push_back(j);
+    c.pull = [&](uint32_t j) {
+        for (uint32_t i = 0; i < n; i++)
+            if (copy_between(g, j, g->d_digests[j] + (size_t)i * part, i, src[i], part)) return 1;
+        return 0;
+    };
+    return run_collective(g, c);
 }
 
 extern "C" int lumen_group_merkle_root(lumen_group *g, uint8_t root[32]) {
     LM_CHECK(nullptr, g && root, "lumen_group_merkle_root: NULL argument");
     group_lock lk(g);
+    G_USABLE(g, "lumen_group_merkle_root");
     LM_CHECK(nullptr, g->n_per_rank && g->d_digests[0], "lumen_group_merkle_root: no gathered digests (lumen_group_all_gather_digests first)");
     if (use(g, 0)) return 1;
     return lumen_merkle_root_device(g->ctx[0], g->d_digests[0], g->n_per_rank * g->W, root);
@@ -789,6 +782,7 @@ extern "C" int lumen_group_merkle_root(lumen_group *g, uint8_t root[32]) {
 extern "C" int lumen_group_digests(lumen_group *g, uint8_t *digests, size_t cap, uint32_t *n_leaves) {
     LM_CHECK(nullptr, g && digests, "lumen_group_digests: NULL argument");
     group_lock lk(g);
+    G_USABLE(g, "lumen_group_digests");
     LM_CHECK(nullptr, g->n_per_rank && g->d_digests[0], "lumen_group_digests: no gathered digests (lumen_group_all_gather_digests first)");
     const size_t bytes = (size_t)g->n_per_rank * g->W * 32;
     LM_CHECK(nullptr, cap >= bytes, "lumen_group_digests: buffer of %zu bytes, %zu needed", cap, bytes);
@@ -799,6 +793,70 @@ extern "C" int lumen_group_digests(lumen_group *g, uint8_t *digests, size_t cap,
     return 0;
 }
 
+// ---- the agreement step of the one-process-per-GPU form (RCCL, fewer local ranks than W)
+namespace {
+
+constexpr uint64_t FNV_BASIS = 1469598103934665603ull;
+template <class It>
+uint64_t fnv(uint64_t h, It first, It last) {
+    for (; first != last; ++first) h = (h ^ (uint64_t)*first) * 1099511628211ull;
+    return h;
+}
+
+struct agree_text {
+    const char *who;      // the entry point
+    const char *scratch;  // its lm_scratch block
+    const char *rejected; // "<who>: rank 3 <rejected>"
+    const char *given;    // "<who>: rank 3 was given <given> than rank 0 (every rank must pass the same<same>)"
+    const char *same;
+};
+
+// Every process derives what it sends and receives from the arguments IT was given, and a rank that returned early on
+// bad arguments of its own would leave its peers inside RCCL for good.  So in that form nothing returns before the ranks
+// have AGREED: what is wrong with the local arguments is only noted (`bad`), every rank all-gathers { fingerprint of the
+// arguments that must be equal, "my arguments are valid", `words` words of payload } -- a fixed-size exchange that cannot
+// mismatch -- and then all ranks fail together or none does; the rank that has a `bad` of its own fails with that.
+// mine: [local rank][words]; theirs: [rank][words].  Blocks the host; untimed and in no statistic.
+int agree(lumen_group *g, const agree_text &t, uint64_t fp, const std::string &bad, uint32_t words, const uint64_t *mine,
+          std::vector<uint64_t> &theirs) {
+    const uint32_t n = (uint32_t)g->ctx.size(), W = g->W, w = 2 + words;
+    std::vector<u64 *> dbuf(n);
+    for (uint32_t i = 0; i < n; i++) {
+        lumen_ctx *c = g->ctx[i];
+        if (use(g, i)) return 1;
+        dbuf[i] = (u64 *)lm_scratch(c, t.scratch, 8 * (size_t)w * (W + 1));
+        u64 *h = (u64 *)lm_stage(c, 8 * w);
+        if (!dbuf[i] || !h) return 1;
+        h[0] = fp, h[1] = bad.empty() ? 1 : 0;
+        if (words) std::copy_n(mine + (size_t)i * words, words, h + 2);
+        G_HIP(hipMemcpyAsync(dbuf[i] + (size_t)w * W, h, 8 * w, hipMemcpyHostToDevice, c->stream));
+        G_HIP(hipEventRecord(c->ev_stage, c->stream));
+    }
+    collective c;
+    c.what = t.who;
+    c.post = [&](uint32_t i) {
+        G_NCCL(g, g->rccl->AllGather(dbuf[i] + (size_t)w * W, dbuf[i], w, ncclUint64, g->comm[i], g->ctx[i]->stream));
+        return 0;
+    };
+    if (run_collective(g, c)) return 1;
+    std::vector<uint64_t> seen((size_t)w * W);
+    for (uint32_t i = 0; i < n; i++) {
+        if (use(g, i)) return 1;
+        G_HIP(hipMemcpyAsync(seen.data(), dbuf[i], 8 * (size_t)w * W, hipMemcpyDeviceToHost, g->ctx[i]->stream));
+        G_HIP(hipStreamSynchronize(g->ctx[i]->stream));
+        LM_CHECK(nullptr, bad.empty(), "%s", bad.c_str()); // (the peers see this rank's flag and fail with it)
+        for (uint32_t p = 0; p < W; p++) LM_CHECK(nullptr, seen[(size_t)w * p + 1] == 1, "%s: rank %u %s", t.who, p, t.rejected);
+        for (uint32_t p = 0; p < W; p++)
+            LM_CHECK(nullptr, seen[(size_t)w * p] == fp, "%s: rank %u was given %s than rank %u (every rank must pass the same%s)", t.who,
+                     p, t.given, g->rank[i], t.same);
+    }
+    theirs.resize((size_t)W * words);
+    for (uint32_t p = 0; p < W; p++) std::copy_n(seen.data() + (size_t)w * p + 2, words, theirs.data() + (size_t)p * words);
+    return 0;
+}
+
+} // namespace
+
 // ---- the query loop over column-sharded leaves
 extern "C" int lumen_group_gather(lumen_group *g, const lumen_set *const *src, const uint32_t *idx, uint32_t nq,
                                   lumen_set **out) {
@@ -807,12 +865,8 @@ extern "C" int lumen_group_gather(lumen_group *g, const lumen_set *const *src, c
     group_lock lk(g);
     G_USABLE(g, "lumen_group_gather");
     const uint32_t n = (uint32_t)g->ctx.size(), W = g->W;
-    // One process per GPU: every process derives the send / receive plan from the (n, idx[]) IT was given, and a rank that
-    // returned early on bad arguments of its own would leave its peers inside RCCL for good.  So in that form nothing
-    // returns before the ranks have AGREED: what is wrong with the local arguments is only noted (`bad`), every rank
-    // all-gathers { fingerprint of (n, idx[]), "my arguments are valid" } -- a fixed-size exchange that cannot mismatch --
-    // and then all ranks fail together or none does.  (This makes the call block the host in that form; with all ranks
-    // in one process there is one idx and the checks return at once.)
+    // One process per GPU: nothing returns before the ranks have agreed on (n, idx[]) -- see agree().  (That makes the call
+    // block the host in that form; with all ranks in one process there is one idx and the checks return at once.)
     const bool per_rank = n < W && g->transport == LUMEN_TRANSPORT_RCCL;
     std::string bad;
     auto note_bad = [&](const char *fmt, ...) {
@@ -852,44 +906,13 @@ extern "C" int lumen_group_gather(lumen_group *g, const lumen_set *const *src, c
         }
     }
     if (per_rank) {
-        uint64_t fp = 1469598103934665603ull ^ nq;
-        for (uint32_t k = 0; k < nq; k++) fp = (fp ^ idx[k]) * 1099511628211ull;
-        std::vector<u64 *> dbuf(n);
-        for (uint32_t i = 0; i < n; i++) {
-            lumen_ctx *c = g->ctx[i];
-            if (use(g, i)) return 1;
-            dbuf[i] = (u64 *)lm_scratch(c, "gather_agree", 16 * (size_t)(W + 1));
-            u64 *h = (u64 *)lm_stage(c, 16);
-            if (!dbuf[i] || !h) return 1;
-            h[0] = fp, h[1] = bad.empty() ? 1 : 0;
-            G_HIP(hipMemcpyAsync(dbuf[i] + 2 * W, h, 16, hipMemcpyHostToDevice, c->stream));
-            G_HIP(hipEventRecord(c->ev_stage, c->stream));
-        }
-        {
-            rccl_group_scope grp(g);
-            if (grp.begin()) return 1;
-            for (uint32_t i = 0; i < n; i++) {
-                if (use(g, i)) return 1;
-                G_NCCL(g, g->rccl->AllGather(dbuf[i] + 2 * W, dbuf[i], 2, ncclUint64, g->comm[i], g->ctx[i]->stream));
-            }
-            if (grp.end()) return 1;
-        }
-        std::vector<uint64_t> seen(2 * (size_t)W);
-        for (uint32_t i = 0; i < n; i++) {
-            if (use(g, i)) return 1;
-            G_HIP(hipMemcpyAsync(seen.data(), dbuf[i], 16 * (size_t)W, hipMemcpyDeviceToHost, g->ctx[i]->stream));
-            G_HIP(hipStreamSynchronize(g->ctx[i]->stream));
-            LM_CHECK(nullptr, bad.empty(), "%s", bad.c_str()); // (the peers see this rank's flag and fail with it)
-            for (uint32_t p = 0; p < W; p++)
-                LM_CHECK(nullptr, seen[2 * p + 1] == 1, "lumen_group_gather: rank %u rejected its arguments (see its own message): no "
-                         "rank sends", p);
-            for (uint32_t p = 0; p < W; p++)
-                LM_CHECK(nullptr, seen[2 * p] == fp, "lumen_group_gather: rank %u was given other query indices than rank %u (every rank "
-                         "must pass the same n and idx[])", p, g->rank[i]);
-        }
+        std::vector<uint64_t> nothing;
+        if (agree(g, {"lumen_group_gather", "gather_agree", "rejected its arguments (see its own message): no rank sends",
+                      "other query indices", " n and idx[]"},
+                  fnv(FNV_BASIS ^ nq, idx, idx + nq), bad, 0, nullptr, nothing))
+            return 1;
     }
     LM_CHECK(nullptr, bad.empty(), "%s", bad.c_str());
-    g->call_seq++;
     set_bin bin(g);
     std::vector<lumen_set *> q(n, nullptr);
     for (uint32_t i = 0; i < n; i++) {
@@ -903,43 +926,31 @@ extern "C" int lumen_group_gather(lumen_group *g, const lumen_set *const *src, c
         if (use(g, 0) || lumen_set_create(g->ctx[0], nq, nl, &stage)) return 1;
         bin.keep(g->ctx[0], stage);
     }
-    for (uint32_t i = 0; i < n; i++) {
-        if (use(g, i)) return 1;
-        const uint64_t sent = g->rank[i] == 0 ? 0 : (uint64_t)local_idx[g->rank[i]].size() * ctw * 8;
-        time_begin(g, "gather_to_root", i, sent);
-    }
-    if (g->transport == LUMEN_TRANSPORT_RCCL) {
-        if (have_root && q[0]) { // rank 0's own columns: a device copy
-            if (use(g, 0)) return 1;
-            G_HIP(hipMemcpyAsync(stage->d, q[0]->d, q[0]->words * 8, hipMemcpyDeviceToDevice, g->ctx[0]->stream));
-        }
-        rccl_group_scope grp(g);
-        if (grp.begin()) return 1;
-        for (uint32_t i = 0; i < n; i++) {
-            if (use(g, i)) return 1;
-            if (g->rank[i] != 0 && q[i])
-                G_NCCL(g, g->rccl->Send(q[i]->d, q[i]->words, ncclUint64, 0, g->comm[i], g->ctx[i]->stream));
-        }
-        if (have_root) {
-            if (use(g, 0)) return 1;
-            for (uint32_t p = 1; p < W; p++)
-                if (off[p + 1] > off[p])
-                    G_NCCL(g, g->rccl->Recv(stage->d + (size_t)off[p] * ctw, (size_t)(off[p + 1] - off[p]) * ctw, ncclUint64, (int)p,
-                                            g->comm[0], g->ctx[0]->stream));
-        }
-        if (grp.end()) return 1;
-    } else {
-        if (ready_all(g)) return 1;
-        if (use(g, 0) || wait_ready(g, 0)) return 1;
+    collective c;
+    c.what = "lumen_group_gather", c.stat = "gather_to_root";
+    for (uint32_t i = 0; i < n; i++) c.sent.push_back(g->rank[i] == 0 ? 0 : (uint64_t)local_idx[g->rank[i]].size() * ctw * 8);
+    c.first = [&]() { // rank 0's own columns: a device copy
+        if (have_root && q[0]) G_HIP(hipMemcpyAsync(stage->d, q[0]->d, q[0]->words * 8, hipMemcpyDeviceToDevice, g->ctx[0]->stream));
+        return 0;
+    };
+    c.post = [&](uint32_t i) {
+        if (g->rank[i] != 0 && q[i]) G_NCCL(g, g->rccl->Send(q[i]->d, q[i]->words, ncclUint64, 0, g->comm[i], g->ctx[i]->stream));
+        if (i + 1 < n || !have_root) return 0;
+        // the root's receives are posted last, behind every local rank's send: a send that fails leaves no receive posted
+        if (use(g, 0)) return 1;
+        for (uint32_t p = 1; p < W; p++)
+            if (off[p + 1] > off[p])
+                G_NCCL(g, g->rccl->Recv(stage->d + (size_t)off[p] * ctw, (size_t)(off[p + 1] - off[p]) * ctw, ncclUint64, (int)p,
+                                        g->comm[0], g->ctx[0]->stream));
+        return 0;
+    };
+    c.dsts = {0};
+    c.pull = [&](uint32_t) {
         for (uint32_t i = 0; i < n; i++)
             if (q[i] && copy_between(g, 0, stage->d + (size_t)off[i] * ctw, i, q[i]->d, q[i]->words * 8)) return 1;
-        G_HIP(hipEventRecord(g->ev_done[0], g->ctx[0]->stream));
-        if (done_all(g, {0})) return 1;
-    }
-    for (uint32_t i = 0; i < n; i++) {
-        if (use(g, i)) return 1;
-        time_end(g, i);
-    }
+        return 0;
+    };
+    if (run_collective(g, c)) return 1;
     if (have_root) {
         if (use(g, 0)) return 1;
         if (lumen_gather(g->ctx[0], stage, perm.data(), nq, out)) return 1;
@@ -952,13 +963,6 @@ extern "C" int lumen_group_gather(lumen_group *g, const lumen_set *const *src, c
 // the block of rank r begins at c_r = the columns of the ranks before it, and z^(c_r) is applied when the partials are
 // summed -- so a rank of the one-process-per-GPU form needs nothing from its peers before it evaluates, and learns the
 // c_r from the one exchange that also carries the partials.
-int lm_poly_eval_check(lumen_ctx *ctx, const uint64_t *values, uint32_t rows, uint32_t count, uint64_t first_column,
-                       uint32_t cols, const char *what);
-int lm_poly_eval_enqueue(lumen_ctx *ctx, const uint64_t *values, uint32_t rows, uint32_t count, uint64_t first_column,
-                         uint32_t cols, uint64_t z, const char *what);
-int lm_poly_eval_finish(lumen_ctx *ctx, uint64_t *partial);
-bool lm_host_is_pinned(const void *p);
-
 extern "C" int lumen_group_poly_eval(lumen_group *g, const uint64_t *const *values, uint32_t rows, const uint32_t *counts,
                                      uint32_t cols, uint64_t z, uint64_t *value) {
     LM_CHECK(nullptr, g, "lumen_group_poly_eval: NULL group");
@@ -966,8 +970,8 @@ extern "C" int lumen_group_poly_eval(lumen_group *g, const uint64_t *const *valu
     G_USABLE(g, "lumen_group_poly_eval");
     const uint32_t n = (uint32_t)g->ctx.size(), W = g->W;
     const uint64_t T = g->ctx[0]->T;
-    // One process per GPU: as in lumen_group_gather, a rank whose own arguments (or evaluation) fail must not return
-    // before the exchange its peers are already waiting in; it only notes what is wrong (`bad`) and says so there.
+    // One process per GPU: a rank whose own arguments (or evaluation) fail only notes what is wrong (`bad`) and says so in
+    // the exchange its peers are already waiting in (agree())
     const bool per_rank = n < W && g->transport == LUMEN_TRANSPORT_RCCL;
     std::string bad;
     auto note_bad = [&](const std::string &why) {
@@ -1002,43 +1006,15 @@ extern "C" int lumen_group_poly_eval(lumen_group *g, const uint64_t *const *valu
     // per global rank: its column count and its partial (the block evaluated from column 0)
     std::vector<uint64_t> cnt(W, 0), par(W, 0);
     if (per_rank) {
-        // all-gather { fingerprint of (rows, cols, z, T), "my block is evaluated", count, partial } -- fixed size
-        uint64_t fp = 1469598103934665603ull;
-        for (uint64_t v : {(uint64_t)rows, (uint64_t)cols, T ? z % T : z, T}) fp = (fp ^ v) * 1099511628211ull;
-        std::vector<u64 *> dbuf(n);
-        for (uint32_t i = 0; i < n; i++) {
-            lumen_ctx *c = g->ctx[i];
-            if (use(g, i)) return 1;
-            dbuf[i] = (u64 *)lm_scratch(c, "poly_agree", 32 * (size_t)(W + 1));
-            u64 *h = (u64 *)lm_stage(c, 32);
-            if (!dbuf[i] || !h) return 1;
-            h[0] = fp, h[1] = bad.empty() ? 1 : 0, h[2] = bad.empty() ? counts[i] : 0, h[3] = part[i];
-            G_HIP(hipMemcpyAsync(dbuf[i] + 4 * W, h, 32, hipMemcpyHostToDevice, c->stream));
-            G_HIP(hipEventRecord(c->ev_stage, c->stream));
-        }
-        {
-            rccl_group_scope grp(g);
-            if (grp.begin()) return 1;
-            for (uint32_t i = 0; i < n; i++) {
-                if (use(g, i)) return 1;
-                G_NCCL(g, g->rccl->AllGather(dbuf[i] + 4 * W, dbuf[i], 4, ncclUint64, g->comm[i], g->ctx[i]->stream));
-            }
-            if (grp.end()) return 1;
-        }
-        std::vector<uint64_t> seen(4 * (size_t)W);
-        for (uint32_t i = 0; i < n; i++) {
-            if (use(g, i)) return 1;
-            G_HIP(hipMemcpyAsync(seen.data(), dbuf[i], 32 * (size_t)W, hipMemcpyDeviceToHost, g->ctx[i]->stream));
-            G_HIP(hipStreamSynchronize(g->ctx[i]->stream));
-            LM_CHECK(nullptr, bad.empty(), "%s", bad.c_str()); // (the peers see this rank's flag and fail with it)
-            for (uint32_t p = 0; p < W; p++)
-                LM_CHECK(nullptr, seen[4 * p + 1] == 1, "lumen_group_poly_eval: rank %u rejected its arguments or failed to "
-                         "evaluate (see its own message)", p);
-            for (uint32_t p = 0; p < W; p++)
-                LM_CHECK(nullptr, seen[4 * p] == fp, "lumen_group_poly_eval: rank %u was given another rows, cols or z than rank %u "
-                         "(every rank must pass the same)", p, g->rank[i]);
-        }
-        for (uint32_t p = 0; p < W; p++) cnt[p] = seen[4 * p + 2], par[p] = seen[4 * p + 3];
+        // agreed on: (rows, cols, z, T); carried along: every rank's count and partial
+        const uint64_t same[] = {rows, cols, T ? z % T : z, T};
+        std::vector<uint64_t> mine, theirs;
+        for (uint32_t i = 0; i < n; i++) mine.push_back(bad.empty() ? counts[i] : 0), mine.push_back(part[i]);
+        if (agree(g, {"lumen_group_poly_eval", "poly_agree", "rejected its arguments or failed to evaluate (see its own message)",
+                      "another rows, cols or z", ""},
+                  fnv(FNV_BASIS, same, same + 4), bad, 2, mine.data(), theirs))
+            return 1;
+        for (uint32_t p = 0; p < W; p++) cnt[p] = theirs[2 * p], par[p] = theirs[2 * p + 1];
     } else {
         LM_CHECK(nullptr, bad.empty(), "%s", bad.c_str());
         for (uint32_t i = 0; i < n; i++) cnt[g->rank[i]] = counts[i], par[g->rank[i]] = part[i];
@@ -1059,13 +1035,10 @@ extern "C" int lumen_group_poly_eval(lumen_group *g, const uint64_t *const *valu
 // ---- host <-> ranks: every local rank's transfer is enqueued before any is waited for, so the W PCIe links of a
 // process that owns W GPUs carry their blocks at the same time (one lumen_set_upload per rank would finish the
 // first DMA before it starts the second: 12.9 GB over one link after the other)
-bool lm_host_is_pinned(const void *p);
-int lm_h2d(lumen_ctx *ctx, void *dev, const void *host, size_t bytes);
-int lm_d2h(lumen_ctx *ctx, void *host, const void *dev, size_t bytes, bool wait);
-
 static int group_io(lumen_group *g, lumen_set *const *sets, uint64_t *const *hosts, bool up, const char *what) {
     LM_CHECK(nullptr, g && sets && hosts, "%s: NULL argument", what);
     group_lock lk(g);
+    G_USABLE(g, what);
     const uint32_t n = (uint32_t)g->ctx.size();
     std::vector<uint32_t> later; // pageable buffers go through the contexts' bounce buffers, one rank after the other
     for (uint32_t i = 0; i < n; i++) {

@@ -170,8 +170,6 @@ __global__ __launch_bounds__(256) void k_ct_wire(const u64 *__restrict__ set, ui
     for (u32 m = tid; m + 1 < N; m += 256) dst[m] = (src[m] >> (8 * lead)) | (src[m + 1] << (8 * a));
 }
 
-bool lm_host_is_pinned(const void *p);
-
 #define LM_WIRE_CHUNK ((size_t)512 << 20) // wire bytes assembled per kernel launch (device scratch of that size)
 static int serialize_run(lumen_ctx *ctx, const lumen_set *set, uint32_t first, uint32_t n, uint8_t *out, size_t cap,
                          bool wait, const char *what) {
@@ -249,8 +247,6 @@ __global__ __launch_bounds__(256) void k_ct_unwire(const uint8_t *__restrict__ w
     const u64 *w = reinterpret_cast<const u64 *>(wire + D - a);
     for (u32 m = tid; m < N; m += 256) dst[m] = (w[m] >> (8 * a)) | (w[m + 1] << (8 * (8 - a)));
 }
-
-int lm_h2d(lumen_ctx *ctx, void *dev, const void *host, size_t bytes);
 
 extern "C" int lumen_ct_deserialize(lumen_ctx *ctx, const uint8_t *bytes, size_t len, uint32_t n, uint32_t num_limbs,
                                     lumen_set **out) {

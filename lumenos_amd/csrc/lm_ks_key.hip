@@ -35,8 +35,6 @@ __global__ __launch_bounds__(256) void k_key_prepare(const u64 *__restrict__ src
     }
 }
 
-int lm_h2d(lumen_ctx *ctx, void *dev, const void *host, size_t bytes);
-
 namespace {
 
 // host words [beta][b|a][L+K][N] -> the key in the gadget product's form, on the device; returns with the stream idle

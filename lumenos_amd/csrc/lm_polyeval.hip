@@ -19,9 +19,6 @@
 #include "lm_common.h"
 #include "lm_polyeval_dev.h"
 
-bool lm_host_is_pinned(const void *p); // lm_ctx.hip
-int lm_h2d(lumen_ctx *ctx, void *dev, const void *host, size_t bytes);
-
 namespace {
 constexpr size_t PE_CHUNK_BYTES = (size_t)128 << 20; // columns staged on the device per launch
 } // namespace

@@ -228,11 +228,20 @@ def ctx_roots(P, S):
     return Oracle().field_roots(T_REF, S)
 
 
-def test_failed_collective_poisons_the_group(small):
+@pytest.mark.parametrize("collective", ["all_to_all", "gather"])
+def test_failed_collective_poisons_the_group(small, collective):
     """RCCL branch only (the test double injects the fault): an ncclSend that fails BETWEEN ncclGroupStart and ncclGroupEnd
-    makes the call return with the RCCL group closed -- which launches half a collective.  The group must then refuse every
-    later collective (naming the first error) instead of queueing work behind streams that may never drain, and
-    lumen_group_destroy must return without waiting for them.  The contexts stay usable."""
+    makes the call return with the RCCL group closed -- which launches half a collective.  That holds for either collective
+    that posts sends: the all-to-all (its second send fails) and the gather to the root (one query, owned by rank 1, whose
+    only send fails).  The group must then refuse EVERY entry point that enqueues on, or waits for, the ranks' streams
+    (naming the first error) instead of queueing work behind streams that may never drain, and lumen_group_destroy must
+    return without waiting for them.  The contexts stay usable.
+
+    The refused lumen_group_encode must not have made a temporary (on a poisoned group it could only leak it).  No counter
+    of live blocks is reachable from here -- torch.cuda.mem_get_info, which tests/test_device_ownership.py reads, cannot
+    resolve the 128 KiB blocks of this shape -- so the order is asserted instead: blocks of unequal size, which a healthy
+    group turns down in its argument checks (they precede the first lumen_lanes_split), are refused as "half-posted" too:
+    the refusal comes before the argument checks, hence before anything is made."""
     if not FAKE:
         pytest.skip("needs the RCCL test double (tests/test_group_rccl.py runs this file through it)")
     import ctypes
@@ -242,22 +251,47 @@ def test_failed_collective_poisons_the_group(small):
     ctxs = ranks_of(ctx, world)
     g = Group(ctxs, transport=TRANSPORT)
     n, nl = 2 * world, 2
-    send = [c.upload(random_cts(P, n, nl, seed=700 + r)) for r, c in enumerate(ctxs)]
+    host = [random_cts(P, n, nl, seed=700 + r) for r in range(world)]
+    send = [c.upload(h) for c, h in zip(ctxs, host)]
     recv = [c.new_set(n, nl) for c in ctxs]
+    idx = np.array([n + 1], dtype=np.uint32)  # one query; rank 1 owns columns n .. 2n - 1
+    zero = random_cts(P, 1, nl, seed=702)[0]
+    uneven = [send[0], ctxs[1].new_set(n + 2, nl)]
+    back = [np.zeros_like(h) for h in host]
     g.all_to_all(send, recv)  # a healthy call first
     g.sync()
-    ctypes.CDLL("librccl.so.1").fake_rccl_fail_send_after(1)  # the second send of the next collective
+    fake = ctypes.CDLL("librccl.so.1")
+    if collective == "all_to_all":
+        fake.fake_rccl_fail_send_after(1)  # the second send of the next collective
+        failing = lambda: g.all_to_all(send, recv)  # noqa: E731
+    else:
+        fake.fake_rccl_fail_send_after(0)  # rank 1's send to the root
+        failing = lambda: g.gather(send, idx)  # noqa: E731
     with pytest.raises(LumenError, match="ncclSend|Send"):
-        g.all_to_all(send, recv)
-    for call in (lambda: g.all_to_all(send, recv), g.sync):
+        failing()
+    refused = {
+        "all_to_all": lambda: g.all_to_all(send, recv),
+        "gather": lambda: g.gather(send, idx),
+        "sync": g.sync,
+        "encode": lambda: g.encode(send, zero, 2),
+        "encode, blocks of unequal size": lambda: g.encode(uneven, zero, 2),
+        "upload": lambda: g.upload(recv, host),
+        "download": lambda: g.download(send, back),
+        "digests": lambda: g.digests(n * world),
+        "merkle_root": g.merkle_root,
+    }
+    for name, call in refused.items():
         with pytest.raises(LumenError, match="failed half-posted"):
             call()
+            pytest.fail(name + " was not refused")
     g.close()  # returns: no wait for the poisoned streams
     # the contexts themselves are fine (the double's unmatched sends sit in a mailbox, nothing blocks a stream)
     g2 = Group(ctxs, transport=TRANSPORT)
+    with pytest.raises(LumenError, match="block 1 holds"):  # what a healthy group says to those blocks, before it makes anything
+        g2.encode(uneven, zero, 2)
     g2.all_to_all(send, recv)
     g2.sync()
-    want = send[1].download()[:n // world]
-    assert np.array_equal(recv[0].download()[n // world:], want)
+    assert np.array_equal(recv[0].download()[n // world:], host[1][:n // world])
+    assert np.array_equal(g2.gather(send, idx).download(), host[1][1:2])
     g2.close()
     ctxs[1].close()
