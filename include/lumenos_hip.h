@@ -359,6 +359,23 @@ int lumen_inner_sum_at_level(lumen_ctx *ctx, const lumen_set *in, uint32_t n, lu
 int lumen_matrix_inner_sum_at_level(lumen_ctx *ctx, const lumen_set *matrix, const uint64_t *pt,
                                     uint32_t rows, lumen_set **out);
 
+/* ---- InnerSum for any length and batch size: Evaluator.InnerSum(ct, batch_size, n), the lazy double-and-add.  The
+ * rotations of the odd bits of n are accumulated over Q and P and take ONE ModDown together; the doublings are the
+ * rotations of the entry points above.  out[j] = sum_{i < n} in[j + i * batch_size] on the slots of each row.
+ * Accepted: a full-width set at any level, 1 <= in->nl <= L; batch_size >= 1, n >= 1 and batch_size * n <= N / 2 (the
+ * sum stays inside one slot row); and batch_size == 1 with n a power of two <= N, where the result is
+ * lumen_inner_sum_at_level's word for word (the row swap at n == N included).  1 or 2 special primes.  The Galois keys
+ * of lumen_inner_sum_general_elements must be loaded.  Output: canonical residues.
+ * The entry points above keep their ranges and their refusals. */
+int lumen_inner_sum_general(lumen_ctx *ctx, const lumen_set *in, uint32_t batch_size, uint32_t n, lumen_set **out);
+/* lumen_matrix_inner_sum_at_level for the same range of rows (batch size 1); a power of two makes exactly its calls */
+int lumen_matrix_inner_sum_general(lumen_ctx *ctx, const lumen_set *matrix, const uint64_t *pt, uint32_t rows,
+                                   lumen_set **out);
+/* the Galois elements lumen_inner_sum_general(., batch_size, n) applies, in order of first use, without duplicates or
+ * the identity: a subset of params.GaloisElementsForInnerSum(batch_size, n).  gal_els: room for 64.  Returns the count;
+ * 0 for arguments the call refuses. */
+uint32_t lumen_inner_sum_general_elements(const lumen_ctx *ctx, uint32_t batch_size, uint32_t n, uint64_t *gal_els);
+
 /* ---- ciphertext x ciphertext: Evaluator.MulRelinNew(ct, ct) -- ServerBFV.MulNew / Mul take an rlwe.Operand, which may
  * be a ciphertext (fhe/bfv.go:34-42) -- with the relinearisation key the client generates and posts in the /keys body
  * (cmd/client/main.go:74-81; lumen_keygen_relin).  For two degree-1 ciphertexts a = (a0, a1), b = (b0, b1) of the same

@@ -35,6 +35,18 @@ struct KsScratch {
 int rotate_decompose(lumen_ctx *ctx, const u64 *acc, uint32_t B, KsTables *tb, const KsScratch &s);
 // steps 3-4a under one key: the gadget product in s.u, its limbs modulo P in the coefficient domain and packed
 int rotate_product(lumen_ctx *ctx, const u64 *acc, uint32_t B, const lm_galois_key &gk, KsTables *tb, const KsScratch &s);
+// ... its two halves.  Step 3: the gadget product in s.u, all nl + K limbs in the NTT domain
+int rotate_mac(lumen_ctx *ctx, const u64 *acc, uint32_t B, const lm_galois_key &gk, KsTables *tb, const KsScratch &s);
+// step 4a on any block of s.u's layout (ks_u_at): its limbs modulo P to the coefficient domain, packed
+int rotate_p_to_coef(lumen_ctx *ctx, u64 *u, uint32_t B, KsTables *tb);
+// after rotate_decompose: acc_out = acc + Rot_galEl(acc) for every column, lazy ([0, 2q)); another block than `acc`
+int rotate_add(lumen_ctx *ctx, const u64 *acc, u64 *acc_out, uint32_t B, const lm_galois_key &gk, KsTables *tb, const KsScratch &s);
+// after rotate_mac under gk: lazy (+)= sigma(u + (c0, 0)) over Q and P, no ModDown; lazy: a block of s.u's size and
+// layout, words canonical; cur in [0, 2q); `first` stores where later terms add
+int rotate_lazy_term(lumen_ctx *ctx, const u64 *cur, u64 *lazy, uint32_t B, const lm_galois_key &gk, bool first, KsTables *tb,
+                     const KsScratch &s);
+// out = ModDown(lazy) + cur for every column, canonical; `out` is another block than `cur`; lazy is consumed
+int lazy_close(lumen_ctx *ctx, const u64 *cur, u64 *out, u64 *lazy, uint32_t B, KsTables *tb, const KsScratch &s);
 // all steps: acc_out = acc + Rot_galEl(acc) for every column, lazy ([0, 2q))
 int rotate_accumulate(lumen_ctx *ctx, const u64 *acc, u64 *acc_out, uint32_t B, const lm_galois_key &gk,
                       KsTables *tb, const KsScratch &s);

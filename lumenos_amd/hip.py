@@ -115,6 +115,9 @@ SYMBOLS = {
     "lumen_inner_sum": (C.c_int, [_vp, _vp, C.c_uint32, _vpp]),
     "lumen_inner_sum_at_level": (C.c_int, [_vp, _vp, C.c_uint32, _vpp]),
     "lumen_matrix_inner_sum_at_level": (C.c_int, [_vp, _vp, _u64p, C.c_uint32, _vpp]),
+    "lumen_inner_sum_general": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, _vpp]),
+    "lumen_matrix_inner_sum_general": (C.c_int, [_vp, _vp, _u64p, C.c_uint32, _vpp]),
+    "lumen_inner_sum_general_elements": (C.c_uint32, [_vp, C.c_uint32, C.c_uint32, _u64p]),
     "lumen_load_relin_key": (C.c_int, [_vp, _u64p, C.c_uint32]),
     "lumen_mul_relin": (C.c_int, [_vp, _vp, _vp, _vpp]),
     "lumen_galois_element": (C.c_uint64, [_vp, C.c_int64]),
@@ -643,6 +646,27 @@ class Context:
         h = C.c_void_p()
         self._ck(self.lib.lumen_matrix_inner_sum_at_level(self.h, matrix.h, _p64(pt), rows, C.byref(h)))
         return DeviceSet(self, h)
+
+    def inner_sum_general(self, s, batch_size, n):
+        """InnerSum(ct, batch_size, n) for any n with batch_size * n <= N / 2 (and batch 1, n a power of two <= N) at the
+        level of `s`: the lazy double-and-add; canonical"""
+        h = C.c_void_p()
+        self._ck(self.lib.lumen_inner_sum_general(self.h, s.h, batch_size, n, C.byref(h)))
+        return DeviceSet(self, h)
+
+    def matrix_inner_sum_general(self, matrix, pt, rows):
+        """matrix_inner_sum_at_level for rows of any length <= N / 2 (and the powers of two <= N)"""
+        pt = np.ascontiguousarray(pt, dtype=np.uint64)
+        assert pt.shape == (matrix.nl, self.N), pt.shape
+        h = C.c_void_p()
+        self._ck(self.lib.lumen_matrix_inner_sum_general(self.h, matrix.h, _p64(pt), rows, C.byref(h)))
+        return DeviceSet(self, h)
+
+    def inner_sum_general_elements(self, batch_size, n):
+        """the Galois elements inner_sum_general(., batch_size, n) applies, in order of first use"""
+        g = np.zeros(64, dtype=np.uint64)
+        cnt = self.lib.lumen_inner_sum_general_elements(self.h, batch_size, n, _p64(g))
+        return [int(x) for x in g[:cnt]]
 
     def load_relin_key(self, evk, montgomery=False):
         """evk: [beta][2][L+K][N], what keygen_relin returns (rlwe.RelinearizationKey, s^2 -> s)"""

@@ -608,6 +608,14 @@ std::map<int, Ciphertexts> ServerBFV::RotateHoistedNew(const Ciphertexts &ct, co
     return out;
 }
 
+Ciphertexts ServerBFV::InnerSumNew(const Ciphertexts &ct, int batchSize, int n) {
+    if (!ct.Handle()) throw std::invalid_argument("InnerSumNew: the operand holds no ciphertexts");
+    if (batchSize < 1 || n < 1) throw std::invalid_argument("InnerSumNew: batchSize and n must be at least 1");
+    lumen_set *set = nullptr;
+    check(lumen_inner_sum_general(Context(), ct.Handle(), (uint32_t)batchSize, (uint32_t)n, &set), "lumen_inner_sum_general");
+    return Ciphertexts(Context(), set, ct.Meta);
+}
+
 Plaintext ServerBFV::Encode(const std::vector<uint64_t> &values) const {
     const int N = params_.N(), nl = (int)params_.Q.size();
     if ((int)values.size() > N) throw std::invalid_argument("cannot Encode: too many values for the ring degree");
@@ -890,8 +898,13 @@ std::pair<LigeroProver, std::vector<uint8_t>> LigeroCommitter::Commit(const Shar
 Ciphertexts matrixInnerSumEval(const Ciphertexts &matrix, const Plaintext &plaintext, int rows, ServerBFV &backend) {
     lumen_set *out = nullptr;
     // Evaluator.InnerSum works at ct.Level(): a matrix below the top level (one rescaled first) takes the entry point
-    // that does, with the plaintext at the matrix's level; a top-level one the call it always took
-    if (matrix.Level() == backend.GetParameters().MaxLevel()) {
+    // that does, with the plaintext at the matrix's level; a top-level one the call it always took.  rows that is no
+    // power of two (InnerSum(col, 1, rows) takes any: ligero.go:325) goes to the lazy double-and-add, at any level.
+    if (rows > 0 && (rows & (rows - 1))) {
+        if (plaintext.Level != matrix.Level()) throw std::invalid_argument("matrixInnerSumEval: plaintext and matrix at different levels");
+        backend.check(lumen_matrix_inner_sum_general(backend.Context(), matrix.Handle(), plaintext.Value.data(), (uint32_t)rows, &out),
+                      "lumen_matrix_inner_sum_general");
+    } else if (matrix.Level() == backend.GetParameters().MaxLevel()) {
         backend.check(lumen_matrix_inner_sum(backend.Context(), matrix.Handle(), plaintext.Value.data(), (uint32_t)rows, &out),
                       "lumen_matrix_inner_sum");
     } else {

@@ -228,6 +228,10 @@ class ServerBFV {
     // Evaluator.RotateHoistedNew(ct, rotations): rotation -> RotateColumnsNew(ct, rotation), the decomposition of c1 done
     // once (lumen_rotate_hoisted); at most 64 distinct rotations
     std::map<int, Ciphertexts> RotateHoistedNew(const Ciphertexts &ct, const std::vector<int> &rotations);
+    // Evaluator.InnerSum(ct, batchSize, n, opOut) into a new set (lumen_inner_sum_general): slot j of each row takes
+    // sum_{i < n} slot[j + i * batchSize]; any n with batchSize * n <= N / 2, and batchSize 1 with n a power of two <= N.
+    // Needs the Galois keys of a subset of GaloisElementsForInnerSum(batchSize, n).
+    Ciphertexts InnerSumNew(const Ciphertexts &ct, int batchSize, int n);
     // Encoder.Encode(values, pt) at MaxLevel ([LATTIGO-RECALL] m * T^-1 form, slot index matrix)
     Plaintext Encode(const std::vector<uint64_t> &values) const;
     // Encryptor.EncryptNew(pt) under pk, host layout [2][L][N]

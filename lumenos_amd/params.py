@@ -207,3 +207,25 @@ def galois_elements_used_by_inner_sum(log_n: int, n: int) -> List[int]:
     if n == N:
         out.append(2 * N - 1)
     return out
+
+
+def galois_elements_used_by_inner_sum_general(log_n: int, batch: int, n: int) -> List[int]:
+    """The keys InnerSum(ct, batch, n) applies for any n with batch * n <= N / 2 (lumen_inner_sum_general_elements), in
+    order of first use: per bit i of n below the top one, the lazy rotation (n - (n & (2^(i+1) - 1))) * batch when the
+    bit is set, then the doubling 2^i * batch.  A subset of galois_elements_for_inner_sum(log_n, batch, n); for batch 1
+    and n a power of two, galois_elements_used_by_inner_sum."""
+    N = 1 << log_n
+    if batch == 1 and n >= 1 and n & (n - 1) == 0 and n <= N:
+        return galois_elements_used_by_inner_sum(log_n, n)
+    if batch < 1 or n < 1 or batch * n > N // 2:
+        return []
+    out: List[int] = []
+    i, j = 0, n
+    while j > 1:
+        rots = ([(n - (n & ((2 << i) - 1))) * batch] if j & 1 else []) + [batch << i]
+        for r in rots:
+            g = galois_element(log_n, r)
+            if g != 1 and g not in out:
+                out.append(g)
+        i, j = i + 1, j >> 1
+    return out
