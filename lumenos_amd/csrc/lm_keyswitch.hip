@@ -26,15 +26,18 @@
 // accumulates the beta products of a coefficient in 128 bits, one reduction per output.
 //
 // This file is one rotation of a batch of columns: its six transform and product kernels, the per-context tables and
-// work lists, and the steps a caller composes -- rotate_decompose, rotate_product and the three ways a rotation ends,
-// rotate_accumulate, rotate_store, rotate_close, and the steps of the lazy double-and-add (rotate_mac, rotate_p_to_coef,
-// rotate_add, rotate_lazy_term with its elementwise kernel k_lazy_gather, lazy_close) -- with lumen_ks_mac_probe, which times the gadget product alone.  The
-// other subjects of the key switch live beside it: the batching of its callers (batches, lanes, groups) in
-// lm_ks_batch.hip; the callers in lm_innersum.hip (InnerSum, matrixInnerSumEval), lm_rotate.hip (lumen_automorphism,
-// lumen_rotate_columns / _rows / _hoisted) and lm_mulrelin.hip (the relinearisation); where the scratch buffers sit in HBM in
-// lm_ks_scratch.hip (mechanism) and lm_placement.h (policy), the end of the last rotation before a rescale -- the rescale's inverse
-// transform with that rotation's ModDown folded in -- in lm_ks_close.hip, Galois- and relinearisation-key loading and lookup in lm_ks_key.hip, the ciphertext x
-// plaintext product (step 0, MulNew) in lm_mulplain.hip, the stream layouts and mul128 in lm_ks_dev.h, and what these
+// work lists, and the steps a caller composes:
+//   rotate_decompose                  steps 1-2, on the ciphertext alone
+//   rotate_product                    steps 3-4a under one key, = rotate_mac (3) then rotate_p_to_coef (4a)
+//   rotate_add, rotate_store,         the three ways a decomposed rotation ends: ModDown into an accumulator, ModDown into
+//   rotate_close                      a plain gather, the closing inverse transform before a rescale (lm_ks_close.hip)
+//   rotate_accumulate                 rotate_decompose + rotate_add
+// with lumen_ks_mac_probe, which times the gadget product alone.  The other subjects of the key switch live beside it:
+// the batching of its callers (batches, lanes, groups) in lm_ks_batch.hip; the callers in lm_innersum.hip (InnerSum with
+// its lazy accumulator, matrixInnerSumEval), lm_rotate.hip (lumen_automorphism, lumen_rotate_columns / _rows / _hoisted)
+// and lm_mulrelin.hip (the relinearisation); where the scratch buffers sit in HBM in lm_ks_scratch.hip (mechanism) and
+// lm_placement.h (policy); Galois- and relinearisation-key loading and lookup in lm_ks_key.hip; the ciphertext x
+// plaintext product (step 0, MulNew) in lm_mulplain.hip; the stream layouts and mul128 in lm_ks_dev.h; and what these
 // units share on the host in lm_ks_host.h.
 #include <cstdlib>
 #include <cstring>
@@ -628,48 +631,6 @@ __global__ LM_GEOM_BOUNDS(lm_geom_fwd(LOGN)) void k_rotdown_ntt(LM_MODDOWN_PARAM
     moddown_body<LOGN, false>(u, acc_in, acc_out, bxp, pinv, index, inv_index, work, B, L, K, mods, tw_all);
 }
 
-// ---- the lazy gather-accumulate of an InnerSum of general length (rotate_lazy_term, lazy_close).  Elementwise over
-// the 2B (L + K) limbs of u's layout (ks_u_at on both sides), right after k_ks_mac, every limb in the NTT domain:
-//     lazy[pw][t][j] = (first ? 0 : lazy[pw][t][j]) + u[pw][t][index[j]] (+ c0[t][index[j]] for w == 0, t < L)
-// The Q limbs of u carry P^-1 (folded into the key, see moddown_body's storer), so Lattigo's P * c0 is plain c0 there;
-// on the limbs modulo P it is 0.  The same index table serves every limb.  One thread per PAIR of outputs: the index
-// words and the accumulator move as 8 / 16-byte accesses, linearly; the two gathered words come from the aligned source
-// block the output block maps to (moddown_body: the top bits of index[j] are a function of the top bits of j), at most
-// N words apart, out of L2.
-// The close (u == NULL, index == NULL: no product, the identity): lazy[pw][t][j] += c1[t][j] for w == 1, t < L alone.
-// RANGES.  u < q (lm_mont_reduce_wide), cur in [0, 2q) (the lazy accumulator of the doublings), the stored word < q:
-// the sum is below 4q < 2^64 for every modulus of a context ((3 logN + 8) q < 2^64) and comes back under q with two
-// conditional subtractions.  Every accumulator word is CANONICAL whatever the number of terms: the inverse transform
-// of the limbs modulo P and the ModDown that close the sum take it as they take a gadget product.
-__global__ __launch_bounds__(256) void k_lazy_gather(const u64 *__restrict__ u, const u64 *__restrict__ cur, u64 *__restrict__ lazy,
-                                                     const uint32_t *__restrict__ index, uint32_t B, uint32_t L, uint32_t K,
-                                                     uint32_t pshift, uint32_t logN, uint32_t first, lm_mods mods) {
-    const uint32_t N = 1u << logN, nq = L * 2 * B; // limbs [0, nq) of the layout are Q limbs: [L][2B]; behind them [2B][K]
-    const size_t total = (size_t)2 * B * (L + K) * (N / 2), stride = (size_t)gridDim.x * blockDim.x;
-    for (size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x; g < total; g += stride) {
-        const uint32_t j = (uint32_t)(g & (N / 2 - 1)) * 2, limb = (uint32_t)(g >> (logN - 1));
-        const uint32_t t = limb < nq ? limb / (2 * B) : L + (limb - nq) % K;
-        const uint32_t pw = limb < nq ? limb % (2 * B) : (limb - nq) / K;
-        const bool with_c = t < L && (pw & 1) == (u ? 0u : 1u); // c0 rides on a term's polynomial 0, c1 on the close's polynomial 1
-        if (!u && !with_c) continue;
-        const u64 q = mods.m[ks_mod_at(t, L, pshift)].q;
-        const size_t o = ((size_t)limb << logN) + j;
-        uint2 p;
-        p.x = j, p.y = j + 1;
-        if (index) p = *reinterpret_cast<const uint2 *>(index + j);
-        ulonglong2 v;
-        v.x = v.y = 0;
-        if (!first) v = *reinterpret_cast<const ulonglong2 *>(lazy + o);
-        if (u) v.x += u[((size_t)limb << logN) + p.x], v.y += u[((size_t)limb << logN) + p.y];
-        if (with_c) {
-            const u64 *c = cur + (((size_t)pw * L + t) << logN); // [B][2][L][N]: polynomial pw = 2b + w, limb t
-            v.x += c[p.x], v.y += c[p.y];
-        }
-        v.x = lm_csub(lm_csub(v.x, 2 * q), q), v.y = lm_csub(lm_csub(v.y, 2 * q), q);
-        *reinterpret_cast<ulonglong2 *>(lazy + o) = v;
-    }
-}
-
 // -------------------------------------------------------------------- host side
 namespace {
 
@@ -1008,65 +969,15 @@ int rotate_add(lumen_ctx *ctx, const u64 *acc, u64 *acc_out, uint32_t B, const l
     return launch_moddown<true>(ctx, acc, acc_out, B, gk, tb, s);
 }
 
-// ---- the lazy term of an InnerSum of general length ([LATTIGO-RECALL] Evaluator.InnerSum, the odd-bit branch): the
-// rotation is accumulated over Q AND P, before any ModDown.  After rotate_mac under the term's key:
-//     lazy = (first ? 0 : lazy) + sigma(u + (c0, 0))
-// in s.u's layout, every limb in the NTT domain.  The close then adds the last `cur` -- c1 here (lazy_close's first
-// launch, a term without u and without a gather), c0 in the ModDown that follows.
-int rotate_lazy_term(lumen_ctx *ctx, const u64 *cur, u64 *lazy, uint32_t B, const lm_galois_key &gk, bool first, KsTables *tb,
-                     const KsScratch &s) {
-    lm_prof_scope ps(ctx, "ks_lazy_gather", (uint64_t)B);
-    hipLaunchKernelGGL(k_lazy_gather, dim3(2048), dim3(256), 0, ctx->stream, s.u, cur, lazy, gk.d_index.get(), B, tb->nl, ctx->K,
-                       ctx->L - tb->nl, ctx->logN, first ? 1u : 0u, ctx->mods);
-    LM_HIP(ctx, hipGetLastError());
-    return 0;
-}
-
-// the identity's gather tables, owned by the context and built at first use: the ModDown of the lazy accumulator
-// permutes nothing (the relinearisation key has such a pair too, but it may not be loaded)
-static int identity_tables(lumen_ctx *ctx, std::shared_ptr<lm_galois_key> *out) {
-    static const char *const NAME = "ks_identity";
-    LM_SHARED_LOCK(ctx);
-    auto gk = lm_ext_get<lm_galois_key>(ctx, NAME);
-    if (!gk) {
-        gk = std::make_shared<lm_galois_key>();
-        std::vector<uint32_t> index(ctx->N);
-        for (uint32_t i = 0; i < ctx->N; i++) index[i] = i;
-        if (gk->d_index.upload(ctx, index, "the identity's index table") || gk->d_inv_index.upload(ctx, index, "the identity's index table"))
-            return 1;
-        lm_ext_put(ctx, NAME, gk);
-    }
-    *out = std::move(gk);
-    return 0;
-}
-
-// out = ModDown(lazy) + cur for every column, canonical; `out` is another block than `cur`, lazy is consumed.
-// lazy_1 += c1 on the Q limbs (elementwise), step 4a on the lazy block, then the rotation's storing ModDown under the
-// identity: it adds `cur`'s c0 to polynomial 0 itself and nothing to polynomial 1.
-int lazy_close(lumen_ctx *ctx, const u64 *cur, u64 *out, u64 *lazy, uint32_t B, KsTables *tb, const KsScratch &s) {
-    std::shared_ptr<lm_galois_key> id;
-    if (int rc = identity_tables(ctx, &id)) return rc;
-    {
-        lm_prof_scope ps(ctx, "ks_lazy_gather", (uint64_t)B);
-        hipLaunchKernelGGL(k_lazy_gather, dim3(2048), dim3(256), 0, ctx->stream, (const u64 *)nullptr, cur, lazy, (const uint32_t *)nullptr, B,
-                           tb->nl, ctx->K, ctx->L - tb->nl, ctx->logN, 0u, ctx->mods);
-        LM_HIP(ctx, hipGetLastError());
-    }
-    if (int rc = rotate_p_to_coef(ctx, lazy, B, tb)) return rc;
-    KsScratch sl = s;
-    sl.u = lazy;
-    return launch_moddown<false>(ctx, cur, out, B, *id, tb, sl);
-}
-
 // After rotate_product: out = Rot_galEl(in) for every column, canonical, [B][2][L][N] both; `out` is another block than `in`.
 int rotate_store(lumen_ctx *ctx, const u64 *in, u64 *out, uint32_t B, const lm_galois_key &gk, KsTables *tb, const KsScratch &s) {
     return launch_moddown<false>(ctx, in, out, B, gk, tb, s);
 }
 
-// coef_out = the coefficient form of acc + Rot_galEl(acc), [B][2][L][N]: the last rotation before a rescale (lm_ks_close.hip)
+// After rotate_decompose: coef_out = the coefficient form of acc + Rot_galEl(acc), [B][2][L][N]: the last rotation before a
+// rescale (lm_ks_close.hip)
 int rotate_close(lumen_ctx *ctx, const u64 *acc, u64 *coef_out, uint32_t B, const lm_galois_key &gk, uint64_t gal_el,
                  KsTables *tb, const KsScratch &s) {
-    if (int rc = rotate_decompose(ctx, acc, B, tb, s)) return rc;
     if (int rc = rotate_product(ctx, acc, B, gk, tb, s)) return rc;
     const uint32_t *work_down = nullptr;
     if (int rc = moddown_work_list(ctx, tb, B, &work_down)) return rc;

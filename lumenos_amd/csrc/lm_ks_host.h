@@ -41,18 +41,13 @@ int rotate_mac(lumen_ctx *ctx, const u64 *acc, uint32_t B, const lm_galois_key &
 int rotate_p_to_coef(lumen_ctx *ctx, u64 *u, uint32_t B, KsTables *tb);
 // after rotate_decompose: acc_out = acc + Rot_galEl(acc) for every column, lazy ([0, 2q)); another block than `acc`
 int rotate_add(lumen_ctx *ctx, const u64 *acc, u64 *acc_out, uint32_t B, const lm_galois_key &gk, KsTables *tb, const KsScratch &s);
-// after rotate_mac under gk: lazy (+)= sigma(u + (c0, 0)) over Q and P, no ModDown; lazy: a block of s.u's size and
-// layout, words canonical; cur in [0, 2q); `first` stores where later terms add
-int rotate_lazy_term(lumen_ctx *ctx, const u64 *cur, u64 *lazy, uint32_t B, const lm_galois_key &gk, bool first, KsTables *tb,
-                     const KsScratch &s);
-// out = ModDown(lazy) + cur for every column, canonical; `out` is another block than `cur`; lazy is consumed
-int lazy_close(lumen_ctx *ctx, const u64 *cur, u64 *out, u64 *lazy, uint32_t B, KsTables *tb, const KsScratch &s);
 // all steps: acc_out = acc + Rot_galEl(acc) for every column, lazy ([0, 2q))
 int rotate_accumulate(lumen_ctx *ctx, const u64 *acc, u64 *acc_out, uint32_t B, const lm_galois_key &gk,
                       KsTables *tb, const KsScratch &s);
-// after rotate_product: out = Rot_galEl(in) for every column, canonical; `out` is another block than `in`
+// after rotate_product: out = Rot_galEl(in) for every column, canonical; `out` is another block than `in`.  (s.u may be
+// any block of its layout that went through rotate_p_to_coef: InnerSum's lazy accumulator ends so, under the identity)
 int rotate_store(lumen_ctx *ctx, const u64 *in, u64 *out, uint32_t B, const lm_galois_key &gk, KsTables *tb, const KsScratch &s);
-// all steps, the last rotation before a rescale: coef_out = the coefficient form of acc + Rot_galEl(acc)
+// after rotate_decompose, the last rotation before a rescale: coef_out = the coefficient form of acc + Rot_galEl(acc)
 int rotate_close(lumen_ctx *ctx, const u64 *acc, u64 *coef_out, uint32_t B, const lm_galois_key &gk, uint64_t gal_el,
                  KsTables *tb, const KsScratch &s);
 // the last rotation of an InnerSum that a rescale follows, after its steps 1-4a (lm_ks_close.hip): out, [B][2][nl][N], gets

@@ -897,21 +897,12 @@ std::pair<LigeroProver, std::vector<uint8_t>> LigeroCommitter::Commit(const Shar
 
 Ciphertexts matrixInnerSumEval(const Ciphertexts &matrix, const Plaintext &plaintext, int rows, ServerBFV &backend) {
     lumen_set *out = nullptr;
-    // Evaluator.InnerSum works at ct.Level(): a matrix below the top level (one rescaled first) takes the entry point
-    // that does, with the plaintext at the matrix's level; a top-level one the call it always took.  rows that is no
-    // power of two (InnerSum(col, 1, rows) takes any: ligero.go:325) goes to the lazy double-and-add, at any level.
-    if (rows > 0 && (rows & (rows - 1))) {
-        if (plaintext.Level != matrix.Level()) throw std::invalid_argument("matrixInnerSumEval: plaintext and matrix at different levels");
-        backend.check(lumen_matrix_inner_sum_general(backend.Context(), matrix.Handle(), plaintext.Value.data(), (uint32_t)rows, &out),
-                      "lumen_matrix_inner_sum_general");
-    } else if (matrix.Level() == backend.GetParameters().MaxLevel()) {
-        backend.check(lumen_matrix_inner_sum(backend.Context(), matrix.Handle(), plaintext.Value.data(), (uint32_t)rows, &out),
-                      "lumen_matrix_inner_sum");
-    } else {
-        if (plaintext.Level != matrix.Level()) throw std::invalid_argument("matrixInnerSumEval: plaintext and matrix at different levels");
-        backend.check(lumen_matrix_inner_sum_at_level(backend.Context(), matrix.Handle(), plaintext.Value.data(), (uint32_t)rows, &out),
-                      "lumen_matrix_inner_sum_at_level");
-    }
+    // Evaluator.InnerSum works at ct.Level() and InnerSum(col, 1, rows) takes any rows (ligero.go:325): one entry point
+    // serves every level and length, and makes lumen_matrix_inner_sum's calls for a power of two at the top level.  The
+    // device reads matrix.Level() + 1 limbs of the plaintext, which holds Level + 1 of them.
+    if (plaintext.Level != matrix.Level()) throw std::invalid_argument("matrixInnerSumEval: plaintext and matrix at different levels");
+    backend.check(lumen_matrix_inner_sum_general(backend.Context(), matrix.Handle(), plaintext.Value.data(), (uint32_t)rows, &out),
+                  "lumen_matrix_inner_sum_general");
     // MulNew: Scale_ct * Scale_pt (Encoder.Encode leaves 1); InnerSum keeps it; the Rescale loop to level 1
     MetaData md = matrix.Meta;
     md.Scale = RescaledScale(backend.GetParameters(), md.Scale, matrix.Level(), 1);

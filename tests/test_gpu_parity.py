@@ -1102,6 +1102,16 @@ def test_empty_sets_through_the_batch_entry_points(oracle, small):
     assert ctx.mul_plain(e4, pt).count == 0
     assert ctx.inner_sum(e4, 8).count == 0
     assert ctx.matrix_inner_sum(e4, pt, 8).count == 0
+    bare = make_context(P)  # no Galois key loaded: a sum of nothing looks none up
+    try:
+        b4 = bare.new_set(0, P.L)
+        assert bare.inner_sum(b4, 8).count == 0
+        assert bare.inner_sum_at_level(b4, 8).count == 0
+        assert bare.inner_sum_general(b4, 1, 7).count == 0
+        assert bare.matrix_inner_sum(b4, pt, 8).count == 0
+        assert bare.matrix_inner_sum_general(b4, pt, 7).count == 0
+    finally:
+        bare.close()
     key = P.keygen_ringswitch(sk, P.keygen_secret_small(8), 8)
     ctx.load_ringswitch_key(8, key)
     assert ctx.ring_switch(e2).shape == (0, 2, 256)
