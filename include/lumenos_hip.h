@@ -53,7 +53,10 @@ typedef struct lumen_group lumen_group;
  * (Lattigo: SubRing.RootsForward; standard form here). */
 typedef struct lumen_params_desc {
     uint32_t abi_version; /* LUMEN_ABI_VERSION */
-    uint32_t log_n;
+    uint32_t log_n; /* 8, 10 .. 14: every entry point; 15: transforms, rescale, products, Encode / Commit / gather / wire
+                     * format, key loading, InnerSum, rotations, relinearisation -- lumen_keygen_*, lumen_encrypt_*,
+                     * lumen_ct_expand_seeded, lumen_decrypt, lumen_verify_columns, lumen_batch_ciphertexts,
+                     * lumen_vdec_witness and lumen_ring_switch fail there with an error that names the degree */
     uint32_t num_q; /* L */
     uint32_t num_p; /* K (alpha) */
     uint64_t plaintext_modulus;

@@ -268,8 +268,10 @@ extern "C" int lumen_ctx_create(const lumen_params_desc *desc, lumen_ctx **out) 
     *out = nullptr;
     LM_CHECK(nullptr, desc->abi_version == LUMEN_ABI_VERSION, "ABI version mismatch: got %u want %u",
              desc->abi_version, LUMEN_ABI_VERSION);
-    LM_CHECK(nullptr, lm_logn_supported(desc->log_n),
-             "log_n %u unsupported: kernels are instantiated for N = 2^8 and 2^10..2^14", desc->log_n);
+    LM_CHECK(nullptr, lm_logn_supported(desc->log_n) || lm_logn_split_supported(desc->log_n),
+             "log_n %u unsupported: kernels are instantiated for N = 2^8 and 2^10..2^14, and the server's path and the key "
+             "switch for N = 2^15",
+             desc->log_n);
     LM_CHECK(nullptr, desc->num_q >= 1 && desc->num_q + desc->num_p <= LM_MAX_LIMBS,
              "bad limb counts L=%u K=%u", desc->num_q, desc->num_p);
     int ndev = 0;
@@ -292,7 +294,8 @@ extern "C" int lumen_ctx_create(const lumen_params_desc *desc, lumen_ctx **out) 
     for (uint32_t i = 0; i < LK; i++) {
         uint64_t q = desc->moduli[i], psi = desc->psi[i];
         // the lazy forward NTT takes inputs below 7q (fused basis extension) and lets values grow
-        // by 3q per stage before its one reduction
+        // by 3q per stage before its one reduction (a split degree, lm_ntt_dev.h: the outer butterfly in the loader is one of
+        // the log_n stages -- the half transform starts below 10q and its storer sees (3 (log_n - 1) + 10) q = (3 log_n + 7) q)
         // ... and the InnerSum accumulator is lazy in [0, 2q) across the rotations (lm_keyswitch.hip, k_moddown_ntt: acc < 2q
         // plus d < 6q must not wrap): 8q < 2^64, implied by the bound below for every log_n >= 0 and stated here because
         // the kernels' comments refer to it
@@ -317,6 +320,9 @@ extern "C" int lumen_ctx_create(const lumen_params_desc *desc, lumen_ctx **out) 
         fwd.insert(fwd.end(), f.begin(), f.end());
         inv.insert(inv.end(), b.begin(), b.end());
     }
+    // a split degree: per modulus the two sub-tables of the half transforms in place of the one table (lm_split_tw)
+    lm_layout_tw(fwd, ctx->logN);
+    lm_layout_tw(inv, ctx->logN);
     if (ctx->sh->tw_fwd.upload(ctx, fwd, "the forward twiddles") || ctx->sh->tw_inv.upload(ctx, inv, "the inverse twiddles")) return 1;
     *out = guard.release();
     return 0;

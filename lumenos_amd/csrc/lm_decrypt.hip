@@ -236,6 +236,7 @@ int lm_decrypt_slots(lumen_ctx *ctx, const lm_decoded &dec, uint32_t count, uint
 extern "C" int lumen_decrypt(lumen_ctx *ctx, const lumen_set *set, uint64_t scale, uint32_t nvalues, uint64_t *values) {
     LM_CHECK(nullptr, ctx && set && values, "lumen_decrypt: NULL argument");
     LM_ENTER(ctx);
+    LM_REFUSE_SPLIT(ctx, "lumen_decrypt");
     if (int rc = lm_decrypt_check(ctx, set, scale, "lumen_decrypt")) return rc;
     LM_CHECK(ctx, nvalues >= 1 && nvalues <= ctx->N, "nvalues=%u out of range [1, N]", nvalues);
     if (!set->count) return 0;

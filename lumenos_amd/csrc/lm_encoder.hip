@@ -19,6 +19,8 @@ extern "C" int lumen_encoder_set(lumen_ctx *ctx, uint64_t psi_t) {
     }
     std::vector<tw_t> f, b;
     lm_build_tw(T, psi_t, logN, f, b);
+    lm_layout_tw(f, logN); // a split degree: the sub-tables of the half transforms, as the context's own tables
+    lm_layout_tw(b, logN);
     std::vector<uint32_t> slot(N);
     const uint64_t m = 2ull * N;
     uint64_t pos = 1;

@@ -291,6 +291,7 @@ extern "C" int lumen_encrypt_pk(lumen_ctx *ctx, const uint64_t *plaintexts, uint
                                 uint64_t first_index, lumen_set **out) {
     LM_CHECK(nullptr, ctx && seed && out, "lumen_encrypt_pk: NULL argument");
     LM_ENTER(ctx);
+    LM_REFUSE_SPLIT(ctx, "lumen_encrypt_pk");
     return encrypt_impl(ctx, plaintexts, nullptr, 0, count, seed, first_index, out);
 }
 
@@ -298,5 +299,6 @@ extern "C" int lumen_encrypt_values(lumen_ctx *ctx, const uint64_t *values, uint
                                     const uint8_t seed[32], uint64_t first_index, lumen_set **out) {
     LM_CHECK(nullptr, ctx && values && seed && out, "lumen_encrypt_values: NULL argument");
     LM_ENTER(ctx);
+    LM_REFUSE_SPLIT(ctx, "lumen_encrypt_values");
     return encrypt_impl(ctx, nullptr, values, rows, count, seed, first_index, out);
 }

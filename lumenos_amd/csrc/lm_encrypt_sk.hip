@@ -136,6 +136,7 @@ extern "C" int lumen_encrypt_sk_values(lumen_ctx *ctx, const uint64_t *values, u
                                        lumen_set **out) {
     LM_CHECK(nullptr, ctx, "lumen_encrypt_sk_values: NULL ctx");
     LM_ENTER(ctx);
+    LM_REFUSE_SPLIT(ctx, "lumen_encrypt_sk_values");
     LM_CHECK(ctx, secret_seed && a_seed && out && (values || !count), "lumen_encrypt_sk_values: NULL argument");
     if (int rc = enc_sk_check(ctx, "lumen_encrypt_sk_values", rows, secret_seed, a_seed)) return rc;
     lumen_set *o = nullptr;
@@ -152,6 +153,7 @@ extern "C" int lumen_encrypt_sk_seeded(lumen_ctx *ctx, const uint64_t *values, u
                                        uint64_t *c0) {
     LM_CHECK(nullptr, ctx, "lumen_encrypt_sk_seeded: NULL ctx");
     LM_ENTER(ctx);
+    LM_REFUSE_SPLIT(ctx, "lumen_encrypt_sk_seeded");
     LM_CHECK(ctx, secret_seed && a_seed && ((values && c0) || !count), "lumen_encrypt_sk_seeded: NULL argument");
     if (int rc = enc_sk_check(ctx, "lumen_encrypt_sk_seeded", rows, secret_seed, a_seed)) return rc;
     if (!count) return 0;
@@ -162,6 +164,7 @@ extern "C" int lumen_ct_expand_seeded(lumen_ctx *ctx, const uint64_t *c0, uint32
                                       uint64_t first_index, lumen_set **out) {
     LM_CHECK(nullptr, ctx, "lumen_ct_expand_seeded: NULL ctx");
     LM_ENTER(ctx);
+    LM_REFUSE_SPLIT(ctx, "lumen_ct_expand_seeded");
     LM_CHECK(ctx, a_seed && out && (c0 || !count), "lumen_ct_expand_seeded: NULL argument");
     const uint32_t N = ctx->N, L = ctx->L;
     const size_t limbs = (size_t)L * N;

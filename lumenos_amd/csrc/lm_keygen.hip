@@ -251,6 +251,7 @@ static std::vector<u64> kg_gadget(const lumen_ctx *ctx, uint32_t rns, uint32_t p
 extern "C" int lumen_keygen_secret(lumen_ctx *ctx, const uint8_t seed[32], uint64_t *sk) {
     LM_CHECK(nullptr, ctx, "lumen_keygen_secret: NULL ctx");
     LM_ENTER(ctx);
+    LM_REFUSE_SPLIT(ctx, "lumen_keygen_secret");
     LM_CHECK(ctx, seed, "lumen_keygen_secret: NULL argument");
     const uint32_t N = ctx->N, L = ctx->L, LK = L + ctx->K;
     const size_t words = (size_t)LK * N;
@@ -282,6 +283,7 @@ extern "C" int lumen_keygen_secret(lumen_ctx *ctx, const uint8_t seed[32], uint6
 extern "C" int lumen_keygen_public(lumen_ctx *ctx, const uint8_t seed[32], uint64_t *pk) {
     LM_CHECK(nullptr, ctx, "lumen_keygen_public: NULL ctx");
     LM_ENTER(ctx);
+    LM_REFUSE_SPLIT(ctx, "lumen_keygen_public");
     LM_CHECK(ctx, seed && pk, "lumen_keygen_public: NULL argument");
     const std::shared_ptr<KgSecret> s = kg_secret_of(ctx);
     LM_KG_NEED_SECRET(ctx, s, "lumen_keygen_public");
@@ -291,6 +293,7 @@ extern "C" int lumen_keygen_public(lumen_ctx *ctx, const uint8_t seed[32], uint6
 extern "C" int lumen_keygen_relin(lumen_ctx *ctx, const uint8_t seed[32], uint64_t *evk, uint32_t flags) {
     LM_CHECK(nullptr, ctx, "lumen_keygen_relin: NULL ctx");
     LM_ENTER(ctx);
+    LM_REFUSE_SPLIT(ctx, "lumen_keygen_relin");
     LM_CHECK(ctx, seed && evk, "lumen_keygen_relin: NULL argument");
     const std::shared_ptr<KgSecret> s = kg_secret_of(ctx);
     LM_KG_NEED_SECRET(ctx, s, "lumen_keygen_relin");
@@ -311,6 +314,7 @@ extern "C" int lumen_keygen_galois(lumen_ctx *ctx, const uint8_t seed[32], const
                                    uint64_t *evk, uint32_t flags) {
     LM_CHECK(nullptr, ctx, "lumen_keygen_galois: NULL ctx");
     LM_ENTER(ctx);
+    LM_REFUSE_SPLIT(ctx, "lumen_keygen_galois");
     LM_CHECK(ctx, seed && (count == 0 || (gal_els && evk)), "lumen_keygen_galois: NULL argument");
     const std::shared_ptr<KgSecret> s = kg_secret_of(ctx);
     LM_KG_NEED_SECRET(ctx, s, "lumen_keygen_galois");
@@ -352,6 +356,7 @@ extern "C" int lumen_keygen_ringswitch(lumen_ctx *ctx, const uint8_t seed[32], u
                                        uint64_t *key, size_t key_words, int8_t *sk_small) {
     LM_CHECK(nullptr, ctx, "lumen_keygen_ringswitch: NULL ctx");
     LM_ENTER(ctx);
+    LM_REFUSE_SPLIT(ctx, "lumen_keygen_ringswitch");
     LM_CHECK(ctx, seed && key && sk_small, "lumen_keygen_ringswitch: NULL argument");
     const std::shared_ptr<KgSecret> s = kg_secret_of(ctx);
     LM_KG_NEED_SECRET(ctx, s, "lumen_keygen_ringswitch");

@@ -207,11 +207,14 @@ __global__ LM_GEOM_BOUNDS(lm_geom_fwd(LOGN)) void k_modup_ntt(const u64 *__restr
     // The grid only holds the (column, digit, target) triples that need an extension (a digit's own
     // limbs reuse the NTT-domain c1), in the order of a host-built work list (modup_work_list): XCD-
     // aware, so that the targets of one digit run back to back on one XCD and share its L2.
-    const uint32_t wk = work[blockIdx.x];
+    // (a split degree: two workgroups per work-list entry, one per half of the target limb -- the packed words have no
+    // spare bit, the half comes from the grid: lm_half_of_block)
+    const lm_half<LOGN> hf = lm_half_of_block<LOGN>();
+    const uint32_t wk = work[hf.block];
     const uint32_t b = wk & 0xFFFF, d = (wk >> 16) & 0xFF, t = wk >> 24; // t: target position (Q limbs then P limbs)
     const uint32_t mt = ks_mod_at(t, L, pshift);                         // its modulus: wave-uniform, as t is
     const bx_t c = bx[d * LK + t];
-    u64 *o = ext + ks_ext_at(b, d, t, B, beta) * N;
+    u64 *o = ext + ks_ext_at(b, d, t, B, beta) * N + hf.off;
     const lm_qc qc = lm_make_qc(mods.m[mt]);
     const u64 *s0 = coef + ((size_t)b * L + d * K) * N;
     const u64 *s1 = c.ns == 2 ? s0 + N : s0; // second limb of the digit
@@ -226,7 +229,11 @@ __global__ LM_GEOM_BOUNDS(lm_geom_fwd(LOGN)) void k_modup_ntt(const u64 *__restr
         y.x = v0, y.y = v1;
         *reinterpret_cast<ulonglong2 *>(o + j) = y;
     };
-    if constexpr (LOGN == 14) { // limb in registers, two workgroups per CU: the runs go through the wave's slot, half by half
+    if constexpr (lm_is_split(LOGN)) { // the half transform, the extension fused into both loads of the outer butterfly
+        lm_lds_runs st{sm};
+        auto after = [&](uint32_t, uint32_t) { lm_linear_out<lm_tlog(LOGN)>(sm, tid, out); };
+        lm_ntt_forward_split<LOGN>(sm, tw_all + (size_t)mt * N, qc, tid, hf, ld, st, after);
+    } else if constexpr (LOGN == 14) { // limb in registers, two workgroups per CU: the runs go through the wave's slot, half by half
         lm_w14_runs st{sm};
         auto after = [&](uint32_t i0, uint32_t) { lm_w14_linear_out(sm, tid, i0, out); };
         lm_ntt_forward_w14(sm, tw_all + (size_t)mt * N, qc, tid, ld, st, after);
@@ -452,7 +459,8 @@ __device__ __forceinline__ void moddown_body(const u64 *__restrict__ u, const u6
     const uint32_t tid = threadIdx.x;
     // host-built, XCD-aware order (moddown_work_list): the Q limbs of one polynomial, which all lift the
     // same two P-limb words, run back to back on one XCD
-    const uint32_t wk = work[blockIdx.x];
+    const lm_half<LOGN> hf = lm_half_of_block<LOGN>(); // a split degree: two workgroups per entry, one per half
+    const uint32_t wk = work[hf.block];
     const uint32_t pw = wk & 0xFFFF; // b*2 + w
     const uint32_t t = wk >> 16;
     const uint32_t w = pw & 1;
@@ -542,7 +550,11 @@ __device__ __forceinline__ void moddown_body(const u64 *__restrict__ u, const u6
     } else {
         // the store phase combines every finished run of 8 with the gadget product u (and c0 for w == 0): both
         // are requested by pre() before the run's butterflies, not after them
-        constexpr int RUN = lm_fwd_run<LOGN>();
+        // A split degree: this workgroup owns half hf.h of the limb, NTT-domain positions [hf.off, hf.off + N/2), as the
+        // output of a transform of TLOG = LOGN - 1 stages.  The storer's pointers start at the half; the gather below
+        // works on blocks of the WHOLE limb (wave `wave` has left block hf.off / BLK + wave in LDS, at local positions).
+        constexpr int TLOG = lm_tlog(LOGN);
+        constexpr int RUN = lm_fwd_run<TLOG>();
         static_assert(RUN <= 8, "lm_load_run moves at most 8 coefficients");
         struct storer_t {
             const u64 *uq, *ain;
@@ -567,7 +579,7 @@ __device__ __forceinline__ void moddown_body(const u64 *__restrict__ u, const u6
                         sm[LM_PAD(i0 + k)] = lm_shoup3<true>(v[k], pi.w, pi.wp, qc.nq, add); // the slots this work item just consumed
                     }
             }
-        } st{uq, ain, sm, qc, pi, w, {}, {}};
+        } st{uq + hf.off, ain + hf.off, sm, qc, pi, w, {}, {}};
         // acc_out[j] = acc_in[j] + d[index[j]]: the automorphism is applied as a gather out of LDS, so the
         // accumulator itself streams through HBM linearly in 16-byte vectors.
         // NO workgroup barrier (round 5).  In the bit-reversed order of the NTT domain an automorphism X -> X^g permutes
@@ -580,9 +592,11 @@ __device__ __forceinline__ void moddown_body(const u64 *__restrict__ u, const u6
         // (profiles/r02_ubench_phases.txt), and the barrier this replaces made the early ones wait for the last.
         // Every lane handles 8 pairs; only the block number jb is fetched early -- the pairs' index and accumulator words are
         // requested in `after`, once the wave's last pass is done (ahead of it they cost 48 VGPRs the last pass needs).
-        constexpr uint32_t NW = lm_nthreads(LOGN) / 64, BLK = N / NW, IT = BLK / 128;
+        // (a split degree: with the whole half as the block the same argument says that output half inv_index[h N/2] / (N/2)
+        // gathers from input half h alone -- in place for g = 1 mod 4, swapped for g = 3 mod 4, the row swap 2N - 1 among them)
+        constexpr uint32_t NW = lm_nthreads(TLOG) / 64, BLK = (1u << TLOG) / NW, IT = BLK / 128;
         const uint32_t wave = tid >> 6, lane = tid & 63;
-        const uint32_t jb = NW > 1 ? (uint32_t)__builtin_amdgcn_readfirstlane((int)(inv_index[wave * BLK] / BLK)) : 0u;
+        const uint32_t jb = NW > 1 ? (uint32_t)__builtin_amdgcn_readfirstlane((int)(inv_index[hf.off + wave * BLK] / BLK)) : 0u;
         auto after = [&](uint32_t, uint32_t) {
             uint2 p[IT];
             ulonglong2 x[IT];
@@ -603,16 +617,19 @@ __device__ __forceinline__ void moddown_body(const u64 *__restrict__ u, const u6
                 // (any u64), this kernel, and the rescale that ends matrixInnerSumEval (lm_rescale.hip).
                 ulonglong2 y;
                 if constexpr (ACCUMULATE) {
-                    y.x = lm_csub(lm_csub(x[k].x + sm[LM_PAD(p[k].x)], 4 * qc.q), 2 * qc.q);
-                    y.y = lm_csub(lm_csub(x[k].y + sm[LM_PAD(p[k].y)], 4 * qc.q), 2 * qc.q);
+                    y.x = lm_csub(lm_csub(x[k].x + sm[LM_PAD(lm_half_local<LOGN>(p[k].x))], 4 * qc.q), 2 * qc.q);
+                    y.y = lm_csub(lm_csub(x[k].y + sm[LM_PAD(lm_half_local<LOGN>(p[k].y))], 4 * qc.q), 2 * qc.q);
                 } else { // the rotation alone: d < 6q, canonical -- no k_acc_canon pass follows
-                    y.x = lm_csub(lm_csub(lm_csub(sm[LM_PAD(p[k].x)], 4 * qc.q), 2 * qc.q), qc.q);
-                    y.y = lm_csub(lm_csub(lm_csub(sm[LM_PAD(p[k].y)], 4 * qc.q), 2 * qc.q), qc.q);
+                    y.x = lm_csub(lm_csub(lm_csub(sm[LM_PAD(lm_half_local<LOGN>(p[k].x))], 4 * qc.q), 2 * qc.q), qc.q);
+                    y.y = lm_csub(lm_csub(lm_csub(sm[LM_PAD(lm_half_local<LOGN>(p[k].y))], 4 * qc.q), 2 * qc.q), qc.q);
                 }
                 *reinterpret_cast<ulonglong2 *>(aout + j) = y;
             }
         };
-        lm_ntt_forward<LOGN>(sm, tw_all + (size_t)t * N, qc, tid, ld, st, after);
+        if constexpr (lm_is_split(LOGN))
+            lm_ntt_forward_split<LOGN>(sm, tw_all + (size_t)t * N, qc, tid, hf, ld, st, after);
+        else
+            lm_ntt_forward<LOGN>(sm, tw_all + (size_t)t * N, qc, tid, ld, st, after);
     }
 }
 
@@ -628,6 +645,17 @@ __global__ LM_GEOM_BOUNDS(lm_geom_fwd(LOGN)) void k_moddown_ntt(LM_MODDOWN_PARAM
 // output set (another block: a workgroup's output block is another workgroup's c0)
 template <int LOGN>
 __global__ LM_GEOM_BOUNDS(lm_geom_fwd(LOGN)) void k_rotdown_ntt(LM_MODDOWN_PARAMS) {
+    moddown_body<LOGN, false>(u, acc_in, acc_out, bxp, pinv, index, inv_index, work, B, L, K, mods, tw_all);
+}
+// The same two bodies for the split degrees (LM_FOR_EACH_SPLIT_LOGN), two workgroups per work-list entry.  Under names of
+// their own: the per-degree resource gates of k_moddown_ntt / k_rotdown_ntt count one instantiation per degree of
+// LM_FOR_EACH_LOGN.
+template <int LOGN>
+__global__ LM_GEOM_BOUNDS(lm_geom_fwd(LOGN)) void k_moddown_split(LM_MODDOWN_PARAMS) {
+    moddown_body<LOGN, true>(u, acc_in, acc_out, bxp, pinv, index, inv_index, work, B, L, K, mods, tw_all);
+}
+template <int LOGN>
+__global__ LM_GEOM_BOUNDS(lm_geom_fwd(LOGN)) void k_rotdown_split(LM_MODDOWN_PARAMS) {
     moddown_body<LOGN, false>(u, acc_in, acc_out, bxp, pinv, index, inv_index, work, B, L, K, mods, tw_all);
 }
 
@@ -844,6 +872,9 @@ static uint32_t intt_pack_slots(lumen_ctx *ctx) {
     return v;
 }
 static uint32_t ks_fused_digits(lumen_ctx *ctx, uint32_t B, uint32_t L) {
+    // a split degree: k_intt_pack's read-back is tied to the pass plan of a one-piece inverse and is not built there --
+    // the switch is ignored (every digit goes through k_pack_v, same residues)
+    if (lm_logn_split_supported(ctx->logN)) return 0;
     const long forced = ctx->tune.ks_fused_digits; // LUMEN_KS_FUSED_DIGITS at context creation / lumen_ctx_set_tuning
     const uint32_t pairs = L / 2; // digits with two limbs
     if (forced >= 0) return std::min<uint32_t>((uint32_t)forced, pairs);
@@ -875,10 +906,16 @@ static int launch_moddown(lumen_ctx *ctx, const u64 *in, u64 *out, uint32_t B, c
     const uint32_t *work_down = nullptr;
     if (int rc = moddown_work_list(ctx, tb, B, &work_down)) return rc;
     lm_prof_scope ps(ctx, ACCUMULATE ? "ks_moddown_ntt" : "ks_rotdown_ntt", (uint64_t)B * 2 * L);
-    return lm_for_logn(ctx, ctx->logN, [&](auto n) {
-        return lm_launch(ctx, ACCUMULATE ? k_moddown_ntt<n> : k_rotdown_ntt<n>, lm_geom_fwd(n), B * 2 * L, s.u, in, out,
-                         tb->d_bxp.get(), tb->d_pinv.get(), gk.d_index.get(), gk.d_inv_index.get(), work_down, B, L, K, ctx->mods,
-                         ctx->sh->tw_fwd.get());
+    return lm_for_logn_split(ctx, ctx->logN, [&](auto n) {
+        constexpr int LN = decltype(n)::value;
+        auto kernel = [] {
+            if constexpr (lm_is_split(LN))
+                return ACCUMULATE ? k_moddown_split<LN> : k_rotdown_split<LN>;
+            else
+                return ACCUMULATE ? k_moddown_ntt<LN> : k_rotdown_ntt<LN>;
+        }();
+        return lm_launch(ctx, kernel, lm_geom_fwd(LN), lm_fwd_grid<LN>(B * 2 * L), s.u, in, out, tb->d_bxp.get(), tb->d_pinv.get(),
+                         gk.d_index.get(), gk.d_inv_index.get(), work_down, B, L, K, ctx->mods, ctx->sh->tw_fwd.get());
     });
 }
 
@@ -917,8 +954,8 @@ int rotate_decompose(lumen_ctx *ctx, const u64 *acc, uint32_t B, KsTables *tb, c
         const uint32_t *work = nullptr;
         if (int rc = modup_work_list(ctx, tb, B, &work)) return rc;
         lm_prof_scope ps(ctx, "ks_modup_ntt", nb);
-        if (int rc = lm_for_logn(ctx, ctx->logN, [&](auto n) {
-                return lm_launch(ctx, k_modup_ntt<n>, lm_geom_fwd(n), (uint32_t)nb, s.coef, acc, s.ext, tb->d_bx.get(), B, L, K, beta,
+        if (int rc = lm_for_logn_split(ctx, ctx->logN, [&](auto n) {
+                return lm_launch(ctx, k_modup_ntt<n>, lm_geom_fwd(n), lm_fwd_grid<n>((uint32_t)nb), s.coef, acc, s.ext, tb->d_bx.get(), B, L, K, beta,
                                  pshift, work, ctx->mods, ctx->sh->tw_fwd.get());
             }))
             return rc;

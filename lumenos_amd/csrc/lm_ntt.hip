@@ -7,11 +7,15 @@
 // transform reads and writes HBM exactly once: 16*N bytes.  Pass structure, wave-owned blocks,
 // lazy butterflies and the hand-scheduled Shoup multiplication: lm_ntt_dev.h.  So are the two launch
 // geometries (lm_geom_lds, lm_geom_fwd), the dispatch on the ring degree (lm_for_logn) and the launch (lm_launch).
+// N = 2^15 does not fit (288 KiB): one workgroup runs two transforms of 2^14 points back to back around an outer radix-2
+// stage and parks half a limb in its own output in between (lm_ntt_forward_split_parked, lm_ntt_inverse_split): 24*N bytes.
 #include "lm_ntt_dev.h"
 
 // forward transforms run lm_ntt_forward_w14 at N = 2^14 (512 threads, two workgroups per CU): lm_geom_fwd
+// a split degree (lm_is_split): the geometry of the half transform, lm_geom_lds(LOGN - 1), and one workgroup per limb that
+// runs the two half transforms back to back (lm_ntt_forward_split_parked, lm_ntt_inverse_split)
 template <int LOGN, bool INV>
-constexpr lm_geom k_limb_ntt_geom = INV ? lm_geom_lds(LOGN) : lm_geom_fwd(LOGN);
+constexpr lm_geom k_limb_ntt_geom = lm_is_split(LOGN) ? lm_geom_lds(lm_tlog(LOGN)) : INV ? lm_geom_lds(LOGN) : lm_geom_fwd(LOGN);
 template <int LOGN, bool INV>
 __global__ LM_GEOM_BOUNDS((k_limb_ntt_geom<LOGN, INV>)) void k_limb_ntt(const u64 *src, size_t src_poly_stride, u64 *dst,
                                                    size_t dst_poly_stride, uint32_t npoly, lm_modmap map,
@@ -35,7 +39,10 @@ __global__ LM_GEOM_BOUNDS((k_limb_ntt_geom<LOGN, INV>)) void k_limb_ntt(const u6
         // wave's LDS block, the first pass reading its runs from there -- loses 2.7 %: tools/exp_inv_lin_load.patch,
         // profiles/r05_exp_linear_store.txt)
         auto ld = [&](uint32_t i0, u64 *v, int count) { lm_load_run(p, i0, v, count); };
-        lm_ntt_inverse<LOGN>(sm, tw, c, tid, ld, st);
+        if constexpr (lm_is_split(LOGN))
+            lm_ntt_inverse_split<LOGN>(sm, tw, c, tid, ld, o, st);
+        else
+            lm_ntt_inverse<LOGN>(sm, tw, c, tid, ld, st);
     } else {
         auto ld = [&](uint32_t i) { return p[i]; };
         // (coalesced output through LDS, lm_linear_out, was measured here too: 11.5 M transforms/s either way -- the plain
@@ -47,7 +54,11 @@ __global__ LM_GEOM_BOUNDS((k_limb_ntt_geom<LOGN, INV>)) void k_limb_ntt(const u6
                 if (k < count) r[k] = lm_reduce_s(v[k], c.q, c.nq, c.qinv64);
             lm_store_run(o, i0, r, count);
         };
-        if constexpr (LOGN == 14)
+        // a split degree: one workgroup, the halves back to back (this kernel runs in place, where a second workgroup
+        // would read what the first has overwritten); the storer sees the whole limb's indices
+        if constexpr (lm_is_split(LOGN))
+            lm_ntt_forward_split_parked<LOGN>(sm, tw, c, tid, ld, o + N / 2, st);
+        else if constexpr (LOGN == 14)
             lm_ntt_forward_w14(sm, tw, c, tid, ld, st);
         else
             lm_ntt_forward<LOGN>(sm, tw, c, tid, ld, st);
@@ -58,7 +69,7 @@ __global__ LM_GEOM_BOUNDS((k_limb_ntt_geom<LOGN, INV>)) void k_limb_ntt(const u6
 static int launch_limb_ntt(lumen_ctx *ctx, uint32_t logn, bool inverse, uint32_t grid, const u64 *src,
                            size_t src_poly_stride, u64 *dst, size_t dst_poly_stride, uint32_t npoly,
                            const lm_modmap &map, const lm_mods &mods, const lm_ninv_t &ninv, const tw_t *tw) {
-    return lm_for_logn(ctx, logn, [&](auto n) {
+    return lm_for_logn_split(ctx, logn, [&](auto n) {
         if (inverse)
             return lm_launch(ctx, k_limb_ntt<n, true>, k_limb_ntt_geom<n, true>, grid, src, src_poly_stride, dst,
                              dst_poly_stride, npoly, map, mods, ninv, tw);

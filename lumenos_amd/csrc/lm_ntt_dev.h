@@ -23,6 +23,7 @@
 #include <cstring>
 #include <type_traits>
 #include <utility>
+#include <vector>
 
 #include "lm_common.h"
 
@@ -109,6 +110,84 @@ static inline bool lm_logn_supported(uint32_t logN) {
 #undef LM_X
     return false;
 }
+// ---- split degrees.  Above 2^14 a limb no longer fits a CU's LDS (lm_lds_for(2^15) = 288 KB of 160).  A transform of
+// such a degree is ONE outer radix-2 stage and two half transforms of LOGN - 1, each of which is the LDS-resident code
+// above with an adapted loader / storer (lm_split_fwd_loader, lm_ntt_inverse_split below, DESIGN.md section 3 "the
+// split transform").  Only the kernels of the server's path and of the key switch are instantiated for these degrees
+// (lm_for_logn_split); every other entry point keeps lm_for_logn and refuses them.
+#define LM_FOR_EACH_SPLIT_LOGN(X) X(15)
+__host__ __device__ constexpr bool lm_is_split(int logN) { return logN > 14; }
+// degree of the transform a workgroup runs: the half transform of a split degree, the degree itself otherwise
+__host__ __device__ constexpr int lm_tlog(int logN) { return lm_is_split(logN) ? logN - 1 : logN; }
+static inline bool lm_logn_split_supported(uint32_t logN) {
+#define LM_X(n) if (logN == n) return true;
+    LM_FOR_EACH_SPLIT_LOGN(LM_X)
+#undef LM_X
+    return false;
+}
+// lm_for_logn plus the split degrees: for the launches whose kernels are instantiated for both lists
+template <class F>
+static inline int lm_for_logn_split(lumen_ctx *ctx, uint32_t logN, F &&f) {
+    switch (logN) {
+#define LM_X(n) \
+    case n: return f(std::integral_constant<int, n>{});
+        LM_FOR_EACH_SPLIT_LOGN(LM_X)
+#undef LM_X
+    default: return lm_for_logn(ctx, logN, std::forward<F>(f));
+    }
+}
+// first statement (behind LM_ENTER) of the entry points that have no kernel for the split degrees: refused before
+// anything is drawn, allocated or launched
+#define LM_REFUSE_SPLIT(ctx, what)                                                                                      \
+    LM_CHECK(ctx, !lm_logn_split_supported((ctx)->logN), "%s: ring degree 2^%u has no kernel instantiation (split degree: " \
+             "transforms, rescale, products and the key switch only)", what, (ctx)->logN)
+// Sub-tables of a split degree, in place of a modulus's table of N entries (forward or inverse, lm_build_tw's order:
+// the stage with m groups reads tw[m + i]): half h in [h N/2, (h + 1) N/2), sub_h[m' + i] = tw[2m' + h m' + i] for
+// m' = 1, 2, .., N/4 -- the table a transform of N/2 points expects, for the stages behind (forward) or before
+// (inverse) the outer one -- and slot 0 of both, which no stage reads, the outer twiddle tw[1].
+static inline void lm_split_tw(tw_t *tw, uint32_t logN) {
+    const uint32_t H = 1u << (logN - 1);
+    std::vector<tw_t> sub((size_t)2 * H);
+    for (uint32_t h = 0; h < 2; h++) {
+        sub[(size_t)h * H] = tw[1];
+        for (uint32_t m = 1; m < H; m <<= 1)
+            for (uint32_t i = 0; i < m; i++) sub[(size_t)h * H + m + i] = tw[2 * m + h * m + i];
+    }
+    memcpy(tw, sub.data(), sub.size() * sizeof(tw_t));
+}
+// a table of [count][2^logN] entries as the kernels of degree logN read it
+static inline void lm_layout_tw(std::vector<tw_t> &tw, uint32_t logN) {
+    if (!lm_logn_split_supported(logN)) return;
+    for (size_t at = 0; at + ((size_t)1 << logN) <= tw.size(); at += (size_t)1 << logN) lm_split_tw(tw.data() + at, logN);
+}
+// Which half a workgroup of a forward-bearing kernel owns, and which logical block (what blockIdx.x is below the split
+// degrees).  The grid of a split degree is twice the logical one, the halves of block k at k and k + gridDim.x / 2: a
+// host-built work list keeps its XCD order when its length is a multiple of 8.
+template <int LOGN>
+struct lm_half {
+    uint32_t block, h, off; // off = h * N/2: first coefficient of the half
+};
+template <int LOGN>
+__device__ __forceinline__ lm_half<LOGN> lm_half_of_block() {
+    if constexpr (lm_is_split(LOGN)) {
+        const uint32_t nb = gridDim.x >> 1, h = blockIdx.x >= nb ? 1u : 0u;
+        return {blockIdx.x - h * nb, h, h << (LOGN - 1)};
+    } else {
+        return {blockIdx.x, 0u, 0u};
+    }
+}
+// position inside its half of NTT-domain position p (where the half's workgroup keeps it in LDS)
+template <int LOGN>
+__device__ __forceinline__ uint32_t lm_half_local(uint32_t p) {
+    if constexpr (lm_is_split(LOGN))
+        return p & ((1u << (LOGN - 1)) - 1);
+    else
+        return p;
+}
+// grid of a forward-bearing kernel with `blocks` logical workgroups
+template <int LOGN>
+static inline uint32_t lm_fwd_grid(uint32_t blocks) { return lm_is_split(LOGN) ? 2 * blocks : blocks; }
+
 // Launches a kernel with dynamic LDS on the context's stream: raises the kernel's dynamic-LDS limit once per
 // context (hipFuncSetAttribute is not free on the launch path), fails through lm_fail.
 template <class... P, class... A>
@@ -450,6 +529,8 @@ __device__ __forceinline__ void lm_wave_sync() {
 // Loader: u64 operator()(uint32_t i) -> coefficient i in [0, 7q)
 // Storer: void operator()(uint32_t i0, const u64 *v, int count) -> `count` consecutive lazy
 //         results (values < (3*logN+7)*q) starting at coefficient i0
+//         (as a half of a split degree the loader's values are below 10q, not 7q, and the bound is the whole degree's:
+//         (3*(logN+1)+7)*q -- lm_split_fwd_loader)
 #ifndef LM_TW_PREFETCH
 #define LM_TW_PREFETCH 1 // fetch the next work item's twiddles before computing the current one
 #endif
@@ -829,10 +910,10 @@ __device__ __forceinline__ void lm_w14_linear_out(const u64 *sm, uint32_t tid, u
 
 // Geometry of the forward kernels that run lm_ntt_forward_w14 at N = 2^14 (k_limb_ntt<14, false>, k_modup_ntt<14>,
 // k_moddown_ntt<14>)
-// and lm_ntt_forward below it.  4 waves per SIMD caps the N = 2^14 kernels at 128 VGPRs, so that two workgroups of
-// 8 waves fit on a CU.
+// and lm_ntt_forward below it (a split degree: the LDS-resident half transform, lm_tlog).  4 waves per SIMD caps the
+// N = 2^14 kernels at 128 VGPRs, so that two workgroups of 8 waves fit on a CU.
 __host__ __device__ constexpr lm_geom lm_geom_fwd(int logN) {
-    return logN == 14 ? lm_geom{LM_W14_THREADS, 4, lm_lds_for(1u << 13)} : lm_geom_lds(logN);
+    return logN == 14 ? lm_geom{LM_W14_THREADS, 4, lm_lds_for(1u << 13)} : lm_geom_lds(lm_tlog(logN));
 }
 
 // ------------------------------------------------------------------ inverse
@@ -1002,4 +1083,100 @@ __device__ __forceinline__ void lm_store_run(u64 *p, uint32_t i0, const u64 *v, 
             *reinterpret_cast<ulonglong2 *>(p + i0 + k) = a;
         }
     }
+}
+
+// ------------------------------------------------------------------ the split transform (LM_FOR_EACH_SPLIT_LOGN)
+// `tw` below is a modulus's table in the split layout (lm_split_tw): half h's sub-table at tw + h N/2, the outer
+// twiddle in its slot 0.
+//
+// Forward.  lo[j] = x[j] + w x[j + N/2], hi[j] = x[j] - w x[j + N/2] with w = tw[1], then half h is an ordinary
+// transform of N/2 points whose outputs are NTT-domain positions [h N/2, (h + 1) N/2).  Two workgroups per limb, one
+// per half (lm_half_of_block): the loader of half h calls the kernel's own loader at j and j + N/2 and does the outer
+// butterfly -- no scratch and no extra launch, but whatever is fused into the load (the basis extensions of the key
+// switch) runs twice per coefficient.  The storer sees indices of the HALF: the kernel offsets its pointers by
+// lm_half::off.  Bounds: the kernel's loader gives x < 7q; the lazy butterfly adds less than 3q to either output, so
+// the half transform starts below 10q and its storer gets values below (3 (LOGN - 1) + 10) q = (3 LOGN + 7) q, the
+// bound of a one-piece transform of LOGN stages (52q at 2^15, under the context's (3 LOGN + 8) q < 2^64).
+template <class Loader>
+struct lm_split_fwd_loader {
+    Loader &ld;
+    const lm_qc &c;
+    tw_t W;
+    uint32_t h, half_n;
+    __device__ __forceinline__ u64 operator()(uint32_t j) {
+        const u64 x = ld(j), y = ld(j + half_n);
+        const u64 s = lm_shoup3<true>(y, W.w, W.wp, c.nq, x);
+        return h ? lm_bfly_diff(x, c.q3, s) : s;
+    }
+};
+template <int LOGN, class Loader, class Storer, class After = lm_no_after>
+__device__ __forceinline__ void lm_ntt_forward_split(u64 *sm, const tw_t *tw, const lm_qc &c, uint32_t tid,
+                                                     const lm_half<LOGN> &hf, Loader &ld, Storer &st, After after = After()) {
+    static_assert(lm_is_split(LOGN), "degrees up to 2^14 run lm_ntt_forward / lm_ntt_forward_w14");
+    const tw_t *twh = tw + hf.off;
+    lm_split_fwd_loader<Loader> wld{ld, c, lm_tw_load<true>(twh, 0), hf.h, 1u << (LOGN - 1)};
+    lm_ntt_forward<LOGN - 1>(sm, twh, c, tid, wld, st, after);
+}
+// The same in ONE workgroup, for a kernel that may run in place (k_limb_ntt: a second workgroup would read input words
+// the first has already overwritten): the loader of the first run forms both outputs of the outer butterfly, keeps lo[j]
+// and parks hi[j], as it is (below 10q), in `park` (N/2 words of global memory: the second half of the kernel's own
+// output, which the second run's storer overwrites); the second run's loader reads it back -- the first pass deals the
+// same indices to a lane in both runs, so a lane reads what it wrote itself.  Every input word is read once.  In place:
+// x[j + N/2] is read by the lane that overwrites it, right before; x[j]'s slot is written by the first run's last
+// pass, behind the barrier that follows every read of the first run.  The storer gets indices of the whole limb.
+template <int LOGN, class Loader, class Storer>
+__device__ __forceinline__ void lm_ntt_forward_split_parked(u64 *sm, const tw_t *tw, const lm_qc &c, uint32_t tid, Loader &ld,
+                                                            u64 *park, Storer &st) {
+    static_assert(lm_is_split(LOGN), "degrees up to 2^14 run lm_ntt_forward / lm_ntt_forward_w14");
+    constexpr uint32_t H = 1u << (LOGN - 1);
+    const tw_t W = lm_tw_load<true>(tw, 0);
+    auto ld0 = [&](uint32_t j) {
+        const u64 x = ld(j), y = ld(j + H);
+        const u64 s = lm_shoup3<true>(y, W.w, W.wp, c.nq, x);
+        park[j] = lm_bfly_diff(x, c.q3, s);
+        return s;
+    };
+    // (the generic passes: the first run's loader holds two words per coefficient, the registers lm_fwd14_xpass spends
+    // on twiddle sets requested across the passes)
+    lm_ntt_forward<LOGN - 1, false>(sm, tw, c, tid, ld0, st);
+    __syncthreads(); // the second half transform reuses the LDS
+    uint32_t tid1 = tid; // nothing derived from the lane index is carried over from the first run (as in k_intt_pack)
+    asm volatile("" : "+v"(tid1));
+    auto ld1 = [&](uint32_t j) { return park[j]; };
+    auto st1 = [&](uint32_t i0, const u64 *v, int count) { st(i0 + H, v, count); };
+    lm_ntt_forward<LOGN - 1, false>(sm, tw + H, c, tid1, ld1, st1);
+}
+
+// Inverse, the mirror image: half h of the NTT-domain input is inverse-transformed on its own with its sub-table (A from
+// half 0, B from half 1, unscaled), then out[j] = (A[j] + B[j]) N^-1 and out[j + N/2] = (A[j] - B[j]) inv[1] N^-1.
+// ONE workgroup runs the two half transforms back to back.  The first parks A, canonical, in `park` (N/2 words of
+// global memory: the kernel's own output, whose first half the join overwrites); the storer of the second reads A[j]
+// back when B[j] leaves its registers -- in the cross-wave last pass a lane sees the same indices in both runs, so it
+// reads what it wrote itself (the read-back of k_intt_pack) -- and hands the kernel's storer the two joined values,
+// which the storer scales by N^-1 as it would a one-piece transform's.  The inverse's storer receives "any value
+// below 2^64" (up to 48q at 2^14): B is brought under 3q first, so A + B < 4q and A + 3q - B < 4q cannot wrap, and the
+// difference leaves its multiplication by inv[1] in [0, 3q).
+// In place (park == the loader's source) is safe as it is for a one-piece transform: every global read of a half
+// transform sits before the barrier in front of its last pass, every write behind it.
+template <int LOGN, class Loader, class Storer>
+__device__ __forceinline__ void lm_ntt_inverse_split(u64 *sm, const tw_t *tw, const lm_qc &c, uint32_t tid, Loader &ld,
+                                                     u64 *park, Storer &st) {
+    static_assert(lm_is_split(LOGN), "degrees up to 2^14 run lm_ntt_inverse");
+    constexpr uint32_t H = 1u << (LOGN - 1);
+    {
+        auto st0 = [&](uint32_t i, u64 v) { park[i] = lm_reduce_s(v, c.q, c.nq, c.qinv64); };
+        lm_ntt_inverse<LOGN - 1>(sm, tw, c, tid, ld, st0);
+    }
+    __syncthreads(); // the second half transform reuses the LDS
+    const tw_t W = lm_tw_load<true>(tw + H, 0);
+    auto ld1 = [&](uint32_t i0, u64 *v, int count) { ld(i0 + H, v, count); };
+    auto st1 = [&](uint32_t i, u64 v) {
+        const u64 a = park[i];
+        const u64 b = lm_shoup3<true>(v, 1ull, c.qinv64, c.nq);
+        st(i, a + b);
+        st(i + H, lm_shoup3<true>(a + c.q3 - b, W.w, W.wp, c.nq));
+    };
+    uint32_t tid1 = tid; // nothing derived from the lane index is carried over from the first run (as in k_intt_pack)
+    asm volatile("" : "+v"(tid1));
+    lm_ntt_inverse<LOGN - 1>(sm, tw + H, c, tid1, ld1, st1);
 }

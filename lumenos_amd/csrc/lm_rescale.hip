@@ -32,7 +32,7 @@ struct rescale_consts {
 };
 
 template <int LOGN>
-__global__ LM_GEOM_BOUNDS(lm_geom_lds(LOGN)) void k_rescale_last(const u64 *__restrict__ src, size_t src_poly_stride,
+__global__ LM_GEOM_BOUNDS(lm_geom_lds(lm_tlog(LOGN))) void k_rescale_last(const u64 *__restrict__ src, size_t src_poly_stride,
                                                        uint32_t last, u64 *__restrict__ tbuf, mod_t md,
                                                        tw_t ninv, u64 half, const tw_t *__restrict__ tw) {
     extern __shared__ __attribute__((aligned(16))) u64 sm[];
@@ -43,24 +43,28 @@ __global__ LM_GEOM_BOUNDS(lm_geom_lds(LOGN)) void k_rescale_last(const u64 *__re
     u64 *o = tbuf + (size_t)blockIdx.x * N;
     auto ld = [&](uint32_t i0, u64 *v, int count) { lm_load_run(p, i0, v, count); };
     auto st = [&](uint32_t i, u64 v) { o[i] = lm_addmod(lm_shoup_cs(v, ninv, c.q, c.nq), half, c.q); };
-    lm_ntt_inverse<LOGN>(sm, tw, c, tid, ld, st);
+    if constexpr (lm_is_split(LOGN)) // one workgroup, the halves back to back; the first one parked in t itself
+        lm_ntt_inverse_split<LOGN>(sm, tw, c, tid, ld, o, st);
+    else
+        lm_ntt_inverse<LOGN>(sm, tw, c, tid, ld, st);
 }
 
 template <int LOGN>
-__global__ LM_GEOM_BOUNDS(lm_geom_lds(LOGN)) void k_rescale_limb(const u64 *src, size_t src_poly_stride, u64 *dst,
+__global__ LM_GEOM_BOUNDS(lm_geom_lds(lm_tlog(LOGN))) void k_rescale_limb(const u64 *src, size_t src_poly_stride, u64 *dst,
                                                        size_t dst_poly_stride, const u64 *__restrict__ tbuf,
                                                        uint32_t npoly, lm_mods mods, rescale_consts rc,
                                                        const tw_t *__restrict__ tw_all) {
     extern __shared__ __attribute__((aligned(16))) u64 sm[];
     constexpr uint32_t N = 1u << LOGN;
     const uint32_t tid = threadIdx.x;
-    const uint32_t limb = blockIdx.x / npoly, poly = blockIdx.x % npoly; // limb-major (L2-friendly twiddles)
+    const lm_half<LOGN> hf = lm_half_of_block<LOGN>(); // a split degree: two workgroups per limb, one per half of the output
+    const uint32_t limb = hf.block / npoly, poly = hf.block % npoly; // limb-major (L2-friendly twiddles)
     const lm_qc c = lm_make_qc(mods.m[limb]);
     const u64 hm = rc.half_mod[limb];
     const tw_t qlinv = rc.qlinv[limb];
     const u64 *t = tbuf + (size_t)poly * N;
-    const u64 *cin = src + (size_t)poly * src_poly_stride + (size_t)limb * N;
-    u64 *o = dst + (size_t)poly * dst_poly_stride + (size_t)limb * N;
+    const u64 *cin = src + (size_t)poly * src_poly_stride + (size_t)limb * N + hf.off;
+    u64 *o = dst + (size_t)poly * dst_poly_stride + (size_t)limb * N + hf.off;
     auto ld = [&](uint32_t i) { return lm_submod(lm_reduce_s(t[i], c.q, c.nq, c.qinv64), hm, c.q); };
     auto st = [&](uint32_t i0, const u64 *v, int count) {
         u64 cv[8], r[8];
@@ -70,7 +74,10 @@ __global__ LM_GEOM_BOUNDS(lm_geom_lds(LOGN)) void k_rescale_limb(const u64 *src,
             if (k < count) r[k] = lm_shoup_cs(lm_submod(cv[k], lm_reduce_s(v[k], c.q, c.nq, c.qinv64), c.q), qlinv, c.q, c.nq);
         lm_store_run(o, i0, r, count);
     };
-    lm_ntt_forward<LOGN>(sm, tw_all + (size_t)limb * N, c, tid, ld, st);
+    if constexpr (lm_is_split(LOGN))
+        lm_ntt_forward_split<LOGN>(sm, tw_all + (size_t)limb * N, c, tid, hf, ld, st);
+    else
+        lm_ntt_forward<LOGN>(sm, tw_all + (size_t)limb * N, c, tid, ld, st);
 }
 
 // ---- multi-step rescale on coefficients
@@ -211,13 +218,13 @@ static int rescale_polys_t(lumen_ctx *ctx, const u64 *src, uint32_t nl, u64 *dst
         }
         {
             lm_prof_scope ps(ctx, "rescale_last_intt", npoly);
-            if (int e = lm_launch(ctx, k_rescale_last<LOGN>, lm_geom_lds(LOGN), npoly, cur, (size_t)nl * N, last, tbuf,
+            if (int e = lm_launch(ctx, k_rescale_last<LOGN>, lm_geom_lds(lm_tlog(LOGN)), npoly, cur, (size_t)nl * N, last, tbuf,
                                   ctx->mods.m[last], ctx->ninv[last], (u64)rc.half, ctx->sh->tw_inv.get() + (size_t)last * N))
                 return e;
         }
         {
             lm_prof_scope ps(ctx, "rescale_limb_ntt", (uint64_t)npoly * last);
-            if (int e = lm_launch(ctx, k_rescale_limb<LOGN>, lm_geom_lds(LOGN), npoly * last, cur, (size_t)nl * N, out,
+            if (int e = lm_launch(ctx, k_rescale_limb<LOGN>, lm_geom_lds(lm_tlog(LOGN)), lm_fwd_grid<LOGN>(npoly * last), cur, (size_t)nl * N, out,
                                   out_stride, tbuf, npoly, ctx->mods, rc, ctx->sh->tw_fwd.get()))
                 return e;
         }
@@ -231,7 +238,7 @@ static int rescale_polys_t(lumen_ctx *ctx, const u64 *src, uint32_t nl, u64 *dst
 // the src layout (may be NULL when nl - target == 1); tbuf: [npoly][N].
 int lm_rescale_polys(lumen_ctx *ctx, const u64 *src, uint32_t nl, u64 *dst, uint32_t target,
                      uint32_t npoly, u64 *work, u64 *tbuf) {
-    return lm_for_logn(ctx, ctx->logN, [&](auto n) { return rescale_polys_t<n>(ctx, src, nl, dst, target, npoly, work, tbuf); });
+    return lm_for_logn_split(ctx, ctx->logN, [&](auto n) { return rescale_polys_t<n>(ctx, src, nl, dst, target, npoly, work, tbuf); });
 }
 
 extern "C" int lumen_rescale(lumen_ctx *ctx, const lumen_set *in, uint32_t target_limbs, lumen_set **out) {

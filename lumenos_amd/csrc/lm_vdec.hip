@@ -135,6 +135,7 @@ extern "C" int lumen_batch_ciphertexts(lumen_ctx *ctx, const lumen_set *cts, con
                                        uint64_t pt_scale, lumen_set **out) {
     LM_CHECK(nullptr, ctx, "lumen_batch_ciphertexts: NULL ctx");
     LM_ENTER(ctx);
+    LM_REFUSE_SPLIT(ctx, "lumen_batch_ciphertexts");
     LM_CHECK(ctx, cts && alphas && out, "lumen_batch_ciphertexts: NULL argument");
     LM_CHECK(ctx, cts->count >= 1, "lumen_batch_ciphertexts: empty set (count == 0)");
     LM_CHECK(ctx, rows >= 1 && rows <= ctx->N, "lumen_batch_ciphertexts: rows=%u out of range [1, N]", rows);
@@ -206,6 +207,7 @@ extern "C" int lumen_vdec_witness(lumen_ctx *ctx, const lumen_set *ct, const uin
                                   int8_t *sk, int64_t *c0, int64_t *c1, int64_t *m_delta, int64_t *err) {
     LM_CHECK(nullptr, ctx, "lumen_vdec_witness: NULL ctx");
     LM_ENTER(ctx);
+    LM_REFUSE_SPLIT(ctx, "lumen_vdec_witness");
     LM_CHECK(ctx, ct && m && sk && c0 && c1 && m_delta, "lumen_vdec_witness: NULL argument");
     LM_CHECK(ctx, rows >= 1 && rows <= ctx->N, "lumen_vdec_witness: rows=%u out of range [1, N]", rows);
     LM_FULL_WIDTH(ctx, ct, "lumen_vdec_witness");

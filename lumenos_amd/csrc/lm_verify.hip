@@ -82,6 +82,7 @@ extern "C" int lumen_verify_columns(lumen_ctx *ctx, const lumen_set *opened, uin
                                     uint64_t *got, uint64_t *values) {
     LM_CHECK(nullptr, ctx, "lumen_verify_columns: ctx is NULL");
     LM_ENTER(ctx);
+    LM_REFUSE_SPLIT(ctx, "lumen_verify_columns");
     LM_CHECK(ctx, opened, "lumen_verify_columns: opened is NULL");
     LM_CHECK(ctx, r, "lumen_verify_columns: r is NULL");
     LM_CHECK(ctx, want_r, "lumen_verify_columns: want_r is NULL");
