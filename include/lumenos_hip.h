@@ -494,6 +494,47 @@ int lumen_keygen_ringswitch(lumen_ctx *ctx, const uint8_t seed[32], uint32_t log
                             uint64_t *key, size_t key_words /* the full [rns][pw2][b|a][L+K][N] size */,
                             int8_t *sk_small /* host [2^log_n_small] */);
 
+/* ---- seeded switching keys: the Galois keys and the relinearisation key travel as their b halves and ONE public
+ * 32-byte seed (cmd/client/main.go:74-81 generates and marshals the whole set; the `/keys` handler of
+ * cmd/server/main.go:66 receives it -- 16 Galois keys and one relinearisation key of 22 MB each at the headline shape,
+ * half of which is the pseudorandom `a`).  The client keeps `a` out of memory altogether and posts
+ * [digit(beta)][limb(L+K)][N] words per key; the server draws `a` where it converts the key anyway.
+ * ADDITION TO THE SAMPLING CONTRACT.  A seeded key takes two seeds:
+ *   seed: key material, as above.  The error of entry e is stream 1 of I(key_id, e) under seed; the secret is the
+ *     context's generated secret;
+ *   a_seed: PUBLIC.  a of limb m of entry e is stream 16 + m of the SAME index I(key_id, e) under a_seed, by the rule
+ *     above: attempt t of coefficient k is word t * N + k, the first x < 2^64 - (2^64 mod q_m) is kept as x mod q_m;
+ *   b = NTT(e) - a*s_out + fac*s_in as above.
+ * So a seeded key expanded by the server is word for word the pair (b, a), and with a_seed == seed b would be exactly
+ * what lumen_keygen_galois / lumen_keygen_relin return -- which the device refuses, because it would publish the secret
+ * seed.
+ * ONE `a` PER KEY.  The error depends on (seed, key id, entry) alone, not on a_seed: generating a key again under the same
+ * two seeds gives the same words, which is harmless.  What MUST NOT happen is the same key -- one (keygen seed, key id) --
+ * published under two different `a`: its seeded form under two a_seeds, or its full form (lumen_keygen_galois /
+ * lumen_keygen_relin draw a under the keygen seed) beside a seeded one.  The two b differ by (a2 - a1) * s_out
+ * coefficient by coefficient, both a are public, and whoever sees both keys has the secret.  So: draw ONE a_seed from the
+ * OS CSPRNG together with the keygen seed, keep it for as long as that seed lives, use it for nothing else, and publish
+ * each key in one of the two forms only.  The library sees one call at a time and cannot enforce this; the host
+ * mirror's fhe::KeyGenerator does.
+ * lumen_keygen_galois_seeded / lumen_keygen_relin_seeded work like their siblings: all keys of a call come from one
+ * launch of each kernel and one download of half the size; LUMEN_KEY_MONTGOMERY applies to b.  `a` is drawn inside
+ * the transform's storer and never written.  Refused like their siblings (no generated secret, K = 0, an even element or
+ * one >= 2N, unknown flags, NULL arguments, a split ring degree), and when the two seeds are equal.
+ * lumen_load_galois_key_seeded / lumen_load_relin_key_seeded need no secret, no keygen state and no encoder.  flags
+ * describes b (LUMEN_KEY_MONTGOMERY: b is in Lattigo's form); a is always drawn canonical.  b takes the conversion and
+ * the range check of lumen_load_galois_key_ex ("key residue out of range (digit, limb)"); a is drawn straight into the
+ * gadget product's layout.  The installed key is the one lumen_load_galois_key_ex(gal_el, (b, a)) installs: shared with
+ * clones, replaced in place when loaded again, and a full and a seeded key of one element replace each other.  They
+ * serve every ring degree their siblings serve, 2^15 included. */
+int lumen_keygen_galois_seeded(lumen_ctx *ctx, const uint8_t seed[32], const uint8_t a_seed[32], const uint64_t *gal_els,
+                               uint32_t count, uint64_t *b_out /* [count][beta][L+K][N] */, uint32_t flags);
+int lumen_keygen_relin_seeded(lumen_ctx *ctx, const uint8_t seed[32], const uint8_t a_seed[32],
+                              uint64_t *b_out /* [beta][L+K][N] */, uint32_t flags);
+int lumen_load_galois_key_seeded(lumen_ctx *ctx, uint64_t gal_el, const uint64_t *b /* [beta][L+K][N] */,
+                                 const uint8_t a_seed[32], uint32_t flags);
+int lumen_load_relin_key_seeded(lumen_ctx *ctx, const uint64_t *b /* [beta][L+K][N] */, const uint8_t a_seed[32],
+                                uint32_t flags);
+
 /* ---- the client's encryptor: witness encryption under the SECRET key, and seeded ciphertexts (fhe/bfv.go:77: the
  * rlwe.NewEncryptor(paramsFHE, sk) that ClientBFV embeds; client.EncryptNew, vdec/batching_test.go:56).  In the protocol
  * the witness belongs to the client; a client that holds its secret on the device (lumen_load_secret_key or

@@ -3,6 +3,7 @@
 // (lm_keygen.hip) and Verify (lm_verify.hip).
 #pragma once
 #include "lm_ks_dev.h"
+#include "lm_sample_dev.h"
 
 struct enc_tinv_t {
     tw_t t[LM_MAX_LIMBS]; // message scale per Q limb: -P * T^-1 mod q_l (K > 0), T^-1 mod q_l (K = 0)
@@ -70,3 +71,16 @@ int lm_sample_small(lumen_ctx *ctx, int8_t *out, const u64 *d_index, u64 base, u
 // a + i * item_stride: [LK][N] words uniform mod q_m from stream 16 + m, NTT domain
 int lm_sample_uniform(lumen_ctx *ctx, u64 *a, size_t item_stride, const u64 *d_index, u64 base, uint32_t nitems, uint32_t LK,
                       const uint8_t seed[32]);
+// the kernel arguments of a launch that draws for itself (k_keygen_evk_seeded, k_key_expand): the seed as the cipher's
+// key words, and the rejection bounds 2^64 - (2^64 mod q_m) of the first LK moduli
+enc_seed_t lm_sample_seed(const uint8_t seed[32]);
+kg_lim_t lm_sample_lim(const lumen_ctx *ctx, uint32_t LK);
+
+// ---- the sample indices of key generation (lm_keygen.hip, THE SAMPLING CONTRACT): I(key_id, e) = key_id * 4096 + e.
+// The loaders of seeded keys (lm_ks_key.hip) draw `a` under the same indices.
+#define LM_KG_INDEX_STRIDE 4096ull
+#define LM_KG_ID_SECRET 0ull
+#define LM_KG_ID_PUBLIC 1ull
+#define LM_KG_ID_RELIN 2ull
+#define LM_KG_ID_RINGSWITCH 3ull
+#define LM_KG_ID_GALOIS 0x10000ull

@@ -21,17 +21,31 @@
 // A keygen seed is key material (OS CSPRNG) and is used for nothing else: streams 0-2 of an index are the ones
 // lumen_encrypt_* would draw, so a keygen seed must never be passed to lumen_encrypt_*.
 //
+// ADDITION: SEEDED KEYS (lumen_keygen_galois_seeded / lumen_keygen_relin_seeded; cmd/client/main.go:74-81 posts the keys
+// whole, the `/keys` handler of cmd/server/main.go:66 receives them).  A seeded key takes two 32-byte seeds:
+//     seed             key material, as above: the error of entry e is stream 1 of I(key_id, e) under seed; the secret is
+//                      the context's generated secret
+//     a_seed           PUBLIC: a for limb m of entry e is stream 16 + m of the SAME index I(key_id, e) under a_seed, by the
+//                      rule above (attempt t of coefficient k is word t * N + k, the first x < 2^64 - (2^64 mod q_m) is kept
+//                      as x mod q_m)
+//     b                = NTT(e) - a * s_out + fac * s_in as before; only b leaves the device
+// So a seeded key expanded by the server (lm_ks_key.hip: k_key_expand draws a under a_seed) is word for word the pair
+// (b, a), and with a_seed == seed b would be exactly lumen_keygen_galois's -- refused, because it would publish the
+// secret seed.
+// ONE `a` PER KEY.  The error depends on (seed, key id, entry) alone, not on a_seed, so generating a key again under the
+// same two seeds gives the same words -- harmless.  What must never happen is the SAME key (seed, key id) published under
+// two different `a`: two seeded forms under two a_seeds, or the full form (whose a is drawn under seed) beside a seeded
+// one.  Their b halves differ by (a2 - a1) * s_out pointwise, both a are public, and the secret follows.  So a keygen
+// seed gets ONE a_seed for its whole life (drawn with it from the OS CSPRNG), and one of the two forms per key.  The
+// library sees one call at a time and cannot check this; the host mirror's KeyGenerator does (fhe.hpp).
+//
 // The samples come from the shared sampler (lm_sample.hip: k_sample_small, k_sample_uniform).  Kernels here:
 // k_keygen_secret_ntt (NTT(s) and NTT(skNew(X^(N/n))) over QP), k_keygen_gather / _square / _shoup (the secret's
-// images), k_keygen_evk (one workgroup per (key, entry, limb): lift + NTT of e, the products fused into the store).
-#include "lm_enc_host.h"
+// images), k_keygen_evk (one workgroup per (key, entry, limb): lift + NTT of e, the products fused into the store) and
+// k_keygen_evk_seeded, the same body whose storer draws a for itself and stores b alone.
+#include <cstring>
 
-#define LM_KG_INDEX_STRIDE 4096ull
-#define LM_KG_ID_SECRET 0ull
-#define LM_KG_ID_PUBLIC 1ull
-#define LM_KG_ID_RELIN 2ull
-#define LM_KG_ID_RINGSWITCH 3ull
-#define LM_KG_ID_GALOIS 0x10000ull
+#include "lm_enc_host.h"
 
 // NTT of small polynomials over QP: slot j of `small` ([nslots][*] int8) -> mont[j][m] = NTT(.) * 2^64 mod q_m (the form
 // the storer of k_keygen_evk multiplies with) and, when given, std[j][m] = NTT(.).  loggap > 0: the polynomial is
@@ -111,27 +125,38 @@ __global__ __launch_bounds__(256) void k_keygen_shoup(const u64 *__restrict__ st
 //   s_out + key * sout_stride and s_in: [LK][N] secrets in Montgomery form; fac [nent][LK]: P * 2^(w j) mod q_m on the
 //   Q limbs of the entry's RNS digit, 0 elsewhere (NULL: 0 everywhere, the public key).
 //   b = NTT(e) - a * s_out + fac * s_in, canonical; MONT: both halves leave multiplied by 2^64 mod q_m.
-template <int LOGN>
-__global__ LM_GEOM_BOUNDS(lm_geom_lds(LOGN)) void k_keygen_evk(const int8_t *__restrict__ small, u64 *__restrict__ out,
-                                                                const u64 *__restrict__ s_out, size_t sout_stride,
-                                                                const u64 *__restrict__ s_in, const u64 *__restrict__ fac,
-                                                                uint32_t nitems, uint32_t nent, uint32_t LK, uint32_t mont,
-                                                                lm_mods mods, lm_ninv_t rmont,
-                                                                const tw_t *__restrict__ tw_all) {
-    extern __shared__ __attribute__((aligned(16))) u64 sm[];
+// The SEEDED form (lumen_keygen_*_seeded) has no `a` in memory at all: out is the packed [nitems][LK][N] block of the b
+// halves and the storer draws the run's `a` itself under the public seed of `dr` -- a run of the last pass is one
+// ChaCha20 block of the limb's stream (half of one at N = 2^8), k_sample_uniform's rule through lm_uniform_run.
+struct kg_draw_t {
+    const u64 *index; // [nitems] sample indices I(key_id, e)
+    enc_seed_t seed;  // a_seed
+    kg_lim_t lim;
+};
+template <int LOGN, bool SEEDED>
+__device__ __forceinline__ void kg_evk_body(u64 *sm, const int8_t *__restrict__ small, u64 *__restrict__ out,
+                                            const u64 *__restrict__ s_out, size_t sout_stride, const u64 *__restrict__ s_in,
+                                            const u64 *__restrict__ fac, uint32_t nitems, uint32_t nent, uint32_t LK,
+                                            uint32_t mont, const lm_mods &mods, const lm_ninv_t &rmont,
+                                            const tw_t *__restrict__ tw_all, const kg_draw_t *dr) {
     constexpr uint32_t N = 1u << LOGN;
     const uint32_t tid = threadIdx.x, m = blockIdx.x / nitems, it = blockIdx.x % nitems, key = it / nent, e = it % nent;
     const mod_t md = mods.m[m];
     const lm_qc qc = lm_make_qc(md);
     const int8_t *se = small + (size_t)it * N;
-    u64 *ob = out + ((size_t)it * 2 * LK + m) * N, *oa = ob + (size_t)LK * N;
+    u64 *ob = out + ((size_t)it * (SEEDED ? 1 : 2) * LK + m) * N, *oa = SEEDED ? nullptr : ob + (size_t)LK * N;
     const u64 *so = s_out + (size_t)key * sout_stride + (size_t)m * N, *si = s_in ? s_in + (size_t)m * N : nullptr;
     const u64 f = fac ? fac[(size_t)e * LK + m] : 0;
     const tw_t R = rmont.t[m];
+    u64 I = 0, bound = 0;
+    if constexpr (SEEDED) I = dr->index[it], bound = dr->lim.t[m];
     auto ld = [&](uint32_t i) -> u64 { return lm_lift_small(se[i], &qc.q); };
     auto st = [&](uint32_t i0, const u64 *v, int n) {
         u64 a[8], b[8], x[8], y[8];
-        lm_load_run(oa, i0, a, n);
+        if constexpr (SEEDED)
+            lm_uniform_run<lm_fwd_run<LOGN>()>(dr->seed, I, LM_UNIFORM_STREAM + m, LOGN, i0, md.q, md.qinv64, bound, a);
+        else
+            lm_load_run(oa, i0, a, n);
         lm_load_run(so, i0, x, n);
         if (f) lm_load_run(si, i0, y, n);
 #pragma unroll
@@ -149,14 +174,35 @@ __global__ LM_GEOM_BOUNDS(lm_geom_lds(LOGN)) void k_keygen_evk(const int8_t *__r
                 r = lm_addmod(r, lm_reduce_s(v[k], qc.q, qc.nq, qc.qinv64), qc.q);
                 if (mont) {
                     r = lm_shoup_cs(r, R, qc.q, qc.nq);
-                    a[k] = lm_shoup_cs(a[k], R, qc.q, qc.nq);
+                    if constexpr (!SEEDED) a[k] = lm_shoup_cs(a[k], R, qc.q, qc.nq);
                 }
                 b[k] = r;
             }
         lm_store_run(ob, i0, b, n);
-        if (mont) lm_store_run(oa, i0, a, n);
+        if constexpr (!SEEDED)
+            if (mont) lm_store_run(oa, i0, a, n);
     };
     lm_ntt_forward<LOGN>(sm, tw_all + (size_t)m * N, qc, tid, ld, st);
+}
+template <int LOGN>
+__global__ LM_GEOM_BOUNDS(lm_geom_lds(LOGN)) void k_keygen_evk(const int8_t *__restrict__ small, u64 *__restrict__ out,
+                                                                const u64 *__restrict__ s_out, size_t sout_stride,
+                                                                const u64 *__restrict__ s_in, const u64 *__restrict__ fac,
+                                                                uint32_t nitems, uint32_t nent, uint32_t LK, uint32_t mont,
+                                                                lm_mods mods, lm_ninv_t rmont,
+                                                                const tw_t *__restrict__ tw_all) {
+    extern __shared__ __attribute__((aligned(16))) u64 sm[];
+    kg_evk_body<LOGN, false>(sm, small, out, s_out, sout_stride, s_in, fac, nitems, nent, LK, mont, mods, rmont, tw_all, nullptr);
+}
+template <int LOGN>
+__global__ LM_GEOM_BOUNDS(lm_geom_lds(LOGN)) void k_keygen_evk_seeded(const int8_t *__restrict__ small, u64 *__restrict__ out,
+                                                                       const u64 *__restrict__ s_out, size_t sout_stride,
+                                                                       const u64 *__restrict__ s_in, const u64 *__restrict__ fac,
+                                                                       uint32_t nitems, uint32_t nent, uint32_t LK,
+                                                                       uint32_t mont, lm_mods mods, lm_ninv_t rmont,
+                                                                       const tw_t *__restrict__ tw_all, kg_draw_t dr) {
+    extern __shared__ __attribute__((aligned(16))) u64 sm[];
+    kg_evk_body<LOGN, true>(sm, small, out, s_out, sout_stride, s_in, fac, nitems, nent, LK, mont, mods, rmont, tw_all, &dr);
 }
 
 // ------------------------------------------------------------------------------------------------- host side
@@ -190,19 +236,25 @@ static int kg_secret_ntt_t(lumen_ctx *ctx, const int8_t *small, u64 *mont, u64 *
 }
 template <int LOGN>
 static int kg_evk_t(lumen_ctx *ctx, const int8_t *small, u64 *out, const u64 *s_out, size_t sout_stride, const u64 *s_in,
-                    const u64 *fac, uint32_t nitems, uint32_t nent, uint32_t mont) {
+                    const u64 *fac, uint32_t nitems, uint32_t nent, uint32_t mont, const kg_draw_t *dr) {
     const uint32_t LK = ctx->L + ctx->K;
-    lm_prof_scope ps(ctx, "keygen_evk_ntt", (uint64_t)nitems * LK);
+    lm_prof_scope ps(ctx, dr ? "keygen_evk_seeded" : "keygen_evk_ntt", (uint64_t)nitems * LK);
+    if (dr)
+        return lm_launch(ctx, k_keygen_evk_seeded<LOGN>, lm_geom_lds(LOGN), nitems * LK, small, out, s_out, sout_stride, s_in,
+                         fac, nitems, nent, LK, mont, ctx->mods, kg_rmont(ctx), ctx->sh->tw_fwd.get(), *dr);
     return lm_launch(ctx, k_keygen_evk<LOGN>, lm_geom_lds(LOGN), nitems * LK, small, out, s_out, sout_stride, s_in, fac, nitems,
                      nent, LK, mont, ctx->mods, kg_rmont(ctx), ctx->sh->tw_fwd.get());
 }
 
 // nkeys keys of nent entries each in ONE launch of each kernel, then one download into the caller's buffer.
-// s_out: the keys' own secrets, sout_stride words apart (0: shared); fac: host [nent][LK] or NULL
+// s_out: the keys' own secrets, sout_stride words apart (0: shared); fac: host [nent][LK] or NULL.
+// a_seed NULL: host_out takes [nitems][b|a][LK][N], `a` drawn under `seed` by k_sample_uniform.  a_seed given (the seeded
+// keys): host_out takes the b halves alone, [nitems][LK][N], and `a` under a_seed exists only in the storer's registers.
 static int kg_run(lumen_ctx *ctx, const uint8_t seed[32], const std::vector<u64> &key_ids, uint32_t nent, const u64 *s_out,
-                  size_t sout_stride, const u64 *s_in, const std::vector<u64> *fac, uint32_t flags, uint64_t *host_out) {
+                  size_t sout_stride, const u64 *s_in, const std::vector<u64> *fac, uint32_t flags, uint64_t *host_out,
+                  const uint8_t *a_seed = nullptr) {
     const uint32_t N = ctx->N, LK = ctx->L + ctx->K, nkeys = (uint32_t)key_ids.size(), nitems = nkeys * nent;
-    const size_t out_words = (size_t)nitems * 2 * LK * N;
+    const size_t out_words = (size_t)nitems * (a_seed ? 1 : 2) * LK * N;
     LM_CHECK(ctx, nent <= LM_KG_INDEX_STRIDE && (uint64_t)nitems * LK <= 65535, "key generation: %u keys of %u entries exceed one launch",
              nkeys, nent);
     std::vector<u64> tab(nitems); // sample indices, then the gadget factors
@@ -218,13 +270,16 @@ static int kg_run(lumen_ctx *ctx, const uint8_t seed[32], const std::vector<u64>
         lm_prof_scope ps(ctx, "keygen_sample", nitems);
         if (int rc = lm_sample_small(ctx, d_e.get(), d_index, 0, nitems, 1, 1, seed)) return rc;
     }
-    {
+    kg_draw_t draw{};
+    if (a_seed) {
+        draw.index = d_index, draw.seed = lm_sample_seed(a_seed), draw.lim = lm_sample_lim(ctx, LK);
+    } else {
         lm_prof_scope ps(ctx, "keygen_uniform", (uint64_t)nitems * LK);
         if (int rc = lm_sample_uniform(ctx, d_out.get() + (size_t)LK * N, (size_t)2 * LK * N, d_index, 0, nitems, LK, seed)) return rc;
     }
     if (int rc = lm_for_logn(ctx, ctx->logN, [&](auto k) {
             return kg_evk_t<k>(ctx, d_e.get(), d_out.get(), s_out, sout_stride, s_in, d_fac, nitems, nent,
-                               (flags & LUMEN_KEY_MONTGOMERY) ? 1u : 0u);
+                               (flags & LUMEN_KEY_MONTGOMERY) ? 1u : 0u, a_seed ? &draw : nullptr);
         }))
         return rc;
     lm_prof_scope ps(ctx, "keygen_download", nitems);
@@ -290,15 +345,29 @@ extern "C" int lumen_keygen_public(lumen_ctx *ctx, const uint8_t seed[32], uint6
     return kg_run(ctx, seed, {LM_KG_ID_PUBLIC}, 1, s->d_mont.get(), 0, nullptr, nullptr, 0, pk);
 }
 
-extern "C" int lumen_keygen_relin(lumen_ctx *ctx, const uint8_t seed[32], uint64_t *evk, uint32_t flags) {
-    LM_CHECK(nullptr, ctx, "lumen_keygen_relin: NULL ctx");
+// The two switching keys in either form.  a_seed NULL: the full key under `seed` alone, out [..][b|a][L+K][N].  a_seed given:
+// the b halves of the seeded key, out [..][L+K][N] (THE SAMPLING CONTRACT: a under a_seed, which must differ from seed).
+#define LM_KG_REFUSE_EQUAL_SEEDS(ctx, what, seed, a_seed)                                                              \
+    LM_CHECK(ctx, !(a_seed) || memcmp(seed, a_seed, 32) != 0,                                                            \
+             "%s: the two seeds are equal (a_seed is public: the server could regenerate e)", what)
+
+// the seeded entry points' own refusal, ahead of the shared helper (where a NULL a_seed means the full form)
+#define LM_KG_NEED_A_SEED(ctx, a_seed, what)              \
+    if ((ctx) && !(a_seed)) {                             \
+        LM_ENTER(ctx);                                    \
+        return lm_fail(ctx, "%s: NULL argument", what);   \
+    }
+
+static int kg_relin(lumen_ctx *ctx, const char *what, const uint8_t *seed, const uint8_t *a_seed, uint64_t *out, uint32_t flags) {
+    LM_CHECK(nullptr, ctx, "%s: NULL ctx", what);
     LM_ENTER(ctx);
-    LM_REFUSE_SPLIT(ctx, "lumen_keygen_relin");
-    LM_CHECK(ctx, seed && evk, "lumen_keygen_relin: NULL argument");
+    LM_REFUSE_SPLIT(ctx, what);
+    LM_CHECK(ctx, seed && out, "%s: NULL argument", what);
     const std::shared_ptr<KgSecret> s = kg_secret_of(ctx);
-    LM_KG_NEED_SECRET(ctx, s, "lumen_keygen_relin");
-    LM_CHECK(ctx, ctx->K >= 1, "lumen_keygen_relin: parameters have no special primes: key switching unavailable");
-    LM_CHECK(ctx, !(flags & ~(uint32_t)LUMEN_KEY_MONTGOMERY), "lumen_keygen_relin: unknown flags 0x%x", flags);
+    LM_KG_NEED_SECRET(ctx, s, what);
+    LM_CHECK(ctx, ctx->K >= 1, "%s: parameters have no special primes: key switching unavailable", what);
+    LM_CHECK(ctx, !(flags & ~(uint32_t)LUMEN_KEY_MONTGOMERY), "%s: unknown flags 0x%x", what, flags);
+    LM_KG_REFUSE_EQUAL_SEEDS(ctx, what, seed, a_seed);
     const uint32_t N = ctx->N, L = ctx->L, K = ctx->K, LK = L + K, beta = (L + K - 1) / K;
     const size_t words = (size_t)LK * N;
     lm_dev<u64> d_s2;
@@ -307,23 +376,24 @@ extern "C" int lumen_keygen_relin(lumen_ctx *ctx, const uint8_t seed[32], uint64
                        ctx->mods);
     LM_HIP(ctx, hipGetLastError());
     const std::vector<u64> fac = kg_gadget(ctx, beta, 1, 0);
-    return kg_run(ctx, seed, {LM_KG_ID_RELIN}, beta, s->d_mont.get(), 0, d_s2.get(), &fac, flags, evk);
+    return kg_run(ctx, seed, {LM_KG_ID_RELIN}, beta, s->d_mont.get(), 0, d_s2.get(), &fac, flags, out, a_seed);
 }
 
-extern "C" int lumen_keygen_galois(lumen_ctx *ctx, const uint8_t seed[32], const uint64_t *gal_els, uint32_t count,
-                                   uint64_t *evk, uint32_t flags) {
-    LM_CHECK(nullptr, ctx, "lumen_keygen_galois: NULL ctx");
+static int kg_galois(lumen_ctx *ctx, const char *what, const uint8_t *seed, const uint8_t *a_seed, const uint64_t *gal_els,
+                     uint32_t count, uint64_t *out, uint32_t flags) {
+    LM_CHECK(nullptr, ctx, "%s: NULL ctx", what);
     LM_ENTER(ctx);
-    LM_REFUSE_SPLIT(ctx, "lumen_keygen_galois");
-    LM_CHECK(ctx, seed && (count == 0 || (gal_els && evk)), "lumen_keygen_galois: NULL argument");
+    LM_REFUSE_SPLIT(ctx, what);
+    LM_CHECK(ctx, seed && (count == 0 || (gal_els && out)), "%s: NULL argument", what);
     const std::shared_ptr<KgSecret> s = kg_secret_of(ctx);
-    LM_KG_NEED_SECRET(ctx, s, "lumen_keygen_galois");
-    LM_CHECK(ctx, ctx->K >= 1, "lumen_keygen_galois: parameters have no special primes: key switching unavailable");
-    LM_CHECK(ctx, !(flags & ~(uint32_t)LUMEN_KEY_MONTGOMERY), "lumen_keygen_galois: unknown flags 0x%x", flags);
+    LM_KG_NEED_SECRET(ctx, s, what);
+    LM_CHECK(ctx, ctx->K >= 1, "%s: parameters have no special primes: key switching unavailable", what);
+    LM_CHECK(ctx, !(flags & ~(uint32_t)LUMEN_KEY_MONTGOMERY), "%s: unknown flags 0x%x", what, flags);
+    LM_KG_REFUSE_EQUAL_SEEDS(ctx, what, seed, a_seed);
     const uint32_t N = ctx->N, L = ctx->L, K = ctx->K, LK = L + K, beta = (L + K - 1) / K;
     const uint64_t mask = 2ull * N - 1;
     for (uint32_t i = 0; i < count; i++)
-        LM_CHECK(ctx, (gal_els[i] & 1) && gal_els[i] <= mask, "lumen_keygen_galois: Galois element %llu is not an odd residue mod 2N",
+        LM_CHECK(ctx, (gal_els[i] & 1) && gal_els[i] <= mask, "%s: Galois element %llu is not an odd residue mod 2N", what,
                  (unsigned long long)gal_els[i]);
     if (!count) return 0;
     // s_out = pi_{g^-1}(s): a gather with the automorphism's index table of g^-1 ([LATTIGO-RECALL] AutomorphismNTTIndex)
@@ -349,7 +419,25 @@ extern "C" int lumen_keygen_galois(lumen_ctx *ctx, const uint8_t seed[32], const
                        LK, ctx->logN, words);
     LM_HIP(ctx, hipGetLastError());
     const std::vector<u64> fac = kg_gadget(ctx, beta, 1, 0);
-    return kg_run(ctx, seed, ids, beta, d_sout.get(), (size_t)LK * N, s->d_mont.get(), &fac, flags, evk);
+    return kg_run(ctx, seed, ids, beta, d_sout.get(), (size_t)LK * N, s->d_mont.get(), &fac, flags, out, a_seed);
+}
+
+extern "C" int lumen_keygen_relin(lumen_ctx *ctx, const uint8_t seed[32], uint64_t *evk, uint32_t flags) {
+    return kg_relin(ctx, "lumen_keygen_relin", seed, nullptr, evk, flags);
+}
+extern "C" int lumen_keygen_galois(lumen_ctx *ctx, const uint8_t seed[32], const uint64_t *gal_els, uint32_t count,
+                                   uint64_t *evk, uint32_t flags) {
+    return kg_galois(ctx, "lumen_keygen_galois", seed, nullptr, gal_els, count, evk, flags);
+}
+extern "C" int lumen_keygen_relin_seeded(lumen_ctx *ctx, const uint8_t seed[32], const uint8_t a_seed[32], uint64_t *b_out,
+                                         uint32_t flags) {
+    LM_KG_NEED_A_SEED(ctx, a_seed, "lumen_keygen_relin_seeded");
+    return kg_relin(ctx, "lumen_keygen_relin_seeded", seed, a_seed, b_out, flags);
+}
+extern "C" int lumen_keygen_galois_seeded(lumen_ctx *ctx, const uint8_t seed[32], const uint8_t a_seed[32],
+                                          const uint64_t *gal_els, uint32_t count, uint64_t *b_out, uint32_t flags) {
+    LM_KG_NEED_A_SEED(ctx, a_seed, "lumen_keygen_galois_seeded");
+    return kg_galois(ctx, "lumen_keygen_galois_seeded", seed, a_seed, gal_els, count, b_out, flags);
 }
 
 extern "C" int lumen_keygen_ringswitch(lumen_ctx *ctx, const uint8_t seed[32], uint32_t log_n_small, uint32_t base_two_w,

@@ -17,12 +17,6 @@
 #include "lm_enc_host.h"
 #include "lm_sample_dev.h"
 
-#define LM_UNIFORM_STREAM 16u
-
-struct kg_lim_t {
-    u64 t[LM_MAX_LIMBS]; // 2^64 - (2^64 mod q_m): words below it are kept
-};
-
 // out: [nitems][ns][N] int8, streams s0 .. s0 + ns - 1 of every item.  One thread per ChaCha20 block: per item the N/16
 // blocks of stream 0 (when s0 = 0), then the N/8 blocks of each Gaussian stream.
 __global__ __launch_bounds__(256) void k_sample_small(int8_t *__restrict__ out, const u64 *__restrict__ index, u64 base,
@@ -56,23 +50,11 @@ __global__ __launch_bounds__(256) void k_sample_uniform(u64 *__restrict__ a, siz
     const uint32_t it = blockIdx.y / LK, m = blockIdx.y % LK;
     const u64 I = index ? index[it] : base + it, q = mods.m[m].q, qinv64 = mods.m[m].qinv64, bound = lim.t[m];
     u64 r[8];
-    uint32_t pending = 0xFFu;
-    for (uint32_t t = 0; pending; t++) {
-        u32 w[16];
-        chacha20_block(seed, t * (N >> 3) + blk, (u32)I, (u32)(I >> 32), LM_UNIFORM_STREAM + m, w);
-#pragma unroll
-        for (int i = 0; i < 8; i++) {
-            const u64 x = (u64)w[2 * i] | ((u64)w[2 * i + 1] << 32);
-            if (((pending >> i) & 1u) && x < bound) {
-                r[i] = lm_reduce(x, q, qinv64);
-                pending &= ~(1u << i);
-            }
-        }
-    }
+    lm_uniform_run<8>(seed, I, LM_UNIFORM_STREAM + m, logN, blk * 8, q, qinv64, bound, r);
     lm_store_run(a + (size_t)it * item_stride + (size_t)m * N, blk * 8, r, 8);
 }
 
-static enc_seed_t sample_seed(const uint8_t seed[32]) {
+enc_seed_t lm_sample_seed(const uint8_t seed[32]) {
     enc_seed_t k;
     memcpy(k.k, seed, 32); // little-endian words, as RFC 8439 reads the key
     return k;
@@ -82,7 +64,7 @@ static enc_cdt_t sample_cdt() {
     memcpy(c.t, H_GAUSS_CDT, sizeof(c.t));
     return c;
 }
-static kg_lim_t sample_lim(const lumen_ctx *ctx, uint32_t LK) {
+kg_lim_t lm_sample_lim(const lumen_ctx *ctx, uint32_t LK) {
     kg_lim_t lim;
     for (uint32_t t = 0; t < LM_MAX_LIMBS; t++) lim.t[t] = 0 - h_r64_mod(ctx->mod[t < LK ? t : 0]);
     return lim;
@@ -91,7 +73,7 @@ static kg_lim_t sample_lim(const lumen_ctx *ctx, uint32_t LK) {
 int lm_sample_small(lumen_ctx *ctx, int8_t *out, const u64 *d_index, u64 base, uint32_t nitems, uint32_t s0, uint32_t ns,
                     const uint8_t seed[32]) {
     const size_t per = (size_t)(ctx->N >> 4) * (2 * ns - (s0 ? 0 : 1));
-    return lm_launch_flat(ctx, k_sample_small, nitems * per, out, d_index, base, nitems, s0, ns, ctx->logN, sample_seed(seed),
+    return lm_launch_flat(ctx, k_sample_small, nitems * per, out, d_index, base, nitems, s0, ns, ctx->logN, lm_sample_seed(seed),
                           sample_cdt());
 }
 
@@ -99,7 +81,7 @@ int lm_sample_uniform(lumen_ctx *ctx, u64 *a, size_t item_stride, const u64 *d_i
                       uint32_t LK, const uint8_t seed[32]) {
     const uint32_t nb = ctx->N >> 3, bs = nb < 256 ? nb : 256;
     hipLaunchKernelGGL(k_sample_uniform, dim3(nb / bs, nitems * LK), dim3(bs), 0, ctx->stream, a, item_stride, d_index, base, LK,
-                       ctx->logN, ctx->mods, sample_lim(ctx, LK), sample_seed(seed));
+                       ctx->logN, ctx->mods, lm_sample_lim(ctx, LK), lm_sample_seed(seed));
     LM_HIP(ctx, hipGetLastError());
     return 0;
 }

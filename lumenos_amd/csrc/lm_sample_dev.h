@@ -3,6 +3,7 @@
 //     keystream(I, s) = ChaCha20(key = seed, nonce = LE64(I) || LE32(s), counter = block)
 #pragma once
 #include "lm_arith.h"
+#include "lm_common.h"
 
 struct enc_seed_t {
     u32 k[8];
@@ -71,4 +72,35 @@ __device__ __forceinline__ uint2 lm_gauss8(const u32 w[16], const enc_cdt_t &cdt
         r.b[i] = (int8_t)((x & 1) ? -a : a);
     }
     return r.v;
+}
+
+// ---- uniform residues: streams 16 + m
+#define LM_UNIFORM_STREAM 16u
+struct kg_lim_t {
+    u64 t[LM_MAX_LIMBS]; // 2^64 - (2^64 mod q_m): words below it are kept
+};
+// RUN consecutive coefficients from i0 (a multiple of RUN) of the limb whose stream is `stream`: RUN = 8 is one
+// ChaCha20 block per attempt, RUN = 4 the half of it that i0 lies in.  Attempt t of coefficients 8 blk .. 8 blk + 7 is
+// the words of block t * N/8 + blk; a coefficient keeps its first word below `bound`, reduced modulo q.
+template <int RUN>
+__device__ __forceinline__ void lm_uniform_run(const enc_seed_t &seed, u64 I, u32 stream, uint32_t logN, uint32_t i0, u64 q,
+                                               u64 qinv64, u64 bound, u64 *r) {
+    static_assert(RUN == 8 || RUN == 4, "a block of the keystream or half of one");
+    const uint32_t N = 1u << logN, blk = i0 >> 3;
+    const u32 upper = RUN == 4 && (i0 & 4) ? ~0u : 0u; // a mask, not a branch: the block's words stay in registers
+    uint32_t pending = (1u << RUN) - 1;
+    for (uint32_t t = 0; pending; t++) {
+        u32 w[16];
+        chacha20_block(seed, t * (N >> 3) + blk, (u32)I, (u32)(I >> 32), stream, w);
+#pragma unroll
+        for (int i = 0; i < RUN; i++) {
+            u32 lo = w[2 * i], hi = w[2 * i + 1];
+            if (RUN == 4) lo ^= (lo ^ w[8 + 2 * i]) & upper, hi ^= (hi ^ w[9 + 2 * i]) & upper;
+            const u64 x = (u64)lo | ((u64)hi << 32);
+            if (((pending >> i) & 1u) && x < bound) {
+                r[i] = lm_reduce(x, q, qinv64);
+                pending &= ~(1u << i);
+            }
+        }
+    }
 }

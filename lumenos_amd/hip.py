@@ -140,6 +140,10 @@ SYMBOLS = {
     "lumen_keygen_galois": (C.c_int, [_vp, _u8p, _u64p, C.c_uint32, _u64p, C.c_uint32]),
     "lumen_keygen_relin": (C.c_int, [_vp, _u8p, _u64p, C.c_uint32]),
     "lumen_keygen_ringswitch": (C.c_int, [_vp, _u8p, C.c_uint32, C.c_uint32, _u64p, C.c_size_t, C.POINTER(C.c_int8)]),
+    "lumen_keygen_galois_seeded": (C.c_int, [_vp, _u8p, _u8p, _u64p, C.c_uint32, _u64p, C.c_uint32]),
+    "lumen_keygen_relin_seeded": (C.c_int, [_vp, _u8p, _u8p, _u64p, C.c_uint32]),
+    "lumen_load_galois_key_seeded": (C.c_int, [_vp, C.c_uint64, _u64p, _u8p, C.c_uint32]),
+    "lumen_load_relin_key_seeded": (C.c_int, [_vp, _u64p, _u8p, C.c_uint32]),
     "lumen_encrypt_sk_values": (C.c_int, [_vp, _u64p, C.c_uint32, C.c_uint32, _u8p, _u8p, C.c_uint64, C.POINTER(_vp)]),
     "lumen_encrypt_sk_seeded": (C.c_int, [_vp, _u64p, C.c_uint32, C.c_uint32, _u8p, _u8p, C.c_uint64, _u64p]),
     "lumen_ct_expand_seeded": (C.c_int, [_vp, _u64p, C.c_uint32, _u8p, C.c_uint64, C.POINTER(_vp)]),
@@ -839,6 +843,47 @@ class Context:
         self._ck(self.lib.lumen_keygen_ringswitch(self.h, seed.ctypes.data_as(_u8p), log_n_small, w, _p64(key), key.size,
                                                   sk_small.ctypes.data_as(C.POINTER(C.c_int8))))
         return key, sk_small
+
+    # seeded switching keys: the b halves and one PUBLIC seed travel, the server draws the a halves (the `/keys` body of
+    # cmd/client/main.go:74-81 at half its size).  seed is key material; a_seed is drawn once with it, never equal to it,
+    # and the only public seed that keygen seed is ever used with (one `a` per key: include/lumenos_hip.h)
+    def seeded_evk_shape(self):
+        """[beta][L+K][N]: the b halves of one switching key"""
+        return ((self.L + self.K - 1) // max(self.K, 1), self.L + self.K, self.N)
+
+    def keygen_galois_seeded(self, seed, a_seed, gal_els, montgomery=False, out=None):
+        """[count][beta][L+K][N]: entry i is what load_galois_key_seeded(gal_els[i], ., a_seed, montgomery) takes"""
+        seed, sa = self._seed(seed), self._seed(a_seed)
+        g = np.ascontiguousarray(gal_els, dtype=np.uint64).reshape(-1)
+        shape = (g.size,) + self.seeded_evk_shape()
+        b = np.zeros(shape, dtype=np.uint64) if out is None else out
+        assert b.shape == shape and b.dtype == np.uint64 and b.flags["C_CONTIGUOUS"]
+        self._ck(self.lib.lumen_keygen_galois_seeded(self.h, seed.ctypes.data_as(_u8p), sa.ctypes.data_as(_u8p), _p64(g),
+                                                     g.size, _p64(b), LUMEN_KEY_MONTGOMERY if montgomery else 0))
+        return b
+
+    def keygen_relin_seeded(self, seed, a_seed, montgomery=False):
+        """[beta][L+K][N]: the b halves of the relinearisation key"""
+        seed, sa = self._seed(seed), self._seed(a_seed)
+        b = np.zeros(self.seeded_evk_shape(), dtype=np.uint64)
+        self._ck(self.lib.lumen_keygen_relin_seeded(self.h, seed.ctypes.data_as(_u8p), sa.ctypes.data_as(_u8p), _p64(b),
+                                                    LUMEN_KEY_MONTGOMERY if montgomery else 0))
+        return b
+
+    def load_galois_key_seeded(self, gal_el, b, a_seed, montgomery=False):
+        """b: [beta][L+K][N] (montgomery describes b); the a halves are drawn on the device under a_seed"""
+        b = np.ascontiguousarray(b, dtype=np.uint64)
+        assert b.shape == self.seeded_evk_shape(), b.shape
+        sa = self._seed(a_seed)
+        self._ck(self.lib.lumen_load_galois_key_seeded(self.h, gal_el, _p64(b), sa.ctypes.data_as(_u8p),
+                                                       LUMEN_KEY_MONTGOMERY if montgomery else 0))
+
+    def load_relin_key_seeded(self, b, a_seed, montgomery=False):
+        b = np.ascontiguousarray(b, dtype=np.uint64)
+        assert b.shape == self.seeded_evk_shape(), b.shape
+        sa = self._seed(a_seed)
+        self._ck(self.lib.lumen_load_relin_key_seeded(self.h, _p64(b), sa.ctypes.data_as(_u8p),
+                                                      LUMEN_KEY_MONTGOMERY if montgomery else 0))
 
     # the client's encryptor (fhe/bfv.go:77): under the context's secret key; secret_seed is key material, a_seed public
     def encrypt_sk_values(self, values, secret_seed, a_seed, first_index=0):

@@ -407,6 +407,9 @@ ClientBFV::ClientBFV(core::PrimeField *plaintextField, const Parameters &params,
     check(lumen_encoder_set(Context(), encoder_root(params)), "lumen_encoder_set");
     keySeed_ = std::make_shared<KeySeedBytes>();
     OsRandom(keySeed_->b, sizeof(keySeed_->b));
+    keyForms_ = std::make_shared<KeyForms>(); // the keygen seed's one public seed, for as long as the seed lives
+    do OsRandom(keyForms_->aSeed.data(), keyForms_->aSeed.size());
+    while (!memcmp(keyForms_->aSeed.data(), keySeed_->b, 32)); // the library refuses equal seeds; 2^-256
     check(lumen_keygen_secret(Context(), keySeed_->b, nullptr), "lumen_keygen_secret");
     encSeed_ = std::make_shared<KeySeedBytes>(); // its own draw: a keygen seed keys nothing else
     OsRandom(encSeed_->b, sizeof(encSeed_->b));
@@ -422,6 +425,23 @@ const uint8_t *ClientBFV::KeySeed() const {
     return keySeed_->b;
 }
 
+const std::array<uint8_t, 32> &ClientBFV::PublicKeySeed() const {
+    if (!keyForms_) throw std::invalid_argument("ClientBFV: the secret key was handed in, not generated on the device");
+    return keyForms_->aSeed;
+}
+
+void ClientBFV::ClaimKeyForm(const std::vector<uint64_t> &keyIds, bool seeded) {
+    if (!keyForms_) throw std::invalid_argument("ClientBFV: the secret key was handed in, not generated on the device");
+    std::lock_guard<std::mutex> lock(keyForms_->mu);
+    for (uint64_t id : keyIds) {
+        const auto it = keyForms_->seeded.find(id);
+        if (it != keyForms_->seeded.end() && it->second != seeded)
+            throw std::logic_error("KeyGenerator: key id " + std::to_string(id) + " was already generated in the " +
+                                   (it->second ? "seeded" : "full") + " form; both forms together reveal the secret key");
+    }
+    for (uint64_t id : keyIds) keyForms_->seeded[id] = seeded;
+}
+
 std::vector<uint64_t> ClientBFV::SecretKeyForTest() {
     std::vector<uint64_t> sk((params_.Q.size() + params_.P.size()) * (size_t)params_.N());
     check(lumen_keygen_secret(Context(), KeySeed(), sk.data()), "lumen_keygen_secret");
@@ -430,7 +450,7 @@ std::vector<uint64_t> ClientBFV::SecretKeyForTest() {
 
 ClientBFV::ClientBFV(ClientBFV &src, OwnedContext clone)
     : ptField_(src.ptField_), params_(src.params_), ctx_(std::move(clone)), device_(src.device_), keySeed_(src.keySeed_),
-      encSeed_(src.encSeed_) {}
+      keyForms_(src.keyForms_), encSeed_(src.encSeed_) {}
 
 std::unique_ptr<ClientBFV> ClientBFV::CopyNew() { return std::unique_ptr<ClientBFV>(new ClientBFV(*this, ctx_.Clone())); }
 
@@ -472,6 +492,14 @@ static size_t evk_words(const Parameters &P) {
     return K ? (L + K - 1) / K * 2 * (L + K) * (size_t)P.N() : 0;
 }
 
+// the sampling contract's key ids (include/lumenos_hip.h)
+static const uint64_t KEY_ID_RELIN = 2, KEY_ID_GALOIS = 0x10000;
+static std::vector<uint64_t> galois_key_ids(const std::vector<uint64_t> &els) {
+    std::vector<uint64_t> ids;
+    for (uint64_t g : els) ids.push_back(KEY_ID_GALOIS + g);
+    return ids;
+}
+
 KeyGenerator::KeyGenerator(ClientBFV &client) : client_(client) {
     if (!client.HasGeneratedSecret())
         throw std::invalid_argument("NewKeyGenerator: the client's secret key was handed in, not generated on the device");
@@ -485,6 +513,7 @@ std::vector<uint64_t> KeyGenerator::GenKeyPairNew() {
 }
 
 std::vector<uint64_t> KeyGenerator::GenRelinearizationKeyNew(uint32_t flags) {
+    client_.ClaimKeyForm({KEY_ID_RELIN}, false);
     std::vector<uint64_t> rlk(std::max<size_t>(evk_words(client_.GetParameters()), 1));
     client_.check(lumen_keygen_relin(client_.Context(), client_.KeySeed(), rlk.data(), flags), "lumen_keygen_relin");
     return rlk;
@@ -493,6 +522,7 @@ std::vector<uint64_t> KeyGenerator::GenRelinearizationKeyNew(uint32_t flags) {
 std::map<uint64_t, std::vector<uint64_t>> KeyGenerator::GenGaloisKeysNew(const std::vector<uint64_t> &galEls, uint32_t flags) {
     const std::set<uint64_t> distinct(galEls.begin(), galEls.end());
     const std::vector<uint64_t> els(distinct.begin(), distinct.end());
+    client_.ClaimKeyForm(galois_key_ids(els), false);
     const size_t words = evk_words(client_.GetParameters());
     // one page-locked block for the whole batch: the transfer is a single DMA
     WireBuffer flat(std::max<size_t>(els.size() * words, 1) * 8);
@@ -513,6 +543,70 @@ KeySet KeyGenerator::GenKeySetNew(int rows, uint32_t flags, bool withRelin) {
     const auto keys = GenGaloisKeysNew(ks.GaloisElements, flags);
     for (uint64_t g : ks.GaloisElements) ks.GaloisKeys.push_back(keys.at(g));
     return ks;
+}
+
+// ---- seeded switching keys: b halves + one public seed per set
+static size_t seeded_evk_words(const Parameters &P) { return evk_words(P) / 2; }
+
+SeededKeySet KeyGenerator::GenGaloisKeysSeeded(const std::vector<uint64_t> &galEls, uint32_t flags) {
+    const std::set<uint64_t> distinct(galEls.begin(), galEls.end());
+    const std::vector<uint64_t> els(distinct.begin(), distinct.end());
+    const size_t words = seeded_evk_words(client_.GetParameters());
+    SeededKeySet set;
+    set.Flags = flags;
+    set.ASeed = client_.PublicKeySeed();
+    client_.ClaimKeyForm(galois_key_ids(els), true);
+    WireBuffer flat(std::max<size_t>(els.size() * words, 1) * 8);
+    uint64_t *w = reinterpret_cast<uint64_t *>(flat.data());
+    client_.check(lumen_keygen_galois_seeded(client_.Context(), client_.KeySeed(), set.ASeed.data(), els.data(),
+                                             (uint32_t)els.size(), w, flags),
+                  "lumen_keygen_galois_seeded");
+    for (size_t i = 0; i < els.size(); i++) set.GaloisB[els[i]].assign(w + i * words, w + (i + 1) * words);
+    return set;
+}
+
+void KeyGenerator::GenRelinearizationKeySeeded(SeededKeySet &set) {
+    if (set.GaloisB.empty() && set.RlkB.empty()) set.ASeed = client_.PublicKeySeed();
+    if (set.ASeed != client_.PublicKeySeed())
+        throw std::invalid_argument("GenRelinearizationKeySeeded: the set is under another public seed than this client's");
+    client_.ClaimKeyForm({KEY_ID_RELIN}, true);
+    std::vector<uint64_t> b(std::max<size_t>(seeded_evk_words(client_.GetParameters()), 1));
+    client_.check(lumen_keygen_relin_seeded(client_.Context(), client_.KeySeed(), set.ASeed.data(), b.data(), set.Flags),
+                  "lumen_keygen_relin_seeded");
+    set.RlkB = std::move(b);
+}
+
+SeededKeySet KeyGenerator::GenKeySetSeeded(int rows, uint32_t flags, bool withRelin) {
+    SeededKeySet set = GenGaloisKeysSeeded(client_.GetParameters().GaloisElementsForInnerSum(1, rows), flags);
+    if (withRelin) GenRelinearizationKeySeeded(set);
+    set.Pk = GenKeyPairNew();
+    return set;
+}
+
+void ServerBFV::LoadSeededKeys(const SeededKeySet &keys) {
+    const size_t words = seeded_evk_words(params_);
+    for (const auto &kv : keys.GaloisB)
+        if (kv.second.size() != words || kv.second.empty())
+            throw std::invalid_argument("LoadSeededKeys: a Galois key is not [beta][L+K][N]");
+    if (!keys.RlkB.empty() && keys.RlkB.size() != words)
+        throw std::invalid_argument("LoadSeededKeys: the relinearisation key is not [beta][L+K][N]");
+    for (const auto &kv : keys.GaloisB)
+        check(lumen_load_galois_key_seeded(Context(), kv.first, kv.second.data(), keys.ASeed.data(), keys.Flags),
+              "lumen_load_galois_key_seeded");
+    if (!keys.RlkB.empty())
+        check(lumen_load_relin_key_seeded(Context(), keys.RlkB.data(), keys.ASeed.data(), keys.Flags), "lumen_load_relin_key_seeded");
+}
+
+std::unique_ptr<ServerBFV> ServerBFV::NewFromKeySet(core::PrimeField *plaintextField, const Parameters &params, int rows,
+                                                    const SeededKeySet &keys, int device) {
+    for (uint64_t g : params.GaloisElementsForInnerSum(1, rows))
+        if (!keys.GaloisB.count(g))
+            throw std::invalid_argument("NewFromKeySet: the seeded set lacks an element of GaloisElementsForInnerSum(1, rows)");
+    if (keys.Pk.size() != (size_t)2 * (params.Q.size() + params.P.size()) * (size_t)params.N())
+        throw std::invalid_argument("NewFromKeySet: the public key is not [2][L+K][N]");
+    std::unique_ptr<ServerBFV> s(new ServerBFV(plaintextField, params, keys.Pk, {}, device));
+    s->LoadSeededKeys(keys);
+    return s;
 }
 
 RingSwitchClient NewRingSwitchClient(ClientBFV &client, int logN, int baseTwoDecomposition) {

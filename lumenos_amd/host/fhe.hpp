@@ -9,6 +9,7 @@
 #include <atomic>
 #include <map>
 #include <memory>
+#include <mutex>
 #include <string>
 #include <vector>
 
@@ -88,6 +89,20 @@ struct KeySet {
     std::vector<std::vector<uint64_t>> GaloisKeys; // [beta][b|a][L+K][N] each
     std::vector<uint64_t> Rlk;                     // [beta][b|a][L+K][N], or empty
     uint32_t Flags = 0;
+};
+
+// The same body in SEEDED form (include/lumenos_hip.h, "seeded switching keys"): every switching key travels as its b
+// half, [beta][L+K][N], and the whole set shares ONE public 32-byte seed from which the server draws the `a` halves
+// (lumen_load_galois_key_seeded / lumen_load_relin_key_seeded) -- half of cmd/client/main.go:74-81's upload.  ASeed is
+// the ONE public seed of the client's keygen seed (ClientBFV::PublicKeySeed: drawn with it from getrandom(2), never equal
+// to it, the same in every set that client generates): a key published under two different `a` gives its secret away
+// (b1 - b2 = (a2 - a1) * s_out), so a client's keys never meet a second one.  The public key travels whole.  No wire format is defined for this struct.
+struct SeededKeySet {
+    std::array<uint8_t, 32> ASeed{};
+    std::vector<uint64_t> Pk;                          // [2][L+K][N], or empty (a set of switching keys alone)
+    std::map<uint64_t, std::vector<uint64_t>> GaloisB; // element -> [beta][L+K][N]
+    std::vector<uint64_t> RlkB;                        // [beta][L+K][N], or empty
+    uint32_t Flags = 0;                                // the form of the b words
 };
 
 // rlwe.MetaData of the ciphertexts of one slice (they are produced by the same calls, so they share it):
@@ -199,6 +214,13 @@ class ServerBFV {
     // the relinearisation key too when the set carries one (SetRelinearizationKey)
     static std::unique_ptr<ServerBFV> NewFromKeySet(core::PrimeField *plaintextField, const Parameters &params, int rows,
                                                     const KeySet &keys, int device = 0);
+    // the same from a seeded set (the `/keys` handler of cmd/server/main.go:66 at half the body): keys.GaloisB must hold
+    // every element of params.GaloisElementsForInnerSum(1, rows); the relinearisation key too when the set carries one
+    static std::unique_ptr<ServerBFV> NewFromKeySet(core::PrimeField *plaintextField, const Parameters &params, int rows,
+                                                    const SeededKeySet &keys, int device = 0);
+    // the switching keys of a seeded set, beside or over whatever is loaded: each key's `a` half is drawn on the device
+    // under keys.ASeed.  A seeded key and a full key of one element replace each other.  keys.Pk is not looked at.
+    void LoadSeededKeys(const SeededKeySet &keys);
     ~ServerBFV();
     core::PrimeField *Field() { return ptField_; }
     const Parameters &GetParameters() const { return params_; }
@@ -322,6 +344,15 @@ class ClientBFV {
     bool HasGeneratedSecret() const { return (bool)keySeed_; }
     // the seed of a generated secret (what the KeyGenerator passes on); throws for a client that was handed its key
     const uint8_t *KeySeed() const;
+    // The PUBLIC seed of this client's seeded switching keys: drawn once, together with the keygen seed, shared with every
+    // CopyNew and used for every SeededKeySet.  Throws for a client that was handed its key.
+    const std::array<uint8_t, 32> &PublicKeySeed() const;
+    // One `a` per key, enforced: records that the keys `keyIds` (the sampling contract's ids: 2 = relinearisation,
+    // 0x10000 + g = Galois element g) leave this client in the seeded (or the full) form and throws std::logic_error,
+    // before anything is generated, if one of them already left it in the other form -- the full form's a is drawn under
+    // the keygen seed, the seeded form's under PublicKeySeed(), and both keys together reveal the secret.  The same form
+    // again is the same words and is allowed.  KeyGenerator calls it; shared with every CopyNew.
+    void ClaimKeyForm(const std::vector<uint64_t> &keyIds, bool seeded);
     // test hook: the generated secret as [L+K][N] NTT-domain residues (regenerated from the seed into a host buffer:
     // the one way it leaves the device)
     std::vector<uint64_t> SecretKeyForTest();
@@ -337,12 +368,20 @@ class ClientBFV {
         uint8_t b[32];
     };
     std::shared_ptr<KeySeedBytes> keySeed_; // shared with every CopyNew
+    struct KeyForms { // what belongs to keySeed_ beyond its bytes; shared with every CopyNew
+        std::array<uint8_t, 32> aSeed{};
+        std::mutex mu;
+        std::map<uint64_t, bool> seeded; // key id -> the form it was generated in
+    };
+    std::shared_ptr<KeyForms> keyForms_;
     std::shared_ptr<KeySeedBytes> encSeed_; // the encryptor's error seed, shared with every CopyNew; keys nothing else
 };
 
 // rlwe.NewKeyGenerator(params) (cmd/client/main.go:74) bound to a client with a generated secret: every key is derived
 // on the device from the client's seed (include/lumenos_hip.h, "SAMPLING CONTRACT"), so generating a key twice, one
 // at a time or in a batch gives the same words.  flags: 0 or LUMEN_KEY_MONTGOMERY.
+// A switching key leaves a client in ONE form, full or seeded (ClientBFV::ClaimKeyForm): asking for the other form of a key
+// already generated throws std::logic_error.
 class KeyGenerator {
   public:
     explicit KeyGenerator(ClientBFV &client); // throws std::invalid_argument for a client that was handed its key
@@ -355,6 +394,14 @@ class KeyGenerator {
     // pk + the Galois keys of params.GaloisElementsForInnerSum(1, rows) in that order: the body of POST /keys
     // withRelin: the set carries the relinearisation key as well, as the reference's /keys body does
     KeySet GenKeySetNew(int rows, uint32_t flags = 0, bool withRelin = false);
+    // GenGaloisKeysNew in seeded form: a set under the client's PublicKeySeed() (never its secret seed, never a second one) holding
+    // the b halves of the (distinct) elements, one launch of each kernel and one transfer of half the size
+    SeededKeySet GenGaloisKeysSeeded(const std::vector<uint64_t> &galEls, uint32_t flags = 0);
+    // GenRelinearizationKeyNew in seeded form, INTO a set of this client's: its b half under the set's Flags.  An empty
+    // (default-constructed) set takes the client's PublicKeySeed(); a set under another seed is refused (std::invalid_argument).
+    void GenRelinearizationKeySeeded(SeededKeySet &set);
+    // pk + the seeded Galois keys of params.GaloisElementsForInnerSum(1, rows): what NewFromKeySet(., SeededKeySet) takes
+    SeededKeySet GenKeySetSeeded(int rows, uint32_t flags = 0, bool withRelin = false);
 
   private:
     ClientBFV &client_;
