@@ -7,7 +7,7 @@
 #include <cstring>
 #include <thread>
 
-#include "lm_ntt_dev.h"
+#include "lm_ntt_plan.h"
 
 thread_local std::string lm_global_err;
 
@@ -293,14 +293,8 @@ extern "C" int lumen_ctx_create(const lumen_params_desc *desc, lumen_ctx **out) 
     uint64_t two_n = 2ull * N;
     for (uint32_t i = 0; i < LK; i++) {
         uint64_t q = desc->moduli[i], psi = desc->psi[i];
-        // the lazy forward NTT takes inputs below 7q (fused basis extension) and lets values grow
-        // by 3q per stage before its one reduction (a split degree, lm_ntt_dev.h: the outer butterfly in the loader is one of
-        // the log_n stages -- the half transform starts below 10q and its storer sees (3 (log_n - 1) + 10) q = (3 log_n + 7) q)
-        // ... and the InnerSum accumulator is lazy in [0, 2q) across the rotations (lm_keyswitch.hip, k_moddown_ntt: acc < 2q
-        // plus d < 6q must not wrap): 8q < 2^64, implied by the bound below for every log_n >= 0 and stated here because
-        // the kernels' comments refer to it
-        static_assert(3 * 0 + 8 >= 8, "the modulus bound (3 log_n + 8) q < 2^64 must imply 8 q < 2^64");
-        const uint64_t qmax = UINT64_MAX / (3ull * desc->log_n + 8);
+        // the bound the kernels' range comments rely on, (3 log_n + 8) q < 2^64: lm_q_bound_factor, lm_ntt_plan.h
+        const uint64_t qmax = UINT64_MAX / lm_q_bound_factor(desc->log_n);
         if (q < (1ull << 20) || q > qmax || (q & (two_n - 1)) != 1)
             return lm_fail(nullptr, "modulus %u (%llu) must be == 1 mod 2N and below %llu", i,
                            (unsigned long long)q, (unsigned long long)qmax);

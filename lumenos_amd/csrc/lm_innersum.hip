@@ -299,7 +299,7 @@ int matrix_inner_sum_run(lumen_ctx *ctx, const lumen_set *matrix, const uint64_t
     bool close = false;
     // (a split degree has no k_ks_close -- its storer is tied to the pass plan of a one-piece inverse: the switch is ignored
     // there, ModDown and the whole rescale run, same residues)
-    if (L > target && rows > 1 && ctx->tune.ks_close_fused && !plan.lazy && !lm_logn_split_supported(ctx->logN)) {
+    if (L > target && rows > 1 && ctx->tune.ks_close_fused && !plan.lazy && !lm_is_split(ctx->logN)) {
         const int rc = lm_rescale_coef_ready(ctx);
         if (rc && rc != 2) return rc;
         close = rc == 0;

@@ -229,18 +229,14 @@ __global__ LM_GEOM_BOUNDS(lm_geom_fwd(LOGN)) void k_modup_ntt(const u64 *__restr
         y.x = v0, y.y = v1;
         *reinterpret_cast<ulonglong2 *>(o + j) = y;
     };
-    if constexpr (lm_is_split(LOGN)) { // the half transform, the extension fused into both loads of the outer butterfly
-        lm_lds_runs st{sm};
-        auto after = [&](uint32_t, uint32_t) { lm_linear_out<lm_tlog(LOGN)>(sm, tid, out); };
-        lm_ntt_forward_split<LOGN>(sm, tw_all + (size_t)mt * N, qc, tid, hf, ld, st, after);
-    } else if constexpr (LOGN == 14) { // limb in registers, two workgroups per CU: the runs go through the wave's slot, half by half
+    if constexpr (LOGN == 14) { // limb in registers, two workgroups per CU: the runs go through the wave's slot, half by half
         lm_w14_runs st{sm};
         auto after = [&](uint32_t i0, uint32_t) { lm_w14_linear_out(sm, tid, i0, out); };
         lm_ntt_forward_w14(sm, tw_all + (size_t)mt * N, qc, tid, ld, st, after);
-    } else {
+    } else { // (a split degree: the half transform, the extension fused into both loads of the outer butterfly)
         lm_lds_runs st{sm};
-        auto after = [&](uint32_t, uint32_t) { lm_linear_out<LOGN>(sm, tid, out); };
-        lm_ntt_forward<LOGN>(sm, tw_all + (size_t)mt * N, qc, tid, ld, st, after);
+        auto after = [&](uint32_t, uint32_t) { lm_linear_out<lm_tlog(LOGN)>(sm, tid, out); };
+        lm_ntt_forward_half<LOGN>(sm, tw_all + (size_t)mt * N, qc, tid, hf, ld, st, after);
     }
 }
 
@@ -626,10 +622,7 @@ __device__ __forceinline__ void moddown_body(const u64 *__restrict__ u, const u6
                 *reinterpret_cast<ulonglong2 *>(aout + j) = y;
             }
         };
-        if constexpr (lm_is_split(LOGN))
-            lm_ntt_forward_split<LOGN>(sm, tw_all + (size_t)t * N, qc, tid, hf, ld, st, after);
-        else
-            lm_ntt_forward<LOGN>(sm, tw_all + (size_t)t * N, qc, tid, ld, st, after);
+        lm_ntt_forward_half<LOGN>(sm, tw_all + (size_t)t * N, qc, tid, hf, ld, st, after);
     }
 }
 
@@ -645,17 +638,6 @@ __global__ LM_GEOM_BOUNDS(lm_geom_fwd(LOGN)) void k_moddown_ntt(LM_MODDOWN_PARAM
 // output set (another block: a workgroup's output block is another workgroup's c0)
 template <int LOGN>
 __global__ LM_GEOM_BOUNDS(lm_geom_fwd(LOGN)) void k_rotdown_ntt(LM_MODDOWN_PARAMS) {
-    moddown_body<LOGN, false>(u, acc_in, acc_out, bxp, pinv, index, inv_index, work, B, L, K, mods, tw_all);
-}
-// The same two bodies for the split degrees (LM_FOR_EACH_SPLIT_LOGN), two workgroups per work-list entry.  Under names of
-// their own: the per-degree resource gates of k_moddown_ntt / k_rotdown_ntt count one instantiation per degree of
-// LM_FOR_EACH_LOGN.
-template <int LOGN>
-__global__ LM_GEOM_BOUNDS(lm_geom_fwd(LOGN)) void k_moddown_split(LM_MODDOWN_PARAMS) {
-    moddown_body<LOGN, true>(u, acc_in, acc_out, bxp, pinv, index, inv_index, work, B, L, K, mods, tw_all);
-}
-template <int LOGN>
-__global__ LM_GEOM_BOUNDS(lm_geom_fwd(LOGN)) void k_rotdown_split(LM_MODDOWN_PARAMS) {
     moddown_body<LOGN, false>(u, acc_in, acc_out, bxp, pinv, index, inv_index, work, B, L, K, mods, tw_all);
 }
 
@@ -857,11 +839,11 @@ static uint32_t intt_pack_slots(lumen_ctx *ctx) {
         if (hipGetDeviceProperties(&prop, ctx->device) != hipSuccess) return 256u;
         // (the query answers 0 for more than 64 KB of dynamic LDS until the kernel is allowed that much)
         (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_intt_pack<LOGN>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)LM_CU_LDS_BYTES);
         constexpr lm_geom g = lm_geom_lds(LOGN);
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_intt_pack<LOGN>, g.threads, g.lds) != hipSuccess || per_cu < 1) {
             // by hand: LDS (160 KB per CU) and the 2048 lanes of a CU
-            per_cu = (int)std::max<size_t>(1, std::min<size_t>(160 * 1024 / g.lds, 2048 / g.threads));
+            per_cu = (int)std::max<size_t>(1, std::min<size_t>(LM_CU_LDS_BYTES / g.lds, 2048 / g.threads));
         }
         (void)hipGetLastError();
         if (ctx->tune.debug)
@@ -874,7 +856,7 @@ static uint32_t intt_pack_slots(lumen_ctx *ctx) {
 static uint32_t ks_fused_digits(lumen_ctx *ctx, uint32_t B, uint32_t L) {
     // a split degree: k_intt_pack's read-back is tied to the pass plan of a one-piece inverse and is not built there --
     // the switch is ignored (every digit goes through k_pack_v, same residues)
-    if (lm_logn_split_supported(ctx->logN)) return 0;
+    if (lm_is_split(ctx->logN)) return 0;
     const long forced = ctx->tune.ks_fused_digits; // LUMEN_KS_FUSED_DIGITS at context creation / lumen_ctx_set_tuning
     const uint32_t pairs = L / 2; // digits with two limbs
     if (forced >= 0) return std::min<uint32_t>((uint32_t)forced, pairs);
@@ -906,15 +888,9 @@ static int launch_moddown(lumen_ctx *ctx, const u64 *in, u64 *out, uint32_t B, c
     const uint32_t *work_down = nullptr;
     if (int rc = moddown_work_list(ctx, tb, B, &work_down)) return rc;
     lm_prof_scope ps(ctx, ACCUMULATE ? "ks_moddown_ntt" : "ks_rotdown_ntt", (uint64_t)B * 2 * L);
-    return lm_for_logn_split(ctx, ctx->logN, [&](auto n) {
+    return lm_for_any_logn(ctx, ctx->logN, [&](auto n) {
         constexpr int LN = decltype(n)::value;
-        auto kernel = [] {
-            if constexpr (lm_is_split(LN))
-                return ACCUMULATE ? k_moddown_split<LN> : k_rotdown_split<LN>;
-            else
-                return ACCUMULATE ? k_moddown_ntt<LN> : k_rotdown_ntt<LN>;
-        }();
-        return lm_launch(ctx, kernel, lm_geom_fwd(LN), lm_fwd_grid<LN>(B * 2 * L), s.u, in, out, tb->d_bxp.get(), tb->d_pinv.get(),
+        return lm_launch(ctx, ACCUMULATE ? k_moddown_ntt<LN> : k_rotdown_ntt<LN>, lm_geom_fwd(LN), lm_fwd_grid<LN>(B * 2 * L), s.u, in, out, tb->d_bxp.get(), tb->d_pinv.get(),
                          gk.d_index.get(), gk.d_inv_index.get(), work_down, B, L, K, ctx->mods, ctx->sh->tw_fwd.get());
     });
 }
@@ -954,7 +930,7 @@ int rotate_decompose(lumen_ctx *ctx, const u64 *acc, uint32_t B, KsTables *tb, c
         const uint32_t *work = nullptr;
         if (int rc = modup_work_list(ctx, tb, B, &work)) return rc;
         lm_prof_scope ps(ctx, "ks_modup_ntt", nb);
-        if (int rc = lm_for_logn_split(ctx, ctx->logN, [&](auto n) {
+        if (int rc = lm_for_any_logn(ctx, ctx->logN, [&](auto n) {
                 return lm_launch(ctx, k_modup_ntt<n>, lm_geom_fwd(n), lm_fwd_grid<n>((uint32_t)nb), s.coef, acc, s.ext, tb->d_bx.get(), B, L, K, beta,
                                  pshift, work, ctx->mods, ctx->sh->tw_fwd.get());
             }))

@@ -5,8 +5,10 @@
 // One workgroup of N/16 threads owns one limb of one polynomial and keeps all N coefficients in LDS
 // (N*9 B with padding: 36/72/144 KiB for N = 2^12/2^13/2^14, under the 160 KiB of a gfx950 CU), so a
 // transform reads and writes HBM exactly once: 16*N bytes.  Pass structure, wave-owned blocks,
-// lazy butterflies and the hand-scheduled Shoup multiplication: lm_ntt_dev.h.  So are the two launch
-// geometries (lm_geom_lds, lm_geom_fwd), the dispatch on the ring degree (lm_for_logn) and the launch (lm_launch).
+// lazy butterflies and the hand-scheduled Shoup multiplication: lm_ntt_dev.h and the headers it gathers, one per subject
+// (lm_shoup.h, lm_ntt_bfly.h, lm_ntt_fwd.h, lm_ntt_w14.h, lm_ntt_inv.h, lm_ntt_split.h).  The two launch geometries
+// (lm_geom_lds, lm_geom_fwd), the dispatch on the ring degree (lm_for_logn, lm_for_any_logn) and the launch (lm_launch):
+// lm_ntt_plan.h.
 // N = 2^15 does not fit (288 KiB): one workgroup runs two transforms of 2^14 points back to back around an outer radix-2
 // stage and parks half a limb in its own output in between (lm_ntt_forward_split_parked, lm_ntt_inverse_split): 24*N bytes.
 #include "lm_ntt_dev.h"
@@ -39,10 +41,7 @@ __global__ LM_GEOM_BOUNDS((k_limb_ntt_geom<LOGN, INV>)) void k_limb_ntt(const u6
         // wave's LDS block, the first pass reading its runs from there -- loses 2.7 %: tools/exp_inv_lin_load.patch,
         // profiles/r05_exp_linear_store.txt)
         auto ld = [&](uint32_t i0, u64 *v, int count) { lm_load_run(p, i0, v, count); };
-        if constexpr (lm_is_split(LOGN))
-            lm_ntt_inverse_split<LOGN>(sm, tw, c, tid, ld, o, st);
-        else
-            lm_ntt_inverse<LOGN>(sm, tw, c, tid, ld, st);
+        lm_ntt_inverse_whole<LOGN>(sm, tw, c, tid, ld, o, st); // a split degree parks the first half in the output itself
     } else {
         auto ld = [&](uint32_t i) { return p[i]; };
         // (coalesced output through LDS, lm_linear_out, was measured here too: 11.5 M transforms/s either way -- the plain
@@ -69,7 +68,7 @@ __global__ LM_GEOM_BOUNDS((k_limb_ntt_geom<LOGN, INV>)) void k_limb_ntt(const u6
 static int launch_limb_ntt(lumen_ctx *ctx, uint32_t logn, bool inverse, uint32_t grid, const u64 *src,
                            size_t src_poly_stride, u64 *dst, size_t dst_poly_stride, uint32_t npoly,
                            const lm_modmap &map, const lm_mods &mods, const lm_ninv_t &ninv, const tw_t *tw) {
-    return lm_for_logn_split(ctx, logn, [&](auto n) {
+    return lm_for_any_logn(ctx, logn, [&](auto n) {
         if (inverse)
             return lm_launch(ctx, k_limb_ntt<n, true>, k_limb_ntt_geom<n, true>, grid, src, src_poly_stride, dst,
                              dst_poly_stride, npoly, map, mods, ninv, tw);

@@ -43,10 +43,7 @@ __global__ LM_GEOM_BOUNDS(lm_geom_lds(lm_tlog(LOGN))) void k_rescale_last(const 
     u64 *o = tbuf + (size_t)blockIdx.x * N;
     auto ld = [&](uint32_t i0, u64 *v, int count) { lm_load_run(p, i0, v, count); };
     auto st = [&](uint32_t i, u64 v) { o[i] = lm_addmod(lm_shoup_cs(v, ninv, c.q, c.nq), half, c.q); };
-    if constexpr (lm_is_split(LOGN)) // one workgroup, the halves back to back; the first one parked in t itself
-        lm_ntt_inverse_split<LOGN>(sm, tw, c, tid, ld, o, st);
-    else
-        lm_ntt_inverse<LOGN>(sm, tw, c, tid, ld, st);
+    lm_ntt_inverse_whole<LOGN>(sm, tw, c, tid, ld, o, st); // a split degree: the halves back to back, the first one parked in t itself
 }
 
 template <int LOGN>
@@ -74,10 +71,7 @@ __global__ LM_GEOM_BOUNDS(lm_geom_lds(lm_tlog(LOGN))) void k_rescale_limb(const 
             if (k < count) r[k] = lm_shoup_cs(lm_submod(cv[k], lm_reduce_s(v[k], c.q, c.nq, c.qinv64), c.q), qlinv, c.q, c.nq);
         lm_store_run(o, i0, r, count);
     };
-    if constexpr (lm_is_split(LOGN))
-        lm_ntt_forward_split<LOGN>(sm, tw_all + (size_t)limb * N, c, tid, hf, ld, st);
-    else
-        lm_ntt_forward<LOGN>(sm, tw_all + (size_t)limb * N, c, tid, ld, st);
+    lm_ntt_forward_half<LOGN>(sm, tw_all + (size_t)limb * N, c, tid, hf, ld, st);
 }
 
 // ---- multi-step rescale on coefficients
@@ -238,7 +232,7 @@ static int rescale_polys_t(lumen_ctx *ctx, const u64 *src, uint32_t nl, u64 *dst
 // the src layout (may be NULL when nl - target == 1); tbuf: [npoly][N].
 int lm_rescale_polys(lumen_ctx *ctx, const u64 *src, uint32_t nl, u64 *dst, uint32_t target,
                      uint32_t npoly, u64 *work, u64 *tbuf) {
-    return lm_for_logn_split(ctx, ctx->logN, [&](auto n) { return rescale_polys_t<n>(ctx, src, nl, dst, target, npoly, work, tbuf); });
+    return lm_for_any_logn(ctx, ctx->logN, [&](auto n) { return rescale_polys_t<n>(ctx, src, nl, dst, target, npoly, work, tbuf); });
 }
 
 extern "C" int lumen_rescale(lumen_ctx *ctx, const lumen_set *in, uint32_t target_limbs, lumen_set **out) {

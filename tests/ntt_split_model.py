@@ -1,9 +1,9 @@
-"""The split transform of lm_ntt_dev.h in Python integers: a negacyclic NTT of N = 2^log_n points as ONE outer radix-2
+"""The split transform of lm_ntt_split.h in Python integers: a negacyclic NTT of N = 2^log_n points as ONE outer radix-2
 stage and two transforms of N/2 points, and its mirror image.
 
 Tables are in lm_build_tw's order (Lattigo's): tw[bitrev(j)] = psi^j, the stage with m groups reads tw[m + i].  The two
 halves read sub-tables of N/2 entries, sub_h[m' + i] = tw[2m' + h m' + i]; slot 0, which no stage reads, holds the
-outer twiddle tw[1] (lm_split_tw).
+outer twiddle tw[1] (lm_split_tw, lm_ntt_plan.h).
 
   forward   lo[j] = x[j] + w x[j + N/2], hi[j] = x[j] - w x[j + N/2], w = tw[1];
             NTT(x) = NTT_{N/2}(lo; sub_0) || NTT_{N/2}(hi; sub_1)

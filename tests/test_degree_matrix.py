@@ -1,4 +1,4 @@
-"""Every kernel that carries a limb transform is a template on the ring degree (LM_FOR_EACH_LOGN, lm_ntt_dev.h): each
+"""Every kernel that carries a limb transform is a template on the ring degree (LM_FOR_EACH_LOGN, lm_ntt_plan.h): each
 degree has its own pass plan -- masked lanes at 2^8, no cross-wave pass at 2^10, one to four cross-wave stages at
 2^11 ... 2^14, a second forward path at 2^14 -- and its own modulus bound (3 log_n + 8) q < 2^64.  This file follows
 that structure: every operation at every instantiated degree, on a chain in the reference's style and on one right
@@ -24,7 +24,7 @@ T_SMALL = 0x3EE0001  # TestRingSwitch (ring_switch_test.go:17)
 # ------------------------------------------------------------------ A. the degree list is pinned
 def test_instantiated_degrees_are_the_tested_degrees():
     """LM_FOR_EACH_LOGN == DEGREES: a degree instantiated without cases here (or dropped) fails the CPU suite."""
-    header = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "lumenos_amd", "csrc", "lm_ntt_dev.h")
+    header = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "lumenos_amd", "csrc", "lm_ntt_plan.h")
     with open(header) as f:
         defs = re.findall(r"^[ \t]*#[ \t]*define[ \t]+LM_FOR_EACH_LOGN\(X\)(.*)$", f.read(), flags=re.M)
     assert len(defs) == 1, defs

@@ -1,5 +1,5 @@
 """tests/ntt_split_model.py -- the sub-table derivation, the outer stage and the join of the split transform
-(lm_ntt_dev.h, LM_FOR_EACH_SPLIT_LOGN) -- against the oracle's Params.limb_ntt / limb_intt: at log_n = 15, the degree the
+(lm_ntt_split.h; LM_FOR_EACH_SPLIT_LOGN, lm_ntt_plan.h) -- against the oracle's Params.limb_ntt / limb_intt: at log_n = 15, the degree the
 library splits, and at two small degrees where a failure is readable; on a prime in the reference's style and on one
 directly under (2^64 - 1) // 53 = (2^64 - 1) // (3 * 15 + 8), the context's bound at 2^15."""
 import os
@@ -43,7 +43,7 @@ def _u64(a):
 
 def test_split_degree_list_is_pinned():
     """LM_FOR_EACH_SPLIT_LOGN == SPLIT_DEGREES, beside LM_FOR_EACH_LOGN (test_degree_matrix.py pins that one)"""
-    header = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "lumenos_amd", "csrc", "lm_ntt_dev.h")
+    header = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "lumenos_amd", "csrc", "lm_ntt_plan.h")
     with open(header) as f:
         defs = re.findall(r"^[ \t]*#[ \t]*define[ \t]+LM_FOR_EACH_SPLIT_LOGN\(X\)(.*)$", f.read(), flags=re.M)
     assert len(defs) == 1, defs

@@ -19,6 +19,7 @@ from oracle.loader import Params
 gpu = pytest.mark.gpu
 
 DEGREES = (8, 10, 11, 12, 13, 14)
+SPLIT_DEGREES = (15,)  # LM_FOR_EACH_SPLIT_LOGN (pinned by test_ntt_split_model.py); their GPU cases: test_degree15.py
 LEVELS = (1, 2, 3, 4, 5)
 T_SMALL = 0x3EE0001
 NEW_SYMBOLS = ("lumen_galois_element", "lumen_automorphism", "lumen_rotate_columns", "lumen_rotate_rows", "lumen_rotate_hoisted")
@@ -45,8 +46,8 @@ def _rotdown_report():
 
 def test_rotdown_uses_no_scratch_at_any_degree():
     hits = _rotdown_report()
-    assert len(hits) == len(DEGREES), sorted(hits)
-    for log_n in DEGREES:
+    assert len(hits) == len(DEGREES + SPLIT_DEGREES), sorted(hits)
+    for log_n in DEGREES + SPLIT_DEGREES:
         assert sum(f"ILi{log_n}E" in k for k in hits) == 1, (log_n, sorted(hits))
     for k, r in hits.items():
         assert r.get("ScratchSize [bytes/lane]", 0) == 0 and r.get("VGPRs Spill", 0) == 0, (k, r)

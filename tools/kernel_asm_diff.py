@@ -1,13 +1,15 @@
 """Same machine code?  Compares the device assembly of two source trees kernel by kernel (no GPU needed).
 
-    python tools/kernel_asm_diff.py OLD_CSRC NEW_CSRC [--jobs 8]
+    python tools/kernel_asm_diff.py OLD_CSRC NEW_CSRC [--jobs 8] [--rename OLD=NEW ...]
 
 Every *.hip of both directories is compiled with
     hipcc -O3 -std=c++17 --offload-arch=gfx950 -ffp-contract=off --cuda-device-only -S
 and the output split by kernel symbol (.amdhsa_kernel): a kernel is everything from its label to its .size line,
 i.e. its instruction stream and its .amdhsa_* block.  Kernels may move between files; the set of symbols over the whole library and
 every kernel's text must be the same.  Lines that name a file or the per-file __hip_cuid_ and the assembler's comments are dropped, and
-the function ordinal inside local labels (.LBB3_7 -> .LBB_7: it counts the functions of the file) is removed."""
+the function ordinal inside local labels (.LBB3_7 -> .LBB_7: it counts the functions of the file) is removed.
+--rename OLD=NEW substitutes NEW for OLD in the old tree's symbols and kernel texts before comparing, for a kernel that changed its
+name and nothing else; OLD and NEW are fragments of the mangled symbol (15k_moddown_split=13k_moddown_ntt)."""
 import argparse
 import glob
 import os
@@ -56,11 +58,21 @@ def main():
     ap.add_argument("old")
     ap.add_argument("new")
     ap.add_argument("--jobs", type=int, default=8)
+    ap.add_argument("--rename", action="append", default=[], metavar="OLD=NEW")
     a = ap.parse_args()
     with tempfile.TemporaryDirectory() as t:
         os.mkdir(t + "/old"), os.mkdir(t + "/new")
         old = kernels(compile_tree(a.old, t + "/old", a.jobs))
         new = kernels(compile_tree(a.new, t + "/new", a.jobs))
+    for r in a.rename:
+        o, n = r.split("=")
+        hit = [k for k in old if o in k]
+        assert hit, f"--rename {r}: no kernel of the old tree has {o} in its symbol"
+        for k in hit:
+            f, text = old.pop(k)
+            assert k.replace(o, n) not in old, f"--rename {r}: {k.replace(o, n)} exists in the old tree"
+            old[k.replace(o, n)] = (f, text.replace(o, n))
+            print(f"renamed: {k} -> {k.replace(o, n)}")
     bad = 0
     for n in sorted(set(old) | set(new)):
         if n not in old or n not in new:
