@@ -81,7 +81,9 @@ int lumen_ctx_wait(lumen_ctx *ctx, lumen_ctx *other);
  * the in-process form for tests and tools: name = "LUMEN_KS_BATCH", "LUMEN_KS_LANES",
  * "LUMEN_KS_FUSED_DIGITS" (value < 0: derived default), "LUMEN_KS_CLOSE_FUSED" (1, the default: the last rotation of
  * lumen_matrix_inner_sum writes the rescale's coefficient-form input itself; 0: ModDown and the whole rescale; same
- * residues), "LUMEN_DEBUG", "LUMEN_MODUP_TGROUP",
+ * residues), "LUMEN_KS_C0_FOLD" (1, the default: on that route the doublings before the last rotation run ModDown for
+ * polynomial 1 alone and polynomial 0's lifts are taken once, at the close; 0: ModDown for both; same residues),
+ * "LUMEN_DEBUG", "LUMEN_MODUP_TGROUP",
  * "LUMEN_MODDOWN_TGROUP" (work-list order of the key switch's two transform kernels), "LUMEN_KS_PLACEMENT" (candidate
  * blocks per key-switch scratch buffer among which a context's first key switch picks by measurement, 0 = none:
  * takes effect when the buffers are next allocated, e.g. after lumen_ctx_trim), "LUMEN_BATCH_CHUNKS" (chunks of columns

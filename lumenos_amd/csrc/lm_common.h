@@ -85,6 +85,10 @@ struct lm_tuning {
     // LUMEN_KS_CLOSE_FUSED: 1 = the last rotation of matrixInnerSumEval's InnerSum ends in k_ks_close (lm_ks_close.hip), the
     // rescale's inverse transform with the last ModDown folded in; 0 = k_moddown_ntt and the whole rescale.  Same residues.
     uint32_t ks_close_fused = 1;
+    // LUMEN_KS_C0_FOLD: 1 = on the route that ends in k_ks_close the doublings of matrixInnerSumEval's InnerSum do not run
+    // ModDown for polynomial 0: its Q limbs are rotated by the gadget product (k_ks_mac_fold), its lifts summed per
+    // coefficient in the coefficient domain (k_lift_fold) and taken once, at the close.  0 = ModDown for both.  Same residues.
+    uint32_t ks_c0_fold = 1;
     uint32_t debug = 0;          // LUMEN_DEBUG
     // LUMEN_MODUP_TGROUP / LUMEN_MODDOWN_TGROUP: target limbs one XCD walks back to back in the work lists of the
     // two transform kernels of a key switch (lm_keyswitch.hip); 1 .. 31

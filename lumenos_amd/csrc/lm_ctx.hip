@@ -194,6 +194,9 @@ static int tuning_set(lm_tuning &t, const char *name, long v) {
     } else if (n == "LUMEN_KS_CLOSE_FUSED") {
         if (!in(0, 1)) return 2;
         t.ks_close_fused = (uint32_t)v;
+    } else if (n == "LUMEN_KS_C0_FOLD") {
+        if (!in(0, 1)) return 2;
+        t.ks_c0_fold = (uint32_t)v;
     } else if (n == "LUMEN_DEBUG") {
         t.debug = v != 0;
     } else if (n == "LUMEN_MODUP_TGROUP") {
@@ -214,7 +217,7 @@ static int tuning_set(lm_tuning &t, const char *name, long v) {
     return 0;
 }
 static void tuning_from_env(lm_tuning &t) {
-    for (const char *n : {"LUMEN_KS_BATCH", "LUMEN_KS_LANES", "LUMEN_KS_FUSED_DIGITS", "LUMEN_KS_CLOSE_FUSED", "LUMEN_DEBUG",
+    for (const char *n : {"LUMEN_KS_BATCH", "LUMEN_KS_LANES", "LUMEN_KS_FUSED_DIGITS", "LUMEN_KS_CLOSE_FUSED", "LUMEN_KS_C0_FOLD", "LUMEN_DEBUG",
                           "LUMEN_MODUP_TGROUP", "LUMEN_MODDOWN_TGROUP", "LUMEN_KS_PLACEMENT", "LUMEN_BATCH_CHUNKS"}) {
         const char *e = getenv(n);
         // an empty override counts as unset; a value out of range is reported and leaves the default

@@ -108,6 +108,7 @@ int sum_walk(const lumen_ctx *ctx, uint32_t batch, uint32_t n, Fn &&fn) {
 struct SumPlan {
     struct Step {
         const lm_galois_key *dbl = nullptr, *term = nullptr; // the doubling's key; the lazy term's, or none
+        uint64_t dbl_el = 0;                                  // the doubling's Galois element (the c0 fold's sigma_coef)
     } it[32];                                                // n < 2^32: at most 31 iterations
     uint32_t cnt = 0;
     uint64_t last_el = 0; // the Galois element of the last doubling (rotate_close)
@@ -122,7 +123,7 @@ int sum_plan(lumen_ctx *ctx, uint32_t batch, uint32_t n, SumPlan *p) {
             if (int rc = ks_find_key(ctx, term, &st.term)) return rc;
             p->lazy = true;
         }
-        p->last_el = dbl;
+        p->last_el = st.dbl_el = dbl;
         return ks_find_key(ctx, dbl, &st.dbl);
     });
 }
@@ -192,15 +193,28 @@ int lazy_close(lumen_ctx *ctx, const u64 *cur, u64 *out, u64 *lazy, uint32_t B, 
 // ---- InnerSum(., batch, n) of the B columns of acc, in place: canonical when the plan has lazy terms, in [0, 2q) when
 // it has none.  `lazy`: the lane's lazy accumulator (a plan with lazy terms).  With close_out (a rescale follows a plan
 // that has a doubling and no lazy term) the last doubling leaves the sum there in coefficient form instead, and acc
-// holds nothing the caller may use.
+// holds nothing the caller may use.  fold_s (with close_out alone): two blocks of ks_fold_words for the c0 fold
+// (LUMEN_KS_C0_FOLD, lm_ks_host.h) -- polynomial 0 then goes through the doublings as (A, S) and is whole again only in
+// close_out.
 int inner_sum_batch(lumen_ctx *ctx, u64 *acc, uint32_t B, const SumPlan &plan, KsTables *tb, const KsScratch &s, u64 *lazy,
-                    u64 *close_out) {
+                    u64 *close_out, u64 *fold_s = nullptr) {
     LM_CHECK(ctx, !close_out || (plan.cnt && !plan.lazy), "InnerSum has no rotation to close");
+    // |S| < (2^cnt - 1) 2^lift_bits must fit three words of two's complement
+    LM_CHECK(ctx, !fold_s || (close_out && ks_fold_serves(ctx, tb, plan.cnt)),
+             "the c0 fold cannot hold the lifts of %u rotations of %u bits in 192", plan.cnt, tb->lift_bits);
     u64 *cur = acc, *other = s.acc2; // ping-pong: the automorphism reads two positions of the old accumulator per output
     bool first = true;
     for (uint32_t r = 0; r < plan.cnt; r++) {
         const SumPlan::Step &st = plan.it[r];
         if (int rc = rotate_decompose(ctx, cur, B, tb, s)) return rc; // once per iteration: s.ext survives the lazy term
+        if (fold_s) { // S ping-pongs as the accumulator does; the first rotation has none to read
+            const u64 *s_in = r ? fold_s + ((r - 1) & 1) * ks_fold_words(ctx, B) : nullptr;
+            u64 *s_out = fold_s + (r & 1) * ks_fold_words(ctx, B);
+            if (r + 1 == plan.cnt) return rotate_close_fold(ctx, cur, close_out, B, *st.dbl, st.dbl_el, tb, s, s_in, s_out);
+            if (int rc = rotate_add_fold(ctx, cur, other, B, *st.dbl, st.dbl_el, tb, s, s_in, s_out)) return rc;
+            std::swap(cur, other);
+            continue;
+        }
         if (st.term) {
             if (int rc = rotate_mac(ctx, cur, B, *st.term, tb, s)) return rc;
             if (int rc = lazy_gather(ctx, s.u, cur, lazy, st.term->d_index.get(), first, B, tb)) return rc;
@@ -304,10 +318,21 @@ int matrix_inner_sum_run(lumen_ctx *ctx, const lumen_set *matrix, const uint64_t
         if (rc && rc != 2) return rc;
         close = rc == 0;
     }
+    // The c0 fold (LUMEN_KS_C0_FOLD): on this route polynomial 0's first reader after MulNew is the closing inverse
+    // transform, so the doublings keep it as (A, S) and run ModDown for polynomial 1 alone (lm_ks_host.h).  Per lane two
+    // blocks of S, one signed three-word integer per coefficient and column.
+    u64 *fold_s[2] = {nullptr, nullptr};
+    if (close && ctx->tune.ks_c0_fold && ks_fold_serves(ctx, run.tb, plan.cnt)) {
+        const size_t bytes = 2 * ks_fold_words(ctx, run.Bmax) * 8;
+        fold_s[0] = (u64 *)lm_scratch(ctx, "ks_fold_s", bytes);
+        fold_s[1] = run.lanes > 1 ? (u64 *)lm_scratch(ctx, "ks_fold_s_b", bytes) : fold_s[0];
+        if (!fold_s[0] || !fold_s[1]) return 1;
+    }
     auto batch_fn = [&](uint32_t g0, uint32_t first, uint32_t B, const KsScratch &s, u64 *a) {
         if (int rc = launch_mul_plain(ctx, matrix->d + (size_t)(g0 + first) * ctw, a, ptT, (size_t)B * ctw, L, B)) // ligero.go:319
             return rc;
-        return inner_sum_batch(ctx, a, B, plan, run.tb, s, lazy[&s == &run.s[1]], close ? work + (size_t)first * ctw : nullptr); // ligero.go:325
+        const int lane = &s == &run.s[1];
+        return inner_sum_batch(ctx, a, B, plan, run.tb, s, lazy[lane], close ? work + (size_t)first * ctw : nullptr, fold_s[lane]); // ligero.go:325
     };
     // the rescale of the group needs both lanes.  ligero.go:331-333
     auto end_of_group = [&](uint32_t g0, uint32_t gn) {

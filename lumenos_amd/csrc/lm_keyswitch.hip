@@ -32,6 +32,9 @@
 //   rotate_add, rotate_store,         the three ways a decomposed rotation ends: ModDown into an accumulator, ModDown into
 //   rotate_close                      a plain gather, the closing inverse transform before a rescale (lm_ks_close.hip)
 //   rotate_accumulate                 rotate_decompose + rotate_add
+//   rotate_add_fold, rotate_close_fold the same two endings under the c0 fold (LUMEN_KS_C0_FOLD, lm_ks_host.h): ModDown for
+//                                     polynomial 1 alone, polynomial 0 rotated by the gadget product itself (k_ks_mac_fold: the
+//                                     kernel's text, lm_ks_mac_kernel.h, is included twice) and its lifts folded per coefficient
 // with lumen_ks_mac_probe, which times the gadget product alone.  The other subjects of the key switch live beside it:
 // the batching of its callers (batches, lanes, groups) in lm_ks_batch.hip; the callers in lm_innersum.hip (InnerSum with
 // its lazy accumulator, matrixInnerSumEval), lm_rotate.hip (lumen_automorphism, lumen_rotate_columns / _rows / _hoisted)
@@ -335,98 +338,13 @@ __device__ __forceinline__ void mac2(mac_acc &p, mac_acc &q, u64 x, u64 k0, u64 
 #endif
 }
 
-__global__ __launch_bounds__(256) void k_ks_mac(const u64 *__restrict__ ext, const u64 *__restrict__ acc,
-                                                const u64 *__restrict__ key, u64 *__restrict__ u, uint32_t B,
-                                                uint32_t L, uint32_t K, uint32_t beta, uint32_t pshift,
-                                                uint32_t key_beta, uint32_t logN, lm_mods mods) {
-    typedef mac_vec<LM_MAC_VEC> vec;
-    const uint32_t N = 1u << logN, LK = L + K;
-    // 1-D grid, XCD-aware: workgroup k runs on XCD k % 8 (round-robin dispatch) and each XCD has its own
-    // L2, so the G column groups that share one slice of the key are dealt to the SAME XCD back to
-    // back -- the slice is fetched into that L2 once instead of once per column group.
-    const uint32_t G = (B + LM_MAC_COLS - 1) / LM_MAC_COLS, per_limb = N / (256 * LM_MAC_VEC) ? N / (256 * LM_MAC_VEC) : 1;
-    const uint32_t slices = per_limb * LK;
-    uint32_t slice, z;
-    if (slices % 8 == 0) {
-        const uint32_t xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
-        z = j % G;
-        slice = (j / G) * 8 + xcd;
-    } else {
-        z = blockIdx.x % G;
-        slice = blockIdx.x / G;
-    }
-    const uint32_t i = ((slice % per_limb) * 256 + threadIdx.x) * LM_MAC_VEC; // first coefficient
-    // limbs in descending order: the extension kernel wrote the highest target group last, so those
-    // digits are the likeliest to still sit in the Infinity Cache
-    // (walking the Q limbs first and the limbs modulo P last, so that what the next three kernels read is what was written
-    // last -- with the extension kernel writing its P-limb targets first -- was measured: this kernel -2 %, the extension
-    // kernel +1.2 %, the step +0.3 %: profiles/r06_exp_ks_p_last_interleaved.txt)
-    const uint32_t t = LK - 1 - slice / per_limb;                             // target position
-    const uint32_t mt = ks_mod_at(t, L, pshift);                              // its modulus and key limb
-    const uint32_t b0 = z * LM_MAC_COLS;
-    if (i >= N) return;
-    const mod_t md = mods.m[mt];
-    const uint32_t own = t < L ? t / K : 0xFFFFFFFFu; // digit whose limbs include t: its "extension" is c1 itself
-    mac_acc a0[LM_MAC_COLS][LM_MAC_VEC], a1[LM_MAC_COLS][LM_MAC_VEC];
-#pragma unroll
-    for (int c = 0; c < LM_MAC_COLS; c++)
-#pragma unroll
-        for (int e = 0; e < LM_MAC_VEC; e++) a0[c][e].clear(), a1[c][e].clear();
-    // columns past the end of the batch re-read the last one (never stored): all loads of a digit are
-    // then unconditional and issued together, one digit ahead of the multiply-adds that consume them
-    struct digit_t {
-        vec k0, k1, x[LM_MAC_COLS];
-    };
-    auto fetch = [&](uint32_t d) {
-        digit_t g;
-        g.k0 = vec::load(key + ks_key_at(d, 0, mt, key_beta) * N + i);
-        g.k1 = vec::load(key + ks_key_at(d, 1, mt, key_beta) * N + i);
-#pragma unroll
-        for (int c = 0; c < LM_MAC_COLS; c++) {
-            const uint32_t bc = b0 + c < B ? b0 + c : B - 1;
-            g.x[c] = d == own ? vec::load(acc + ((size_t)(bc * 2 + 1) * L + t) * N + i)
-                              : vec::load_once(ext + ks_ext_at(bc, d, t, B, beta) * N + i);
-        }
-        return g;
-    };
-    // software pipeline over the digits: the loads of digit d + PF are issued before the multiply-adds of digit d
-    // (the ring of PF + 1 register sets is indexed statically: the loop advances by whole turns of it)
-    constexpr int PF = LM_MAC_PREFETCH;
-    digit_t q[PF + 1];
-#pragma unroll
-    for (int j = 0; j < PF; j++)
-        if ((uint32_t)j < beta) q[j] = fetch(j);
-    for (uint32_t d0 = 0; d0 < beta; d0 += PF + 1) {
-#pragma unroll
-        for (int j = 0; j <= PF; j++) {
-            const uint32_t d = d0 + j;
-            if (d < beta) { // wave-uniform
-                if (d + PF < beta) q[(j + PF) % (PF + 1)] = fetch(d + PF);
-#pragma unroll
-                for (int c = 0; c < LM_MAC_COLS; c++)
-#pragma unroll
-                    for (int e = 0; e < LM_MAC_VEC; e++) mac2(a0[c][e], a1[c][e], q[j].x[c].v[e], q[j].k0.v[e], q[j].k1.v[e]);
-            }
-        }
-    }
-#pragma unroll
-    for (int c = 0; c < LM_MAC_COLS; c++) {
-        if (b0 + c < B) {
-            u64 *o = u + ks_u_at((b0 + c) * 2, t, B, L, K) * N + i, *o1 = u + ks_u_at((b0 + c) * 2 + 1, t, B, L, K) * N + i;
-            vec r0, r1;
-#pragma unroll
-            for (int e = 0; e < LM_MAC_VEC; e++) {
-                u64 lo, hi;
-                a0[c][e].value(lo, hi);
-                r0.v[e] = lm_mont_reduce_wide(lo, hi, md.q, md.qneg, md.qinv64, beta);
-                a1[c][e].value(lo, hi);
-                r1.v[e] = lm_mont_reduce_wide(lo, hi, md.q, md.qneg, md.qinv64, beta);
-            }
-            r0.store(o);
-            r1.store(o1);
-        }
-    }
-}
+// the kernel twice, out of one text (lm_ks_mac_kernel.h): k_ks_mac, and k_ks_mac_fold with the c0 fold in its epilogue
+#define LM_KS_MAC_FOLD 0
+#include "lm_ks_mac_kernel.h"
+#undef LM_KS_MAC_FOLD
+#define LM_KS_MAC_FOLD 1
+#include "lm_ks_mac_kernel.h"
+#undef LM_KS_MAC_FOLD
 
 // ---- steps 4+5: ModDown, add c0, automorphism, accumulate.  One workgroup per (column b,
 // poly w, Q limb t): the lift of the (coefficient-domain) P limbs into q_t is fused into the load,
@@ -715,13 +633,28 @@ int get_tables_at(lumen_ctx *ctx, uint32_t nl, KsTables **out) {
         const uint64_t q = ctx->mod[t];
         pinv[t] = h_tw(h_invmod(h_p_mod(ctx, q), q), q);
     }
+    // the c0 fold: 2M and the bound of a lift, |W - 2M| < 2M (K == 2) or the residue itself, < p (K == 1); S modulo q_t
+    {
+        unsigned __int128 M = 1;
+        for (uint32_t a = 0; a < K; a++) M *= ctx->mod[ctx->L + a]; // two moduli below 2^61
+        const unsigned __int128 bound = K == 2 ? 2 * M : M;
+        tb.m2_lo = K == 2 ? (u64)(2 * M) : 0, tb.m2_hi = K == 2 ? (u64)((2 * M) >> 64) : 0;
+        for (tb.lift_bits = 0; tb.lift_bits < 128 && (bound >> tb.lift_bits); tb.lift_bits++) {}
+    }
+    std::vector<sfold_t> sfold(L);
+    for (uint32_t t = 0; t < L; t++) {
+        const uint64_t q = ctx->mod[t];
+        const uint64_t r63 = (1ull << 63) % q, r64 = h_mulmod(r63, 2 % q, q), r128 = h_mulmod(r64, r64, q);
+        sfold[t].r64 = h_tw(r64, q), sfold[t].r128 = h_tw(r128, q);
+        sfold[t].off = q - h_mulmod(r63, r128, q), sfold[t].pad = 0;
+    }
     std::vector<uint16_t> pairs;
     for (uint32_t t = 0; t < LK; t++)
         for (uint32_t d = 0; d < tb.beta; d++)
             if (!bx[(size_t)d * LK + t].own) pairs.push_back((uint16_t)(d | (t << 8)));
     tb.pairs = pairs;
     if (tb.d_bx.upload(ctx, bx, "the key switch's extension constants") || tb.d_bxp.upload(ctx, bxp, "the key switch's lift constants") ||
-        tb.d_pinv.upload(ctx, pinv, "the key switch's P^-1 table"))
+        tb.d_pinv.upload(ctx, pinv, "the key switch's P^-1 table") || tb.d_sfold.upload(ctx, sfold, "the c0 fold's reduction constants"))
         return 1;
     ctx->ext[name] = sp;
     *out = sp.get();
@@ -805,12 +738,14 @@ static int modup_work_list(lumen_ctx *ctx, KsTables *tb, uint32_t B, const uint3
 
 // The same for ModDown: (polynomial pw = 2b + w, Q limb t); XCD x takes the polynomials pw == x (mod 8),
 // targets in groups of LM_MODDOWN_TGROUP, the group's targets innermost.
-static int moddown_work_list(lumen_ctx *ctx, KsTables *tb, uint32_t B, const uint32_t **out) {
+// c1_only (the c0 fold: polynomial 0 needs no ModDown): the entries of polynomial 1 alone, B L of them, under a key of
+// their own; XCD x then takes the COLUMNS b == x (mod 8) -- by pw the odd polynomials would sit on four of the eight.
+static int moddown_work_list(lumen_ctx *ctx, KsTables *tb, uint32_t B, const uint32_t **out, bool c1_only = false) {
     const uint32_t LM_MODDOWN_TGROUP = ctx->tune.moddown_tgroup;
     LM_SHARED_LOCK(ctx);
     // packed as polynomial 2b + w (16 bits) | target limb (16)
     LM_CHECK(ctx, B >= 1 && 2 * (uint64_t)B <= 65535, "key-switch batch of %u columns does not fit the packed work list", B);
-    const uint32_t cache_key = B | (LM_MODDOWN_TGROUP << 17);
+    const uint32_t cache_key = B | (LM_MODDOWN_TGROUP << 17) | (c1_only ? 1u << 31 : 0u);
     auto it = tb->d_work_down.find(cache_key);
     if (it != tb->d_work_down.end()) {
         *out = it->second.get();
@@ -820,9 +755,9 @@ static int moddown_work_list(lumen_ctx *ctx, KsTables *tb, uint32_t B, const uin
     std::vector<std::vector<uint32_t>> lists(8);
     for (uint32_t x = 0; x < 8; x++)
         for (uint32_t t0 = 0; t0 < L; t0 += LM_MODDOWN_TGROUP)
-            for (uint32_t pw = x; pw < 2 * B; pw += 8)
+            for (uint32_t pw = c1_only ? 2 * x + 1 : x; pw < 2 * B; pw += c1_only ? 16 : 8)
                 for (uint32_t t = t0; t < std::min<uint32_t>(t0 + LM_MODDOWN_TGROUP, L); t++) lists[x].push_back(pw | (t << 16));
-    return interleave_work_lists(ctx, lists, (size_t)2 * B * L, "ModDown", tb->d_work_down, cache_key, out);
+    return interleave_work_lists(ctx, lists, (size_t)(c1_only ? 1 : 2) * B * L, "ModDown", tb->d_work_down, cache_key, out);
 }
 
 // digits whose packing is fused into the c1 inverse transform (k_intt_pack): the largest count whose
@@ -878,19 +813,31 @@ static int launch_ks_mac(lumen_ctx *ctx, const u64 *ext, const u64 *acc, const u
     LM_HIP(ctx, hipGetLastError());
     return 0;
 }
+// ... of a doubling whose c0 is folded (k_ks_mac_fold): polynomial 0 of acc_out is written here, under gk's tables
+static int launch_ks_mac_fold(lumen_ctx *ctx, const u64 *ext, const u64 *acc, const lm_galois_key &gk, u64 *u, u64 *acc_out, uint32_t B,
+                              KsTables *tb) {
+    const uint32_t L = tb->nl, K = ctx->K, pshift = ctx->L - L, key_beta = (ctx->L + K - 1) / K;
+    LM_CHECK(ctx, ctx->N >= 256 && LM_MAC_VEC == 1, "the folded gadget product works on blocks of 256 coefficients");
+    const dim3 grid((ctx->N / 256) * (L + K) * ((B + LM_MAC_COLS - 1) / LM_MAC_COLS));
+    hipLaunchKernelGGL(k_ks_mac_fold, grid, dim3(256), 0, ctx->stream, ext, acc, gk.d_key.get(), u, B, L, K, tb->beta, pshift, key_beta,
+                       ctx->logN, ctx->mods, acc_out, gk.d_index.get(), gk.d_inv_index.get());
+    LM_HIP(ctx, hipGetLastError());
+    return 0;
+}
 
 // 4b + 5. lift to Q, NTT, combine, automorphism: accumulated into out = in + ... (ACCUMULATE, k_moddown_ntt) or stored as a
 // plain gather (k_rotdown_ntt)
 template <bool ACCUMULATE>
 static int launch_moddown(lumen_ctx *ctx, const u64 *in, u64 *out, uint32_t B, const lm_galois_key &gk, KsTables *tb,
-                          const KsScratch &s) {
+                          const KsScratch &s, bool c1_only = false) {
     const uint32_t L = tb->nl, K = ctx->K;
     const uint32_t *work_down = nullptr;
-    if (int rc = moddown_work_list(ctx, tb, B, &work_down)) return rc;
-    lm_prof_scope ps(ctx, ACCUMULATE ? "ks_moddown_ntt" : "ks_rotdown_ntt", (uint64_t)B * 2 * L);
+    if (int rc = moddown_work_list(ctx, tb, B, &work_down, c1_only)) return rc;
+    const uint32_t items = (c1_only ? 1 : 2) * B * L; // one forward transform each
+    lm_prof_scope ps(ctx, ACCUMULATE ? "ks_moddown_ntt" : "ks_rotdown_ntt", (uint64_t)items);
     return lm_for_any_logn(ctx, ctx->logN, [&](auto n) {
         constexpr int LN = decltype(n)::value;
-        return lm_launch(ctx, ACCUMULATE ? k_moddown_ntt<LN> : k_rotdown_ntt<LN>, lm_geom_fwd(LN), lm_fwd_grid<LN>(B * 2 * L), s.u, in, out, tb->d_bxp.get(), tb->d_pinv.get(),
+        return lm_launch(ctx, ACCUMULATE ? k_moddown_ntt<LN> : k_rotdown_ntt<LN>, lm_geom_fwd(LN), lm_fwd_grid<LN>(items), s.u, in, out, tb->d_bxp.get(), tb->d_pinv.get(),
                          gk.d_index.get(), gk.d_inv_index.get(), work_down, B, L, K, ctx->mods, ctx->sh->tw_fwd.get());
     });
 }
@@ -995,6 +942,43 @@ int rotate_close(lumen_ctx *ctx, const u64 *acc, u64 *coef_out, uint32_t B, cons
     const uint32_t *work_down = nullptr;
     if (int rc = moddown_work_list(ctx, tb, B, &work_down)) return rc;
     return ks_close_launch(ctx, acc, coef_out, B, gk, gal_el, tb, s, work_down);
+}
+
+// ---- the c0 fold (lm_ks_host.h).  Three words of two's complement hold |S| < 2^191, and S is a signed sum of
+// 2^rotations - 1 lifts, each below 2^lift_bits in magnitude; k_ks_mac_fold works on aligned blocks of 256 coefficients
+// and k_ks_close is not built for a split degree.
+// The fold also needs doublings to save on: per 64-column batch at N = 2^14 a folded doubling saves 86 us of ModDown and
+// costs 29 us in the gadget product and a lift fold (8 us the first, 26 us after it), and the close costs 16 us more and
+// a lift fold of its own.  A plan of two rotations has ONE doubling: -86 + 29 + 8 + 26 + 16 = -7 us of a call of about
+// 2.2 ms -- measured, tools/c0_fold_rows.py: not distinguishable from noise, under the project's 1 % bar (EXPERIMENTS R19) --
+// so it keeps the plain route; from three rotations on
+// every further doubling saves 31 us.  -DLM_KS_FOLD_MIN_ROTATIONS=2 builds the variant that measurement used.
+#ifndef LM_KS_FOLD_MIN_ROTATIONS
+#define LM_KS_FOLD_MIN_ROTATIONS 3
+#endif
+bool ks_fold_serves(const lumen_ctx *ctx, const KsTables *tb, uint32_t rotations) {
+    return ctx->N >= 256 && !lm_is_split(ctx->logN) && ctx->K >= 1 && ctx->K <= 2 && rotations >= LM_KS_FOLD_MIN_ROTATIONS &&
+           rotations + tb->lift_bits <= 191;
+}
+
+int rotate_add_fold(lumen_ctx *ctx, const u64 *acc, u64 *acc_out, uint32_t B, const lm_galois_key &gk, uint64_t gal_el, KsTables *tb,
+                    const KsScratch &s, const u64 *s_in, u64 *s_out) {
+    {
+        lm_prof_scope ps(ctx, "ks_mac", (uint64_t)B);
+        if (int rc = launch_ks_mac_fold(ctx, s.ext, acc, gk, s.u, acc_out, B, tb)) return rc;
+    }
+    if (int rc = rotate_p_to_coef(ctx, s.u, B, tb)) return rc;
+    if (int rc = lift_fold_launch(ctx, s.u, s_in, s_out, B, gal_el, tb)) return rc;
+    return launch_moddown<true>(ctx, acc, acc_out, B, gk, tb, s, true);
+}
+
+int rotate_close_fold(lumen_ctx *ctx, const u64 *acc, u64 *coef_out, uint32_t B, const lm_galois_key &gk, uint64_t gal_el,
+                      KsTables *tb, const KsScratch &s, const u64 *s_in, u64 *s_out) {
+    if (int rc = rotate_product(ctx, acc, B, gk, tb, s)) return rc;
+    if (int rc = lift_fold_launch(ctx, s.u, s_in, s_out, B, gal_el, tb)) return rc;
+    const uint32_t *work_down = nullptr;
+    if (int rc = moddown_work_list(ctx, tb, B, &work_down)) return rc;
+    return ks_close_launch(ctx, acc, coef_out, B, gk, gal_el, tb, s, work_down, s_out);
 }
 
 // Times the gadget product alone on caller-chosen device blocks: how its speed depends on WHERE in HBM its

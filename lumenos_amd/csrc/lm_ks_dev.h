@@ -24,6 +24,39 @@ __device__ __forceinline__ u64 bx_apply(const bx_t &c, u64 a, u64 b, const lm_qc
     return lm_shoup3<true>(a, c.b57.w, c.b57.wp, qc.nq, b + c.c_t);
 }
 
+// ---- the c0 fold of matrixInnerSumEval's doublings (k_ks_mac_fold, k_lift_fold, k_ks_close): the lifts of polynomial 0
+// are summed per coefficient as ONE signed integer S, whatever the Q limb, in three 64-bit words, two's complement.
+struct lm_s192 {
+    u64 a, b, c; // weights 1, 2^64, 2^128
+};
+__host__ __device__ __forceinline__ lm_s192 lm_s192_add(const lm_s192 &x, const lm_s192 &y) {
+    lm_s192 r;
+    r.a = x.a + y.a;
+    const u64 c0 = r.a < x.a ? 1u : 0u;
+    r.b = x.b + y.b;
+    u64 c1 = r.b < x.b ? 1u : 0u;
+    r.b += c0;
+    c1 += r.b < c0 ? 1u : 0u; // (at most one of the two additions of the middle word wraps)
+    r.c = x.c + y.c + c1;
+    return r;
+}
+__host__ __device__ __forceinline__ lm_s192 lm_s192_neg(const lm_s192 &x) {
+    return lm_s192_add(lm_s192{~x.a, ~x.b, ~x.c}, lm_s192{1, 0, 0});
+}
+// S mod q_t at the close: with s2' = (top word) xor 2^63 the integer is s0 + s1 2^64 + (s2' - 2^63) 2^128, every term
+// unsigned, so S == s0 + s1 r64 + s2' r128 + off (mod q), off = q - (2^63 r128 mod q): the sign is a multiple of q away
+struct sfold_t {
+    tw_t r64, r128; // 2^64 mod q_t, 2^128 mod q_t
+    u64 off, pad;
+};
+// lazily, below 10q < 2^64 (q < 2^60)
+__device__ __forceinline__ u64 lm_s192_mod(const sfold_t &f, u64 s0, u64 s1, u64 s2, const lm_qc &qc) {
+    const u64 r0 = lm_shoup3<true>(s0, 1ull, qc.qinv64, qc.nq);
+    const u64 r1 = lm_shoup3<true>(s1, f.r64.w, f.r64.wp, qc.nq);
+    const u64 r2 = lm_shoup3<true>(s2 ^ (1ull << 63), f.r128.w, f.r128.wp, qc.nq);
+    return r0 + r1 + r2 + f.off;
+}
+
 // Layout of the key switch's three big streams, in limbs of N words: LIMB-MAJOR (round 6).  The gadget product walks
 // ONE modulus t at a time over every (column, digit); with the modulus outermost everything one of its workgroups
 // touches -- 4 columns x beta digits of `ext`, the 2 beta key limbs, its 8 output limbs -- sits in a few MB of

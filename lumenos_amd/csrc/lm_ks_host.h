@@ -13,12 +13,15 @@ struct KsTables {
     lm_dev<bx_t> d_bx;   // [beta][L+K], targets by position (ks_mod_at)
     lm_dev<bx_t> d_bxp;  // [L]  (P -> q_t)
     lm_dev<tw_t> d_pinv; // [L]  P^-1 mod q_t
+    lm_dev<sfold_t> d_sfold; // [L]  the c0 fold's reduction of S modulo q_t (lm_ks_dev.h)
+    u64 m2_lo = 0, m2_hi = 0; // 2M = 2 p_0 p_1, the offset of a two-limb lift W - 2M (K == 1: 0, the lift is the residue)
+    uint32_t lift_bits = 0;   // |W - 2M| < 2^lift_bits
     uint32_t nl = 0;     // the level: Q limbs of the ciphertexts it switches
     uint32_t beta = 0;   // ceil(nl / K) digits
     lm_ninv_t yscale; // per modulus: N^-1 * (M/m)^-1 mod m of the source group the modulus sits in
     std::vector<uint16_t> pairs; // (digit | target << 8) of every extension the key switch needs, target-major
     std::map<uint32_t, lm_dev<uint32_t>> d_work; // per batch size: the workgroup order of the extension kernel
-    std::map<uint32_t, lm_dev<uint32_t>> d_work_down; // ... and of the ModDown kernel
+    std::map<uint32_t, lm_dev<uint32_t>> d_work_down; // ... and of the ModDown kernel (bit 31 of the key: polynomial 1 alone)
 };
 int get_tables(lumen_ctx *ctx, KsTables **out); // the top level's
 // the tables of the level with nl limbs, 1 <= nl <= L, built at its first use and cached (nl == L: get_tables)
@@ -52,9 +55,27 @@ int rotate_close(lumen_ctx *ctx, const u64 *acc, u64 *coef_out, uint32_t B, cons
                  KsTables *tb, const KsScratch &s);
 // the last rotation of an InnerSum that a rescale follows, after its steps 1-4a (lm_ks_close.hip): out, [B][2][nl][N], gets
 // the COEFFICIENT form of acc + Rot_galEl(acc), canonical -- what the rescale's inverse transform would have made of it.
-// work_down: ModDown's work list for B columns at the level of `tb`.
+// work_down: ModDown's work list for B columns at the level of `tb`.  fold_s: the folded lifts of polynomial 0, this
+// rotation's included (the c0 fold, below), or NULL.
 int ks_close_launch(lumen_ctx *ctx, const u64 *acc, u64 *out, uint32_t B, const lm_galois_key &gk, uint64_t gal_el,
-                    KsTables *tb, const KsScratch &s, const uint32_t *work_down);
+                    KsTables *tb, const KsScratch &s, const uint32_t *work_down, const u64 *fold_s = nullptr);
+
+// ---- the c0 fold (LUMEN_KS_C0_FOLD): the doublings of a plain InnerSum that ends in rotate_close keep
+// polynomial 0 as c0 = A - P^-1 NTT(S).  A: polynomial 0 of the accumulator, rotated by the gadget product itself
+// (k_ks_mac_fold); S: one signed three-word integer per coefficient, [B][3][N], rotated in the coefficient domain
+// (k_lift_fold, lm_ks_close.hip); ModDown runs for polynomial 1 alone.  A rotation reads s_in (NULL: the first, S = 0)
+// and writes s_out, another block.
+// can S of `rotations` doublings be held, and is the ring one the fold's kernels serve?
+bool ks_fold_serves(const lumen_ctx *ctx, const KsTables *tb, uint32_t rotations);
+inline size_t ks_fold_words(const lumen_ctx *ctx, uint32_t B) { return (size_t)B * 3 * ctx->N; }
+// after rotate_decompose: acc_out = acc + Rot_galEl(acc) in the folded form, lazy
+int rotate_add_fold(lumen_ctx *ctx, const u64 *acc, u64 *acc_out, uint32_t B, const lm_galois_key &gk, uint64_t gal_el, KsTables *tb,
+                    const KsScratch &s, const u64 *s_in, u64 *s_out);
+// after rotate_decompose, the last rotation: as rotate_close, from the folded form
+int rotate_close_fold(lumen_ctx *ctx, const u64 *acc, u64 *coef_out, uint32_t B, const lm_galois_key &gk, uint64_t gal_el,
+                      KsTables *tb, const KsScratch &s, const u64 *s_in, u64 *s_out);
+// s_out = s_in + sigma_coef(s_in + W - 2M), W the packed limbs modulo P of polynomial 0 in u (after rotate_p_to_coef)
+int lift_fold_launch(lumen_ctx *ctx, const u64 *u, const u64 *s_in, u64 *s_out, uint32_t B, uint64_t gal_el, KsTables *tb);
 // the scratch of a batch of B columns on `lane`, placed by measurement at a context's first key switch (lm_ks_scratch.hip).
 // tb: always the TOP level's tables, whatever level asks -- the blocks are sized, and the candidates timed, once.
 int get_scratch(lumen_ctx *ctx, uint32_t B, KsTables *tb, KsScratch *s, int lane = 0, u64 **group_acc = nullptr,
