@@ -174,7 +174,8 @@ int lumen_encode_shard(lumen_ctx *ctx, const lumen_set *matrix, const uint64_t *
  *     --lumen_encode (on the lane shard, with the same slice of the one Enc(0))--> lane shard of the S
  *     encoded columns --all-to-all--> W blocks of own encoded columns --lumen_lanes_assemble--> full width.
  * A rank uploads 1/W of the matrix and no work is replicated.  Lane sets are accepted by create /
- * destroy / slice / upload / download / fill_random / gather and lumen_encode only.
+ * destroy / slice / upload / download / fill_random / gather, lumen_encode and the elementwise lumen_add / _sub /
+ * _mul_scalar / _mul_scalar_then_add / _linear_combination only.
  * These are the building blocks; a host program uses the group entry points further down
  * (lumen_group_encode runs the whole sequence, exchange included, inside the library). */
 int lumen_set_create_lanes(lumen_ctx *ctx, uint32_t count, uint32_t num_limbs, uint32_t log_world, lumen_set **out);
@@ -430,6 +431,48 @@ int lumen_rotate_columns(lumen_ctx *ctx, const lumen_set *in, int64_t k, lumen_s
 int lumen_rotate_rows(lumen_ctx *ctx, const lumen_set *in, lumen_set **out);
 int lumen_rotate_hoisted(lumen_ctx *ctx, const lumen_set *in, const uint64_t *gal_els, uint32_t n_els,
                          lumen_set **outs /* [n_els] new sets */);
+
+/* ---- the evaluator's linear operations: Evaluator.Add / Sub / Mul(ct, uint64) / MulThenAdd of the *bgv.Evaluator that
+ * ServerBFV embeds (fhe/bfv.go:13-21), with a ciphertext, a scalar or a plaintext operand -- the calls fhe/ntt.go:27-236 and
+ * vdec/batching.go:24-34 make one ciphertext at a time, here on whole sets, so that a caller can write another butterfly
+ * network, another code or another batching on resident sets.  Inputs are canonical NTT-domain words; outputs are
+ * canonical.  The library is scale-agnostic here as everywhere: the caller tracks the scale.
+ * SCALARS.  A scalar word w is what Evaluator.Mul(ct, uint64) sees: limb i is multiplied by centre_T(w mod T) mod q_i, the
+ * representative of w mod T in (-T/2, T/2] taken modulo q_i.  The raw Montgomery-form words of RootForwardUint64 that
+ * fhe/ntt.go passes go in as they are.  On a plain context, whose one modulus is T, that is w mod T.
+ * lumen_linear_combination: out = sum_{t<n} w[t] * in[t], 1 <= n <= 8, in ONE pass: every input word is read once and every
+ * output word written once.  w[t] == 1 and w[t] == -1 (mod T) are additions and subtractions with no multiply.
+ * lumen_add (AddNew / Add), lumen_sub, lumen_mul_scalar (Mul(ct, uint64)) and lumen_mul_scalar_then_add (MulThenAdd:
+ * acc += w * a) are its cases n <= 2 -- the same code.
+ * COUNTS.  Every ciphertext operand has the result's count or count 1: one ciphertext combines with every ciphertext of
+ * the other operands, as in lumen_mul_relin.
+ * LEVELS.  Operands may have different limb counts; the result has the smallest and each operand contributes its first
+ * limbs (Lattigo's min-level rule: dropping a level is taking a prefix).  A plaintext pt is host [a's limbs][N] raw
+ * residues in the form lumen_mul_plain takes (Encoder.Encode's output); a residue >= q_l is refused the same way.
+ * lumen_add_plain / lumen_sub_plain: out = (c0 +- pt, c1).  lumen_mul_plain_then_add: acc += a (.) (pt * T), i.e.
+ * lumen_mul_plain followed by lumen_add, word for word; the accumulator takes the first limbs of a and pt where they are
+ * deeper than it.
+ * DESTINATION.  *out == NULL on entry: a new set.  Otherwise *out is an existing set of exactly the result's count, limb
+ * count and lane width, and is written.  It may BE one of the operands (the same ciphertexts, limbs and storage): the
+ * operations work in place, and an in-place butterfly over a resident set allocates nothing.  Any other overlap of an
+ * operand's device range with the destination's -- an overlapping but unequal lumen_set_slice, say -- is refused.  a == b
+ * is allowed.  `acc` of the two _then_add forms is read and written in place and may not overlap a.
+ * Lane-sharded sets (lumen_set_create_lanes) are accepted by the five scalar forms: all operands and the destination must
+ * have one lane width.  The three plaintext forms take full-width sets.  Sets created by another context of the same
+ * device are accepted, as elsewhere.  Every ring degree a context can have is served, 2^15 included.
+ * lumen_mul_counter grows by the result's count in lumen_mul_scalar (the counter lives in the ServerBFV.Mul / MulNew
+ * wrappers, bfv.go:34-42); the other seven calls are the embedded evaluator's own and leave it alone.
+ * Refused with a message, before any launch: NULL arguments; n == 0 or n > 8; counts that are neither equal nor 1; a
+ * destination of another count, limb count or lane width than the result; mixed lane widths; a forbidden overlap; a
+ * plaintext residue out of range; a context without a plaintext modulus. */
+int lumen_add(lumen_ctx *ctx, const lumen_set *a, const lumen_set *b, lumen_set **out);
+int lumen_sub(lumen_ctx *ctx, const lumen_set *a, const lumen_set *b, lumen_set **out);
+int lumen_mul_scalar(lumen_ctx *ctx, const lumen_set *a, uint64_t w, lumen_set **out);
+int lumen_mul_scalar_then_add(lumen_ctx *ctx, const lumen_set *a, uint64_t w, lumen_set *acc);
+int lumen_linear_combination(lumen_ctx *ctx, const lumen_set *const *in, const uint64_t *w, uint32_t n, lumen_set **out);
+int lumen_add_plain(lumen_ctx *ctx, const lumen_set *a, const uint64_t *pt, lumen_set **out);
+int lumen_sub_plain(lumen_ctx *ctx, const lumen_set *a, const uint64_t *pt, lumen_set **out);
+int lumen_mul_plain_then_add(lumen_ctx *ctx, const lumen_set *a, const uint64_t *pt, lumen_set *acc);
 
 /* ---- fhe.RingSwitchServer (fhe/ring_switch.go:93-113): Evaluator.ApplyEvaluationKey of every
  * ciphertext of `in` into the ring of degree 2^log_n_small with the single modulus q_0, at level 0.

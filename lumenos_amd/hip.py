@@ -126,6 +126,14 @@ SYMBOLS = {
     "lumen_rotate_rows": (C.c_int, [_vp, _vp, _vpp]),
     "lumen_rotate_hoisted": (C.c_int, [_vp, _vp, _u64p, C.c_uint32, _vpp]),
     "lumen_mul_tensor": (C.c_int, [_vp, _vp, _vp, _u64p]),
+    "lumen_add": (C.c_int, [_vp, _vp, _vp, _vpp]),
+    "lumen_sub": (C.c_int, [_vp, _vp, _vp, _vpp]),
+    "lumen_mul_scalar": (C.c_int, [_vp, _vp, C.c_uint64, _vpp]),
+    "lumen_mul_scalar_then_add": (C.c_int, [_vp, _vp, C.c_uint64, _vp]),
+    "lumen_linear_combination": (C.c_int, [_vp, _vpp, _u64p, C.c_uint32, _vpp]),
+    "lumen_add_plain": (C.c_int, [_vp, _vp, _u64p, _vpp]),
+    "lumen_sub_plain": (C.c_int, [_vp, _vp, _u64p, _vpp]),
+    "lumen_mul_plain_then_add": (C.c_int, [_vp, _vp, _u64p, _vp]),
     "lumen_gather": (C.c_int, [_vp, _vp, _u32p, C.c_uint32, _vpp]),
     "lumen_plain_inner_products": (C.c_int, [_vp, _vp, _u64p, _u64p]),
     "lumen_poly_eval_columns": (C.c_int, [_vp, _u64p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint64, _u64p]),
@@ -719,6 +727,54 @@ class Context:
         out = np.zeros((a.count, 3, a.nl, self.N), dtype=np.uint64)
         self._ck(self.lib.lumen_mul_tensor(self.h, a.h, b.h, _p64(out)))
         return out
+
+    # the evaluator's linear operations (Evaluator.Add / Sub / Mul(ct, uint64) / MulThenAdd): out=None makes a new set,
+    # out=<set> writes an existing one of the result's shape, which may be one of the operands (in place)
+    def _into(self, out, call):
+        h = C.c_void_p(out.h.value if out is not None else None)
+        self._ck(call(C.byref(h)))
+        return out if out is not None else DeviceSet(self, h)
+
+    def add(self, a, b, out=None):
+        return self._into(out, lambda h: self.lib.lumen_add(self.h, a.h, b.h, h))
+
+    def sub(self, a, b, out=None):
+        return self._into(out, lambda h: self.lib.lumen_sub(self.h, a.h, b.h, h))
+
+    def mul_scalar(self, a, w, out=None):
+        """Evaluator.Mul(ct, uint64): limb i times centre_T(w mod T) mod q_i; mul_counter grows by the result's count"""
+        return self._into(out, lambda h: self.lib.lumen_mul_scalar(self.h, a.h, int(w), h))
+
+    def mul_scalar_then_add(self, a, w, acc):
+        """MulThenAdd(ct, uint64, acc): acc += w * a, in place"""
+        self._ck(self.lib.lumen_mul_scalar_then_add(self.h, a.h, int(w), acc.h))
+        return acc
+
+    def linear_combination(self, sets, ws, out=None):
+        """sum_t ws[t] * sets[t] for 1 to 8 operands in one pass; scalars as in mul_scalar (1 and T - 1: no multiply)"""
+        ws = np.ascontiguousarray([int(w) for w in ws], dtype=np.uint64)
+        assert ws.size == len(sets)
+        hs = (C.c_void_p * max(len(sets), 1))(*[s.h for s in sets])
+        return self._into(out, lambda h: self.lib.lumen_linear_combination(self.h, hs, _p64(ws) if ws.size else _p64(np.zeros(1, np.uint64)),
+                                                                          len(sets), h))
+
+    def add_plain(self, a, pt, out=None):
+        """Add(ct, pt): c0 + pt; pt [a.nl][N] as Encoder.Encode leaves it"""
+        pt = np.ascontiguousarray(pt, dtype=np.uint64)
+        assert pt.shape == (a.nl, self.N), pt.shape
+        return self._into(out, lambda h: self.lib.lumen_add_plain(self.h, a.h, _p64(pt), h))
+
+    def sub_plain(self, a, pt, out=None):
+        pt = np.ascontiguousarray(pt, dtype=np.uint64)
+        assert pt.shape == (a.nl, self.N), pt.shape
+        return self._into(out, lambda h: self.lib.lumen_sub_plain(self.h, a.h, _p64(pt), h))
+
+    def mul_plain_then_add(self, a, pt, acc):
+        """MulThenAdd(ct, pt, acc): acc += mul_plain(a, pt), in place"""
+        pt = np.ascontiguousarray(pt, dtype=np.uint64)
+        assert pt.shape == (a.nl, self.N), pt.shape
+        self._ck(self.lib.lumen_mul_plain_then_add(self.h, a.h, _p64(pt), acc.h))
+        return acc
 
     def plain_inner_products(self, s, vec):
         """out[j] = sum_i s[j][i] * vec[i] mod q_0 for a one-limb set (the plain prover, ligero.go:886-918)"""

@@ -390,6 +390,7 @@ int ServerBFV::MulCounter() const { return (int)lumen_mul_counter(Context()); }
 
 // ------------------------------------------------------------------ ClientBFV
 void ClientBFV::check(int rc, const char *what) const { ctx_.check(rc, what); }
+int ClientBFV::MulCounter() const { return (int)lumen_mul_counter(Context()); }
 
 ClientBFV::ClientBFV(core::PrimeField *plaintextField, const Parameters &params, const std::vector<uint64_t> &sk, int device)
     : ptField_(plaintextField), params_(params), device_(device) {
@@ -708,6 +709,139 @@ Ciphertexts ServerBFV::InnerSumNew(const Ciphertexts &ct, int batchSize, int n) 
     lumen_set *set = nullptr;
     check(lumen_inner_sum_general(Context(), ct.Handle(), (uint32_t)batchSize, (uint32_t)n, &set), "lumen_inner_sum_general");
     return Ciphertexts(Context(), set, ct.Meta);
+}
+
+// ---- the embedded evaluator's linear operations, for ServerBFV and ClientBFV alike
+namespace {
+void need_set(const char *what, const Ciphertexts &ct) {
+    if (!ct.Handle()) throw std::invalid_argument(std::string(what) + ": an operand holds no ciphertexts");
+}
+void need_scales(const char *what, uint64_t a, uint64_t b) {
+    if (a != b)
+        throw std::invalid_argument(std::string(what) + ": operands of scale " + std::to_string(a) + " and " + std::to_string(b) +
+                                    ": scales are not matched here, bring the operands to one scale first");
+}
+} // namespace
+
+void LinearEvaluator::finish(lumen_set *set, const MetaData &md, Ciphertexts &out) {
+    if (out.Handle() == set)
+        out.Meta = md; // written in place
+    else
+        out = Ciphertexts(Context(), set, md);
+}
+
+void LinearEvaluator::Add(const Ciphertexts &a, const Ciphertexts &b, Ciphertexts &out) {
+    need_set("Add", a), need_set("Add", b), need_scales("Add", a.Scale(), b.Scale());
+    const MetaData md = a.Meta;
+    lumen_set *set = out.Handle();
+    check(lumen_add(Context(), a.Handle(), b.Handle(), &set), "lumen_add");
+    finish(set, md, out);
+}
+
+void LinearEvaluator::Sub(const Ciphertexts &a, const Ciphertexts &b, Ciphertexts &out) {
+    need_set("Sub", a), need_set("Sub", b), need_scales("Sub", a.Scale(), b.Scale());
+    const MetaData md = a.Meta;
+    lumen_set *set = out.Handle();
+    check(lumen_sub(Context(), a.Handle(), b.Handle(), &set), "lumen_sub");
+    finish(set, md, out);
+}
+
+Ciphertexts LinearEvaluator::AddNew(const Ciphertexts &a, const Ciphertexts &b) {
+    Ciphertexts out;
+    Add(a, b, out);
+    return out;
+}
+
+Ciphertexts LinearEvaluator::SubNew(const Ciphertexts &a, const Ciphertexts &b) {
+    Ciphertexts out;
+    Sub(a, b, out);
+    return out;
+}
+
+void LinearEvaluator::Mul(const Ciphertexts &ct, uint64_t w, Ciphertexts &out) {
+    need_set("Mul", ct);
+    const MetaData md = ct.Meta; // a scalar leaves the scale alone
+    lumen_set *set = out.Handle();
+    check(lumen_mul_scalar(Context(), ct.Handle(), w, &set), "lumen_mul_scalar");
+    finish(set, md, out);
+}
+
+Ciphertexts LinearEvaluator::MulNew(const Ciphertexts &ct, uint64_t w) {
+    Ciphertexts out;
+    Mul(ct, w, out);
+    return out;
+}
+
+void LinearEvaluator::MulThenAdd(const Ciphertexts &ct, uint64_t w, Ciphertexts &acc) {
+    need_set("MulThenAdd", ct), need_set("MulThenAdd", acc), need_scales("MulThenAdd", acc.Scale(), ct.Scale());
+    check(lumen_mul_scalar_then_add(Context(), ct.Handle(), w, acc.Handle()), "lumen_mul_scalar_then_add");
+}
+
+Ciphertexts LinearEvaluator::LinearCombinationNew(const std::vector<const Ciphertexts *> &in, const std::vector<uint64_t> &w) {
+    if (in.empty() || in.size() != w.size())
+        throw std::invalid_argument("LinearCombinationNew: " + std::to_string(in.size()) + " operands for " + std::to_string(w.size()) +
+                                    " scalars");
+    std::vector<const lumen_set *> sets;
+    for (const Ciphertexts *c : in) {
+        if (!c) throw std::invalid_argument("LinearCombinationNew: an operand is null");
+        need_set("LinearCombinationNew", *c), need_scales("LinearCombinationNew", in[0]->Scale(), c->Scale());
+        sets.push_back(c->Handle());
+    }
+    lumen_set *set = nullptr;
+    check(lumen_linear_combination(Context(), sets.data(), w.data(), (uint32_t)sets.size(), &set), "lumen_linear_combination");
+    return Ciphertexts(Context(), set, in[0]->Meta);
+}
+
+// the first limbs of a plaintext at ct's level or above
+const uint64_t *LinearEvaluator::limbs_for(const char *what, const Ciphertexts &ct, const Plaintext &pt) const {
+    need_set(what, ct);
+    const size_t N = (size_t)GetParameters().N();
+    if (pt.Level < ct.Level() || pt.Value.size() != (size_t)(pt.Level + 1) * N)
+        throw std::invalid_argument(std::string(what) + ": a plaintext of level " + std::to_string(pt.Level) + " (" +
+                                    std::to_string(pt.Value.size()) + " words) for ciphertexts of level " + std::to_string(ct.Level()));
+    return pt.Value.data();
+}
+
+void LinearEvaluator::plain_sum(const char *what, const Ciphertexts &ct, const Plaintext &pt, Ciphertexts &out, bool sub) {
+    const uint64_t *words = limbs_for(what, ct, pt);
+    need_scales(what, ct.Scale(), pt.Scale);
+    const MetaData md = ct.Meta;
+    lumen_set *set = out.Handle();
+    check((sub ? lumen_sub_plain : lumen_add_plain)(Context(), ct.Handle(), words, &set), sub ? "lumen_sub_plain" : "lumen_add_plain");
+    finish(set, md, out);
+}
+
+void LinearEvaluator::Add(const Ciphertexts &ct, const Plaintext &pt, Ciphertexts &out) { plain_sum("Add", ct, pt, out, false); }
+void LinearEvaluator::Sub(const Ciphertexts &ct, const Plaintext &pt, Ciphertexts &out) { plain_sum("Sub", ct, pt, out, true); }
+
+Ciphertexts LinearEvaluator::AddNew(const Ciphertexts &ct, const Plaintext &pt) {
+    Ciphertexts out;
+    plain_sum("Add", ct, pt, out, false);
+    return out;
+}
+
+Ciphertexts LinearEvaluator::SubNew(const Ciphertexts &ct, const Plaintext &pt) {
+    Ciphertexts out;
+    plain_sum("Sub", ct, pt, out, true);
+    return out;
+}
+
+Ciphertexts LinearEvaluator::MulNew(const Ciphertexts &ct, const Plaintext &pt) {
+    const uint64_t *words = limbs_for("MulNew", ct, pt);
+    lumen_set *set = nullptr;
+    check(lumen_mul_plain(Context(), ct.Handle(), words, &set), "lumen_mul_plain");
+    MetaData md = ct.Meta;
+    const uint64_t T = GetParameters().T;
+    md.Scale = MulMod(ct.Scale() % T, pt.Scale % T, T); // bgv: Scale_ct * Scale_pt
+    return Ciphertexts(Context(), set, md);
+}
+
+void LinearEvaluator::MulThenAdd(const Ciphertexts &ct, const Plaintext &pt, Ciphertexts &acc) {
+    const uint64_t *words = limbs_for("MulThenAdd", ct, pt);
+    need_set("MulThenAdd", acc);
+    const uint64_t T = GetParameters().T;
+    need_scales("MulThenAdd", acc.Scale(), MulMod(ct.Scale() % T, pt.Scale % T, T));
+    check(lumen_mul_plain_then_add(Context(), ct.Handle(), words, acc.Handle()), "lumen_mul_plain_then_add");
 }
 
 Plaintext ServerBFV::Encode(const std::vector<uint64_t> &values) const {

@@ -71,6 +71,7 @@ struct Parameters {
 struct Plaintext { // *rlwe.Plaintext: one polynomial, NTT domain, [level+1][N]
     std::vector<uint64_t> Value;
     int Level = 0;
+    uint64_t Scale = 1; // MetaData.Scale modulo T: Encoder.Encode of unscaled values leaves 1
 };
 
 class ServerBFV;
@@ -202,8 +203,51 @@ std::string MetaDataJSON(const MetaData &md, uint64_t plaintextModulus);
 // installs head = MetaData | LE64(2), poly_head = LE64(level+1), limb_head = LE64(N) on the backend
 void SetCiphertextFormat(ServerBFV &backend, const MetaData &md, int level);
 
+// The linear operations of the *bgv.Evaluator that both ServerBFV (fhe/bfv.go:13-21) and ClientBFV (bfv.go:60-81) embed,
+// on whole slices (include/lumenos_hip.h, "the evaluator's linear operations"): the calls fhe/ntt.go:27-236 and
+// vdec/batching.go:24-34 make.  One implementation over the owner's context; ServerBFV and ClientBFV inherit it.
+// The ...New forms return a new slice.  The forms with `out` write an existing slice of the result's shape -- which may
+// be one of the operands, as in backend.Add(batchCt, t, batchCt) -- or fill an empty one.  An operand of one ciphertext
+// meets every ciphertext of the other; operands of different levels give the lower level (Lattigo's min-level rule).
+// MetaData: the result takes the first operand's; Mul by a scalar keeps the scale; a plaintext product multiplies the
+// scales modulo T.  RECORDED DEVIATION: Add and Sub require equal Scale() and throw std::invalid_argument
+// naming both scales otherwise, where Lattigo would match the scales by a multiplication; MulThenAdd(ct, pt, acc)
+// requires acc.Scale() == ct.Scale() * pt.Scale mod T.  MulCounter() is the library's: Mul / MulNew by a scalar or a
+// plaintext count, Add, Sub and MulThenAdd do not (bfv.go:34-42 wraps Mul and MulNew alone).
+class LinearEvaluator {
+  public:
+    virtual ~LinearEvaluator() = default;
+    virtual lumen_ctx *Context() const = 0;
+    virtual const Parameters &GetParameters() const = 0;
+    virtual void check(int rc, const char *what) const = 0;
+    Ciphertexts AddNew(const Ciphertexts &a, const Ciphertexts &b);
+    void Add(const Ciphertexts &a, const Ciphertexts &b, Ciphertexts &out);
+    Ciphertexts SubNew(const Ciphertexts &a, const Ciphertexts &b);
+    void Sub(const Ciphertexts &a, const Ciphertexts &b, Ciphertexts &out);
+    // Evaluator.Add / Sub(ct, pt): c0 +- pt; pt at ct's level or above (its first limbs are taken), of ct's scale
+    Ciphertexts AddNew(const Ciphertexts &ct, const Plaintext &pt);
+    void Add(const Ciphertexts &ct, const Plaintext &pt, Ciphertexts &out);
+    Ciphertexts SubNew(const Ciphertexts &ct, const Plaintext &pt);
+    void Sub(const Ciphertexts &ct, const Plaintext &pt, Ciphertexts &out);
+    // Evaluator.Mul(ct, uint64): the scalar is w mod T, centred (the raw words of RootForwardUint64 go in as they are)
+    Ciphertexts MulNew(const Ciphertexts &ct, uint64_t w);
+    void Mul(const Ciphertexts &ct, uint64_t w, Ciphertexts &out);
+    // Evaluator.MulNew(ct, pt) (lumen_mul_plain): pt at ct's level or above
+    Ciphertexts MulNew(const Ciphertexts &ct, const Plaintext &pt);
+    // Evaluator.MulThenAdd(ct, uint64 | pt, acc): acc += ct * operand, in place; acc may not be ct
+    void MulThenAdd(const Ciphertexts &ct, uint64_t w, Ciphertexts &acc);
+    void MulThenAdd(const Ciphertexts &ct, const Plaintext &pt, Ciphertexts &acc);
+    // sum_t w[t] * in[t] for 1 to 8 slices of one scale, in one pass over the device (lumen_linear_combination)
+    Ciphertexts LinearCombinationNew(const std::vector<const Ciphertexts *> &in, const std::vector<uint64_t> &w);
+
+  private:
+    void finish(lumen_set *set, const MetaData &md, Ciphertexts &out);
+    const uint64_t *limbs_for(const char *what, const Ciphertexts &ct, const Plaintext &pt) const;
+    void plain_sum(const char *what, const Ciphertexts &ct, const Plaintext &pt, Ciphertexts &out, bool sub);
+};
+
 // fhe.ServerBFV (fhe/bfv.go:13-58): plaintext field + parameters + evaluator/encoder/encryptor
-class ServerBFV {
+class ServerBFV : public LinearEvaluator {
   public:
     // NewBackendBFV(plaintextField, params, pk, evk).  pk: [2][L][N] NTT domain; evk: Galois keys in
     // the layout of lumen_load_galois_key.
@@ -312,7 +356,7 @@ class ServerBFV {
 // [L+K][N], NTT domain, what lumen_load_secret_key takes) or GENERATED ON THE DEVICE (NewWithGeneratedSecret:
 // lumen_keygen_secret under a 32-byte seed from getrandom(2)); a client of the second kind is what fhe::KeyGenerator
 // and NewRingSwitchClient derive the public, relinearisation, Galois and ring-switch keys from.
-class ClientBFV {
+class ClientBFV : public LinearEvaluator { // (the reference's ClientBFV embeds an evaluator too: vdec.BatchCiphertexts runs on it)
   public:
     // NewClientBFV(plaintextField, paramsFHE, sk)
     ClientBFV(core::PrimeField *plaintextField, const Parameters &params, const std::vector<uint64_t> &sk, int device = 0);
@@ -326,6 +370,7 @@ class ClientBFV {
     const Parameters &GetParameters() const { return params_; }
     lumen_ctx *Context() const { return ctx_.get(); }
     int Device() const { return device_; }
+    int MulCounter() const; // the library's counter of this client's context
     void check(int rc, const char *what) const; // throws std::runtime_error with lumen_last_error
     // ClientBFV.CopyNew (bfv.go:96-98): the same key and tables, its own streams and scratch (lumen_ctx_clone); must
     // not outlive the client it was made from
