@@ -13,28 +13,12 @@
 #include <string>
 #include <vector>
 
-#include "../../lumenos_amd/host/fhe.hpp"
+#include "twin.hpp"
 
 using namespace lumenos;
 
-#define REQUIRE(cond, ...)                                       \
-    do {                                                         \
-        if (!(cond)) {                                           \
-            fprintf(stderr, "FAIL %s:%d: ", __FILE__, __LINE__); \
-            fprintf(stderr, __VA_ARGS__);                        \
-            fprintf(stderr, "\n");                               \
-            return 1;                                            \
-        }                                                        \
-    } while (0)
-
 static const uint64_t Modulus = 144115188075593729ull; // fhe/ligero_test.go:16, cmd/server/main.go:22
 static const int rhoInv = 2;
-
-static fhe::Parameters make_params(int LogN, int cols, int numQ) {
-    fhe::ParametersLiteral lit = fhe::GenerateBGVParamsForNTT(cols, LogN, Modulus);
-    while ((int)lit.LogQ.size() < numQ) lit.LogQ.push_back(56);
-    return fhe::Parameters::FromLiteral(lit);
-}
 
 // the server's whole answer to an uploaded witness, then the client's check of it; throws what Verify throws
 static fhe::Proof prove_and_open(fhe::ServerBFV &server, fhe::ClientBFV &client, fhe::LigeroCommitter &ligero,
@@ -88,13 +72,7 @@ static int e2e_mode(int argc, char **argv) {
             REQUIRE(!memcmp(&expanded[(size_t)j * 2 * L * N], &upload.C0[(size_t)j * L * N], L * N * 8), "c0 of column %d", j);
         printf("PASS ExpandSeeded = the client's EncryptColumnsNew under the same seeds, bit for bit\n");
     }
-    uint64_t z = 0;
-    while (z < 2) {
-        uint8_t b[8];
-        fhe::OsRandom(b, 8);
-        memcpy(&z, b, 8);
-        z %= Modulus;
-    }
+    const uint64_t z = random_point(Modulus);
     fhe::LigeroCommitter ligero = fhe::LigeroCommitter::NewLigeroCommitter(128, rows, cols, rhoInv);
     const uint64_t value = server->EvaluateColumns(columns, rows, cols, cols, z);
     core::Transcript refTranscript("demo");
@@ -139,12 +117,6 @@ static int e2e_mode(int argc, char **argv) {
 }
 
 int main(int argc, char **argv) {
-    try {
-        if (argc >= 2 && !strcmp(argv[1], "e2e")) return e2e_mode(argc, argv);
-    } catch (const std::exception &e) {
-        fprintf(stderr, "FAIL exception: %s\n", e.what());
-        return 1;
-    }
-    fprintf(stderr, "usage: test_encrypt_sk_host e2e <logN> <rows> <cols> <numQ>\n");
-    return 2;
+    return twin_main(argc, argv, "usage: test_encrypt_sk_host e2e <logN> <rows> <cols> <numQ>",
+                     {{"e2e", e2e_mode}});
 }

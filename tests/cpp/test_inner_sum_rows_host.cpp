@@ -14,19 +14,9 @@
 #include <string>
 #include <vector>
 
-#include "../../lumenos_amd/host/fhe.hpp"
+#include "twin.hpp"
 
 using namespace lumenos;
-
-#define REQUIRE(cond, ...)                                       \
-    do {                                                         \
-        if (!(cond)) {                                           \
-            fprintf(stderr, "FAIL %s:%d: ", __FILE__, __LINE__); \
-            fprintf(stderr, __VA_ARGS__);                        \
-            fprintf(stderr, "\n");                               \
-            return 1;                                            \
-        }                                                        \
-    } while (0)
 
 static const uint64_t Modulus = 144115188075593729ull; // fhe/ligero_test.go:16, cmd/server/main.go:22
 static const int rhoInv = 2;
@@ -81,13 +71,7 @@ static int e2e_mode(int argc, char **argv) {
     }
 
     // ---- the server (cmd/server/main.go:187-266), then the client (cmd/client/main.go:181-221)
-    uint64_t z = 0;
-    while (z < 2) {
-        uint8_t b[8];
-        fhe::OsRandom(b, 8);
-        memcpy(&z, b, 8);
-        z %= Modulus;
-    }
+    const uint64_t z = random_point(Modulus);
     fhe::LigeroCommitter ligero = fhe::LigeroCommitter::NewLigeroCommitter(128, rows, cols, rhoInv);
     auto commit = ligero.Commit(cts, *server, nullptr);
     core::Transcript transcript("demo");
@@ -146,12 +130,6 @@ static int e2e_mode(int argc, char **argv) {
 }
 
 int main(int argc, char **argv) {
-    try {
-        if (argc >= 2 && !strcmp(argv[1], "e2e")) return e2e_mode(argc, argv);
-    } catch (const std::exception &e) {
-        fprintf(stderr, "FAIL exception: %s\n", e.what());
-        return 1;
-    }
-    fprintf(stderr, "usage: test_inner_sum_rows_host e2e <logN> <rows> <cols> <numQ>\n");
-    return 2;
+    return twin_main(argc, argv, "usage: test_inner_sum_rows_host e2e <logN> <rows> <cols> <numQ>",
+                     {{"e2e", e2e_mode}});
 }

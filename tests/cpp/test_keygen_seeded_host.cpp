@@ -15,29 +15,13 @@
 #include <string>
 #include <vector>
 
-#include "../../lumenos_amd/host/fhe.hpp"
 #include "../../oracle/lo_common.h"
+#include "twin.hpp"
 
 using namespace lumenos;
 
-#define REQUIRE(cond, ...)                                       \
-    do {                                                         \
-        if (!(cond)) {                                           \
-            fprintf(stderr, "FAIL %s:%d: ", __FILE__, __LINE__); \
-            fprintf(stderr, __VA_ARGS__);                        \
-            fprintf(stderr, "\n");                               \
-            return 1;                                            \
-        }                                                        \
-    } while (0)
-
 static const uint64_t Modulus = 144115188075593729ull; // fhe/ligero_test.go:16, cmd/server/main.go:22
 static const int rhoInv = 2;
-
-static fhe::Parameters make_params(int LogN, int cols, int numQ) {
-    fhe::ParametersLiteral lit = fhe::GenerateBGVParamsForNTT(cols, LogN, Modulus);
-    while ((int)lit.LogQ.size() < numQ) lit.LogQ.push_back(56);
-    return fhe::Parameters::FromLiteral(lit);
-}
 
 // a of limb m (modulus q) of the entry with sample index I under aSeed: stream 16 + m as little-endian 64-bit words,
 // attempt t of coefficient k is word t * N + k, the first x < 2^64 - (2^64 mod q) is kept as x mod q
@@ -150,13 +134,7 @@ static int e2e_mode(int argc, char **argv) {
     std::vector<uint64_t> columns((size_t)cols * rows);
     for (int j = 0; j < cols; j++)
         for (int i = 0; i < rows; i++) columns[(size_t)j * rows + i] = matrix[(size_t)i * cols + j];
-    uint64_t z = 0;
-    while (z < 2) {
-        uint8_t b[8];
-        fhe::OsRandom(b, 8);
-        memcpy(&z, b, 8);
-        z %= Modulus;
-    }
+    const uint64_t z = random_point(Modulus);
     fhe::LigeroCommitter ligero = fhe::LigeroCommitter::NewLigeroCommitter(128, rows, cols, rhoInv);
     fhe::Ciphertexts cts = server->EncryptColumnsNew(columns, rows, cols);
     fhe::Ciphertexts pair = server->EncryptColumnsNew(std::vector<uint64_t>(columns.begin(), columns.begin() + 2 * (size_t)rows), rows, 2);
@@ -211,12 +189,6 @@ static int e2e_mode(int argc, char **argv) {
 }
 
 int main(int argc, char **argv) {
-    try {
-        if (argc >= 2 && !strcmp(argv[1], "e2e")) return e2e_mode(argc, argv);
-    } catch (const std::exception &e) {
-        fprintf(stderr, "FAIL exception: %s\n", e.what());
-        return 1;
-    }
-    fprintf(stderr, "usage: test_keygen_seeded_host e2e <logN> <rows> <cols> <numQ>\n");
-    return 2;
+    return twin_main(argc, argv, "usage: test_keygen_seeded_host e2e <logN> <rows> <cols> <numQ>",
+                     {{"e2e", e2e_mode}});
 }

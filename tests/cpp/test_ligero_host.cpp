@@ -15,24 +15,14 @@
 #include <memory>
 #include <vector>
 
-#include "../../lumenos_amd/host/fhe.hpp"
 #include "../../oracle/lo_common.h"
+#include "twin.hpp"
 
 extern "C" {
 void lo_decrypt_phase(const lo_params *p, const uint64_t *sk, const uint64_t *ct, uint32_t nl, uint64_t *phase);
 }
 
 using namespace lumenos;
-
-#define REQUIRE(cond, ...)                          \
-    do {                                            \
-        if (!(cond)) {                              \
-            fprintf(stderr, "FAIL %s:%d: ", __FILE__, __LINE__); \
-            fprintf(stderr, __VA_ARGS__);           \
-            fprintf(stderr, "\n");                  \
-            return 1;                               \
-        }                                           \
-    } while (0)
 
 static const uint64_t Modulus = 144115188075593729ull; // fhe/ligero_test.go:16
 static const int rhoInv = 2;

@@ -13,28 +13,12 @@
 #include <string>
 #include <vector>
 
-#include "../../lumenos_amd/host/fhe.hpp"
+#include "twin.hpp"
 
 using namespace lumenos;
 
-#define REQUIRE(cond, ...)                                       \
-    do {                                                         \
-        if (!(cond)) {                                           \
-            fprintf(stderr, "FAIL %s:%d: ", __FILE__, __LINE__); \
-            fprintf(stderr, __VA_ARGS__);                        \
-            fprintf(stderr, "\n");                               \
-            return 1;                                            \
-        }                                                        \
-    } while (0)
-
 static const uint64_t T = 144115188075593729ull; // cmd/server/main.go:22, fhe/ligero_test.go:16
 static const int COLS = 8;
-
-static std::vector<uint64_t> decrypt(fhe::ClientBFV &client, const fhe::Ciphertexts &cts, int n) {
-    std::vector<uint64_t> out((size_t)cts.Len() * n);
-    client.check(lumen_decrypt(client.Context(), cts.Handle(), cts.Scale(), (uint32_t)n, out.data()), "lumen_decrypt");
-    return out;
-}
 
 // matrix[a:a+1]: a view of one ciphertext (destroyed before its parent)
 static fhe::Ciphertexts view_of(fhe::LinearEvaluator &ev, const fhe::Ciphertexts &set, int i) {
@@ -83,16 +67,7 @@ static int e2e_mode(int argc, char **argv) {
     std::unique_ptr<fhe::ClientBFV> client = fhe::ClientBFV::NewWithGeneratedSecret(&ptField, params);
     fhe::KeyGenerator kgen(*client);
     const fhe::KeySet keys = kgen.GenKeySetNew(rows, 0);
-    std::vector<uint64_t> x((size_t)COLS * rows);
-    {
-        std::vector<uint8_t> rnd(x.size() * 8);
-        fhe::OsRandom(rnd.data(), rnd.size());
-        for (size_t i = 0; i < x.size(); i++) {
-            uint64_t a;
-            memcpy(&a, &rnd[i * 8], 8);
-            x[i] = a % T;
-        }
-    }
+    const std::vector<uint64_t> x = random_values((size_t)COLS * rows, T);
     const fhe::SeededCiphertexts up = client->EncryptColumnsSeeded(x, rows, COLS);
     std::unique_ptr<fhe::ServerBFV> server = fhe::ServerBFV::NewFromKeySet(&ptField, params, rows, keys);
     fhe::Ciphertexts cx = server->ExpandSeeded(up);
@@ -194,12 +169,6 @@ static int e2e_mode(int argc, char **argv) {
 }
 
 int main(int argc, char **argv) {
-    try {
-        if (argc >= 2 && !strcmp(argv[1], "e2e")) return e2e_mode(argc, argv);
-    } catch (const std::exception &e) {
-        fprintf(stderr, "FAIL exception: %s\n", e.what());
-        return 1;
-    }
-    fprintf(stderr, "usage: test_linear_host e2e <logN> <rows> <cols>\n");
-    return 2;
+    return twin_main(argc, argv, "usage: test_linear_host e2e <logN> <rows> <cols>",
+                     {{"e2e", e2e_mode}});
 }

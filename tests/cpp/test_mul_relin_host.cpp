@@ -13,19 +13,9 @@
 #include <string>
 #include <vector>
 
-#include "../../lumenos_amd/host/fhe.hpp"
+#include "twin.hpp"
 
 using namespace lumenos;
-
-#define REQUIRE(cond, ...)                                       \
-    do {                                                         \
-        if (!(cond)) {                                           \
-            fprintf(stderr, "FAIL %s:%d: ", __FILE__, __LINE__); \
-            fprintf(stderr, __VA_ARGS__);                        \
-            fprintf(stderr, "\n");                               \
-            return 1;                                            \
-        }                                                        \
-    } while (0)
 
 static const uint64_t T = 0x3ee0001ull;
 
@@ -36,14 +26,6 @@ static fhe::Ciphertexts rescale_to(fhe::ServerBFV &server, const fhe::Ciphertext
     fhe::MetaData md = in.Meta;
     md.Scale = fhe::RescaledScale(server.GetParameters(), in.Scale(), in.Level(), level);
     return fhe::Ciphertexts(server.Context(), out, md);
-}
-
-// the client's Decryptor + Encoder.Decode on a set the server produced (same GPU): [count][rows]
-static std::vector<uint64_t> decrypt(fhe::ServerBFV &server, fhe::ClientBFV &client, const fhe::Ciphertexts &cts, int rows) {
-    server.check(lumen_sync(server.Context()), "lumen_sync");
-    std::vector<uint64_t> out((size_t)cts.Len() * rows);
-    client.check(lumen_decrypt(client.Context(), cts.Handle(), cts.Scale(), (uint32_t)rows, out.data()), "lumen_decrypt");
-    return out;
 }
 
 static int e2e_mode(int argc, char **argv) {
@@ -60,16 +42,7 @@ static int e2e_mode(int argc, char **argv) {
     const fhe::KeySet keys = kgen.GenKeySetNew(rows, LUMEN_KEY_MONTGOMERY, true);
     REQUIRE(!keys.Rlk.empty() && keys.Rlk.size() == keys.GaloisKeys.at(0).size(), "the key set carries no relinearisation key");
     REQUIRE(kgen.GenKeySetNew(rows, 0).Rlk.empty(), "GenKeySetNew(rows, flags) grew a relinearisation key");
-    std::vector<uint64_t> x((size_t)count * rows), y((size_t)count * rows);
-    {
-        std::vector<uint8_t> rnd((x.size() + y.size()) * 8);
-        fhe::OsRandom(rnd.data(), rnd.size());
-        for (size_t i = 0; i < x.size(); i++) {
-            uint64_t a, b;
-            memcpy(&a, &rnd[i * 16], 8), memcpy(&b, &rnd[i * 16 + 8], 8);
-            x[i] = a % T, y[i] = b % T;
-        }
-    }
+    const std::vector<uint64_t> x = random_values((size_t)count * rows, T), y = random_values((size_t)count * rows, T);
     const fhe::SeededCiphertexts upX = client->EncryptColumnsSeeded(x, rows, count), upY = client->EncryptColumnsSeeded(y, rows, count);
 
     // ---- the server: the posted key set, no secret
@@ -132,12 +105,6 @@ static int e2e_mode(int argc, char **argv) {
 }
 
 int main(int argc, char **argv) {
-    try {
-        if (argc >= 2 && !strcmp(argv[1], "e2e")) return e2e_mode(argc, argv);
-    } catch (const std::exception &e) {
-        fprintf(stderr, "FAIL exception: %s\n", e.what());
-        return 1;
-    }
-    fprintf(stderr, "usage: test_mul_relin_host e2e <logN> <rows> <count>\n");
-    return 2;
+    return twin_main(argc, argv, "usage: test_mul_relin_host e2e <logN> <rows> <count>",
+                     {{"e2e", e2e_mode}});
 }

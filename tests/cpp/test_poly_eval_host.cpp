@@ -15,20 +15,10 @@
 #include <string>
 #include <vector>
 
-#include "../../lumenos_amd/host/fhe.hpp"
 #include "../../oracle/lo_common.h"
+#include "twin.hpp"
 
 using namespace lumenos;
-
-#define REQUIRE(cond, ...)                                       \
-    do {                                                         \
-        if (!(cond)) {                                           \
-            fprintf(stderr, "FAIL %s:%d: ", __FILE__, __LINE__); \
-            fprintf(stderr, __VA_ARGS__);                        \
-            fprintf(stderr, "\n");                               \
-            return 1;                                            \
-        }                                                        \
-    } while (0)
 
 static const uint64_t Modulus = 144115188075593729ull; // fhe/ligero_test.go:16, cmd/server/main.go:22
 static const int rhoInv = 2;
@@ -85,13 +75,7 @@ static int e2e_mode(int argc, char **argv) {
     for (int j = 0; j < cols; j++)
         for (int i = 0; i < rows; i++) columns[(size_t)j * rows + i] = matrix[(size_t)i * cols + j];
     // the client's point: random, != 0 and != 1 (the twin of TestLigeroE2E proves at 1 only)
-    uint64_t z = 0;
-    while (z < 2) {
-        uint8_t b[8];
-        fhe::OsRandom(b, 8);
-        memcpy(&z, b, 8);
-        z %= Modulus;
-    }
+    const uint64_t z = random_point(Modulus);
     printf("point z = %llu\n", (unsigned long long)z);
 
     fhe::Ciphertexts cts = server.EncryptColumnsNew(columns, rows, cols);
@@ -156,13 +140,6 @@ static int e2e_mode(int argc, char **argv) {
 }
 
 int main(int argc, char **argv) {
-    try {
-        if (argc > 1 && !strcmp(argv[1], "host")) return host_mode(argc, argv);
-        if (argc > 1 && !strcmp(argv[1], "e2e")) return e2e_mode(argc, argv);
-    } catch (const std::exception &e) {
-        fprintf(stderr, "FAIL: %s\n", e.what());
-        return 1;
-    }
-    fprintf(stderr, "usage: test_poly_eval_host host|e2e ...\n");
-    return 2;
+    return twin_main(argc, argv, "usage: test_poly_eval_host host|e2e ...",
+                     {{"host", host_mode}, {"e2e", e2e_mode}});
 }

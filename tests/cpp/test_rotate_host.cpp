@@ -14,29 +14,11 @@
 #include <string>
 #include <vector>
 
-#include "../../lumenos_amd/host/fhe.hpp"
+#include "twin.hpp"
 
 using namespace lumenos;
 
-#define REQUIRE(cond, ...)                                       \
-    do {                                                         \
-        if (!(cond)) {                                           \
-            fprintf(stderr, "FAIL %s:%d: ", __FILE__, __LINE__); \
-            fprintf(stderr, __VA_ARGS__);                        \
-            fprintf(stderr, "\n");                               \
-            return 1;                                            \
-        }                                                        \
-    } while (0)
-
 static const uint64_t T = 0x3ee0001ull;
-
-// the client's Decryptor + Encoder.Decode on a set the server produced (same GPU): [count][N]
-static std::vector<uint64_t> decrypt(fhe::ServerBFV &server, fhe::ClientBFV &client, const fhe::Ciphertexts &cts, int n) {
-    server.check(lumen_sync(server.Context()), "lumen_sync");
-    std::vector<uint64_t> out((size_t)cts.Len() * n);
-    client.check(lumen_decrypt(client.Context(), cts.Handle(), cts.Scale(), (uint32_t)n, out.data()), "lumen_decrypt");
-    return out;
-}
 
 // what a rotation by k (swap: then the row swap) makes of the columns x, [count][N]
 static std::vector<uint64_t> permuted(const std::vector<uint64_t> &x, int N, long k, bool swap) {
@@ -69,16 +51,7 @@ static int e2e_mode(int argc, char **argv) {
                                        params.GaloisElementForRowRotation()};
     const std::map<uint64_t, std::vector<uint64_t>> gks = kgen.GenGaloisKeysNew(els, LUMEN_KEY_MONTGOMERY);
     REQUIRE(gks.size() == els.size(), "GenGaloisKeysNew returned %zu keys for %zu elements", gks.size(), els.size());
-    std::vector<uint64_t> x((size_t)count * N);
-    {
-        std::vector<uint8_t> rnd(x.size() * 8);
-        fhe::OsRandom(rnd.data(), rnd.size());
-        for (size_t i = 0; i < x.size(); i++) {
-            uint64_t a;
-            memcpy(&a, &rnd[i * 8], 8);
-            x[i] = a % T;
-        }
-    }
+    const std::vector<uint64_t> x = random_values((size_t)count * N, T);
     const fhe::SeededCiphertexts up = client->EncryptColumnsSeeded(x, N, count);
 
     // ---- the server: the posted key set, the rotations' keys beside it, no secret
@@ -146,12 +119,6 @@ static int e2e_mode(int argc, char **argv) {
 }
 
 int main(int argc, char **argv) {
-    try {
-        if (argc >= 2 && !strcmp(argv[1], "e2e")) return e2e_mode(argc, argv);
-    } catch (const std::exception &e) {
-        fprintf(stderr, "FAIL exception: %s\n", e.what());
-        return 1;
-    }
-    fprintf(stderr, "usage: test_rotate_host e2e <logN> <rows> <count>\n");
-    return 2;
+    return twin_main(argc, argv, "usage: test_rotate_host e2e <logN> <rows> <count>",
+                     {{"e2e", e2e_mode}});
 }

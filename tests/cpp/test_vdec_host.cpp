@@ -14,19 +14,9 @@
 #include <string>
 #include <vector>
 
-#include "../../lumenos_amd/host/fhe.hpp"
+#include "twin.hpp"
 
 using namespace lumenos;
-
-#define REQUIRE(cond, ...)                                       \
-    do {                                                         \
-        if (!(cond)) {                                           \
-            fprintf(stderr, "FAIL %s:%d: ", __FILE__, __LINE__); \
-            fprintf(stderr, __VA_ARGS__);                        \
-            fprintf(stderr, "\n");                               \
-            return 1;                                            \
-        }                                                        \
-    } while (0)
 
 static const uint64_t Modulus = 0x3ee0001ull; // ring_switch_test.go:17, the vdec tests' plaintext modulus
 static const int rhoInv = 2;
@@ -150,13 +140,6 @@ static int e2e_mode(int argc, char **argv) {
 }
 
 int main(int argc, char **argv) {
-    try {
-        if (argc >= 2 && !strcmp(argv[1], "host")) return host_mode(argc, argv);
-        if (argc >= 2 && !strcmp(argv[1], "e2e")) return e2e_mode(argc, argv);
-    } catch (const std::exception &e) {
-        fprintf(stderr, "FAIL exception: %s\n", e.what());
-        return 1;
-    }
-    fprintf(stderr, "usage: test_vdec_host host <name> <rows> <cols> <T> | e2e <logN> <rows> <cols>\n");
-    return 2;
+    return twin_main(argc, argv, "usage: test_vdec_host host <name> <rows> <cols> <T> | e2e <logN> <rows> <cols>",
+                     {{"host", host_mode}, {"e2e", e2e_mode}});
 }

@@ -22,7 +22,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import numpy as np  # noqa: E402
 
-from helpers import T_REF, make_context, make_params, random_cts  # noqa: E402
+from helpers import DEGREES, T_REF, T_SMALL, make_context, make_params, random_cts  # noqa: E402
 from oracle.loader import Oracle  # noqa: E402
 
 
@@ -148,14 +148,13 @@ def one_case(o, rng, case):
     ctx.close()
     # ring switch on the gadget path the number of special primes selects (a context of its own: K = 0 too)
     kp = int(rng.choice([0, 1, 2]))
-    T_small = 0x3EE0001
-    P2 = make_params(o, log_n, int(rng.integers(1, 4)), num_p=kp, T=T_small)
+    P2 = make_params(o, log_n, int(rng.integers(1, 4)), num_p=kp, T=T_SMALL)
     P2.seed(int(rng.integers(1, 2**31)))
     ctx2 = make_context(P2)
     sk2 = P2.keygen_secret()
     pk2 = P2.keygen_public(sk2)
-    small = int(rng.choice([x for x in (8, 10, 11, 12, 13, 14) if x <= log_n]))
-    ctr = np.stack([P2.rescale_to_level1(P2.encrypt(pk2, P2.encode(rng.integers(0, T_small, size=P2.N, dtype=np.uint64))))
+    small = int(rng.choice([x for x in DEGREES if x <= log_n]))
+    ctr = np.stack([P2.rescale_to_level1(P2.encrypt(pk2, P2.encode(rng.integers(0, T_SMALL, size=P2.N, dtype=np.uint64))))
                     for _ in range(2)])
     sks = P2.keygen_secret_small(small)
     key = P2.keygen_ringswitch(sk2, sks, small)

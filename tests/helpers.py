@@ -8,16 +8,22 @@ import numpy as np
 from oracle.loader import Params
 
 T_REF = 144115188075593729  # cmd/server/main.go:22, fhe/ligero_test.go:16
+T_SMALL = 0x3EE0001  # TestRingSwitch (ring_switch_test.go:17); the plaintext modulus of the reference's vdec tests
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+DEGREES = (8, 10, 11, 12, 13, 14)  # LM_FOR_EACH_LOGN (lm_ntt_plan.h): test_degree_matrix.py pins the tuple to the macro
+SPLIT_DEGREES = (15,)  # LM_FOR_EACH_SPLIT_LOGN (pinned by test_ntt_split_model.py); their GPU cases: test_degree15.py
+CHAINS = ("reference", "bound")
 
 
 def build_cpp_twin(name, with_oracle=True):
     """tests/cpp/<name>.cpp -> tests/cpp/<name>, linked against the host mirror, the HIP library and (with_oracle) the
-    CPU oracle, each built first; rebuilt only when the source or one of those libraries is newer."""
+    CPU oracle, each built first; rebuilt only when the source, twin.hpp or one of those libraries is newer."""
     from lumenos_amd import _build
     host = _build.build_host()
     src, exe = os.path.join(ROOT, "tests", "cpp", name + ".cpp"), os.path.join(ROOT, "tests", "cpp", name)
-    dirs, libs, deps = [os.path.dirname(host), os.path.dirname(_build.LIB)], ["-llumenos_host", "-llumenos_hip"], [src, host]
+    dirs, libs = [os.path.dirname(host), os.path.dirname(_build.LIB)], ["-llumenos_host", "-llumenos_hip"]
+    deps = [src, os.path.join(ROOT, "tests", "cpp", "twin.hpp"), host]
     if with_oracle:
         from oracle import loader
         loader.build()
@@ -29,6 +35,19 @@ def build_cpp_twin(name, with_oracle=True):
     subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", src, "-o", exe] + ["-L" + d for d in dirs] + libs +
                           ["-Wl,-rpath," + ":".join(dirs)])
     return exe
+
+
+def twin(name, *args, timeout=600, with_oracle=True, env=None):
+    """tests/cpp/<name>, built if need be, run with `args`: the CompletedProcess, output captured as text"""
+    exe = build_cpp_twin(name, with_oracle=with_oracle)
+    return subprocess.run([exe] + [str(a) for a in args], capture_output=True, text=True, timeout=timeout, env=env)
+
+
+def twin_usage(name, with_oracle=True):
+    """The twin builds against the mirror (twin() builds it, and runs what it built), and without a mode it prints its
+    usage line and exits with status 2.  For the twins whose usage line begins with the e2e mode."""
+    out = twin(name, timeout=60, with_oracle=with_oracle)
+    assert out.returncode == 2 and f"usage: {name} e2e" in out.stderr
 
 
 def gen_primes(oracle, bits, n, two_n, exclude=(T_REF,)):
@@ -51,6 +70,39 @@ def make_params(oracle, log_n, num_q, num_p=2, T=T_REF):
 def make_context(P, device=0):
     from lumenos_amd.hip import Context
     return Context(P.logN, P.moduli[:P.L], P.moduli[P.L:], P.psi, P.T, device=device)
+
+
+def bound_chain(oracle, log_n, num_q, num_p, T=T_REF):
+    """num_q + num_p primes == 1 mod 2N directly below the context's bound (2^64 - 1) // (3 log_n + 8)."""
+    qmax = (2**64 - 1) // (3 * log_n + 8)
+    pr = _ntt_primes_near(qmax, 2 << log_n, num_q + num_p)
+    assert all(qmax - (217 << (log_n + 1)) < q <= qmax for q in pr), pr
+    return Params.from_moduli(oracle, log_n, pr[:num_q], pr[num_q:], T)
+
+
+def canonical(P, x):
+    """every word of x[..., l, :] below the chain's modulus l: [count][2][nl][N] sets and key-shaped arrays alike"""
+    return all(int(x[..., l, :].max()) < P.moduli[l] for l in range(x.shape[-2]))
+
+
+def bitrev(x, bits):
+    """the low `bits` bits of every word of the array x, reversed"""
+    r = np.zeros_like(x)
+    for b in range(bits):
+        r |= ((x >> np.uint64(b)) & np.uint64(1)) << np.uint64(bits - 1 - b)
+    return r
+
+
+def both_routes(ctx, switch, call, default=1):
+    """(switch on, switch off) of the same call; the context is left at `default`"""
+    assert ctx.set_tuning(switch, 1) is None
+    try:
+        on = call()
+        ctx.set_tuning(switch, 0)
+        off = call()
+    finally:
+        ctx.set_tuning(switch, default)
+    return on, off
 
 
 def random_cts(P, count, nl, seed):

@@ -15,66 +15,29 @@ import pytest
 import inner_sum_model as ism
 import keygen_model as km
 import mul_relin_model as mrm
-from helpers import T_REF, _adversarial_cts, _ntt_primes_near, make_context, make_params, random_cts
-from oracle.loader import Params
+from cells import KeyedCell
+from helpers import CHAINS, T_REF, _adversarial_cts, bound_chain, canonical, make_params, random_cts
 
 gpu = pytest.mark.gpu
 
 LOG_N = 15
 N = 1 << LOG_N
-CHAINS = ("reference", "bound")
 KEY_SEED = bytes(range(32))
 # the defaults of lm_tuning (lm_common.h)
 DEFAULTS = {"LUMEN_KS_FUSED_DIGITS": -1, "LUMEN_KS_CLOSE_FUSED": 1, "LUMEN_MODUP_TGROUP": 3, "LUMEN_MODDOWN_TGROUP": 1,
             "LUMEN_KS_BATCH": 64, "LUMEN_KS_LANES": 0}
 
 
-def _canonical(P, got):
-    return all(int(got[..., l, :].max()) < P.moduli[l] for l in range(got.shape[-2]))
-
-
-class _Cell:
-    """One chain: parameters, a secret, a context, three three-limb ciphertexts; Galois keys are generated by the oracle
-    and loaded at their first use"""
+class _Cell(KeyedCell):
+    """One chain: parameters, a secret, a context, three three-limb ciphertexts"""
 
     def __init__(self, oracle, chain):
         self.chain = chain
-        if chain == "reference":
-            self.P = P = make_params(oracle, LOG_N, 3)
-        else:
-            qmax = (2**64 - 1) // (3 * LOG_N + 8)
-            pr = _ntt_primes_near(qmax, 2 << LOG_N, 5)
-            assert all(qmax - (217 << (LOG_N + 1)) < q <= qmax and q % (1 << 16) == 1 for q in pr), pr
-            self.P = P = Params.from_moduli(oracle, LOG_N, pr[:3], pr[3:], T_REF)
-        assert (P.L, P.K, P.N) == (3, 2, N)
-        P.seed(1500 + len(chain))
-        self.sk = P.keygen_secret()
-        self.ctx = make_context(P)
+        P = make_params(oracle, LOG_N, 3) if chain == "reference" else bound_chain(oracle, LOG_N, 3, 2)
+        assert (P.L, P.K, P.N) == (3, 2, N) and all(q % (1 << 16) == 1 for q in P.moduli), P.moduli
+        super().__init__(P, 1500 + len(chain))
         self.cts = random_cts(P, 3, 3, seed=15) if chain == "reference" else _adversarial_cts(P, 3, seed=15)
         self.cts.setflags(write=False)
-        self.evks, self._want = {}, {}
-
-    def key(self, g):
-        if g not in self.evks:
-            self.evks[g] = self.P.keygen_galois(self.sk, g)
-            self.ctx.load_galois_key(g, self.evks[g])
-        return self.evks[g]
-
-    __call__ = key  # the key source tests/inner_sum_model.py takes
-
-    def keys(self, gl):
-        return [self.key(g) for g in gl]
-
-    def at(self, nl):
-        return np.ascontiguousarray(self.cts[:, :, :nl])
-
-    def cached(self, name, fn):
-        if name not in self._want:
-            w = fn()
-            if isinstance(w, np.ndarray):
-                w.setflags(write=False)
-            self._want[name] = w
-        return self._want[name]
 
     def rotation(self, g):
         return self.cached(("rot", g), lambda: np.stack([self.P.automorphism(c, g, self.key(g)) for c in self.cts]))
@@ -92,7 +55,7 @@ class _Cell:
 def cell(request, oracle):
     c = _Cell(oracle, request.param)
     yield c
-    c.ctx.close()
+    c.close()
 
 
 def _ntt_of(P, cts, inverse):
@@ -165,7 +128,7 @@ def test_inner_sum(cell):
     want = cell.cached("inner4", lambda: np.stack([P.inner_sum(c, 4, evks) for c in cell.cts]))
     got = ctx.inner_sum(ctx.upload(cell.cts), 4).download()
     assert np.array_equal(got, want)
-    assert _canonical(P, got)
+    assert canonical(P, got)
 
 
 @gpu
@@ -184,7 +147,7 @@ def test_inner_sum_at_level(cell, nl):
     want = np.stack([P.inner_sum(c, 4, evks) for c in cell.at(nl)])
     got = ctx.inner_sum_at_level(ctx.upload(cell.at(nl)), 4).download()
     assert np.array_equal(got, want)
-    assert _canonical(P, got)
+    assert canonical(P, got)
 
 
 @gpu
@@ -216,7 +179,7 @@ def test_inner_sum_general_one_lazy_term(cell):
     want = np.stack([ism.inner_sum(P, c, 1, 3, cell) for c in cts])
     got = ctx.inner_sum_general(ctx.upload(cts), 1, 3).download()
     assert np.array_equal(got, want)
-    assert _canonical(P, got)
+    assert canonical(P, got)
 
 
 # ------------------------------------------------------------------ rotations
@@ -227,7 +190,7 @@ def test_rotate_columns_by_one(cell):
     assert g == 5
     got = ctx.rotate_columns(ctx.upload(cell.cts), 1).download()
     assert np.array_equal(got, cell.rotation(g))
-    assert _canonical(cell.P, got)
+    assert canonical(cell.P, got)
 
 
 @gpu
@@ -240,7 +203,7 @@ def test_rotate_rows_swaps_the_halves(cell):
     want = cell.rotation(g)
     got = ctx.rotate_rows(ctx.upload(cell.cts)).download()
     assert np.array_equal(got, want)
-    assert _canonical(P, got)
+    assert canonical(P, got)
 
 
 @gpu
@@ -253,7 +216,7 @@ def test_automorphism(cell, g):
     want = cell.rotation(g)
     got = ctx.automorphism(ctx.upload(cell.cts), g).download()
     assert np.array_equal(got, want)
-    assert _canonical(P, got)
+    assert canonical(P, got)
 
 
 @gpu
@@ -294,7 +257,7 @@ def test_mul_relin(cell):
     assert got.shape == (2, 2, 3, N)
     for c in range(2):
         assert np.array_equal(got[c], mrm.relinearise(P, want_d[c], rlk)), c
-    assert _canonical(P, got)
+    assert canonical(P, got)
 
 
 # ------------------------------------------------------------------ encode and commit

@@ -11,14 +11,11 @@ import re
 import numpy as np
 import pytest
 
-from helpers import T_REF, _adversarial_cts, _ntt_primes_near, make_context, make_params, random_cts
+from cells import KeyedCell
+from helpers import CHAINS, DEGREES, T_REF, T_SMALL, _adversarial_cts, bound_chain, make_context, make_params, random_cts
 from oracle.loader import Params
 
 gpu = pytest.mark.gpu
-
-DEGREES = (8, 10, 11, 12, 13, 14)
-CHAINS = ("reference", "bound")
-T_SMALL = 0x3EE0001  # TestRingSwitch (ring_switch_test.go:17)
 
 
 # ------------------------------------------------------------------ A. the degree list is pinned
@@ -35,42 +32,28 @@ def test_instantiated_degrees_are_the_tested_degrees():
 
 
 # ------------------------------------------------------------------ B. every operation at every degree, two chains
-def _bound_chain(oracle, log_n, num_q, num_p, T=T_REF):
-    """num_q + num_p primes == 1 mod 2N directly below the context's bound (2^64 - 1) // (3 log_n + 8)."""
-    pr = _ntt_primes_near((2**64 - 1) // (3 * log_n + 8), 2 << log_n, num_q + num_p)
-    return Params.from_moduli(oracle, log_n, pr[:num_q], pr[num_q:], T)
-
-
 def _rescaled(P, ct, target):
     while ct.shape[1] > target:
         ct = P.rescale(ct)
     return ct
 
 
-class _Cell:
+class _Cell(KeyedCell):
     """One (degree, chain): L = 5, K = 2, keys of an InnerSum of 16, public and secret key, encoder tables."""
     n = 16
 
     def __init__(self, oracle, log_n, chain):
         from lumenos_amd import params as lp
         self.chain, self.log_n = chain, log_n
-        self.P = P = make_params(oracle, log_n, 5) if chain == "reference" else _bound_chain(oracle, log_n, 5, 2)
+        P = make_params(oracle, log_n, 5) if chain == "reference" else bound_chain(oracle, log_n, 5, 2)
         assert (P.L, P.K) == (5, 2)
-        if chain == "bound":
-            qmax = (2**64 - 1) // (3 * log_n + 8)
-            assert all(qmax - (217 << (log_n + 1)) < q <= qmax for q in P.moduli), P.moduli
-        P.seed(1000 * log_n + len(chain))
-        self.sk = P.keygen_secret()
+        super().__init__(P, 1000 * log_n + len(chain))
         self.pk = P.keygen_public(self.sk)
         self.gl = P.inner_sum_galois_elements(self.n)
-        self.evks = [P.keygen_galois(self.sk, g) for g in self.gl]
-        self.ctx = ctx = make_context(P)
-        for g, e in zip(self.gl, self.evks):
-            ctx.load_galois_key(g, e)
-        ctx.load_public_key(self.pk)
-        ctx.load_secret_key(self.sk)
-        ctx.encoder_set(lp.encoder_psi(T_REF, log_n))
-        self._inner = None
+        self.sum_keys = self.keys(self.gl)
+        self.ctx.load_public_key(self.pk)
+        self.ctx.load_secret_key(self.sk)
+        self.ctx.encoder_set(lp.encoder_psi(T_REF, log_n))
 
     def inputs(self, seed):
         """Three five-limb ciphertexts.  Bound chain: rows 0 and 1 are the adversarial patterns (all q-1, alternating,
@@ -81,17 +64,17 @@ class _Cell:
 
     def inner_sum_case(self):
         """(inputs, the oracle's InnerSum of them): shared by the three forced digit splits"""
-        if self._inner is None:
+        def make():
             cts = self.inputs(seed=160 + self.log_n)
-            self._inner = cts, np.stack([self.P.inner_sum(c, self.n, self.evks) for c in cts])
-        return self._inner
+            return cts, np.stack([self.P.inner_sum(c, self.n, self.sum_keys) for c in cts])
+        return self.cached("inner", make)
 
 
 @pytest.fixture(scope="module", params=list(itertools.product(DEGREES, CHAINS)), ids=lambda p: f"logn{p[0]}-{p[1]}")
 def cell(request, oracle):
     c = _Cell(oracle, *request.param)
     yield c
-    c.ctx.close()
+    c.close()
 
 
 @gpu
@@ -142,7 +125,7 @@ def test_matrix_inner_sum(cell):
     cts = cell.inputs(seed=71 + cell.log_n)
     pt = P.encode(np.random.default_rng(cell.log_n).integers(0, 2**63, size=cell.n, dtype=np.uint64))
     got = ctx.matrix_inner_sum(ctx.upload(cts), pt, cell.n).download()
-    assert np.array_equal(got, P.matrix_inner_sum(cts, pt, cell.n, cell.evks))
+    assert np.array_equal(got, P.matrix_inner_sum(cts, pt, cell.n, cell.sum_keys))
 
 
 @gpu
@@ -212,7 +195,7 @@ def test_lazy_accumulator_at_the_modulus_bound_every_degree(oracle, log_n, nq, n
     """test_lazy_accumulator_at_the_modulus_bound (test_gpu_parity.py) over DEGREES: the InnerSum accumulator's ways out
     -- L = 3 (the single-limb rescale kernels read the lazy words), L <= 2 (k_acc_canon) and lumen_inner_sum
     (k_acc_canon) -- with moduli right under each degree's own bound and all-(q-1) rows among the inputs."""
-    P = _bound_chain(oracle, log_n, nq, npr)
+    P = bound_chain(oracle, log_n, nq, npr)
     P.seed(11)
     sk = P.keygen_secret()
     ctx = make_context(P)
@@ -241,7 +224,7 @@ def test_ring_switch_at_the_modulus_bound(oracle, log_n, num_p):
     hybrid digit; 1: base-2^13 digits + ModDown; 0: no ModDown), into 2^8 and into the degree itself (k_rs_digit_ntt,
     k_rs_moddown): bit-exact vs the oracle for real encryptions and for the adversarial rows, and the real ones decrypt
     under the small key to the sub-ring coefficients of the input's plaintext."""
-    P = _bound_chain(oracle, log_n, 3, num_p, T=T_SMALL)
+    P = bound_chain(oracle, log_n, 3, num_p, T=T_SMALL)
     P.seed(log_n * 10 + num_p)
     sk = P.keygen_secret()
     pk = P.keygen_public(sk)
@@ -270,7 +253,7 @@ def test_ring_switch_at_the_modulus_bound(oracle, log_n, num_p):
 
 
 # ------------------------------------------------------------------ C. the 2^13 and 2^12 benchmark shapes, full width
-class _Shape:
+class _Shape(KeyedCell):
     """8192x4096 / LogN = 13 (L = 12, K = 2) and 2048x1024 / LogN = 12 (L = 10, K = 2) exactly as bench.py builds them,
     with the keys of an InnerSum over the whole ring."""
 
@@ -278,24 +261,20 @@ class _Shape:
         from lumenos_amd import params as lp
         B = lp.generate_bgv_params_for_ntt(cols, log_n)
         self.log_n = log_n
-        self.P = P = Params.from_moduli(oracle, log_n, B.q, B.p, B.T)
+        P = Params.from_moduli(oracle, log_n, B.q, B.p, B.T)
         assert P.psi == B.psi and B.T == T_REF and (P.L, P.K) == (num_q, 2)
-        P.seed(log_n)
-        self.sk = P.keygen_secret()
+        super().__init__(P, log_n)
         self.pk = P.keygen_public(self.sk)
         self.gl = P.inner_sum_galois_elements(P.N)
         assert len(self.gl) == log_n and self.gl[-1] == 2 * P.N - 1  # log_n - 1 column rotations + the row swap
-        self.evks = [P.keygen_galois(self.sk, g) for g in self.gl]
-        self.ctx = make_context(P)
-        for g, e in zip(self.gl, self.evks):
-            self.ctx.load_galois_key(g, e)
+        self.sum_keys = self.keys(self.gl)
 
 
 @pytest.fixture(scope="module", params=[(4096, 13, 12), (1024, 12, 10)], ids=["8192x4096-logn13", "2048x1024-logn12"])
 def shape(request, oracle):
     s = _Shape(oracle, *request.param)
     yield s
-    s.ctx.close()
+    s.close()
 
 
 @gpu
@@ -320,7 +299,7 @@ def test_benchmark_shape_matrix_inner_sum(shape):
     cts = P.encrypt(shape.pk, P.encode(col))[None]
     pt = P.encode(r)
     got = ctx.matrix_inner_sum(ctx.upload(cts), pt, rows).download()
-    assert np.array_equal(got, P.matrix_inner_sum(cts, pt, rows, shape.evks))
+    assert np.array_equal(got, P.matrix_inner_sum(cts, pt, rows, shape.sum_keys))
     want = int(np.sum(col.astype(object) * (r.astype(object) % T_REF)) % T_REF)
     assert int(P.decrypt(shape.sk, got[0], 1, P.rescale_scale(P.L, 2))[0]) == want
 
@@ -340,7 +319,7 @@ def test_benchmark_shape_inner_sum_batch_of_64(shape):
         ctx.set_tuning("LUMEN_KS_FUSED_DIGITS", -1)
     assert np.array_equal(fused, plain)
     for c in (0, 63):
-        assert np.array_equal(fused[c], P.inner_sum(cts[c], P.N, shape.evks)), c
+        assert np.array_equal(fused[c], P.inner_sum(cts[c], P.N, shape.sum_keys)), c
 
 
 @gpu
@@ -368,28 +347,26 @@ DEFAULTS = {"LUMEN_MODUP_TGROUP": 3, "LUMEN_MODDOWN_TGROUP": 1, "LUMEN_KS_BATCH"
 CHECKED_COLUMNS = (0, 4, 5, 12, 13, 60, 61, 63, 64, 66)  # first and last columns of the batches the values below cut
 
 
-class _Variant:
+class _Variant(KeyedCell):
     """A keyed context, 67 random columns (more than a batch, no multiple of 8) and the oracle's results.  L + K = 7
     at 2^10 and 2^13 (no group size of 2, 3 or 4 divides it), three limbs at 2^14."""
     n, cols = 16, 67
 
     def __init__(self, oracle, log_n, num_q):
         self.log_n = log_n
-        self.P = P = make_params(oracle, log_n, num_q)
-        P.seed(700 + log_n)
-        self.sk = P.keygen_secret()
-        self.gl = P.inner_sum_galois_elements(self.n)
-        self.evks = [P.keygen_galois(self.sk, g) for g in self.gl]
+        P = make_params(oracle, log_n, num_q)
+        super().__init__(P, 700 + log_n)
+        sum_keys = self.load_inner_sum(self.n)
         self.cts = random_cts(P, self.cols, num_q, seed=67 + log_n)
         self.pt = P.encode(np.random.default_rng(log_n).integers(0, 2**63, size=self.n, dtype=np.uint64))
-        self.want = P.matrix_inner_sum(self.cts, self.pt, self.n, self.evks)
-        self.want_inner = {c: P.inner_sum(self.cts[c], self.n, self.evks) for c in CHECKED_COLUMNS}
-        self.ctx = self.keyed_context()
+        self.want = P.matrix_inner_sum(self.cts, self.pt, self.n, sum_keys)
+        self.want_inner = {c: P.inner_sum(self.cts[c], self.n, sum_keys) for c in CHECKED_COLUMNS}
         self.dev = self.ctx.upload(self.cts)
 
     def keyed_context(self):
+        """another context with the cell's keys"""
         ctx = make_context(self.P)
-        for g, e in zip(self.gl, self.evks):
+        for g, e in self.evks.items():
             ctx.load_galois_key(g, e)
         return ctx
 
@@ -404,7 +381,7 @@ class _Variant:
 def variant(request, oracle):
     v = _Variant(oracle, *request.param)
     yield v
-    v.ctx.close()
+    v.close()
 
 
 def _run_under(v, settings):

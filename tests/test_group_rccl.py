@@ -175,10 +175,10 @@ def test_server_group_twin_through_the_rccl_branch(shape):
     as librccl.so.1; the twin is a C++ process, no other RCCL in it): the reference's test shape on 4 ranks, with the ring
     switch on 8, and the HEADLINE configuration -- 16384 x 4096, LogN = 14, L = 12 -- on 8 ranks.  Same Merkle root and a
     byte-identical marshaled proof (4.46 GB at the headline size) as the one-GPU run."""
-    from tests.test_host_mirror import build_binary
+    from helpers import twin
     build_fakes()
-    res = subprocess.run([build_binary()] + [str(x) for x in shape], capture_output=True, text=True, timeout=1500,
-                         env=child_env(FAKE_DIR, LUMEN_TWIN_RCCL_SHARED_DEVICE="1"))
+    res = twin("test_ligero_host", *shape, timeout=1500,
+               env=child_env(FAKE_DIR, LUMEN_TWIN_RCCL_SHARED_DEVICE="1"))
     tail = res.stdout[-2500:] + res.stderr[-2500:]
     assert res.returncode == 0, tail
     assert "PASS TestLigeroE2E" in res.stdout

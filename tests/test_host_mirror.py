@@ -5,15 +5,11 @@ import subprocess
 
 import pytest
 
-from helpers import ROOT, build_cpp_twin
-
-
-def build_binary():
-    return build_cpp_twin("test_ligero_host")
+from helpers import ROOT, build_cpp_twin, twin
 
 
 def test_host_mirror_builds():
-    assert os.path.exists(build_binary())
+    assert os.path.exists(build_cpp_twin("test_ligero_host"))
 
 
 def test_host_transcript_and_field_match_oracle(oracle):
@@ -90,7 +86,7 @@ def test_ligero_e2e_host_mirror(shape, sizes):
     (MetaData block + length words) to the published proofs; with a ring-switch degree the run is the
     "experimental" configuration (MatR / MatZ ring-switched to LogN = 10) against ITS logged sizes."""
     args = [str(x) for x in shape[:4]] + ([str(shape[4])] if shape[4] else [])
-    res = subprocess.run([build_binary()] + args, capture_output=True, text=True, timeout=1500)
+    res = twin("test_ligero_host", *args, timeout=1500)
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-2000:]
     assert "PASS TestLigeroE2E" in res.stdout
     for name in SPANS:
@@ -119,7 +115,7 @@ def test_ligero_e2e_server_group_matches_one_gpu(shape):
     two all-to-alls, the digest all-gather and the query gather inside the library (lumen_group_*, copy transport) --
     and must give the same Merkle root and a byte-identical marshaled proof."""
     args = [str(x) for x in shape]
-    res = subprocess.run([build_binary()] + args, capture_output=True, text=True, timeout=1500)
+    res = twin("test_ligero_host", *args, timeout=1500)
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-2000:]
     assert "PASS TestLigeroE2E" in res.stdout
     assert f"ServerGroup: {shape[5]} ranks, transport copy" in res.stdout

@@ -48,23 +48,18 @@ def test_inner_product_on_a_matrix_rescaled_to_three_limbs(oracle):
         ctx.close()
 
 
-def _host_binary():
-    from helpers import build_cpp_twin
-    return build_cpp_twin("test_inner_product_levels_host", with_oracle=False)
-
-
 def test_host_binary_builds():
     import os
-    assert os.path.exists(_host_binary())
+    from helpers import build_cpp_twin
+    assert os.path.exists(build_cpp_twin("test_inner_product_levels_host", with_oracle=False))
 
 
 @gpu
 def test_host_mirror_routes_a_lower_level_matrix():
     """fhe::matrixInnerSumEval on a matrix rescaled to three of five limbs (tests/cpp/test_inner_product_levels_host.cpp):
     level 1 out, the rescales' scale, the plain inner products; a plaintext at another level is refused."""
-    import subprocess
-    res = subprocess.run([_host_binary(), "run", str(LOG_N), str(ROWS), "4", "5", str(NL)], capture_output=True, text=True,
-                         timeout=300)
+    from helpers import twin
+    res = twin("test_inner_product_levels_host", "run", LOG_N, ROWS, 4, 5, NL, timeout=300, with_oracle=False)
     print(res.stdout)
     assert res.returncode == 0, res.stdout[-3000:] + res.stderr[-3000:]
     for what in ("3 limbs: 4 inner products of 16 rows", "level mismatch is refused", "top level: the same values"):

@@ -12,7 +12,7 @@ doubling's decomposition; a sum with lazy terms closes with one more gather, one
 import numpy as np
 import pytest
 
-from test_inner_sum_general import _Cell
+from cells import GeneralSumCell
 
 gpu = pytest.mark.gpu
 
@@ -32,10 +32,10 @@ def expected(N, batch, n, fused=False):
 
 @pytest.fixture(scope="module")
 def cell(oracle):
-    c = _Cell(oracle, 10)
+    c = GeneralSumCell(oracle, 10)
     c.ctx.prof_enable(True)
     yield c
-    c.ctx.close()
+    c.close()
 
 
 def census(ctx, call, exp, batches, nl):
@@ -110,8 +110,8 @@ def test_three_batches(cell):
     from helpers import random_cts
     P, ctx = cell.P, cell.ctx
     cts = random_cts(P, 5, 3, seed=191)
-    cell.key.load_for(1, 7)
-    want = np.stack([model.inner_sum(P, c, 1, 7, cell.key) for c in cts])
+    cell.load_for(1, 7)
+    want = np.stack([model.inner_sum(P, c, 1, 7, cell) for c in cts])
     try:
         ctx.set_tuning("LUMEN_KS_BATCH", 2)
         got = census(ctx, lambda: ctx.inner_sum_general(ctx.upload(cts), 1, 7), expected(P.N, 1, 7), [2, 2, 1], 3)

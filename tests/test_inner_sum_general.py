@@ -12,87 +12,19 @@ import numpy as np
 import pytest
 
 import inner_sum_model as model
-from helpers import T_REF, _adversarial_cts, _ntt_primes_near, make_context, make_params, random_cts
+from cells import GeneralSumCell, KeyedCell, cell_cache
+from helpers import (DEGREES, T_REF, T_SMALL, _adversarial_cts, _ntt_primes_near, canonical, make_context, make_params,
+                     random_cts)
 from oracle.loader import Params
 
 gpu = pytest.mark.gpu
 
-DEGREES = (8, 10, 11, 12, 13, 14)
 LEVELS = (1, 2, 3, 4, 5)
-T_SMALL = 0x3EE0001
-
-
-def _canonical(P, got):
-    return all(int(got[:, :, l].max()) < P.moduli[l] for l in range(got.shape[2]))
-
-
-class _Keys:
-    """Galois keys generated by the oracle and loaded into `ctx` at their first use"""
-
-    def __init__(self, P, sk, ctx):
-        self.P, self.sk, self.ctx, self.evks = P, sk, ctx, {}
-
-    def __call__(self, g):
-        if g not in self.evks:
-            self.evks[g] = self.P.keygen_galois(self.sk, g)
-            self.ctx.load_galois_key(g, self.evks[g])
-        return self.evks[g]
-
-    def load_for(self, batch, n):
-        for g in self.ctx.inner_sum_general_elements(batch, n):
-            self(g)
-
-
-class _Cell:
-    """One degree on the reference-style chain: L = 5, K = 2, three five-limb ciphertexts; the model's results are
-    computed once per (level, batch, n) and left unchanged"""
-
-    def __init__(self, oracle, log_n):
-        self.P = P = make_params(oracle, log_n, 5)
-        assert (P.L, P.K) == (5, 2)
-        P.seed(7000 + log_n)
-        self.sk = P.keygen_secret()
-        self.ctx = make_context(P)
-        self.key = _Keys(P, self.sk, self.ctx)
-        self.cts = random_cts(P, 3, 5, seed=900 + log_n)
-        self.cts.setflags(write=False)
-        self._want, self._matrix = {}, {}
-
-    def at(self, nl):
-        return np.ascontiguousarray(self.cts[:, :, :nl])
-
-    def want(self, nl, batch, n):
-        k = (nl, batch, n)
-        if k not in self._want:
-            self.key.load_for(batch, n)
-            w = np.stack([model.inner_sum(self.P, c, batch, n, self.key) for c in self.at(nl)])
-            w.setflags(write=False)
-            self._want[k] = w
-        return self._want[k]
-
-    def matrix(self, nl, rows):
-        k = (nl, rows)
-        if k not in self._matrix:
-            self.key.load_for(1, rows)
-            pt = self.P.encode(np.random.default_rng(rows + nl).integers(0, 2**63, size=rows, dtype=np.uint64), nl=nl)
-            w = np.stack([model.matrix_inner_sum(self.P, c, pt, rows, self.key) for c in self.at(nl)])
-            w.setflags(write=False)
-            self._matrix[k] = (pt, w)
-        return self._matrix[k]
 
 
 @pytest.fixture(scope="module")
 def cells(oracle):
-    made = {}
-
-    def get(log_n):
-        if log_n not in made:
-            made[log_n] = _Cell(oracle, log_n)
-        return made[log_n]
-
-    yield get
-    for c in made.values():
-        c.ctx.close()
+    yield from cell_cache(lambda *k: GeneralSumCell(oracle, *k))
 
 
 def _check(cell, nl, batch, n):
@@ -102,7 +34,7 @@ def _check(cell, nl, batch, n):
     assert got.shape == (3, 2, nl, P.N)
     for c in range(3):
         assert np.array_equal(got[c], want[c]), (nl, batch, n, c)
-    assert _canonical(P, got)
+    assert canonical(P, got)
 
 
 @gpu
@@ -150,8 +82,8 @@ def test_batch_edges(cells):
     cell = cells(10)
     P, ctx = cell.P, cell.ctx
     cts = random_cts(P, 5, 3, seed=191)
-    cell.key.load_for(1, 7)
-    want = np.stack([model.inner_sum(P, c, 1, 7, cell.key) for c in cts])
+    cell.load_for(1, 7)
+    want = np.stack([model.inner_sum(P, c, 1, 7, cell) for c in cts])
     try:
         ctx.set_tuning("LUMEN_KS_BATCH", 2)
         got = ctx.inner_sum_general(ctx.upload(cts), 1, 7).download()
@@ -165,17 +97,15 @@ def test_one_special_prime(oracle):
     """K = 1, chain (3 Q, 1 P), nl = 1, 2, 3: every digit is a single limb at every level"""
     P = make_params(oracle, 10, 3, num_p=1)
     assert (P.L, P.K) == (3, 1)
-    P.seed(71)
-    sk = P.keygen_secret()
-    ctx = make_context(P)
+    key = KeyedCell(P, 71)
+    ctx = key.ctx
     try:
-        key = _Keys(P, sk, ctx)
         key.load_for(1, 7)
         for nl in (1, 2, 3):
             cts = random_cts(P, 3, nl, seed=370 + nl)
             got = ctx.inner_sum_general(ctx.upload(cts), 1, 7).download()
             assert np.array_equal(got, np.stack([model.inner_sum(P, c, 1, 7, key) for c in cts])), nl
-            assert _canonical(P, got), nl
+            assert canonical(P, got), nl
     finally:
         ctx.close()
 
@@ -189,17 +119,15 @@ def test_at_the_modulus_bound(oracle, log_n, n):
     pr = _ntt_primes_near(qmax, 2 << log_n, 7)
     P = Params.from_moduli(oracle, log_n, pr[:5], pr[5:], T_REF)
     assert (P.L, P.K) == (5, 2) and all(q <= qmax for q in P.moduli)
-    P.seed(277 + log_n)
-    sk = P.keygen_secret()
-    ctx = make_context(P)
+    key = KeyedCell(P, 277 + log_n)
+    ctx = key.ctx
     try:
-        key = _Keys(P, sk, ctx)
         key.load_for(1, n)
         for nl in (2, 3):
             cts = _adversarial_cts(P, nl, seed=29 + nl)
             got = ctx.inner_sum_general(ctx.upload(cts), 1, n).download()
             assert np.array_equal(got, np.stack([model.inner_sum(P, c, 1, n, key) for c in cts])), nl
-            assert _canonical(P, got), nl
+            assert canonical(P, got), nl
     finally:
         ctx.close()
 
@@ -216,7 +144,7 @@ def test_matrix_inner_sum(cells, log_n, nl, rows):
     got = ctx.matrix_inner_sum_general(ctx.upload(cell.at(nl)), pt, rows).download()
     assert got.shape == (3, 2, min(nl, 2), P.N)
     assert np.array_equal(got, want)
-    assert _canonical(P, got)
+    assert canonical(P, got)
 
 
 @gpu
@@ -242,7 +170,7 @@ def test_order_of_calls(cells):
     mixed, plain = make_context(P), make_context(P)
     try:
         for ctx in (mixed, plain):
-            for g, e in cell.key.evks.items():
+            for g, e in cell.evks.items():
                 ctx.load_galois_key(g, e)
         assert np.array_equal(mixed.inner_sum_general(mixed.upload(cell.cts), 1, 7).download(), want7)
         got = mixed.inner_sum(mixed.upload(cell.cts), 16).download()
@@ -259,14 +187,13 @@ def test_decrypts_to_the_sums(oracle):
     each row to sum_{i < 12} v[j + i] of that row"""
     P = make_params(oracle, 10, 3, T=T_SMALL)
     N, h = P.N, P.N // 2
-    P.seed(5100)
-    sk = P.keygen_secret()
-    pk = P.keygen_public(sk)
-    v = np.arange(1, N + 1, dtype=np.uint64)
-    ct = P.encrypt(pk, P.encode(v))
-    ctx = make_context(P)
+    key = KeyedCell(P, 5100)
+    sk, ctx = key.sk, key.ctx
     try:
-        _Keys(P, sk, ctx).load_for(1, 12)
+        pk = P.keygen_public(sk)
+        v = np.arange(1, N + 1, dtype=np.uint64)
+        ct = P.encrypt(pk, P.encode(v))
+        key.load_for(1, 12)
         got = P.decrypt(sk, ctx.inner_sum_general(ctx.upload(ct[None]), 1, 12).download()[0], N)
         want = np.concatenate([sum(np.roll(r.astype(object), -i) for i in range(12)) for r in (v[:h], v[h:])]) % P.T
         assert np.array_equal(got.astype(object), want)
@@ -280,7 +207,7 @@ def test_errors(oracle, cells):
     cell = cells(10)
     P, ctx = cell.P, cell.ctx
     lib = ctx.lib
-    cell.key.load_for(1, 7)
+    cell.load_for(1, 7)
 
     def fails(fn, text):
         with pytest.raises(LumenError) as e:
@@ -320,7 +247,7 @@ def test_errors(oracle, cells):
     # a missing key, named by element
     missing = P.galois_element(96)
     used = ctx.inner_sum_general_elements(1, 100)  # rotations 1, 2, then the lazy term of bit 2: 100 - 4 = 96
-    assert missing not in cell.key.evks and used[2] == missing and all(g in cell.key.evks for g in used[:2])
+    assert missing not in cell.evks and used[2] == missing and all(g in cell.evks for g in used[:2])
     fails(lambda: ctx.inner_sum_general(s3, 1, 100), f"Galois key for element {missing} not loaded")
     fails(lambda: ctx.matrix_inner_sum_general(s3, pt3, 100), f"Galois key for element {missing} not loaded")
     # a lane-sharded set

@@ -14,76 +14,47 @@ runs two lanes by default, 8 is the one-wave workgroup."""
 import numpy as np
 import pytest
 
-from helpers import T_REF, _adversarial_cts, _ntt_primes_near, make_context, make_params, random_cts
+from cells import KeyedCell, cell_cache
+from helpers import DEGREES, T_REF, _adversarial_cts, _ntt_primes_near, canonical, make_context, make_params, random_cts
 from oracle.loader import Params
 
 gpu = pytest.mark.gpu
 
-DEGREES = (8, 10, 11, 12, 13, 14)
 LEVELS = (1, 2, 3, 4)
 
 
-def _keyed(P, sk, n):
-    """(Galois elements of an InnerSum of n, their keys, a context that holds them)"""
-    gl = P.inner_sum_galois_elements(n)
-    evks = [P.keygen_galois(sk, g) for g in gl]
-    ctx = make_context(P)
-    for g, e in zip(gl, evks):
-        ctx.load_galois_key(g, e)
-    return gl, evks, ctx
-
-
-def _canonical(P, got):
-    return all(int(got[:, :, l].max()) < P.moduli[l] for l in range(got.shape[2]))
-
-
-class _Cell:
+class _Cell(KeyedCell):
     """One degree on the reference-style chain: L = 5, K = 2, the keys of an InnerSum of n = 16 (n = N = 256 at
     LogN = 8: the row swap runs), three five-limb ciphertexts; the oracle's results are computed once per level."""
 
     def __init__(self, oracle, log_n):
         self.log_n = log_n
-        self.P = P = make_params(oracle, log_n, 5)
+        P = make_params(oracle, log_n, 5)
         assert (P.L, P.K) == (5, 2)
         self.n = P.N if log_n == 8 else 16
-        P.seed(2000 + log_n)
-        self.sk = P.keygen_secret()
-        self.gl, self.evks, self.ctx = _keyed(P, self.sk, self.n)
+        super().__init__(P, 2000 + log_n)
+        self.gl = P.inner_sum_galois_elements(self.n)
+        self.sum_keys = self.keys(self.gl)
         if log_n == 8:
             assert self.gl[-1] == 2 * P.N - 1
         self.cts = random_cts(P, 3, 5, seed=900 + log_n)
-        self._inner, self._matrix = {}, {}
-
-    def at(self, nl):
-        return np.ascontiguousarray(self.cts[:, :, :nl])
 
     def inner(self, nl):
-        if nl not in self._inner:
-            self._inner[nl] = np.stack([self.P.inner_sum(c, self.n, self.evks) for c in self.at(nl)])
-        return self._inner[nl]
+        return self.cached(("inner", nl), lambda: np.stack([self.P.inner_sum(c, self.n, self.sum_keys) for c in self.at(nl)]))
 
     def matrix(self, nl):
         """(pt, the oracle's matrixInnerSumEval) with rows = 16"""
-        if nl not in self._matrix:
+        def make():
             values = np.random.default_rng(self.log_n + nl).integers(0, 2**63, size=16, dtype=np.uint64)
             pt = self.P.encode(values, nl=nl)
-            self._matrix[nl] = pt, self.P.matrix_inner_sum(self.at(nl), pt, 16, self.evks)
-        return self._matrix[nl]
+            return pt, self.P.matrix_inner_sum(self.at(nl), pt, 16, self.sum_keys)
+        return self.cached(("matrix", nl), make)
 
 
 @pytest.fixture(scope="module")
 def cells(oracle):
     """log_n -> its _Cell, built at first use and shared by every test of the module"""
-    made = {}
-
-    def get(log_n):
-        if log_n not in made:
-            made[log_n] = _Cell(oracle, log_n)
-        return made[log_n]
-
-    yield get
-    for c in made.values():
-        c.ctx.close()
+    yield from cell_cache(lambda *k: _Cell(oracle, *k))
 
 
 @gpu
@@ -97,7 +68,7 @@ def test_inner_sum_at_level(cells, log_n, nl):
     want = cell.inner(nl)
     for c in range(3):
         assert np.array_equal(got[c], want[c]), c
-    assert _canonical(P, got)
+    assert canonical(P, got)
 
 
 @gpu
@@ -154,8 +125,8 @@ def test_batch_edges_below_the_top(cells):
     P, ctx = cell.P, cell.ctx
     cts = random_cts(P, 5, 3, seed=53)
     pt, _ = cell.matrix(3)
-    want_inner = np.stack([P.inner_sum(c, cell.n, cell.evks) for c in cts])
-    want_matrix = P.matrix_inner_sum(cts, pt, 16, cell.evks)
+    want_inner = np.stack([P.inner_sum(c, cell.n, cell.sum_keys) for c in cts])
+    want_matrix = P.matrix_inner_sum(cts, pt, 16, cell.sum_keys)
     try:
         ctx.set_tuning("LUMEN_KS_BATCH", 2)
         dev = ctx.upload(cts)
@@ -173,16 +144,15 @@ def test_one_special_prime(oracle, log_n):
     """K = 1, chain (3 Q, 1 P), nl = 1, 2, 3: every digit is a single limb at every level"""
     P = make_params(oracle, log_n, 3, num_p=1)
     assert (P.L, P.K) == (3, 1)
-    P.seed(30 + log_n)
-    sk = P.keygen_secret()
     n = 16
-    gl, evks, ctx = _keyed(P, sk, n)
+    key = KeyedCell(P, 30 + log_n)
+    evks, ctx = key.load_inner_sum(n), key.ctx
     try:
         for nl in (1, 2, 3):
             cts = random_cts(P, 3, nl, seed=31 * log_n + nl)
             got = ctx.inner_sum_at_level(ctx.upload(cts), n).download()
             assert np.array_equal(got, np.stack([P.inner_sum(c, n, evks) for c in cts])), nl
-            assert _canonical(P, got), nl
+            assert canonical(P, got), nl
     finally:
         ctx.close()
 
@@ -196,16 +166,15 @@ def test_at_the_modulus_bound(oracle, log_n):
     pr = _ntt_primes_near(qmax, 2 << log_n, 7)
     P = Params.from_moduli(oracle, log_n, pr[:5], pr[5:], T_REF)
     assert (P.L, P.K) == (5, 2) and all(q <= qmax for q in P.moduli)
-    P.seed(77 + log_n)
-    sk = P.keygen_secret()
     n = 16
-    gl, evks, ctx = _keyed(P, sk, n)
+    key = KeyedCell(P, 77 + log_n)
+    evks, ctx = key.load_inner_sum(n), key.ctx
     try:
         for nl in (2, 3):
             cts = _adversarial_cts(P, nl, seed=13 + nl)
             got = ctx.inner_sum_at_level(ctx.upload(cts), n).download()
             assert np.array_equal(got, np.stack([P.inner_sum(c, n, evks) for c in cts])), nl
-            assert _canonical(P, got), nl
+            assert canonical(P, got), nl
             pt = P.encode(np.arange(1, P.N + 1, dtype=np.uint64), nl=nl)
             got = ctx.matrix_inner_sum_at_level(ctx.upload(cts), pt, n).download()
             assert np.array_equal(got, P.matrix_inner_sum(cts, pt, n, evks)), nl
@@ -223,7 +192,7 @@ def test_order_of_levels_does_not_matter(cells):
     mixed, top_only = make_context(P), make_context(P)
     try:
         for ctx in (mixed, top_only):
-            for g, e in zip(cell.gl, cell.evks):
+            for g, e in zip(cell.gl, cell.sum_keys):
                 ctx.load_galois_key(g, e)
         pt5 = P.encode(np.arange(3, 19, dtype=np.uint64))
         assert np.array_equal(mixed.inner_sum_at_level(mixed.upload(cell.at(2)), cell.n).download(), cell.inner(2))
@@ -235,7 +204,7 @@ def test_order_of_levels_does_not_matter(cells):
         assert np.array_equal(mixed.matrix_inner_sum_at_level(mixed.upload(cell.at(3)), pt, 16).download(), want)
         assert np.array_equal(top_only.inner_sum(top_only.upload(cell.cts), cell.n).download(), top)
         assert np.array_equal(top_only.matrix_inner_sum(top_only.upload(cell.cts), pt5, 16).download(), top_matrix)
-        assert np.array_equal(top_matrix, P.matrix_inner_sum(cell.cts, pt5, 16, cell.evks))
+        assert np.array_equal(top_matrix, P.matrix_inner_sum(cell.cts, pt5, 16, cell.sum_keys))
     finally:
         mixed.close()
         top_only.close()

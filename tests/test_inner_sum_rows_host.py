@@ -3,28 +3,18 @@
 -- client keys generated on the device, encrypt -> InnerSumNew against the plain column sums -> Commit -> Prove ->
 Decrypt -> Verify with rows = 12 at LogN = 12, 1024 columns, ten Q limbs (the shape of tests/test_keygen_host.py's run).
 MatR / MatZ are compared with the plain sums formed in the twin: LigeroProveReference takes powers of two >= 512 only."""
-import os
-import subprocess
-
 import pytest
 
-from helpers import build_cpp_twin
-
-
-def build_binary():
-    return build_cpp_twin("test_inner_sum_rows_host", with_oracle=False)
+from helpers import twin, twin_usage
 
 
 def test_twin_builds_and_prints_its_usage():
-    exe = build_binary()
-    assert os.path.exists(exe)
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=60)
-    assert out.returncode == 2 and "usage: test_inner_sum_rows_host e2e" in out.stderr
+    twin_usage("test_inner_sum_rows_host", with_oracle=False)
 
 
 @pytest.mark.gpu
 def test_twelve_rows_end_to_end():
-    res = subprocess.run([build_binary(), "e2e", "12", "12", "1024", "10"], capture_output=True, text=True, timeout=600)
+    res = twin("test_inner_sum_rows_host", "e2e", 12, 12, 1024, 10, with_oracle=False)
     assert res.returncode == 0, res.stdout[-3000:] + res.stderr[-3000:]
     for line in ("PASS the 4 elements InnerSum(1, 12) applies are among the", "PASS InnerSumNew(ct, 1, 12)",
                  "PASS decrypt: MatR / MatZ = the plain sum_i r_i M[i][j] / sum_i b_i M[i][j] (rows=12)", "PASS client verify: rows=12",

@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 
 import keygen_model as km
-from helpers import T_REF, make_context, make_params
+from helpers import T_REF, canonical, make_context, make_params
 from lumenos_amd.hip import LUMEN_KEY_MONTGOMERY, SYMBOLS
 
 SEED = bytes(range(32))
@@ -31,10 +31,6 @@ def _model_galois(oracle, shape, g):
         P, s = _params(oracle, *shape)
         _cache[key] = km.galois_key(P, SEED, s, g)
     return _cache[key]
-
-
-def _canonical(P, key):
-    return all(int(key[..., m, :].max()) < q for m, q in enumerate(P.moduli))
 
 
 # ------------------------------------------------------------------ CPU: the model's vectors contain the hard cases
@@ -73,7 +69,7 @@ def test_model_k0_ringswitch_shape(oracle):
     """(10, 1, 0): TestRingSwitch's P-less shape -- five base-2^13 entries of one limb, fac = 2^(13 j)"""
     P, s = _params(oracle, 10, 1, 0, T_RS)
     key, _ = km.ringswitch_key(P, SEED, s, 8, 13)
-    assert key.shape == (1, 5, 2, 1, P.N) and _canonical(P, key)
+    assert key.shape == (1, 5, 2, 1, P.N) and canonical(P, key)
     assert [km.gadget_factor(P, 0, j, 0, 13) for j in range(5)] == [pow(2, 13 * j, P.moduli[0]) for j in range(5)]
 
 
@@ -124,7 +120,7 @@ def test_every_key_word_matches_model(oracle, shape):
     gal = list(dict.fromkeys(P.inner_sum_galois_elements(8) + P.inner_sum_galois_elements(P.N)))
     assert 2 * P.N - 1 in gal
     got = ctx.keygen_galois(SEED, gal)
-    assert got.shape == (len(gal),) + P.evk_shape() and _canonical(P, got)
+    assert got.shape == (len(gal),) + P.evk_shape() and canonical(P, got)
     want = np.stack([_model_galois(oracle, shape, g)[0] for g in gal])
     for i, g in enumerate(gal):
         assert np.array_equal(got[i, :, 1], want[i, :, 1]), ("a", g)

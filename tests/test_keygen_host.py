@@ -2,22 +2,16 @@
 fhe::ClientBFV::NewWithGeneratedSecret, fhe::KeyGenerator, fhe::NewRingSwitchClient and the server's
 ServerBFV::NewFromKeySet.  CPU: the key set's Galois elements cover what InnerSum applies.  GPU:
 tests/cpp/test_keygen_host.cpp runs the whole protocol with no CPU-generated key anywhere."""
-import subprocess
-
 import pytest
 
-from helpers import build_cpp_twin, make_params
-
-
-def build_binary():
-    return build_cpp_twin("test_keygen_host")
+from helpers import make_params, twin
 
 
 @pytest.mark.parametrize("log_n,rows", [(12, 2048), (12, 4096), (14, 16384), (10, 8)])
 def test_key_set_elements_cover_inner_sum(oracle, log_n, rows):
     """GenKeySetNew generates GaloisElementsForInnerSum(1, rows): log2(rows) + 1 rotations, the row swap iff
     rows > N/2, all odd residues below 2N, and among them every element the oracle's InnerSum applies, in its order."""
-    out = subprocess.run([build_binary(), "elements", str(log_n), str(rows)], capture_output=True, text=True, timeout=300)
+    out = twin("test_keygen_host", "elements", log_n, rows, timeout=300)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
     gen = [int(l.split()[1]) for l in out.stdout.splitlines() if l.startswith("gen ")]
     used = [int(l.split()[1]) for l in out.stdout.splitlines() if l.startswith("used ")]
@@ -35,7 +29,7 @@ def test_client_generates_keys_server_proves_client_verifies(ring_switch):
     """TestLigeroE2E's shape (2048 x 1024, LogN 12, L 10) with every key generated on the device; with the ring switch
     to LogN 10 the switched MatR / MatZ are decrypted under skNew (no Verify, as in the reference)."""
     args = ["e2e", "12", "2048", "1024", "10"] + ([str(ring_switch)] if ring_switch else [])
-    res = subprocess.run([build_binary()] + args, capture_output=True, text=True, timeout=900)
+    res = twin("test_keygen_host", *args, timeout=900)
     print(res.stdout)
     assert res.returncode == 0, res.stdout[-3000:] + res.stderr[-3000:]
     want = ["keys generated on the device", "key generation is deterministic"]
@@ -51,6 +45,6 @@ def test_refused_server_leaves_no_context():
     after the server's context and field table exist; the constructor throws that message and
     fhe::LiveContextsForTest() is back where it was.  Then a server and a CopyNew of it on each of two threads at once,
     destroyed there: the count returns again."""
-    res = subprocess.run([build_binary(), "refuse"], capture_output=True, text=True, timeout=300)
+    res = twin("test_keygen_host", "refuse", timeout=300)
     assert res.returncode == 0, res.stdout[-3000:] + res.stderr[-3000:]
     assert "PASS refused server leaves no context" in res.stdout

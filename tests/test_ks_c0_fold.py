@@ -12,7 +12,8 @@ GPU: switch on against switch off, np.array_equal, at every degree / column coun
 import numpy as np
 import pytest
 
-from helpers import make_context, make_params, random_cts
+from cells import KeyedCell, cell_cache
+from helpers import bitrev, both_routes, make_params, random_cts
 
 gpu = pytest.mark.gpu
 SWITCH = "LUMEN_KS_C0_FOLD"
@@ -152,22 +153,15 @@ def test_reduction_of_signed_words(v):
         assert s192_mod(x, q) % q == v % q
 
 
-def _bitrev(x, bits):
-    r = np.zeros_like(x)
-    for b in range(bits):
-        r |= ((x >> np.uint64(b)) & np.uint64(1)) << np.uint64(bits - 1 - b)
-    return r
-
-
 @pytest.mark.parametrize("log_n", [8, 10, 14])
 def test_index_tables_permute_aligned_256_blocks(log_n):
     """The folded gadget product's workgroup owns 256 consecutive NTT-domain positions and writes the one output block
     that gathers from them: every index table of InnerSum(N) maps aligned blocks of 256 onto blocks of 256."""
     N = 1 << log_n
     i = np.arange(N, dtype=np.uint64)
-    t1 = np.uint64(2) * _bitrev(i, log_n) + np.uint64(1)
+    t1 = np.uint64(2) * bitrev(i, log_n) + np.uint64(1)
     for g in _elements(N, log_n):
-        idx = _bitrev((((np.uint64(g) * t1) & np.uint64(2 * N - 1)) - np.uint64(1)) >> np.uint64(1), log_n)
+        idx = bitrev((((np.uint64(g) * t1) & np.uint64(2 * N - 1)) - np.uint64(1)) >> np.uint64(1), log_n)
         blocks = (idx >> np.uint64(8)).reshape(N // 256, 256)
         assert (blocks == blocks[:, :1]).all(), g
         assert sorted(blocks[:, 0].tolist()) == list(range(N // 256)), g
@@ -190,36 +184,20 @@ def test_new_kernels_pass_the_resource_gate():
 
 
 # ------------------------------------------------------------------ GPU
-def _both_routes(ctx, call):
-    """(switch on, switch off) of the same call; the context is left as it was created"""
-    try:
-        ctx.set_tuning(SWITCH, 1)
-        on = call()
-        ctx.set_tuning(SWITCH, 0)
-        off = call()
-    finally:
-        ctx.set_tuning(SWITCH, _DEFAULT)
-    return on, off
-
-
 _DEFAULT = 1
 
 
-class _Cell:
+class _Cell(KeyedCell):
     """One degree, K = 2 (3 Q limbs, 2 P) or K = 1 (3 Q, 1 P), with the keys of InnerSum(N), which hold those of every
     shorter power of two, and five ciphertexts."""
 
     def __init__(self, oracle, log_n, k):
-        self.P = P = make_params(oracle, log_n, 3, num_p=k)
+        P = make_params(oracle, log_n, 3, num_p=k)
         assert (P.L, P.K) == (3, k)
-        P.seed(1700 + 10 * log_n + k)
-        sk = P.keygen_secret()
+        super().__init__(P, 1700 + 10 * log_n + k)
         self.gl = P.inner_sum_galois_elements(P.N)
         assert self.gl[-1] == 2 * P.N - 1
-        self.keys = {g: P.keygen_galois(sk, g) for g in self.gl}
-        self.ctx = make_context(P)
-        for g, e in self.keys.items():
-            self.ctx.load_galois_key(g, e)
+        self.keys(self.gl)
         self.cts = random_cts(P, 5, 3, seed=1717 + log_n + k)
         self.cts.setflags(write=False)
         self.pt = P.encode(np.random.default_rng(log_n + k).integers(0, 2**63, size=P.N, dtype=np.uint64))
@@ -227,16 +205,7 @@ class _Cell:
 
 @pytest.fixture(scope="module")
 def cells(oracle):
-    made = {}
-
-    def get(log_n, k):
-        if (log_n, k) not in made:
-            made[log_n, k] = _Cell(oracle, log_n, k)
-        return made[log_n, k]
-
-    yield get
-    for c in made.values():
-        c.ctx.close()
+    yield from cell_cache(lambda *k: _Cell(oracle, *k))
 
 
 @gpu
@@ -251,7 +220,7 @@ def test_switch_on_equals_switch_off(cells, log_n, k, rows, cols):
     ctx, N = cell.ctx, cell.P.N
     rows = N if rows == "N" else N // 4
     dev = ctx.upload(np.ascontiguousarray(cell.cts[:cols]))
-    on, off = _both_routes(ctx, lambda: ctx.matrix_inner_sum(dev, cell.pt, rows).download())
+    on, off = both_routes(ctx, SWITCH, lambda: ctx.matrix_inner_sum(dev, cell.pt, rows).download())
     assert on.shape == (cols, 2, 2, N)
     assert np.array_equal(on, off)
 
@@ -264,7 +233,7 @@ def test_against_the_oracle_and_the_scopes_count_the_route(cells):
     cell = cells(10, 2)
     P, ctx = cell.P, cell.ctx
     cts = np.ascontiguousarray(cell.cts[:3])
-    want = P.matrix_inner_sum(cts, cell.pt, 8, [cell.keys[g] for g in P.inner_sum_galois_elements(8)])
+    want = P.matrix_inner_sum(cts, cell.pt, 8, cell.load_inner_sum(8))
     dev = ctx.upload(cts)
     seen = {}
     ctx.prof_enable(True)
@@ -314,7 +283,7 @@ def test_batches_and_lanes_keep_their_own_lifts(cells, batch, lanes):
     try:
         ctx.set_tuning("LUMEN_KS_BATCH", batch)
         ctx.set_tuning("LUMEN_KS_LANES", lanes)
-        on, off = _both_routes(ctx, lambda: ctx.matrix_inner_sum(dev, cell.pt, 16).download())
+        on, off = both_routes(ctx, SWITCH, lambda: ctx.matrix_inner_sum(dev, cell.pt, 16).download())
     finally:
         ctx.set_tuning("LUMEN_KS_BATCH", 64)
         ctx.set_tuning("LUMEN_KS_LANES", 0)
@@ -348,7 +317,7 @@ def test_headline_chain_rows_16384(oracle, cols):
     cell = _headline_cell(oracle)
     ctx = cell.ctx
     dev = ctx.upload(np.ascontiguousarray(cell.cts[:cols]))
-    on, off = _both_routes(ctx, lambda: ctx.matrix_inner_sum(dev, cell.pt, 1 << 14).download())
+    on, off = both_routes(ctx, SWITCH, lambda: ctx.matrix_inner_sum(dev, cell.pt, 1 << 14).download())
     assert on.shape == (cols, 2, 2, 1 << 14)
     assert np.array_equal(on, off)
 
@@ -361,11 +330,11 @@ def _headline_cell(oracle):
     if not _HEADLINE:
         from lumenos_amd import params as lp
         from oracle.loader import Params
-        from test_moddown_w14 import _Keys
         H = lp.generate_bgv_params_for_ntt(4096, 14)
         P = Params.from_moduli(oracle, 14, list(H.q), list(H.p), H.T)
         assert (P.L, P.K) == (12, 2)
-        k = _Keys(P, 1710)
+        k = KeyedCell(P, 1710)
+        assert len(k.load_inner_sum(1 << 14)) == 14
         k.cts = random_cts(P, 3, P.L, seed=1730)
         k.pt = P.encode(np.random.default_rng(1740).integers(0, 2**63, size=P.N, dtype=np.uint64))
         _HEADLINE.append(k)

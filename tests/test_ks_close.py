@@ -17,12 +17,12 @@ off.  The shapes are the smallest that can still go wrong:
 import numpy as np
 import pytest
 
-from helpers import T_REF, _adversarial_cts, _ntt_primes_near, make_context, make_params, random_cts
+from cells import KeyedCell, cell_cache
+from helpers import DEGREES, T_REF, _adversarial_cts, _ntt_primes_near, both_routes, make_context, make_params, random_cts
 from oracle.loader import Params
 
 gpu = pytest.mark.gpu
 
-DEGREES = (8, 10, 11, 12, 13, 14)
 SWITCH = "LUMEN_KS_CLOSE_FUSED"
 
 
@@ -85,63 +85,31 @@ def test_coefficient_index_and_sign_of_every_inner_sum_element(log_n):
 
 
 # ------------------------------------------------------------------ device
-def _both_routes(ctx, call):
-    """(switch on, switch off) of the same call; the context is left at the default"""
-    assert ctx.set_tuning(SWITCH, 1) is None
-    try:
-        fused = call()
-        ctx.set_tuning(SWITCH, 0)
-        plain = call()
-    finally:
-        ctx.set_tuning(SWITCH, 1)
-    return fused, plain
-
-
-class _Cell:
+class _Cell(KeyedCell):
     """One degree on the reference-style chain, L = 5, K = 2, with the keys of an InnerSum over the whole ring (which
     hold those of every shorter one), three ciphertexts and the oracle's matrixInnerSumEval of them per (level, rows)."""
 
     def __init__(self, oracle, log_n):
         self.log_n = log_n
-        self.P = P = make_params(oracle, log_n, 5)
+        P = make_params(oracle, log_n, 5)
         assert (P.L, P.K) == (5, 2)
-        P.seed(1300 + log_n)
-        self.sk = P.keygen_secret()
+        super().__init__(P, 1300 + log_n)
         self.gl = P.inner_sum_galois_elements(P.N)
         assert self.gl[-1] == 2 * P.N - 1 and self.gl[:2] == [5, 25]
-        self.keys = {g: P.keygen_galois(self.sk, g) for g in self.gl}
-        self.ctx = make_context(P)
-        for g, e in self.keys.items():
-            self.ctx.load_galois_key(g, e)
+        self.keys(self.gl)
         self.cts = random_cts(P, 3, 5, seed=1313 + log_n)
-        self._want = {}
-
-    def evks(self, rows):
-        return [self.keys[g] for g in self.P.inner_sum_galois_elements(rows)]
-
-    def at(self, nl):
-        return np.ascontiguousarray(self.cts[:, :, :nl])
 
     def want(self, nl, rows):
-        if (nl, rows) not in self._want:
+        def make():
             values = np.random.default_rng(self.log_n + nl + rows).integers(0, 2**63, size=rows, dtype=np.uint64)
             pt = self.P.encode(values, nl=nl)
-            self._want[nl, rows] = pt, self.P.matrix_inner_sum(self.at(nl), pt, rows, self.evks(rows))
-        return self._want[nl, rows]
+            return pt, self.P.matrix_inner_sum(self.at(nl), pt, rows, self.load_inner_sum(rows))
+        return self.cached((nl, rows), make)
 
 
 @pytest.fixture(scope="module")
 def cells(oracle):
-    made = {}
-
-    def get(log_n):
-        if log_n not in made:
-            made[log_n] = _Cell(oracle, log_n)
-        return made[log_n]
-
-    yield get
-    for c in made.values():
-        c.ctx.close()
+    yield from cell_cache(lambda *k: _Cell(oracle, *k))
 
 
 def _rows(cell, rows):
@@ -157,7 +125,7 @@ def test_every_degree_rows_and_columns(cells, log_n, rows, cols):
     ctx, rows = cell.ctx, _rows(cell, rows)
     pt, want = cell.want(5, rows)
     dev = ctx.upload(np.ascontiguousarray(cell.cts[:cols]))
-    fused, plain = _both_routes(ctx, lambda: ctx.matrix_inner_sum(dev, pt, rows).download())
+    fused, plain = both_routes(ctx, SWITCH, lambda: ctx.matrix_inner_sum(dev, pt, rows).download())
     assert fused.shape == (cols, 2, 2, cell.P.N)
     assert np.array_equal(fused, want[:cols])
     assert np.array_equal(plain, fused)
@@ -208,13 +176,13 @@ def test_batch_edge_and_group_offset(cells, batch, cols, nl, lanes):
     rows = 4
     cts = np.ascontiguousarray(random_cts(P, cols, 5, seed=97 + cols)[:, :, :nl])
     pt, _ = cell.want(nl, rows)
-    want = P.matrix_inner_sum(cts, pt, rows, cell.evks(rows))
+    want = P.matrix_inner_sum(cts, pt, rows, cell.load_inner_sum(rows))
     try:
         ctx.set_tuning("LUMEN_KS_BATCH", batch)
         ctx.set_tuning("LUMEN_KS_LANES", lanes)
         dev = ctx.upload(cts)
         call = ctx.matrix_inner_sum if nl == P.L else ctx.matrix_inner_sum_at_level
-        fused, plain = _both_routes(ctx, lambda: call(dev, pt, rows).download())
+        fused, plain = both_routes(ctx, SWITCH, lambda: call(dev, pt, rows).download())
     finally:
         ctx.set_tuning("LUMEN_KS_BATCH", 64)
         ctx.set_tuning("LUMEN_KS_LANES", 0)
@@ -232,7 +200,7 @@ def test_below_the_top_level(cells, log_n, rows, nl):
     ctx, rows = cell.ctx, _rows(cell, rows)
     pt, want = cell.want(nl, rows)
     dev = ctx.upload(cell.at(nl))
-    fused, plain = _both_routes(ctx, lambda: ctx.matrix_inner_sum_at_level(dev, pt, rows).download())
+    fused, plain = both_routes(ctx, SWITCH, lambda: ctx.matrix_inner_sum_at_level(dev, pt, rows).download())
     assert np.array_equal(fused, want)
     assert np.array_equal(plain, fused)
 
@@ -261,7 +229,7 @@ def test_one_special_prime(oracle, log_n, rows):
     ctx, pt, want = _fresh_case(P, 3, rows, cts, seed=43 + log_n)
     try:
         dev = ctx.upload(cts)
-        fused, plain = _both_routes(ctx, lambda: ctx.matrix_inner_sum(dev, pt, rows).download())
+        fused, plain = both_routes(ctx, SWITCH, lambda: ctx.matrix_inner_sum(dev, pt, rows).download())
     finally:
         ctx.close()
     assert np.array_equal(fused, want)
@@ -283,7 +251,7 @@ def test_lazy_sums_at_the_modulus_bound(oracle, log_n, rows, nq, npr):
     ctx, pt, want = _fresh_case(P, nq, rows, cts, seed=11)
     try:
         dev = ctx.upload(cts)
-        fused, plain = _both_routes(ctx, lambda: ctx.matrix_inner_sum(dev, pt, rows).download())
+        fused, plain = both_routes(ctx, SWITCH, lambda: ctx.matrix_inner_sum(dev, pt, rows).download())
     finally:
         ctx.close()
     assert np.array_equal(fused, want)
@@ -302,7 +270,7 @@ def test_headline_chain_one_column(oracle):
     ctx, pt, want = _fresh_case(P, P.L, P.N, cts, seed=1414)
     try:
         dev = ctx.upload(cts)
-        fused, plain = _both_routes(ctx, lambda: ctx.matrix_inner_sum(dev, pt, P.N).download())
+        fused, plain = both_routes(ctx, SWITCH, lambda: ctx.matrix_inner_sum(dev, pt, P.N).download())
     finally:
         ctx.close()
     assert np.array_equal(fused, want)

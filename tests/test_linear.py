@@ -12,27 +12,18 @@ import numpy as np
 import pytest
 
 import linear_model as lm
-from helpers import T_REF, _adversarial_cts, _ntt_primes_near, make_context, make_params, random_cts
-from oracle.loader import Params
+from helpers import T_REF, T_SMALL, _adversarial_cts, bound_chain, canonical, make_context, make_params, random_cts
 
 gpu = pytest.mark.gpu
 LOG_N = 8
-T_VDEC = 0x3ee0001
-
-
-def _canonical(P, got):
-    return all(int(got[:, :, l].max()) < P.moduli[l] for l in range(got.shape[2]))
 
 
 class _Cell:
+    """One chain, a context and two sets of three ciphertexts: no secret and no key, so not a cells.KeyedCell"""
+
     def __init__(self, oracle, chain, log_n=LOG_N):
         self.chain = chain
-        if chain == "reference":
-            self.P = P = make_params(oracle, log_n, 3)
-        else:
-            qmax = (2**64 - 1) // (3 * log_n + 8)
-            pr = _ntt_primes_near(qmax, 2 << log_n, 5)
-            self.P = P = Params.from_moduli(oracle, log_n, pr[:3], pr[3:], T_REF)
+        self.P = P = make_params(oracle, log_n, 3) if chain == "reference" else bound_chain(oracle, log_n, 3, 2)
         assert (P.L, P.K) == (3, 2)
         self.ctx = make_context(P)
         self.a, self.b = (random_cts(P, 3, 3, seed=21), random_cts(P, 3, 3, seed=22)) if chain == "reference" else \
@@ -70,7 +61,7 @@ def test_add_sub_pairwise_and_against_one(cell):
     for dev, model in ((ctx.add, lm.add), (ctx.sub, lm.sub)):
         for (x, xh), (y, yh) in (((a, cell.a), (b, cell.b)), ((a, cell.a), (one, one_h)), ((one, one_h), (a, cell.a))):
             got = dev(x, y).download()
-            assert got.shape == cell.a.shape and _canonical(P, got)
+            assert got.shape == cell.a.shape and canonical(P, got)
             assert np.array_equal(got, model(P, xh, yh))
     assert ctx.mul_counter() == before
 
@@ -97,7 +88,7 @@ def test_mul_scalar_values_and_counter(cell):
         before = ctx.mul_counter()
         got = ctx.mul_scalar(a, w).download()
         assert ctx.mul_counter() - before == 3, w
-        assert _canonical(P, got) and np.array_equal(got, lm.mul_scalar(P, cell.a, w)), w
+        assert canonical(P, got) and np.array_equal(got, lm.mul_scalar(P, cell.a, w)), w
     before = ctx.mul_counter()
     acc = ctx.upload(cell.b)
     ctx.mul_scalar_then_add(a, int(cell.roots[3]), acc)
@@ -129,7 +120,7 @@ def test_linear_combination(cell, n):
     before = ctx.mul_counter()
     got = ctx.linear_combination(sets, ws)
     assert ctx.mul_counter() == before
-    assert (got.count, got.nl) == (3, 2) and _canonical(P, got.download())
+    assert (got.count, got.nl) == (3, 2) and canonical(P, got.download())
     assert np.array_equal(got.download(), want)
     # the same sum formed with pairwise calls
     acc = ctx.mul_scalar(sets[0], ws[0])
@@ -147,7 +138,7 @@ def test_linear_combination_largest_lazy_sums(cell):
     s = ctx.upload(tops)
     for w in (T - 1, T - 2, 1):
         got = ctx.linear_combination([s] * 8, [w] * 8).download()
-        assert _canonical(P, got) and np.array_equal(got, lm.linear_combination(P, [tops] * 8, [w] * 8)), w
+        assert canonical(P, got) and np.array_equal(got, lm.linear_combination(P, [tops] * 8, [w] * 8)), w
     ws = [T - 2, 1, T - 1, T - 2, T - 2, 1, T - 2, T - 2]
     assert np.array_equal(ctx.linear_combination([s] * 8, ws).download(), lm.linear_combination(P, [tops] * 8, ws))
 
@@ -224,14 +215,14 @@ def test_ntt_base_cases_from_the_public_calls(cell, size):
 @pytest.fixture(scope="module")
 def fresh(oracle):
     from lumenos_amd import params as lp
-    P = make_params(oracle, 10, 3, T=T_VDEC)
+    P = make_params(oracle, 10, 3, T=T_SMALL)
     P.seed(78)
     sk = P.keygen_secret()
     pk = P.keygen_public(sk)
     m = np.random.default_rng(17).integers(0, P.T, size=(3, 16), dtype=np.uint64)
     cts = np.stack([P.encrypt(pk, P.encode(mi)) for mi in m])
     ctx = make_context(P)
-    ctx.encoder_set(lp.encoder_psi(T_VDEC, 10))
+    ctx.encoder_set(lp.encoder_psi(T_SMALL, 10))
     ctx.load_secret_key(sk)
     yield SimpleNamespace(P=P, ctx=ctx, m=m, cts=cts)
     ctx.close()

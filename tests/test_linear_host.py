@@ -3,28 +3,18 @@ MulNew, MulThenAdd, LinearCombinationNew).  CPU: the twin builds against the mir
 at TestLigeroE2E's parameters -- keys generated on the device, 8 encrypted columns, fhe.NTT's hard-coded cases rebuilt
 from Add / Sub / Mul against fhe::NTT, vdec.BatchCiphertexts spelt MulNew + Add against vdec::BatchCiphertexts, both
 decrypted by the client, and the refusal to add two scales."""
-import os
-import subprocess
-
 import pytest
 
-from helpers import build_cpp_twin
-
-
-def build_binary():
-    return build_cpp_twin("test_linear_host", with_oracle=False)
+from helpers import twin, twin_usage
 
 
 def test_twin_builds_and_prints_its_usage():
-    exe = build_binary()
-    assert os.path.exists(exe)
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=60)
-    assert out.returncode == 2 and "usage: test_linear_host e2e" in out.stderr
+    twin_usage("test_linear_host", with_oracle=False)
 
 
 @pytest.mark.gpu
 def test_ntt_and_batching_from_the_mirrors_linear_calls():
-    res = subprocess.run([build_binary(), "e2e", "12", "2048", "1024"], capture_output=True, text=True, timeout=600)
+    res = twin("test_linear_host", "e2e", 12, 2048, 1024, with_oracle=False)
     assert res.returncode == 0, res.stdout[-3000:] + res.stderr[-3000:]
     for line in ("PASS fhe.NTT size 2 from", "PASS fhe.NTT size 4 from", "PASS fhe.NTT size 8 from",
                  "PASS vdec.BatchCiphertexts spelt MulNew + Add", "PASS Add of two scales is refused"):

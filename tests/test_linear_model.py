@@ -6,9 +6,7 @@ import pytest
 
 import linear_model as lm
 import vdec_model as vm
-from helpers import T_REF, make_params, random_cts
-
-T_VDEC = 0x3ee0001  # the plaintext modulus of the reference's vdec tests
+from helpers import T_REF, T_SMALL, make_params, random_cts
 
 
 @pytest.mark.parametrize("size", [2, 4, 8])
@@ -23,7 +21,7 @@ def test_ntt_base_cases_from_add_sub_mul_scalar(oracle, size):
 
 def test_centred_scalar_is_the_oracles(oracle):
     q = 0x3fffffffffc0001
-    for T in (T_REF, T_VDEC, q):
+    for T in (T_REF, T_SMALL, q):
         for w in (0, 1, T - 1, T >> 1, (T >> 1) + 1, 2**64 - 1, 0x123456789abcdef):
             assert lm.centred_scalar(w, T, q) == int(oracle.lib.lo_centered_scalar(w, T, q)), (T, w)
     assert lm.centred_scalar(2**64 - 1, q, q) == (2**64 - 1) % q  # a plain context: w mod T
@@ -32,7 +30,7 @@ def test_centred_scalar_is_the_oracles(oracle):
 @pytest.fixture(scope="module")
 def fresh(oracle):
     """LogN = 10, three limbs, T = 0x3ee0001: a secret, three fresh encryptions and their messages"""
-    P = make_params(oracle, 10, 3, T=T_VDEC)
+    P = make_params(oracle, 10, 3, T=T_SMALL)
     P.seed(77)
     sk = P.keygen_secret()
     pk = P.keygen_public(sk)

@@ -6,7 +6,8 @@ stop at InnerSum(32), five tables -- against the oracle through the C ABI, bit-e
 import numpy as np
 import pytest
 
-from helpers import T_REF, _adversarial_cts, _ntt_primes_near, make_context, random_cts
+from cells import KeyedCell
+from helpers import _adversarial_cts, bitrev, bound_chain, random_cts
 from oracle.loader import Params
 
 gpu = pytest.mark.gpu
@@ -28,19 +29,12 @@ def test_moddown_w14_fits_four_waves_per_simd():
     assert r["Occupancy [waves/SIMD]"] == 4, r
 
 
-def _bitrev(x, bits):
-    r = np.zeros_like(x)
-    for b in range(bits):
-        r |= ((x >> np.uint64(b)) & np.uint64(1)) << np.uint64(bits - 1 - b)
-    return r
-
-
 def _index_table(gal_el):
     """The gather table as lumen_load_galois_key builds d_index (ring.AutomorphismNTTIndex)."""
     i = np.arange(N, dtype=np.uint64)
-    t1 = np.uint64(2) * _bitrev(i, LOG_N) + np.uint64(1)
+    t1 = np.uint64(2) * bitrev(i, LOG_N) + np.uint64(1)
     t2 = (((np.uint64(gal_el) * t1) & np.uint64(2 * N - 1)) - np.uint64(1)) >> np.uint64(1)
-    return _bitrev(t2, LOG_N).astype(np.uint32)
+    return bitrev(t2, LOG_N).astype(np.uint32)
 
 
 def test_index_tables_permute_aligned_1024_blocks(oracle):
@@ -66,26 +60,13 @@ def _headline():
     return lp.generate_bgv_params_for_ntt(4096, LOG_N)
 
 
-def _bound_chain(oracle, num_q, num_p):
-    """num_q + num_p primes == 1 mod 2N directly below the degree's bound (2^64 - 1) // (3 log_n + 8)
-    (as test_degree_matrix._bound_chain)."""
-    pr = _ntt_primes_near((2**64 - 1) // (3 * LOG_N + 8), 2 << LOG_N, num_q + num_p)
-    return Params.from_moduli(oracle, LOG_N, pr[:num_q], pr[num_q:], T_REF)
-
-
-class _Keys:
+class _Keys(KeyedCell):
     """A chain with the 14 keys of InnerSum(16384), on the oracle and loaded into a context."""
 
     def __init__(self, P, seed):
-        self.P = P
-        P.seed(seed)
-        sk = P.keygen_secret()
-        self.gl = P.inner_sum_galois_elements(N)
-        assert len(self.gl) == 14
-        self.evks = [P.keygen_galois(sk, g) for g in self.gl]
-        self.ctx = make_context(P)
-        for g, e in zip(self.gl, self.evks):
-            self.ctx.load_galois_key(g, e)
+        super().__init__(P, seed)
+        self.sum_keys = self.load_inner_sum(N)
+        assert len(self.sum_keys) == 14
 
 
 @pytest.fixture(scope="module")
@@ -97,7 +78,7 @@ def headline(oracle):
     # three columns and their oracle result, computed once: the one-column case takes the first
     k.cts = random_cts(P, 3, P.L, seed=1430)
     k.pt = P.encode(np.random.default_rng(1440).integers(0, 2**63, size=N, dtype=np.uint64))
-    k.want = P.matrix_inner_sum(k.cts, k.pt, N, k.evks)
+    k.want = P.matrix_inner_sum(k.cts, k.pt, N, k.sum_keys)
     for a in (k.cts, k.pt, k.want):
         a.setflags(write=False)
     yield k
@@ -109,13 +90,13 @@ def headline(oracle):
 def test_inner_sum_16384_at_the_modulus_bound(oracle, num_p):
     """lumen_inner_sum, n = 16384 (all 14 index tables), Q = 3 limbs right under the degree's modulus bound, two P
     limbs and one (up1 == up0 in the loader); rows: all q-1, alternating, spike, uniform.  Bit-exact, canonical."""
-    P = _bound_chain(oracle, 3, num_p)
+    P = bound_chain(oracle, LOG_N, 3, num_p)
     assert (P.L, P.K) == (3, num_p)
     k = _Keys(P, 1400 + num_p)
     try:
         cts = _adversarial_cts(P, 3, seed=1420 + num_p)
         got = k.ctx.inner_sum(k.ctx.upload(cts), N).download()
-        want = np.stack([P.inner_sum(c, N, k.evks) for c in cts])
+        want = np.stack([P.inner_sum(c, N, k.sum_keys) for c in cts])
         assert np.array_equal(got, want)
         assert all(int(got[:, :, l].max()) < P.moduli[l] for l in range(3))
     finally:

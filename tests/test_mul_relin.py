@@ -11,41 +11,24 @@ import pytest
 
 import keygen_model as km
 import mul_relin_model as model
-from helpers import T_REF, _adversarial_cts, _ntt_primes_near, make_context, make_params, random_cts
-from oracle.loader import Params
-from test_degree_matrix import CHAINS, DEGREES  # the tuple that test_degree_matrix pins to LM_FOR_EACH_LOGN
+from cells import KeyedCell, cell_cache
+from helpers import (CHAINS, DEGREES, T_SMALL, _adversarial_cts, bound_chain, canonical, make_context, make_params,
+                     random_cts)
 
 gpu = pytest.mark.gpu
 
-T_SMALL = 0x3EE0001
 KEY_SEED = bytes(range(32))
 SECRET_SEED = bytes(range(40, 72))
 A_SEED = bytes([0xA5] * 32)
 
 
-def _bound_chain(oracle, log_n, num_q, num_p, T=T_REF):
-    """num_q + num_p primes == 1 mod 2N directly below the context's bound (2^64 - 1) // (3 log_n + 8)"""
-    pr = _ntt_primes_near((2**64 - 1) // (3 * log_n + 8), 2 << log_n, num_q + num_p)
-    return Params.from_moduli(oracle, log_n, pr[:num_q], pr[num_q:], T)
-
-
-def _canonical(P, got):
-    return all(int(got[..., l, :].max()) < P.moduli[l] for l in range(got.shape[-2]))
-
-
-class _Keyed:
+class _Keyed(KeyedCell):
     """Parameters, a secret, its relinearisation key and a context that holds it"""
 
     def __init__(self, P, seed):
-        self.P = P
-        P.seed(seed)
-        self.sk = P.keygen_secret()
+        super().__init__(P, seed)
         self.rlk, _ = km.relin_key(P, KEY_SEED, self.sk)
-        self.ctx = make_context(P)
         self.ctx.load_relin_key(self.rlk)
-
-    def close(self):
-        self.ctx.close()
 
 
 def _inputs(P, chain, nl, seed):
@@ -62,11 +45,8 @@ def _inputs(P, chain, nl, seed):
 @pytest.mark.parametrize("chain", CHAINS)
 @pytest.mark.parametrize("log_n", DEGREES)
 def test_tensor_and_product_every_degree(oracle, log_n, chain, K):
-    P = make_params(oracle, log_n, 3, num_p=K) if chain == "reference" else _bound_chain(oracle, log_n, 3, K)
+    P = make_params(oracle, log_n, 3, num_p=K) if chain == "reference" else bound_chain(oracle, log_n, 3, K)
     assert (P.L, P.K) == (3, K)
-    if chain == "bound":
-        qmax = (2**64 - 1) // (3 * log_n + 8)
-        assert all(qmax - (217 << (log_n + 1)) < q <= qmax for q in P.moduli), P.moduli
     k = _Keyed(P, 300 + 10 * log_n + K)
     try:
         ctx = k.ctx
@@ -80,7 +60,7 @@ def test_tensor_and_product_every_degree(oracle, log_n, chain, K):
         assert got.shape == (3, 2, 3, P.N)
         for c in range(3):
             assert np.array_equal(got[c], model.relinearise(P, want_d[c], k.rlk)), c
-        assert _canonical(P, got)
+        assert canonical(P, got)
     finally:
         k.close()
 
@@ -90,7 +70,7 @@ def test_tensor_and_product_every_degree(oracle, log_n, chain, K):
 def test_tensor_at_the_modulus_bound(oracle, log_n):
     """Words q - 1 in both operands on the largest moduli a context takes: every product of the tensor kernel at its
     largest (the lazy T-scaled operand below 3q, two products below 6 q^2 in one reduction)"""
-    P = _bound_chain(oracle, log_n, 3, 2)
+    P = bound_chain(oracle, log_n, 3, 2)
     ctx = make_context(P)
     try:
         a = _adversarial_cts(P, 3, seed=5)
@@ -106,26 +86,17 @@ def test_tensor_at_the_modulus_bound(oracle, log_n):
 
 
 # ------------------------------------------------------------------ every level of a chain of four
-class _LevelCell:
+class _LevelCell(_Keyed):
     def __init__(self, oracle, log_n):
         P = make_params(oracle, log_n, 4)
         assert (P.L, P.K) == (4, 2)
-        self.k = _Keyed(P, 77 + log_n)
+        super().__init__(P, 77 + log_n)
         self.a, self.b = random_cts(P, 3, 4, seed=log_n), random_cts(P, 3, 4, seed=log_n + 50)
 
 
 @pytest.fixture(scope="module")
 def level_cells(oracle):
-    made = {}
-
-    def get(log_n):
-        if log_n not in made:
-            made[log_n] = _LevelCell(oracle, log_n)
-        return made[log_n]
-
-    yield get
-    for c in made.values():
-        c.k.close()
+    yield from cell_cache(lambda *k: _LevelCell(oracle, *k))
 
 
 @gpu
@@ -135,46 +106,46 @@ def test_every_level(level_cells, log_n, nl):
     """L = 4, K = 2: nl = 1 one single-limb digit, 2 one packed digit, 3 a packed digit and a single-limb last one,
     4 two packed digits"""
     cell = level_cells(log_n)
-    P, ctx = cell.k.P, cell.k.ctx
+    P, ctx = cell.P, cell.ctx
     a, b = np.ascontiguousarray(cell.a[:, :, :nl]), np.ascontiguousarray(cell.b[:, :, :nl])
     da, db = ctx.upload(a), ctx.upload(b)
     assert np.array_equal(ctx.mul_tensor(da, db), model.mul_tensor_sets(P, a, b))
     got = ctx.mul_relin(da, db).download()
     assert got.shape == (3, 2, nl, P.N)
-    assert np.array_equal(got, model.mul_relin_sets(P, a, b, cell.k.rlk))
+    assert np.array_equal(got, model.mul_relin_sets(P, a, b, cell.rlk))
 
 
 # ------------------------------------------------------------------ one small shape shared by the launch-form tests
-class _Small:
+class _Small(_Keyed):
     """LogN = 10, L = 3, K = 2: five ciphertexts against five, with the model's products"""
 
     def __init__(self, oracle):
-        self.P = P = make_params(oracle, 10, 3)
-        self.k = _Keyed(P, 4242)
+        P = make_params(oracle, 10, 3)
+        super().__init__(P, 4242)
         self.a, self.b = random_cts(P, 5, 3, seed=1), random_cts(P, 5, 3, seed=2)
-        self.want = model.mul_relin_sets(P, self.a, self.b, self.k.rlk)
+        self.want = model.mul_relin_sets(P, self.a, self.b, self.rlk)
 
 
 @pytest.fixture(scope="module")
 def small(oracle):
     s = _Small(oracle)
     yield s
-    s.k.close()
+    s.close()
 
 
 @gpu
 def test_forms_pairwise_broadcast_squares(small):
-    P, ctx = small.P, small.k.ctx
+    P, ctx = small.P, small.ctx
     da, db = ctx.upload(small.a), ctx.upload(small.b)
     before = ctx.mul_counter()
     assert np.array_equal(ctx.mul_relin(da, db).download(), small.want)
     assert ctx.mul_counter() == before + 5
     one = ctx.upload(small.b[3:4])
-    assert np.array_equal(ctx.mul_relin(da, one).download(), model.mul_relin_sets(P, small.a, small.b[3:4], small.k.rlk))
+    assert np.array_equal(ctx.mul_relin(da, one).download(), model.mul_relin_sets(P, small.a, small.b[3:4], small.rlk))
     before = ctx.mul_counter()
     assert np.array_equal(ctx.mul_tensor(da, one), model.mul_tensor_sets(P, small.a, small.b[3:4]))
     assert ctx.mul_counter() == before  # the parity hook counts nothing
-    assert np.array_equal(ctx.mul_relin(da, da).download(), model.mul_relin_sets(P, small.a, small.a, small.k.rlk))
+    assert np.array_equal(ctx.mul_relin(da, da).download(), model.mul_relin_sets(P, small.a, small.a, small.rlk))
     empty = ctx.mul_relin(ctx.new_set(0, 3), one)
     assert empty.count == 0
 
@@ -186,7 +157,7 @@ def test_forms_pairwise_broadcast_squares(small):
 def test_batches_and_lanes(small, settings):
     """count = 5 with LUMEN_KS_BATCH = 2: two full batches and a remainder, on one lane and alternating between two:
     the words of the default launch (one batch of five), which are the model's"""
-    ctx = small.k.ctx
+    ctx = small.ctx
     da, db = ctx.upload(small.a), ctx.upload(small.b)
     default = ctx.mul_relin(da, db).download()
     assert np.array_equal(default, small.want)
@@ -207,7 +178,7 @@ def test_batches_and_lanes(small, settings):
 def test_more_than_one_group_of_batches(small, lanes):
     """LUMEN_KS_BATCH = 1 on eleven ciphertexts: a group of eight batches, then a group of three, which reuses the
     first one's accumulator slices"""
-    P, ctx = small.P, small.k.ctx
+    P, ctx = small.P, small.ctx
     a = np.concatenate([small.a, small.b, small.a[:1]])
     b = np.concatenate([small.b, small.a, small.b[:1]])
     da, db = ctx.upload(a), ctx.upload(b)
@@ -221,14 +192,14 @@ def test_more_than_one_group_of_batches(small, lanes):
         ctx.set_tuning("LUMEN_KS_LANES", 0)
     assert np.array_equal(got, default)
     assert np.array_equal(got[:5], small.want) and np.array_equal(got[10], small.want[0])
-    assert np.array_equal(got[5:10], model.mul_relin_sets(P, small.b, small.a, small.k.rlk))
+    assert np.array_equal(got[5:10], model.mul_relin_sets(P, small.b, small.a, small.rlk))
 
 
 @gpu
 def test_batches_and_lanes_at_2_14(level_cells):
     """the same at the degree that runs one lane by default"""
     cell = level_cells(14)
-    ctx = cell.k.ctx
+    ctx = cell.ctx
     a, b = np.concatenate([cell.a, cell.b[:2]]), np.concatenate([cell.b, cell.a[:2]])
     da, db = ctx.upload(a), ctx.upload(b)
     default = ctx.mul_relin(da, db).download()
@@ -245,7 +216,7 @@ def test_batches_and_lanes_at_2_14(level_cells):
 @gpu
 def test_on_a_clone(small):
     """key loaded on the parent, product on the clone"""
-    ctx = small.k.ctx
+    ctx = small.ctx
     clone = ctx.clone()
     try:
         got = clone.mul_relin(clone.upload(small.a), clone.upload(small.b)).download()
@@ -260,14 +231,14 @@ def test_key_in_montgomery_form_and_loaded_again(small):
     ctx = make_context(P)
     try:
         da, db = ctx.upload(small.a), ctx.upload(small.b)
-        ctx.load_relin_key(km.montgomery(P, small.k.rlk), montgomery=True)
+        ctx.load_relin_key(km.montgomery(P, small.rlk), montgomery=True)
         assert np.array_equal(ctx.mul_relin(da, db).download(), small.want)
         # loading again replaces the key: another key, other words; the first one back, the first words
         P.seed(99)
         other, _ = km.relin_key(P, bytes(range(1, 33)), P.keygen_secret())
         ctx.load_relin_key(other)
         assert np.array_equal(ctx.mul_relin(da, db).download(), model.mul_relin_sets(P, small.a, small.b, other))
-        ctx.load_relin_key(small.k.rlk)
+        ctx.load_relin_key(small.rlk)
         assert np.array_equal(ctx.mul_relin(da, db).download(), small.want)
     finally:
         ctx.close()
@@ -279,13 +250,13 @@ def test_galois_element_one_is_not_the_relinearisation_key(small):
     P = small.P
     ctx = make_context(P)
     try:
-        g1 = P.keygen_galois(small.k.sk, 1)
+        g1 = P.keygen_galois(small.sk, 1)
         ctx.load_galois_key(1, g1)
         da, db = ctx.upload(small.a), ctx.upload(small.b)
         with pytest.raises(Exception) as e:
             ctx.mul_relin(da, db)
         assert "no relinearisation key" in str(e.value)
-        ctx.load_relin_key(small.k.rlk)
+        ctx.load_relin_key(small.rlk)
         ctx.load_galois_key(1, g1)
         assert np.array_equal(ctx.mul_relin(da, db).download(), small.want)
     finally:
@@ -300,16 +271,16 @@ def test_coexists_with_inner_sum(small, first):
     P = small.P
     n = 16
     gl = P.inner_sum_galois_elements(n)
-    evks = [P.keygen_galois(small.k.sk, g) for g in gl]
+    evks = [P.keygen_galois(small.sk, g) for g in gl]
     ctx = make_context(P)
     try:
         for g, e in zip(gl, evks):
             ctx.load_galois_key(g, e)
-        ctx.load_relin_key(small.k.rlk)
+        ctx.load_relin_key(small.rlk)
         for nl in (2, 3):
             a, b = np.ascontiguousarray(small.a[:, :, :nl]), np.ascontiguousarray(small.b[:, :, :nl])
             da, db = ctx.upload(a), ctx.upload(b)
-            want_mul = small.want if nl == 3 else model.mul_relin_sets(P, a, b, small.k.rlk)
+            want_mul = small.want if nl == 3 else model.mul_relin_sets(P, a, b, small.rlk)
             want_sum = np.stack([P.inner_sum(c, n, evks) for c in a])
             steps = [lambda: np.array_equal(ctx.mul_relin(da, db).download(), want_mul),
                      lambda: np.array_equal(ctx.inner_sum_at_level(da, n).download(), want_sum)]
@@ -354,7 +325,7 @@ def test_end_to_end_device_keys(oracle):
 def test_refusals(oracle, small):
     import ctypes as C
     from lumenos_amd.hip import LumenError
-    P, ctx = small.P, small.k.ctx
+    P, ctx = small.P, small.ctx
     lib = ctx.lib
 
     def fails(fn, text):
@@ -378,11 +349,11 @@ def test_refusals(oracle, small):
     last(lib.lumen_mul_tensor(ctx.h, da.h, db.h, None), "NULL argument")
     last(lib.lumen_mul_tensor(ctx.h, None, db.h, p64(out3)), "NULL argument")
     last(lib.lumen_load_relin_key(ctx.h, None, 0), "NULL argument")
-    last(lib.lumen_load_relin_key(None, p64(small.k.rlk), 0), "NULL argument")
+    last(lib.lumen_load_relin_key(None, p64(small.rlk), 0), "NULL argument")
     # unknown flags
-    last(lib.lumen_load_relin_key(ctx.h, p64(small.k.rlk), 2), "unknown flags", ctx.h)
+    last(lib.lumen_load_relin_key(ctx.h, p64(small.rlk), 2), "unknown flags", ctx.h)
     # a key residue out of range, like a Galois key's
-    bad = small.k.rlk.copy()
+    bad = small.rlk.copy()
     bad[1, 0, 2, 5] = P.moduli[2]
     fails(lambda: ctx.load_relin_key(bad), "out of range")
     # different levels, count mismatch
@@ -413,7 +384,7 @@ def test_refusals(oracle, small):
     try:
         s0 = c0.upload(random_cts(P0, 1, 2, seed=4))
         fails(lambda: c0.mul_relin(s0, s0), "no special primes")
-        last(lib.lumen_load_relin_key(c0.h, p64(small.k.rlk), 0), "no special primes", c0.h)
+        last(lib.lumen_load_relin_key(c0.h, p64(small.rlk), 0), "no special primes", c0.h)
         assert c0.mul_tensor(s0, s0).shape == (1, 3, 2, P0.N)  # the tensor needs no key and no special prime
     finally:
         c0.close()

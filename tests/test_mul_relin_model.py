@@ -18,9 +18,8 @@ import pytest
 
 import keygen_model as km
 import mul_relin_model as model
-from helpers import T_REF, make_params
+from helpers import T_REF, T_SMALL, make_params
 
-T_SMALL = 0x3EE0001  # the plaintext modulus of the reference's vdec tests
 LOG_N, L = 10, 3
 DECRYPTS = {(T_SMALL, 2), (T_SMALL, 3), (T_REF, 3)}
 SEED = bytes(range(40, 72))

@@ -8,7 +8,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BIN = os.path.join(ROOT, "tests", "cpp", "test_placement_host")
 
 
-def build_binary():
+def _build():
     src = os.path.join(ROOT, "tests", "cpp", "test_placement_host.cpp")
     inc = os.path.join(ROOT, "lumenos_amd", "csrc")
     deps = [src, os.path.join(inc, "lm_placement.h")]
@@ -23,7 +23,7 @@ def test_placement_policy():
     candidate never replaces the pick; (d) draws beyond each buffer's first stay within free / 2, the group accumulator
     is drawn at most four times; (e) every drawn, unchosen block is released exactly once and fixed blocks never -- on
     success, with a buffer that has no candidate, and when eval fails on its first or on a later call."""
-    out = subprocess.run([build_binary()], capture_output=True, text=True, timeout=120)
+    out = subprocess.run([_build()], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
     assert "FAIL" not in out.stdout
     for name in ("argmin, eval count, release on success", "ties keep the current pick", "budget and draw order",

@@ -3,18 +3,13 @@ through the C++ host mirror.  CPU: core::DensePoly::Evaluate against Horner in P
 flattening.  GPU: tests/cpp/test_poly_eval_host.cpp proves at a random z != 1 and holds the verifier's claim
 InnerProduct(MatZ, [1, z, z^2, ...]) (fhe/ligero.go:569) to the device P(z) and the host Horner."""
 import random
-import subprocess
 
 import numpy as np
 import pytest
 
-from helpers import build_cpp_twin
+from helpers import twin
 
 T = 144115188075593729  # fhe/ligero_test.go:16
-
-
-def build_binary():
-    return build_cpp_twin("test_poly_eval_host")
 
 
 def horner(coefficients, z, t=T):
@@ -32,8 +27,7 @@ def test_dense_poly_evaluate_matches_python_horner(tmp_path, rows, cols, kind):
     z = 0, 1, T-1 and a random point, against Horner in Python integers over the row-major flattening."""
     points = [0, 1, T - 1, random.Random(rows * 131 + cols).randrange(2, T - 1)]
     path = tmp_path / "m.bin"
-    out = subprocess.run([build_binary(), "host", str(rows), str(cols), kind, str(path)] + [str(z) for z in points],
-                         capture_output=True, text=True, timeout=300)
+    out = twin("test_poly_eval_host", "host", rows, cols, kind, path, *points, timeout=300)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
     m = np.fromfile(path, dtype=np.uint64)
     assert m.size == rows * cols and int(m.max()) < T
@@ -53,7 +47,7 @@ def test_claimed_value_at_a_random_point_end_to_end(shape):
     """TestLigeroE2E's shape (2048 x 1024, LogN 12; also over a ServerGroup of two ranks on the one GPU) and the
     headline one (16384 x 4096, LogN 14): encrypt on the device, Commit, Prove at a random z != 1, decrypt MatZ with
     lumen_decrypt; sum_j z^j MatZ[j] = device P(z) (whole and in uneven column blocks) = host Horner."""
-    res = subprocess.run([build_binary(), "e2e"] + [str(x) for x in shape], capture_output=True, text=True, timeout=1500)
+    res = twin("test_poly_eval_host", "e2e", *shape, timeout=1500)
     assert res.returncode == 0, res.stdout[-3000:] + res.stderr[-3000:]
     print(res.stdout)  # the span times (device and host evaluation), shown with -s
     assert "PASS claimed value" in res.stdout

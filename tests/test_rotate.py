@@ -13,15 +13,14 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from helpers import T_REF, _adversarial_cts, _ntt_primes_near, make_context, make_params, random_cts
+from cells import KeyedCell, cell_cache
+from helpers import (DEGREES, SPLIT_DEGREES, T_REF, T_SMALL, _adversarial_cts, _ntt_primes_near, canonical, make_context,
+                     make_params, random_cts)
 from oracle.loader import Params
 
 gpu = pytest.mark.gpu
 
-DEGREES = (8, 10, 11, 12, 13, 14)
-SPLIT_DEGREES = (15,)  # LM_FOR_EACH_SPLIT_LOGN (pinned by test_ntt_split_model.py); their GPU cases: test_degree15.py
 LEVELS = (1, 2, 3, 4, 5)
-T_SMALL = 0x3EE0001
 NEW_SYMBOLS = ("lumen_galois_element", "lumen_automorphism", "lumen_rotate_columns", "lumen_rotate_rows", "lumen_rotate_hoisted")
 
 
@@ -80,58 +79,29 @@ def test_index_tables_of_the_rotations_permute_aligned_1024_blocks(oracle):
 
 
 # ------------------------------------------------------------------ GPU
-def _canonical(P, got):
-    return all(int(got[:, :, l].max()) < P.moduli[l] for l in range(got.shape[2]))
-
-
 def _oracle_rot(P, cts, g, evk):
     return np.stack([P.automorphism(c, g, evk) for c in cts])
 
 
-class _Cell:
-    """One degree on the reference-style chain: L = 5, K = 2, three five-limb ciphertexts.  Galois keys are generated
-    (by the oracle) and loaded at their first use; the oracle's rotations are computed once per (level, element)."""
+class _Cell(KeyedCell):
+    """One degree on the reference-style chain: L = 5, K = 2, three five-limb ciphertexts; the oracle's rotations are
+    computed once per (level, element)."""
 
     def __init__(self, oracle, log_n):
         self.log_n = log_n
-        self.P = P = make_params(oracle, log_n, 5)
+        P = make_params(oracle, log_n, 5)
         assert (P.L, P.K) == (5, 2)
-        P.seed(5000 + log_n)
-        self.sk = P.keygen_secret()
-        self.ctx = make_context(P)
+        super().__init__(P, 5000 + log_n)
         self.cts = random_cts(P, 3, 5, seed=700 + log_n)
         self.cts.setflags(write=False)
-        self.evks, self._want = {}, {}
-
-    def key(self, g):
-        if g not in self.evks:
-            self.evks[g] = self.P.keygen_galois(self.sk, g)
-            self.ctx.load_galois_key(g, self.evks[g])
-        return self.evks[g]
-
-    def at(self, nl):
-        return np.ascontiguousarray(self.cts[:, :, :nl])
 
     def want(self, nl, g):
-        if (nl, g) not in self._want:
-            w = self.at(nl) if g == 1 else _oracle_rot(self.P, self.at(nl), g, self.key(g))
-            w.setflags(write=False)
-            self._want[(nl, g)] = w
-        return self._want[(nl, g)]
+        return self.cached((nl, g), lambda: self.at(nl) if g == 1 else _oracle_rot(self.P, self.at(nl), g, self.key(g)))
 
 
 @pytest.fixture(scope="module")
 def cells(oracle):
-    made = {}
-
-    def get(log_n):
-        if log_n not in made:
-            made[log_n] = _Cell(oracle, log_n)
-        return made[log_n]
-
-    yield get
-    for c in made.values():
-        c.ctx.close()
+    yield from cell_cache(lambda *k: _Cell(oracle, *k))
 
 
 @gpu
@@ -146,7 +116,7 @@ def test_automorphism_every_degree_and_level(cells, log_n, nl):
         assert got.shape == (3, 2, nl, P.N)
         for c in range(3):
             assert np.array_equal(got[c], want[c]), (g, c)
-        assert _canonical(P, got), g
+        assert canonical(P, got), g
 
 
 @gpu
@@ -162,7 +132,7 @@ def test_other_elements(cells, log_n):
         want = cell.want(5, g)
         got = ctx.automorphism(dev, g).download()
         assert np.array_equal(got, want), g
-        assert _canonical(P, got), g
+        assert canonical(P, got), g
     bare = make_context(P)
     try:
         assert np.array_equal(bare.automorphism(bare.upload(cell.cts), 1).download(), cell.cts)
@@ -294,7 +264,7 @@ def test_one_special_prime(oracle, log_n):
                 got = ctx.automorphism(dev, g).download()
                 assert np.array_equal(got, _oracle_rot(P, cts, g, e)), (nl, g)
                 assert np.array_equal(o.download(), got), (nl, g)
-                assert _canonical(P, got), (nl, g)
+                assert canonical(P, got), (nl, g)
     finally:
         ctx.close()
 
@@ -323,7 +293,7 @@ def test_at_the_modulus_bound(oracle, log_n):
             for g, e in zip(els, evks):
                 got = ctx.automorphism(dev, g).download()
                 assert np.array_equal(got, _oracle_rot(P, cts, g, e)), (nl, g)
-                assert _canonical(P, got), (nl, g)
+                assert canonical(P, got), (nl, g)
     finally:
         ctx.close()
 

@@ -2,29 +2,19 @@
 RotateHoistedNew).  CPU: the twin builds against the mirror.  GPU: tests/cpp/test_rotate_host.cpp -- keys generated on
 the device (KeyGenerator::GenGaloisKeysNew), columns of N slots encrypted under the secret key, the server rotates by
 1 and -3, swaps the rows and rotates hoisted by {1, 2, 5}; the client decrypts the slot permutation."""
-import os
-import subprocess
-
 import pytest
 
-from helpers import build_cpp_twin
-
-
-def build_binary():
-    return build_cpp_twin("test_rotate_host", with_oracle=False)
+from helpers import twin, twin_usage
 
 
 def test_twin_builds_and_prints_its_usage():
-    exe = build_binary()
-    assert os.path.exists(exe)
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=60)
-    assert out.returncode == 2 and "usage: test_rotate_host e2e" in out.stderr
+    twin_usage("test_rotate_host", with_oracle=False)
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("shape", [(12, 16, 3), (14, 64, 2)], ids=["logn12", "logn14"])
 def test_rotations_of_encrypted_columns_end_to_end(shape):
-    res = subprocess.run([build_binary(), "e2e"] + [str(x) for x in shape], capture_output=True, text=True, timeout=600)
+    res = twin("test_rotate_host", "e2e", *shape, with_oracle=False)
     assert res.returncode == 0, res.stdout[-3000:] + res.stderr[-3000:]
     for line in ("PASS RotateColumnsNew by 1 and -3", "PASS RotateRowsNew", "PASS RotateHoistedNew {1, 2, 5}",
                  "PASS identity, input untouched, CopyNew shares the keys"):

@@ -10,8 +10,7 @@ import numpy as np
 import pytest
 
 import vdec_model as vm
-from helpers import T_REF, make_context, make_params, random_cts
-from test_degree_matrix import CHAINS, DEGREES, T_SMALL, _bound_chain
+from helpers import CHAINS, DEGREES, T_REF, T_SMALL, bound_chain, make_context, make_params, random_cts
 
 gpu = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -75,7 +74,7 @@ def _cell(oracle, log_n, chain):
     from lumenos_amd import params as lp
     key = ("cell", log_n, chain)
     if key not in _cache:
-        P = make_params(oracle, log_n, 5) if chain == "reference" else _bound_chain(oracle, log_n, 5, 2)
+        P = make_params(oracle, log_n, 5) if chain == "reference" else bound_chain(oracle, log_n, 5, 2)
         ctx = make_context(P)
         ctx.encoder_set(lp.encoder_psi(T_REF, log_n))
         _cache[key] = (P, ctx)

@@ -1,17 +1,9 @@
 """Proof.ProveDecrypt through the C++ host mirror (cmd/client/main.go:203-208 up to the call into lazer).  CPU:
 vdec::BatchColumns against the oracle's transcript and Python integers.  GPU: tests/cpp/test_vdec_host.cpp runs the
 client of TestLigeroPPD with T = 0x3ee0001 (rows 128, cols 64, logN 11) and checks the witness's relation."""
-import subprocess
-
 import pytest
 
-from helpers import build_cpp_twin
-
-T_SMALL = 0x3EE0001
-
-
-def build_binary():
-    return build_cpp_twin("test_vdec_host")
+from helpers import T_SMALL, twin
 
 
 @pytest.mark.parametrize("name,rows,cols,T", [("vdec", 5, 3, T_SMALL), ("vdec", 1, 7, 144115188075593729), ("other", 4, 1, T_SMALL)])
@@ -19,7 +11,7 @@ def test_batch_columns_matches_python(oracle, name, rows, cols, T):
     """batching.go:43-64: one SampleUints("pod_alpha", rows words) per column, in column order; raw words, reduced where
     they are multiplied; m[i] = sum_j col_j[i] * alpha_j[i] mod T."""
     from oracle.loader import Transcript
-    out = subprocess.run([build_binary(), "host", name, str(rows), str(cols), str(T)], capture_output=True, text=True, timeout=300)
+    out = twin("test_vdec_host", "host", name, rows, cols, T, timeout=300)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
     got = {"col": {}, "alpha": {}, "m": {}}
     nxt = None
@@ -41,7 +33,7 @@ def test_batch_columns_matches_python(oracle, name, rows, cols, T):
 
 @pytest.mark.gpu
 def test_client_proves_decryption_up_to_lazer():
-    res = subprocess.run([build_binary(), "e2e", "11", "128", "64"], capture_output=True, text=True, timeout=600)
+    res = twin("test_vdec_host", "e2e", 11, 128, 64)
     print(res.stdout)  # the span times, shown with -s
     assert res.returncode == 0, res.stdout[-3000:] + res.stderr[-3000:]
     for span in ("Verifiable decrypt (", "Batching decrypted columns (", "Batching ciphertexts (", "Witness generation ("):

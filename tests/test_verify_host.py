@@ -3,17 +3,12 @@ EncryptedProof::Decrypt, Proof::Verify over lumen_verify_columns).  CPU: what Ve
 it touches the device, and its error strings, against the oracle's transcript and Python integers.  GPU:
 tests/cpp/test_verify_host.cpp proves at a random z != 1, verifies, and tampers with the marshaled bytes."""
 import random
-import subprocess
 
 import pytest
 
-from helpers import build_cpp_twin
+from helpers import twin
 
 T = 144115188075593729  # fhe/ligero_test.go:16
-
-
-def build_binary():
-    return build_cpp_twin("test_verify_host")
 
 
 @pytest.mark.parametrize("name,rows,cols,queries", [("demo", 2048, 1024, 309), ("test", 512, 16, 24), ("x", 7, 3, 5)])
@@ -24,8 +19,7 @@ def test_what_verify_derives_from_the_transcript_matches_python(oracle, name, ro
     from oracle.loader import Transcript
     rho = 2
     z = random.Random(rows * 31 + cols).randrange(2, T - 1)
-    out = subprocess.run([build_binary(), "host", name, str(rows), str(cols), str(rho), str(queries), str(z)],
-                         capture_output=True, text=True, timeout=300)
+    out = twin("test_verify_host", "host", name, rows, cols, rho, queries, z, timeout=300)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
     got = {"r": {}, "a": {}, "b": {}, "query": {}, "message": {}}
     w = None
@@ -59,7 +53,7 @@ def test_client_unmarshals_decrypts_and_verifies_end_to_end(shape):
     """TestLigeroE2E's shape (2048 x 1024, LogN 12) and the headline one (16384 x 4096, LogN 14): the honest proof
     verifies under the reference's four client spans; each tampering throws the reference's string for the reference's
     column."""
-    res = subprocess.run([build_binary(), "e2e"] + [str(x) for x in shape], capture_output=True, text=True, timeout=1500)
+    res = twin("test_verify_host", "e2e", *shape, timeout=1500)
     print(res.stdout)  # the span times, shown with -s
     assert res.returncode == 0, res.stdout[-3000:] + res.stderr[-3000:]
     for span in ("Decrypt queried columns (", "Decrypt row inner products (", "Decrypt proof (", "Verify proof ("):
