@@ -87,7 +87,10 @@ int lumen_ctx_wait(lumen_ctx *ctx, lumen_ctx *other);
  * "LUMEN_MODDOWN_TGROUP" (work-list order of the key switch's two transform kernels), "LUMEN_KS_PLACEMENT" (candidate
  * blocks per key-switch scratch buffer among which a context's first key switch picks by measurement, 0 = none:
  * takes effect when the buffers are next allocated, e.g. after lumen_ctx_trim), "LUMEN_BATCH_CHUNKS" (chunks of columns
- * per limb in lumen_batch_ciphertexts, 0 .. 4096, 0 = derived from the CU count; the residues do not depend on it).  An
+ * per limb in lumen_batch_ciphertexts, 0 .. 4096, 0 = derived from the CU count; the residues do not depend on it),
+ * "LUMEN_DOT_PAIRS" (coefficient pairs per block of the dot product's tensor kernel, 256 or 512, 0 = by the size of the
+ * launch; same residues), "LUMEN_DOT_PARTS" (blocks the terms of one sum are split over there, 1 .. 256, 0 = by the size
+ * of the launch; same residues).  An
  * unknown name or a value out of a switch's range is an error and changes nothing. */
 int lumen_ctx_set_tuning(lumen_ctx *ctx, const char *name, long value);
 /* TEST HOOK (not a tuning switch, never read from the environment): lumen_group_create then lets LUMEN_TRANSPORT_RCCL
@@ -407,6 +410,35 @@ uint32_t lumen_inner_sum_general_elements(const lumen_ctx *ctx, uint32_t batch_s
 int lumen_load_relin_key(lumen_ctx *ctx, const uint64_t *evk, uint32_t flags);
 int lumen_mul_relin(lumen_ctx *ctx, const lumen_set *a, const lumen_set *b, lumen_set **out);
 int lumen_mul_tensor(lumen_ctx *ctx, const lumen_set *a, const lumen_set *b, uint64_t *host_out /* [count][3][nl][N] */);
+
+/* ---- sums of ciphertext products with ONE relinearisation per sum: the dot product of two encrypted vectors, or an
+ * encrypted matrix times an encrypted vector, on the *bgv.Evaluator that ServerBFV embeds (fhe/bfv.go:13-21; the product is
+ * fhe/bfv.go:34-42 with ciphertext operands).  It stands for the Lattigo sequence ([LATTIGO-RECALL])
+ *     acc = MulNew(a_0, b_0)            (no relinearisation: degree 2)
+ *     MulThenAdd(a_i, b_i, acc)         for 0 < i < n
+ *     Relinearize(acc)
+ * in which the degree-2 terms add up and the hybrid key switch runs once per sum.  `a` holds groups * n ciphertexts of one
+ * level, 1 <= nl <= L; term i of group g is a[g n + i].  `b` holds as many (pairwise: b[g n + i]) or exactly n (one vector
+ * against every group, matrix x vector: b[i]); with a's count == n the two forms coincide.  a == b is allowed (sums of
+ * squares).  With e = g n + i, for every Q limb l < nl, coefficient-wise mod q_l:
+ *     D0 = T sum_i a0_e b0_e      D1 = T sum_i (a0_e b1_e + a1_e b0_e)      D2 = T sum_i a1_e b1_e
+ *     (k0, k1) = the hybrid key switch of D2 at level nl under the relinearisation key
+ *     out[g] = (D0 + k0, D1 + k1)                                            (canonical residues)
+ * out: a new set of `groups` ciphertexts at the level of a; a's count == 0 gives an empty set.  The scale is
+ * scale_a * scale_b mod T as for lumen_mul_relin (all terms of a sum must share it: the caller tracks it).
+ * NOISE: one key-switch term per sum, where n calls of lumen_mul_relin added up carry n; the products' own noise adds,
+ * about n * T^2 * N * B, and must stay under Q_level / 2.  The words differ from the sum of n lumen_mul_relin results
+ * (the key switch is not linear in its digits' rounding); both decrypt alike.
+ * lumen_mul_counter grows by a's count (the products formed).  Batching, lanes and scratch are lumen_mul_relin's, over
+ * the `groups` outputs.  Every ring degree lumen_mul_relin serves is served, 2^15 included.
+ * lumen_mul_tensor_dot: (D0, D1, D2) before relinearisation, for parity tests: host, [groups][3][nl][N]; needs no key and
+ * no special prime; leaves lumen_mul_counter as it is.
+ * Refused with a message, before any device work: NULL arguments; n == 0; a's count no multiple of n; b's count neither
+ * a's nor n; operands of different levels; a lane-sharded set; a limb count outside [1, L]; and, lumen_mul_relin_dot alone:
+ * no special primes (K = 0) or more than two; no relinearisation key loaded. */
+int lumen_mul_relin_dot(lumen_ctx *ctx, const lumen_set *a, const lumen_set *b, uint32_t n, lumen_set **out);
+int lumen_mul_tensor_dot(lumen_ctx *ctx, const lumen_set *a, const lumen_set *b, uint32_t n,
+                         uint64_t *host_out /* [groups][3][nl][N] */);
 
 /* ---- rotations: Evaluator.Automorphism, RotateColumnsNew, RotateRowsNew and RotateHoistedNew of the *bgv.Evaluator that
  * ServerBFV embeds (fhe/bfv.go:13-21), with the Galois keys lumen_load_galois_key[_ex] loaded (lumen_keygen_galois makes

@@ -98,6 +98,10 @@ struct lm_tuning {
     uint32_t ks_placement = 6;
     // LUMEN_BATCH_CHUNKS: chunks of columns per Q limb in k_batch_mac (lm_vdec.hip); 0 = limbs * chunks at about the CU count
     uint32_t batch_chunks = 0;
+    // LUMEN_DOT_PAIRS: coefficient pairs per block of k_tensor_dot (lm_mulrelin.hip), 256 or 512; 0 = by the size of the launch
+    uint32_t dot_pairs = 0;
+    // LUMEN_DOT_PARTS: blocks a group's terms are split over in k_tensor_dot, 1 .. 256 (at most the terms); 0 = by the size of the launch
+    uint32_t dot_parts = 0;
     // lumen_test_allow_shared_device_rccl (tests only; not reachable through lumen_ctx_set_tuning or the environment):
     // LUMEN_TRANSPORT_RCCL accepts ranks that share a device, for the test double tests/cpp/fake_rccl.cpp
     uint32_t rccl_shared_device = 0;

@@ -211,6 +211,12 @@ static int tuning_set(lm_tuning &t, const char *name, long v) {
     } else if (n == "LUMEN_BATCH_CHUNKS") { // 0: the derived default
         if (!in(0, 4096)) return 2;
         t.batch_chunks = (uint32_t)v;
+    } else if (n == "LUMEN_DOT_PAIRS") { // 0: by the size of the launch
+        if (v != 0 && v != 256 && v != 512) return 2;
+        t.dot_pairs = (uint32_t)v;
+    } else if (n == "LUMEN_DOT_PARTS") { // 0: by the size of the launch
+        if (!in(0, 256)) return 2;
+        t.dot_parts = (uint32_t)v;
     } else {
         return 1;
     }
@@ -218,7 +224,7 @@ static int tuning_set(lm_tuning &t, const char *name, long v) {
 }
 static void tuning_from_env(lm_tuning &t) {
     for (const char *n : {"LUMEN_KS_BATCH", "LUMEN_KS_LANES", "LUMEN_KS_FUSED_DIGITS", "LUMEN_KS_CLOSE_FUSED", "LUMEN_KS_C0_FOLD", "LUMEN_DEBUG",
-                          "LUMEN_MODUP_TGROUP", "LUMEN_MODDOWN_TGROUP", "LUMEN_KS_PLACEMENT", "LUMEN_BATCH_CHUNKS"}) {
+                          "LUMEN_MODUP_TGROUP", "LUMEN_MODDOWN_TGROUP", "LUMEN_KS_PLACEMENT", "LUMEN_BATCH_CHUNKS", "LUMEN_DOT_PAIRS", "LUMEN_DOT_PARTS"}) {
         const char *e = getenv(n);
         // an empty override counts as unset; a value out of range is reported and leaves the default
         if (e && *e && tuning_set(t, n, atol(e)))

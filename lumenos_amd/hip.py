@@ -126,6 +126,8 @@ SYMBOLS = {
     "lumen_rotate_rows": (C.c_int, [_vp, _vp, _vpp]),
     "lumen_rotate_hoisted": (C.c_int, [_vp, _vp, _u64p, C.c_uint32, _vpp]),
     "lumen_mul_tensor": (C.c_int, [_vp, _vp, _vp, _u64p]),
+    "lumen_mul_relin_dot": (C.c_int, [_vp, _vp, _vp, C.c_uint32, _vpp]),
+    "lumen_mul_tensor_dot": (C.c_int, [_vp, _vp, _vp, C.c_uint32, _u64p]),
     "lumen_add": (C.c_int, [_vp, _vp, _vp, _vpp]),
     "lumen_sub": (C.c_int, [_vp, _vp, _vp, _vpp]),
     "lumen_mul_scalar": (C.c_int, [_vp, _vp, C.c_uint64, _vpp]),
@@ -726,6 +728,19 @@ class Context:
         """the degree-2 ciphertexts (d0, d1, d2) of a x b before relinearisation: [count][3][limbs][N]"""
         out = np.zeros((a.count, 3, a.nl, self.N), dtype=np.uint64)
         self._ck(self.lib.lumen_mul_tensor(self.h, a.h, b.h, _p64(out)))
+        return out
+
+    def mul_relin_dot(self, a, b, n):
+        """One ciphertext per group of n terms: sum_i a[g n + i] * b[g n + i] (b of a's count) or sum_i a[g n + i] * b[i]
+        (b of n ciphertexts), relinearised ONCE per sum -- MulNew, MulThenAdd ..., Relinearize"""
+        h = C.c_void_p()
+        self._ck(self.lib.lumen_mul_relin_dot(self.h, a.h, b.h, n, C.byref(h)))
+        return DeviceSet(self, h)
+
+    def mul_tensor_dot(self, a, b, n):
+        """the summed degree-2 ciphertexts (D0, D1, D2) of mul_relin_dot before relinearisation: [groups][3][limbs][N]"""
+        out = np.zeros((a.count // n if n else 0, 3, a.nl, self.N), dtype=np.uint64)
+        self._ck(self.lib.lumen_mul_tensor_dot(self.h, a.h, b.h, n, _p64(out)))
         return out
 
     # the evaluator's linear operations (Evaluator.Add / Sub / Mul(ct, uint64) / MulThenAdd): out=None makes a new set,

@@ -659,6 +659,21 @@ Ciphertexts ServerBFV::MulRelinNew(const Ciphertexts &a, const Ciphertexts &b) {
     return Ciphertexts(Context(), set, md);
 }
 
+Ciphertexts ServerBFV::DotRelinNew(const Ciphertexts &a, const Ciphertexts &b, uint32_t n) {
+    if (!a.Handle() || !b.Handle()) throw std::invalid_argument("DotRelinNew: an operand holds no ciphertexts");
+    if (n == 0) throw std::invalid_argument("DotRelinNew: a sum of no terms (n == 0)");
+    if (a.Len() % (int)n) throw std::invalid_argument("DotRelinNew: the first operand's count is no multiple of n");
+    if (b.Len() != a.Len() && b.Len() != (int)n)
+        throw std::invalid_argument("DotRelinNew: the second operand has neither the first one's count nor n ciphertexts");
+    if (a.Level() != b.Level()) throw std::invalid_argument("DotRelinNew: the operands have different levels");
+    lumen_set *set = nullptr;
+    check(lumen_mul_relin_dot(Context(), a.Handle(), b.Handle(), n, &set), "lumen_mul_relin_dot");
+    MetaData md = a.Meta;
+    const uint64_t T = params_.T;
+    md.Scale = MulMod(a.Scale() % T, b.Scale() % T, T); // bgv: Scale_a * Scale_b, MulRelinNew's
+    return Ciphertexts(Context(), set, md);
+}
+
 void ServerBFV::LoadGaloisKeys(const std::map<uint64_t, std::vector<uint64_t>> &keys, uint32_t flags) {
     for (const auto &kv : keys)
         if (kv.second.size() != evk_words(params_) || kv.second.empty())

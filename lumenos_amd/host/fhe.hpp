@@ -278,6 +278,12 @@ class ServerBFV : public LinearEvaluator {
     // holds one ciphertext; a and b of one level (a and b may be the same object: squares).  The result's Scale() is
     // a.Scale() * b.Scale() mod T; MulCounter() grows by a.Len().  Needs the relinearisation key.
     Ciphertexts MulRelinNew(const Ciphertexts &a, const Ciphertexts &b);
+    // Sums of n products with ONE relinearisation each -- Evaluator.MulNew(a_0, b_0), MulThenAdd(a_i, b_i, acc) for the
+    // other terms, Relinearize(acc) --: out[g] = sum_i a[g n + i] * b[g n + i] when b has a's count, sum_i a[g n + i] * b[i]
+    // when b holds n ciphertexts (matrix x vector).  One level, a and b may be the same object; Scale() and the key are
+    // MulRelinNew's, MulCounter() grows by a.Len().  std::invalid_argument: empty operands, n == 0, a.Len() no multiple of
+    // n, b.Len() neither a.Len() nor n, different levels (lumen_mul_relin_dot).
+    Ciphertexts DotRelinNew(const Ciphertexts &a, const Ciphertexts &b, uint32_t n);
     // Galois keys for arbitrary elements, beside whatever the constructor loaded (evk.GaloisKeys of an
     // rlwe.MemEvaluationKeySet holds any element the client generated): element -> [beta][b|a][L+K][N] as
     // KeyGenerator::GenGaloisKeysNew returns them, in `flags`' form.  CopyNews share them; loading an element again replaces its key.
