@@ -464,6 +464,48 @@ int lumen_rotate_rows(lumen_ctx *ctx, const lumen_set *in, lumen_set **out);
 int lumen_rotate_hoisted(lumen_ctx *ctx, const lumen_set *in, const uint64_t *gal_els, uint32_t n_els,
                          lumen_set **outs /* [n_els] new sets */);
 
+/* ---- the diagonal linear transform: a plaintext matrix times an encrypted vector by the diagonal method,
+ *     out = sum_k diag_k (.) Rot_k(ct)
+ * [LATTIGO-RECALL] Evaluator.MultiplyByDiagMatrix, the non-BSGS branch of LinearTransformation / LinearTransformationsNew
+ * of the lintrans evaluator, which sits on the *bgv.Evaluator that ServerBFV embeds (fhe/bfv.go:13-21).  Single-hoisted:
+ * one decomposition of c1, per non-zero diagonal one gadget product and one multiply-accumulate over Q and P, and ONE
+ * ModDown for the whole sum -- where lumen_rotate_hoisted followed by lumen_mul_plain_then_add pays one ModDown, one
+ * output set and one product pass per diagonal.  Limits: no baby-step / giant-step (double-hoisted) form; column
+ * rotations only (no row swap among the diagonals); 1 or 2 special primes.  Prove does not use the transform.
+ * lumen_lintrans_load (LinearTransformation's encoding, NewLinearTransformation + Encode): n >= 1 diagonals at the level of
+ * nl limbs, 1 <= nl <= L.  k[d]: the diagonal's index, |k| < N/2, taken modulo N/2; its Galois element is
+ * lumen_galois_element(k).  pts: host [n][nl + K][N], diagonal d as a plaintext over Q and P -- limbs 0..nl-1 residues
+ * modulo q_0..q_{nl-1}, limbs nl..nl+K-1 residues modulo the special primes, NTT domain, canonical, in the form
+ * Encoder.Encode leaves and lumen_mul_plain takes (m * T^-1).  The multiplier is m_k = pt_k * T per limb, as MulNew's; it
+ * is formed once, here, and stays on the device until lumen_lintrans_destroy (ctx: the loading context or a clone; NULL
+ * after the context is gone).  A transform serves the context that loaded it and its clones.
+ * lumen_lintrans_galois_elements: the elements of the non-zero diagonals in the order given, into gal_els (room for n);
+ * returns their number.  The keys of exactly these must be loaded (lumen_load_galois_key[_ex]).
+ * lumen_linear_transform (LinearTransformationNew): `in`, a set of any count at the transform's level, is not modified.
+ * With dig = the digits of c1, (u0, u1)_k = the gadget product of dig under the key of g_k over the nl limbs of Q and the
+ * K of P, and sigma_g the NTT-domain permutation of lumen_automorphism:
+ *     acc = sum_{k != 0} m_k (.) sigma_{g_k}(u0_k + (P c0 on Q, 0 on P), u1_k)          (over Q and P, no ModDown)
+ *     out = ModDown(acc) (+ m_0 (.) (c0, c1) when 0 is among the diagonals)            (canonical residues)
+ * in a new set of the same count and level.  The scale is lumen_mul_plain's.  The words differ from those of the rotations
+ * multiplied and added up one by one (the floor of ModDown does not commute with the sum); both decrypt alike.
+ * A transform with diagonal 0 alone needs no key, runs no key switch and gives lumen_mul_plain's words.  count == 0 gives
+ * an empty set and looks no key up.  lumen_mul_counter does not move (it counts the Mul / MulNew wrappers, as for the
+ * rotations).  Batching, lanes and scratch are the key switch's; every ring degree is served, 2^15 included.
+ * lumen_linear_transforms (LinearTransformationsNew): outs[i] = lumen_linear_transform(in, lts[i]) word for word, with the
+ * decomposition of c1 done once per batch and shared by the transforms.  n_lts == 0 does nothing.  On failure every
+ * outs[i] is NULL.
+ * Refused with a message, before anything is allocated or enqueued: NULL arguments; n == 0; nl outside [1, L]; |k| >= N/2;
+ * two diagonals equal modulo N/2; a residue >= its modulus; no special primes (K = 0) or more than two; a set at another
+ * level than the transform's; a transform of another context; a lane-sharded set; no key loaded for a diagonal's element. */
+typedef struct lumen_lintrans lumen_lintrans;
+int lumen_lintrans_load(lumen_ctx *ctx, const int64_t *k, const uint64_t *pts /* host [n][nl+K][N] */, uint32_t n,
+                        uint32_t nl, lumen_lintrans **out);
+void lumen_lintrans_destroy(lumen_ctx *ctx, lumen_lintrans *lt);
+uint32_t lumen_lintrans_galois_elements(const lumen_lintrans *lt, uint64_t *gal_els);
+int lumen_linear_transform(lumen_ctx *ctx, const lumen_set *in, const lumen_lintrans *lt, lumen_set **out);
+int lumen_linear_transforms(lumen_ctx *ctx, const lumen_set *in, const lumen_lintrans *const *lts, uint32_t n_lts,
+                            lumen_set **outs /* [n_lts] new sets */);
+
 /* ---- the evaluator's linear operations: Evaluator.Add / Sub / Mul(ct, uint64) / MulThenAdd of the *bgv.Evaluator that
  * ServerBFV embeds (fhe/bfv.go:13-21), with a ciphertext, a scalar or a plaintext operand -- the calls fhe/ntt.go:27-236 and
  * vdec/batching.go:24-34 make one ciphertext at a time, here on whole sets, so that a caller can write another butterfly

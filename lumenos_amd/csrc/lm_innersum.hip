@@ -138,7 +138,10 @@ int general_check(lumen_ctx *ctx, uint32_t batch, uint32_t n, const char *what) 
     return 0;
 }
 
-// ---- the lazy accumulator: a block of s.u's size and layout per lane, words canonical
+} // namespace
+
+// ---- the lazy accumulator: a block of s.u's size and layout per lane, words canonical.  lazy_blocks, identity_tables and
+// lazy_close are the diagonal linear transform's too (lm_ks_host.h)
 
 // one more block per lane, of the gadget product's size at the top level
 int lazy_blocks(lumen_ctx *ctx, const KsRun &run, u64 **lazy) {
@@ -151,7 +154,7 @@ int lazy_blocks(lumen_ctx *ctx, const KsRun &run, u64 **lazy) {
 // A term, after rotate_mac under its key (u = s.u, index = the key's gather table): lazy = (first ? 0 : lazy) +
 // sigma(u + (c0, 0)) over Q and P, no ModDown; `first` stores where later terms add.  The close's first step (u and index
 // NULL, the identity): lazy_1 += cur.c1 on the Q limbs.  cur in [0, 2q).
-int lazy_gather(lumen_ctx *ctx, const u64 *u, const u64 *cur, u64 *lazy, const uint32_t *index, bool first, uint32_t B, KsTables *tb) {
+static int lazy_gather(lumen_ctx *ctx, const u64 *u, const u64 *cur, u64 *lazy, const uint32_t *index, bool first, uint32_t B, KsTables *tb) {
     lm_prof_scope ps(ctx, "ks_lazy_gather", (uint64_t)B);
     hipLaunchKernelGGL(k_lazy_gather, dim3(2048), dim3(256), 0, ctx->stream, u, cur, lazy, index, B, tb->nl, ctx->K, ctx->L - tb->nl,
                        ctx->logN, first ? 1u : 0u, ctx->mods);
@@ -189,6 +192,8 @@ int lazy_close(lumen_ctx *ctx, const u64 *cur, u64 *out, u64 *lazy, uint32_t B, 
     sl.u = lazy;
     return rotate_store(ctx, cur, out, B, *id, tb, sl);
 }
+
+namespace {
 
 // ---- InnerSum(., batch, n) of the B columns of acc, in place: canonical when the plan has lazy terms, in [0, 2q) when
 // it has none.  `lazy`: the lane's lazy accumulator (a plan with lazy terms).  With close_out (a rescale follows a plan

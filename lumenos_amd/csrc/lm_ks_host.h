@@ -2,7 +2,7 @@
 // (lm_keyswitch.hip), the batch driver of its callers (lm_ks_batch.hip), the callers themselves -- InnerSum and
 // matrixInnerSumEval (lm_innersum.hip), the rotation on its own (lm_rotate.hip), the ciphertext x ciphertext product
 // that ends in a key switch (lm_mulrelin.hip) --, the placement of the scratch buffers (lm_ks_scratch.hip), the closing
-// rotation before a rescale (lm_ks_close.hip), the switching keys (lm_ks_key.hip) and the ciphertext x plaintext
+// rotation before a rescale (lm_ks_close.hip), the diagonal linear transform (lm_lintrans.hip), the switching keys (lm_ks_key.hip) and the ciphertext x plaintext
 // product that precedes an InnerSum (lm_mulplain.hip).
 #pragma once
 #include "lm_ks_dev.h"
@@ -83,8 +83,20 @@ int get_scratch(lumen_ctx *ctx, uint32_t B, KsTables *tb, KsScratch *s, int lane
 
 // step 0, MulNew(ct, pt) (lm_mulplain.hip): the plaintext as the device multiplier pt * T, and out = ct (.) it
 int upload_ptT(lumen_ctx *ctx, const uint64_t *pt, uint32_t nl, u64 **out);
+// the conversion alone, device to device: raw residues [np][N] by position at the level of nl limbs, np == nl (over Q)
+// or nl + K (over Q and P: a diagonal of lumen_lintrans_load), to pt * T in Montgomery form
+int launch_pt_prepare(lumen_ctx *ctx, const u64 *raw, u64 *ptM, uint32_t nl, uint32_t np);
 int launch_mul_plain(lumen_ctx *ctx, const u64 *ct, u64 *out, const u64 *ptT, size_t words, uint32_t nl,
                      uint32_t ncts);
+
+// ---- InnerSum's lazy accumulator over Q and P (lm_innersum.hip), shared with the diagonal linear transform
+// (lm_lintrans.hip).  lazy_blocks: per lane one block of s.u's size and layout at the top level.  identity_tables: the
+// identity's gather tables, owned by the context.  lazy_close: out = ModDown(lazy) + cur for every column, canonical; cur
+// in [0, 2q), `out` another block than `cur`, lazy is consumed.
+struct KsRun;
+int lazy_blocks(lumen_ctx *ctx, const KsRun &run, u64 **lazy);
+int identity_tables(lumen_ctx *ctx, std::shared_ptr<lm_galois_key> *out);
+int lazy_close(lumen_ctx *ctx, const u64 *cur, u64 *out, u64 *lazy, uint32_t B, KsTables *tb, const KsScratch &s);
 
 // the relinearisation key as a switching key with identity gather tables (lm_ks_key.hip); empty before lumen_load_relin_key
 std::shared_ptr<lm_galois_key> lm_relin_key(lumen_ctx *ctx);

@@ -125,6 +125,11 @@ SYMBOLS = {
     "lumen_rotate_columns": (C.c_int, [_vp, _vp, C.c_int64, _vpp]),
     "lumen_rotate_rows": (C.c_int, [_vp, _vp, _vpp]),
     "lumen_rotate_hoisted": (C.c_int, [_vp, _vp, _u64p, C.c_uint32, _vpp]),
+    "lumen_lintrans_load": (C.c_int, [_vp, C.POINTER(C.c_int64), _u64p, C.c_uint32, C.c_uint32, _vpp]),
+    "lumen_lintrans_destroy": (None, [_vp, _vp]),
+    "lumen_lintrans_galois_elements": (C.c_uint32, [_vp, _u64p]),
+    "lumen_linear_transform": (C.c_int, [_vp, _vp, _vp, _vpp]),
+    "lumen_linear_transforms": (C.c_int, [_vp, _vp, _vpp, C.c_uint32, _vpp]),
     "lumen_mul_tensor": (C.c_int, [_vp, _vp, _vp, _u64p]),
     "lumen_mul_relin_dot": (C.c_int, [_vp, _vp, _vp, C.c_uint32, _vpp]),
     "lumen_mul_tensor_dot": (C.c_int, [_vp, _vp, _vp, C.c_uint32, _u64p]),
@@ -331,6 +336,25 @@ class DeviceSet:
     def __del__(self):
         try:
             self.free()
+        except Exception:
+            pass
+
+
+class Lintrans:
+    """A resident diagonal linear transform (lumen_lintrans): the diagonals as device multipliers at one level."""
+
+    def __init__(self, ctx, handle, ks, nl):
+        self.ctx, self.h, self.ks, self.nl = ctx, handle, list(ks), nl
+
+    def close(self):
+        if self.h:
+            # a transform outliving its context (interpreter shutdown order) is released without waiting for its stream
+            self.ctx.lib.lumen_lintrans_destroy(self.ctx.h if self.ctx.h else None, self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
         except Exception:
             pass
 
@@ -723,6 +747,36 @@ class Context:
         hs = (C.c_void_p * max(g.size, 1))()
         self._ck(self.lib.lumen_rotate_hoisted(self.h, s.h, _p64(g) if g.size else _p64(np.zeros(1, dtype=np.uint64)), g.size, hs))
         return [DeviceSet(self, C.c_void_p(hs[i])) for i in range(g.size)]
+
+    def lintrans_load(self, diags, nl=None):
+        """LinearTransformation: diags {k: pt_k}, pt_k a plaintext over Q and P, [nl + K][N] residues in Encoder.Encode's
+        form (limbs of the level's Q, then of P); |k| < N / 2.  nl=None: the top level"""
+        nl = self.L if nl is None else nl
+        ks = np.array([int(k) for k in diags], dtype=np.int64)
+        pts = np.ascontiguousarray([np.asarray(diags[k], dtype=np.uint64) for k in diags], dtype=np.uint64)
+        assert pts.shape == (len(ks), nl + self.K, self.N), pts.shape
+        h = C.c_void_p()
+        self._ck(self.lib.lumen_lintrans_load(self.h, ks.ctypes.data_as(C.POINTER(C.c_int64)), _p64(pts), len(ks), nl, C.byref(h)))
+        return Lintrans(self, h, ks, nl)
+
+    def lintrans_galois_elements(self, lt):
+        """the Galois elements of the transform's non-zero diagonals, in the order given: the keys it needs"""
+        g = np.zeros(max(len(lt.ks), 1), dtype=np.uint64)
+        cnt = self.lib.lumen_lintrans_galois_elements(lt.h, _p64(g))
+        return [int(x) for x in g[:cnt]]
+
+    def linear_transform(self, s, lt):
+        """LinearTransformationNew: sum_k diag_k (.) Rot_k(ct) for every ciphertext of `s`, hoisted, one ModDown"""
+        h = C.c_void_p()
+        self._ck(self.lib.lumen_linear_transform(self.h, s.h, lt.h, C.byref(h)))
+        return DeviceSet(self, h)
+
+    def linear_transforms(self, s, lts):
+        """LinearTransformationsNew: one set per transform, the decomposition of c1 shared by all"""
+        hs = (C.c_void_p * max(len(lts), 1))()
+        ls = (C.c_void_p * max(len(lts), 1))(*[lt.h for lt in lts])
+        self._ck(self.lib.lumen_linear_transforms(self.h, s.h, ls, len(lts), hs))
+        return [DeviceSet(self, C.c_void_p(hs[i])) for i in range(len(lts))]
 
     def mul_tensor(self, a, b):
         """the degree-2 ciphertexts (d0, d1, d2) of a x b before relinearisation: [count][3][limbs][N]"""

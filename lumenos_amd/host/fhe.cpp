@@ -718,6 +718,66 @@ std::map<int, Ciphertexts> ServerBFV::RotateHoistedNew(const Ciphertexts &ct, co
     return out;
 }
 
+// ---- the diagonal linear transform
+LinearTransformation &LinearTransformation::operator=(LinearTransformation &&o) noexcept {
+    if (this != &o) {
+        if (lt_) lumen_lintrans_destroy(ctx_, lt_);
+        ctx_ = o.ctx_, lt_ = o.lt_, level_ = o.level_, diagonals_ = o.diagonals_;
+        o.ctx_ = nullptr, o.lt_ = nullptr, o.level_ = -1, o.diagonals_ = 0;
+    }
+    return *this;
+}
+
+LinearTransformation::~LinearTransformation() {
+    if (lt_) lumen_lintrans_destroy(ctx_, lt_);
+}
+
+std::vector<uint64_t> LinearTransformation::GaloisElements() const {
+    std::vector<uint64_t> els(std::max<size_t>(diagonals_, 1));
+    els.resize(lumen_lintrans_galois_elements(lt_, els.data()));
+    return els;
+}
+
+LinearTransformation ServerBFV::NewLinearTransformation(const std::map<int, std::vector<uint64_t>> &diagonals, int level) {
+    if (diagonals.empty()) throw std::invalid_argument("NewLinearTransformation: no diagonal");
+    if (level < 0 || level >= (int)params_.Q.size()) throw std::invalid_argument("NewLinearTransformation: no such level");
+    std::vector<int64_t> ks;
+    std::vector<uint64_t> pts;
+    for (const auto &kv : diagonals) {
+        const Plaintext pt = EncodeQP(kv.second, level);
+        ks.push_back(kv.first);
+        pts.insert(pts.end(), pt.Value.begin(), pt.Value.end());
+    }
+    LinearTransformation lt;
+    check(lumen_lintrans_load(Context(), ks.data(), pts.data(), (uint32_t)ks.size(), (uint32_t)level + 1, &lt.lt_), "lumen_lintrans_load");
+    lt.ctx_ = Context(), lt.level_ = level, lt.diagonals_ = ks.size();
+    return lt;
+}
+
+Ciphertexts ServerBFV::LinearTransformationNew(const Ciphertexts &ct, const LinearTransformation &lt) {
+    if (!ct.Handle()) throw std::invalid_argument("LinearTransformationNew: the operand holds no ciphertexts");
+    if (!lt.Handle()) throw std::invalid_argument("LinearTransformationNew: an empty transformation");
+    lumen_set *set = nullptr;
+    check(lumen_linear_transform(Context(), ct.Handle(), lt.Handle(), &set), "lumen_linear_transform");
+    return Ciphertexts(Context(), set, ct.Meta);
+}
+
+std::vector<Ciphertexts> ServerBFV::LinearTransformationsNew(const Ciphertexts &ct, const std::vector<const LinearTransformation *> &lts) {
+    if (!ct.Handle()) throw std::invalid_argument("LinearTransformationsNew: the operand holds no ciphertexts");
+    std::vector<const lumen_lintrans *> hs;
+    for (const LinearTransformation *lt : lts) {
+        if (!lt || !lt->Handle()) throw std::invalid_argument("LinearTransformationsNew: an empty transformation");
+        hs.push_back(lt->Handle());
+    }
+    std::vector<lumen_set *> sets(std::max<size_t>(hs.size(), 1), nullptr);
+    const lumen_lintrans *none = nullptr; // (the list pointer is never NULL, even for no transformation at all)
+    check(lumen_linear_transforms(Context(), ct.Handle(), hs.empty() ? &none : hs.data(), (uint32_t)hs.size(), sets.data()),
+          "lumen_linear_transforms");
+    std::vector<Ciphertexts> out;
+    for (size_t i = 0; i < hs.size(); i++) out.emplace_back(Context(), sets[i], ct.Meta);
+    return out;
+}
+
 Ciphertexts ServerBFV::InnerSumNew(const Ciphertexts &ct, int batchSize, int n) {
     if (!ct.Handle()) throw std::invalid_argument("InnerSumNew: the operand holds no ciphertexts");
     if (batchSize < 1 || n < 1) throw std::invalid_argument("InnerSumNew: batchSize and n must be at least 1");
@@ -859,20 +919,29 @@ void LinearEvaluator::MulThenAdd(const Ciphertexts &ct, const Plaintext &pt, Cip
     check(lumen_mul_plain_then_add(Context(), ct.Handle(), words, acc.Handle()), "lumen_mul_plain_then_add");
 }
 
-Plaintext ServerBFV::Encode(const std::vector<uint64_t> &values) const {
-    const int N = params_.N(), nl = (int)params_.Q.size();
+Plaintext ServerBFV::Encode(const std::vector<uint64_t> &values) const { return encode_limbs(values, params_.MaxLevel(), false); }
+
+Plaintext ServerBFV::EncodeQP(const std::vector<uint64_t> &values, int level) const {
+    if (level < 0 || level > params_.MaxLevel()) throw std::invalid_argument("cannot EncodeQP: no such level");
+    return encode_limbs(values, level, true);
+}
+
+// the limbs of Q up to `level`, then (withP) those of P: one lift of every coefficient, in [0, T)
+Plaintext ServerBFV::encode_limbs(const std::vector<uint64_t> &values, int level, bool withP) const {
+    const int N = params_.N(), nq = level + 1, nl = nq + (withP ? (int)params_.P.size() : 0);
     if ((int)values.size() > N) throw std::invalid_argument("cannot Encode: too many values for the ring degree");
     std::vector<uint64_t> m(N, 0);
     for (size_t i = 0; i < values.size(); i++) m[slot_index_[i]] = values[i] % params_.T; // raw u64 reduce implicitly
     host_ntt(m, params_.T, psiT_, params_.LogN, true);
     Plaintext pt;
-    pt.Level = nl - 1;
+    pt.Level = level;
     pt.Value.resize((size_t)nl * N);
     for (int l = 0; l < nl; l++) {
-        const uint64_t q = params_.Q[l], tinv = InvMod(params_.T % q, q);
+        const size_t mi = l < nq ? (size_t)l : params_.Q.size() + (size_t)(l - nq); // Psi: Q then P
+        const uint64_t q = l < nq ? params_.Q[l] : params_.P[l - nq], tinv = InvMod(params_.T % q, q);
         std::vector<uint64_t> limb(N);
         for (int k = 0; k < N; k++) limb[k] = MulMod(m[k] % q, tinv, q);
-        host_ntt(limb, q, params_.Psi[l], params_.LogN, false);
+        host_ntt(limb, q, params_.Psi[mi], params_.LogN, false);
         memcpy(&pt.Value[(size_t)l * N], limb.data(), (size_t)N * 8);
     }
     return pt;

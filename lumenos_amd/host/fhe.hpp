@@ -193,6 +193,31 @@ struct SeededCiphertexts {
     std::vector<uint64_t> C0; // [Count][L][N], NTT domain
 };
 
+// lintrans.LinearTransformation ([LATTIGO-RECALL] NewLinearTransformation + EncodeLinearTransformation, the non-BSGS
+// form): the diagonals of a plaintext matrix, encoded over Q and P at one level and resident on the device as the
+// multipliers of lumen_linear_transform (lumen_lintrans_load).  ServerBFV::NewLinearTransformation makes one; it owns the
+// device object, is move-only and must not outlive the server it was made on (CopyNews of that server may apply it).
+class LinearTransformation {
+  public:
+    LinearTransformation() = default;
+    LinearTransformation(LinearTransformation &&o) noexcept { *this = std::move(o); }
+    LinearTransformation &operator=(LinearTransformation &&o) noexcept;
+    LinearTransformation(const LinearTransformation &) = delete;
+    ~LinearTransformation();
+    int Level() const { return level_; }
+    // the Galois elements of the non-zero diagonals, in ascending order of the diagonal's index: the keys the evaluation
+    // needs ([LATTIGO-RECALL] LinearTransformation.GaloisElements(params))
+    std::vector<uint64_t> GaloisElements() const;
+    const lumen_lintrans *Handle() const { return lt_; }
+
+  private:
+    friend class ServerBFV;
+    lumen_ctx *ctx_ = nullptr;
+    lumen_lintrans *lt_ = nullptr;
+    int level_ = -1;
+    size_t diagonals_ = 0;
+};
+
 // Scale after `for ct.Level() > target { Rescale }` from level `from`: scale * prod q_l^-1 mod T
 uint64_t RescaledScale(const Parameters &params, uint64_t scale, int fromLevel, int toLevel);
 // The MetaData block rlwe.Ciphertext.WriteTo puts in front of the polynomials, as recalled
@@ -304,8 +329,20 @@ class ServerBFV : public LinearEvaluator {
     // sum_{i < n} slot[j + i * batchSize]; any n with batchSize * n <= N / 2, and batchSize 1 with n a power of two <= N.
     // Needs the Galois keys of a subset of GaloisElementsForInnerSum(batchSize, n).
     Ciphertexts InnerSumNew(const Ciphertexts &ct, int batchSize, int n);
+    // The diagonal method on the embedded evaluator (bfv.go:13-21; [LATTIGO-RECALL] lintrans Evaluator.LinearTransformationNew /
+    // LinearTransformationsNew, the non-BSGS branch): out = sum_k diag_k (.) RotateColumns(ct, k), single-hoisted with ONE
+    // ModDown for the sum (lumen_linear_transform).  diagonals: k -> up to N slot values, |k| < N/2; level: the level of the
+    // ciphertexts it will meet.  ct at the transform's level; the result keeps ct's MetaData (Encode leaves scale 1) and
+    // MulCounter() does not move.  Needs the Galois keys of lt.GaloisElements() (KeyGenerator::GenGaloisKeysNew,
+    // LoadGaloisKeys); diagonal 0 alone needs none.  No BSGS form, column rotations only, at most two special primes.
+    LinearTransformation NewLinearTransformation(const std::map<int, std::vector<uint64_t>> &diagonals, int level);
+    Ciphertexts LinearTransformationNew(const Ciphertexts &ct, const LinearTransformation &lt);
+    std::vector<Ciphertexts> LinearTransformationsNew(const Ciphertexts &ct, const std::vector<const LinearTransformation *> &lts);
     // Encoder.Encode(values, pt) at MaxLevel ([LATTIGO-RECALL] m * T^-1 form, slot index matrix)
     Plaintext Encode(const std::vector<uint64_t> &values) const;
+    // the same extended to the limbs modulo P, at `level`: Value is [level + 1 limbs of Q][K limbs of P][N], every
+    // coefficient's lift in [0, T) and the factor T^-1 as in Encode -- a diagonal as lumen_lintrans_load takes it
+    Plaintext EncodeQP(const std::vector<uint64_t> &values, int level) const;
     // Encryptor.EncryptNew(pt) under pk, host layout [2][L][N]
     std::vector<uint64_t> EncryptNew(const Plaintext &pt);
     // the same for a batch of MaxLevel plaintexts, on the device (lumen_encrypt_pk): the witness
@@ -334,6 +371,7 @@ class ServerBFV : public LinearEvaluator {
 
   private:
     ServerBFV(ServerBFV &src, OwnedContext clone);
+    Plaintext encode_limbs(const std::vector<uint64_t> &values, int level, bool withP) const;
     friend class ServerGroup;
     core::PrimeField *ptField_;
     Parameters params_;
