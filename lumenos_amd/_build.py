@@ -137,3 +137,37 @@ def build_host(force=False):
            "-L" + CSRC, "-llumenos_hip", "-Wl,-rpath," + CSRC]
     subprocess.check_call(cmd)
     return HOST_LIB
+
+
+# ---- the test-only probe over the device headers' arithmetic primitives (tests/test_arith_probe.py)
+ARITH_PROBE_SRC = os.path.join(HERE, "..", "tests", "cpp", "arith_probe.hip")
+# variant -> (library, extra flags): the hand-scheduled Shoup chain, and the chain left to the compiler
+ARITH_PROBES = {"asm": (os.path.join(HERE, "..", "tests", "cpp", "libarith_probe.so"), []),
+                "c": (os.path.join(HERE, "..", "tests", "cpp", "libarith_probe_c.so"), ["-DLM_ASM_SHOUP=0"])}
+
+
+def build_arith_probe(jobs=2):
+    """tests/cpp/arith_probe.hip -> tests/cpp/libarith_probe.so (LM_ASM_SHOUP=1, the default) and libarith_probe_c.so
+    (-DLM_ASM_SHOUP=0), with the code-generation flags of build(); the compiler's resource remarks of each are kept
+    beside it as <library>.res.json (kernel -> figures, _resource_usage).  Rebuilt only when the probe's source or a
+    header of csrc is newer.  At most `jobs` (and at most the CPUs this process may run on) compilations at a time.
+    Returns {variant: library}."""
+    import json
+    deps = [ARITH_PROBE_SRC] + glob.glob(os.path.join(CSRC, "*.h")) + [os.path.join(HERE, "..", "include", "lumenos_hip.h")]
+    newest = max(os.path.getmtime(d) for d in deps)
+    todo = [(lib, extra) for lib, extra in ARITH_PROBES.values()
+            if not (os.path.exists(lib) and os.path.exists(lib + ".res.json") and os.path.getmtime(lib) > newest)]
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    flags = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-ffp-contract=off", "-Wall", "-Wno-unused-function",
+             "-Rpass-analysis=kernel-resource-usage", "-I", CSRC, "-shared"]
+    jobs = max(1, min(jobs, len(os.sched_getaffinity(0))))
+    for at in range(0, len(todo), jobs):
+        procs = [(lib, subprocess.Popen([hipcc, *flags, *extra, ARITH_PROBE_SRC, "-o", lib], stdout=subprocess.PIPE,
+                                        stderr=subprocess.STDOUT)) for lib, extra in todo[at:at + jobs]]
+        for lib, p in procs:
+            text = p.communicate()[0].decode()
+            if p.returncode != 0:
+                raise RuntimeError(f"hipcc failed on {ARITH_PROBE_SRC} -> {lib}:\n{text}")
+            with open(lib + ".res.json", "w") as f:
+                json.dump(_resource_usage(text), f, indent=1, sort_keys=True)
+    return {v: os.path.normpath(lib) for v, (lib, _) in ARITH_PROBES.items()}

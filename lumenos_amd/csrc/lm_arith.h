@@ -5,8 +5,11 @@
 //
 // Multiplication by a constant uses Shoup's precomputed quotient
 // (w' = floor(w * 2^64 / q)): a*w mod q = a*w - floor(a*w'/2^64)*q, which for
-// ANY 64-bit a lands in [0, 2q).  Multiplication by key material uses
+// ANY 64-bit a lands in [0, 2q) with the exact quotient (lm_shoup_lazy below) and
+// in [0, 3q) with the quotient estimate of the multiply-add chain the kernels use
+// (lm_shoup3, lm_shoup.h: exact or one short).  Multiplication by key material uses
 // Montgomery form with 128-bit accumulation (one reduction per output).
+// (tests/test_arith_probe.py)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

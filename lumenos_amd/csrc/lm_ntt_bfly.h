@@ -19,7 +19,9 @@ __device__ __forceinline__ uint32_t lm_pad_at(uint32_t base, uint32_t pbase, int
 
 // Butterflies (written out stage by stage in lm_fwd_stages / lm_inv_stages):
 //   forward (Cooley-Tukey), fully lazy:   s = x + w*y (x rides in the multiplication's addend slot),
-//       y' = (2x + 3q) - s, x' = s: both outputs grow by < 3q per stage;
+//       y' = (2x + 3q) - s, x' = s: both outputs grow by at most 3q per stage (x' by less; y' = x + 3q - (w*y lazily)
+//       by exactly 3q when the lazy product is 0, i.e. when y or w is), so R stages on inputs below B leave values below
+//       B + 3Rq;
 //   inverse (Gentleman-Sande), lazy inside a pass: in stage st of a pass both inputs are below
 //       C = 3q * 2^st; x' = x + y is left to grow (< 2C), y' = w * (x + C - y) goes through the Shoup
 //       multiplication (any input below 2^64) and lands in [0, 3q); lm_inv_stages brings the sums
@@ -101,16 +103,28 @@ struct lm_inv_twset {
 
 // R inverse stages on inputs in [0, 3q) with preloaded twiddles.
 // Output e[i] has taken the sum branch in its last k stages (k = R for i = 0, else R-1-floor(log2 i))
-// and is below 3q * 2^k <= 48q.  Unless this is the transform's last pass (whose storer multiplies by
+// and is below 3q * 2^k <= 48q (NARROW, below: e[0] of four stages below 24q).  Unless this is the transform's last pass (whose storer multiplies by
 // N^-1 and takes any value below 2^64) the outputs are brought back under 3q: k conditional
 // subtractions, or one multiplication-free Shoup reduction when k >= 3.
-template <int R, bool UW, bool LAST, bool FIRST>
+// NO WRAP: the sums of stage st stay below 6q * 2^st and so do its differences x + C - y, so R stages need
+// 3q * 2^R <= 2^64.  For R <= 3 every context's modulus bound gives that (32q < 2^64 at the least, lm_q_bound_factor).
+// A four-stage pass needs 48q <= 2^64, which the bound gives from log_n = 14 up only (3 * 14 + 8 = 50), while every
+// degree from 2^10 up has such a pass -- and what a pass is fed lies ANYWHERE below 3q (sums brought home by lm_csub),
+// so at q = 2^64 / 38 the sum of sixteen inputs does pass 2^64 on ordinary data.  NARROW (lm_inv_narrow(log_n): the
+// degrees whose bound is under 48q) therefore brings the two sums of eight, e[0] and e[8], under 12q before the fourth
+// stage -- two conditional subtractions per sixteen coefficients: that stage's sums then stay below 24q, its
+// differences below 12q + 24q = 36q <= 38q, and e[0] leaves below 24q like e[1].  lm_ntt_plan.h holds every degree's
+// pass list to these figures (lm_inv_fits); tests/test_arith_probe.py runs both forms at the largest modulus of every
+// degree that has a four-stage pass.
+template <int R, bool UW, bool LAST, bool FIRST, bool NARROW = false>
 __device__ __forceinline__ void lm_inv_stages(u64 *e, const lm_inv_twset<R, UW, FIRST> &T, const lm_qc &c) {
     static_assert(R <= 4, "3q * 2^R must stay below 2^64");
 #pragma unroll
     for (int st = 0; st < R; st++) {
         const int half = 1 << st, span = half << 1;
         const u64 C = c.q3 << st;
+        if constexpr (NARROW && R == 4)
+            if (st == 3) e[0] = lm_csub(e[0], c.q3 << 2), e[8] = lm_csub(e[8], c.q3 << 2);
         // all sums and differences of the stage first, then the multiplications (as in the forward stages)
         u64 dif[(1 << R) / 2];
 #pragma unroll

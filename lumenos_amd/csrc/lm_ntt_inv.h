@@ -19,7 +19,7 @@ __device__ __forceinline__ void lm_inv_first(u64 *s, const tw_t *tw, const lm_qc
         lm_inv_twset<R, false, true> T;
         T.load(tw, LOGN, 0, w);
         ld(base, e, 1 << R);
-        lm_inv_stages<R, false, false, true>(e, T, c);
+        lm_inv_stages<R, false, false, true, lm_inv_narrow(LOGN)>(e, T, c);
 #pragma unroll
         for (int k = 0; k < (1 << R); k++) s[LM_PAD(base + k)] = e[k];
     }
@@ -46,7 +46,7 @@ __device__ __forceinline__ void lm_inv_mid(u64 *s, const tw_t *tw, const lm_qc &
         for (int k = 0; k < (1 << R); k++) e[k] = s[lm_pad_at<LT>(base, pb, k)];
         if (LM_INV_TW_PREFETCH && m + 1 < D::reps) T[(m + 1) & 1].load(tw, LOGN, LT, D::local(tid, m + 1) >> LT);
         if (!LM_INV_TW_PREFETCH && m) T[0].load(tw, LOGN, LT, blk);
-        lm_inv_stages<R, UW, false, false>(e, T[LM_INV_TW_PREFETCH ? (m & 1) : 0], c);
+        lm_inv_stages<R, UW, false, false, lm_inv_narrow(LOGN)>(e, T[LM_INV_TW_PREFETCH ? (m & 1) : 0], c);
 #pragma unroll
         for (int k = 0; k < (1 << R); k++) s[lm_pad_at<LT>(base, pb, k)] = e[k];
     }
@@ -75,7 +75,7 @@ __device__ __forceinline__ void lm_inv_last(const u64 *s, const tw_t *tw, const 
         // a storer with a member pre(w) is told the work item before its butterflies run: whatever it
         // reads from global memory for coefficients w + (k << log_t0), k < 2^R, is then in flight under them
         if constexpr (lm_has_pre<Storer>::value) st.pre(w);
-        lm_inv_stages<R, true, true, false>(e, T, c);
+        lm_inv_stages<R, true, true, false, lm_inv_narrow(LOGN)>(e, T, c);
 #pragma unroll
         for (int k = 0; k < (1 << R); k++) {
             if constexpr (lm_has_slot<Storer>::value)

@@ -191,6 +191,21 @@ static inline void lm_layout_tw(std::vector<tw_t> &tw, uint32_t logN) {
 // must not wrap, 8q < 2^64 -- the factor at log_n = 0, so implied for every degree.
 __host__ __device__ constexpr uint64_t lm_q_bound_factor(uint32_t log_n) { return 3ull * log_n + 8; }
 static_assert(lm_q_bound_factor(0) >= 8, "the modulus bound (3 log_n + 8) q < 2^64 must imply 8 q < 2^64");
+// The inverse transform's passes (lm_inv_stages, lm_ntt_bfly.h) let values reach 6q * 2^(R-1) in a pass of R stages: 48q
+// in a four-stage pass, which the bound covers from log_n = 14 up.  Below that the four-stage pass runs NARROW (its two
+// sums of eight brought under 12q before the fourth stage) and peaks at 36q.  Every degree's pass list is held to it.
+__host__ __device__ constexpr bool lm_inv_narrow(int log_n) { return lm_q_bound_factor((uint32_t)log_n) < 48; }
+__host__ __device__ constexpr uint64_t lm_inv_pass_peak(int R, bool narrow) { return R == 4 && narrow ? 36 : 3ull << R; }
+// log_n: the context's degree (its bound); tlog: the degree of the transform a workgroup runs (its pass list)
+__host__ __device__ constexpr bool lm_inv_fits(int log_n, int tlog) {
+    for (int i = 0; i < lm_npasses(tlog); i++)
+        if (lm_inv_pass_peak(lm_pass_r(tlog, i), lm_inv_narrow(tlog)) > lm_q_bound_factor((uint32_t)log_n)) return false;
+    return true;
+}
+#define LM_X(n) static_assert(lm_inv_fits(n, lm_tlog(n)), "an inverse pass's peak (48q, or 36q narrowed) must stay under the modulus bound");
+LM_FOR_EACH_LOGN(LM_X)
+LM_FOR_EACH_SPLIT_LOGN(LM_X)
+#undef LM_X
 #define LM_X(n) static_assert(3ull * n + 7 < lm_q_bound_factor(n), "the split transform's storer bound (3 log_n + 7) q must stay under the modulus bound");
 LM_FOR_EACH_SPLIT_LOGN(LM_X)
 #undef LM_X

@@ -37,6 +37,14 @@ def build_cpp_twin(name, with_oracle=True):
     return exe
 
 
+def build_arith_probe(jobs=2):
+    """tests/cpp/arith_probe.hip -> {"asm": tests/cpp/libarith_probe.so, "c": tests/cpp/libarith_probe_c.so}
+    (lumenos_amd._build.build_arith_probe, which build() calls as well): rebuilt only when stale, at most `jobs`
+    compilations at a time."""
+    from lumenos_amd import _build
+    return _build.build_arith_probe(jobs)
+
+
 def twin(name, *args, timeout=600, with_oracle=True, env=None):
     """tests/cpp/<name>, built if need be, run with `args`: the CompletedProcess, output captured as text"""
     exe = build_cpp_twin(name, with_oracle=with_oracle)
