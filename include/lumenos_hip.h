@@ -470,8 +470,9 @@ int lumen_rotate_hoisted(lumen_ctx *ctx, const lumen_set *in, const uint64_t *ga
  * of the lintrans evaluator, which sits on the *bgv.Evaluator that ServerBFV embeds (fhe/bfv.go:13-21).  Single-hoisted:
  * one decomposition of c1, per non-zero diagonal one gadget product and one multiply-accumulate over Q and P, and ONE
  * ModDown for the whole sum -- where lumen_rotate_hoisted followed by lumen_mul_plain_then_add pays one ModDown, one
- * output set and one product pass per diagonal.  Limits: no baby-step / giant-step (double-hoisted) form; column
- * rotations only (no row swap among the diagonals); 1 or 2 special primes.  Prove does not use the transform.
+ * output set and one product pass per diagonal.  lumen_lintrans_load_bsgs gives the double-hoisted (baby-step / giant-step)
+ * form of the same transform, below.  Limits: column rotations only (no row swap among the diagonals); 1 or 2 special
+ * primes.  Prove does not use the transform.
  * lumen_lintrans_load (LinearTransformation's encoding, NewLinearTransformation + Encode): n >= 1 diagonals at the level of
  * nl limbs, 1 <= nl <= L.  k[d]: the diagonal's index, |k| < N/2, taken modulo N/2; its Galois element is
  * lumen_galois_element(k).  pts: host [n][nl + K][N], diagonal d as a plaintext over Q and P -- limbs 0..nl-1 residues
@@ -479,8 +480,10 @@ int lumen_rotate_hoisted(lumen_ctx *ctx, const lumen_set *in, const uint64_t *ga
  * Encoder.Encode leaves and lumen_mul_plain takes (m * T^-1).  The multiplier is m_k = pt_k * T per limb, as MulNew's; it
  * is formed once, here, and stays on the device until lumen_lintrans_destroy (ctx: the loading context or a clone; NULL
  * after the context is gone).  A transform serves the context that loaded it and its clones.
- * lumen_lintrans_galois_elements: the elements of the non-zero diagonals in the order given, into gal_els (room for n);
- * returns their number.  The keys of exactly these must be loaded (lumen_load_galois_key[_ex]).
+ * lumen_lintrans_galois_elements: the elements of the non-zero diagonals in the order given -- of a double-hoisted
+ * transform: of its babies i != 0, ascending, then of its giants j != 0, ascending -- into gal_els (room for 2n: a
+ * double-hoisted transform may need a baby's and a giant's key per diagonal); returns their number.  The keys of exactly
+ * these must be loaded (lumen_load_galois_key[_ex]).
  * lumen_linear_transform (LinearTransformationNew): `in`, a set of any count at the transform's level, is not modified.
  * With dig = the digits of c1, (u0, u1)_k = the gadget product of dig under the key of g_k over the nl limbs of Q and the
  * K of P, and sigma_g the NTT-domain permutation of lumen_automorphism:
@@ -496,12 +499,35 @@ int lumen_rotate_hoisted(lumen_ctx *ctx, const lumen_set *in, const uint64_t *ga
  * outs[i] is NULL.
  * Refused with a message, before anything is allocated or enqueued: NULL arguments; n == 0; nl outside [1, L]; |k| >= N/2;
  * two diagonals equal modulo N/2; a residue >= its modulus; no special primes (K = 0) or more than two; a set at another
- * level than the transform's; a transform of another context; a lane-sharded set; no key loaded for a diagonal's element. */
+ * level than the transform's; a transform of another context; a lane-sharded set; no key loaded for a diagonal's element.
+ *
+ * The double-hoisted form ([LATTIGO-RECALL] MultiplyByDiagMatrixBSGS).  lumen_lintrans_load_bsgs takes lumen_lintrans_load's
+ * arguments -- the diagonals are NOT pre-rotated by the caller -- and n1 >= 1 baby steps.  With e = k mod N/2 a diagonal is
+ * e = j + i, i = e mod n1 its baby, j = e - i its giant; the load forms m'_e = sigma_{g_j}^-1(m_e) on the device.  Then
+ *     baby_0 = (P c0, P c1) on Q, 0 on P;   baby_i = sigma_{g_i}(gadget(dig, key g_i) + (P c0 on Q, 0))        (i != 0, no ModDown)
+ *     tmp_j  = sum_i m'_{j+i} (.) baby_i                                                  (over Q and P, both polynomials)
+ *     acc    = tmp_0 + sum_{j != 0} sigma_{g_j}(gadget(decompose(ModDown(tmp_j)[1]), key g_j) + (tmp_j[0], 0))
+ *     out    = ModDown(acc)                                                              (ONE, canonical residues)
+ * so D diagonals cost about n1 + D / n1 gadget products and keys instead of D; a giant adds one decomposition and a
+ * ModDown of one polynomial.  lumen_linear_transform and lumen_linear_transforms take such an object wherever they take a
+ * single-hoisted one, mixed freely; outs[i] still equals the single call word for word (a double-hoisted transform with
+ * giants decomposes c1 for itself, the single-hoisted ones of a call keep sharing one decomposition).  When every
+ * diagonal is a baby (n1 above the largest e) the words are the single-hoisted transform's; n1 = 1 makes every diagonal
+ * a giant; diagonal 0 alone needs no key and gives lumen_mul_plain's words.  Levels, ring degrees, K, counts, the
+ * counter and the refusals are lumen_lintrans_load's and lumen_linear_transform's; n1 == 0 is refused by name.  Each
+ * giant that occurs holds one more block of the gadget product's size per lane while a batch runs;
+ * the batch of such a call is halved until the blocks fit a quarter of the device's memory.
+ * lumen_lintrans_best_baby_steps (host only): the power of two n1 in [1, N/2], N = 2^log_n, that minimises the number of
+ * keys, (distinct babies != 0) + (distinct giants != 0); the smaller on a tie; 0 for NULL, n == 0, a log_n outside
+ * [1, 31] or a k outside (-N/2, N/2). */
 typedef struct lumen_lintrans lumen_lintrans;
 int lumen_lintrans_load(lumen_ctx *ctx, const int64_t *k, const uint64_t *pts /* host [n][nl+K][N] */, uint32_t n,
                         uint32_t nl, lumen_lintrans **out);
 void lumen_lintrans_destroy(lumen_ctx *ctx, lumen_lintrans *lt);
-uint32_t lumen_lintrans_galois_elements(const lumen_lintrans *lt, uint64_t *gal_els);
+int lumen_lintrans_load_bsgs(lumen_ctx *ctx, const int64_t *k, const uint64_t *pts /* host [n][nl+K][N] */, uint32_t n,
+                             uint32_t nl, uint32_t n1, lumen_lintrans **out);
+uint32_t lumen_lintrans_best_baby_steps(uint32_t log_n, const int64_t *k, uint32_t n);
+uint32_t lumen_lintrans_galois_elements(const lumen_lintrans *lt, uint64_t *gal_els /* room for 2n */);
 int lumen_linear_transform(lumen_ctx *ctx, const lumen_set *in, const lumen_lintrans *lt, lumen_set **out);
 int lumen_linear_transforms(lumen_ctx *ctx, const lumen_set *in, const lumen_lintrans *const *lts, uint32_t n_lts,
                             lumen_set **outs /* [n_lts] new sets */);

@@ -901,17 +901,19 @@ int rotate_mac(lumen_ctx *ctx, const u64 *acc, uint32_t B, const lm_galois_key &
     return launch_ks_mac(ctx, s.ext, acc, gk.d_key.get(), s.u, B, tb);
 }
 
-// 4a. P limbs of u -> coefficient domain (in place) and packed; u: any block of s.u's layout (ks_u_at)
-int rotate_p_to_coef(lumen_ctx *ctx, u64 *u, uint32_t B, KsTables *tb) {
+// 4a. P limbs of u -> coefficient domain (in place) and packed; u: any block of s.u's layout (ks_u_at).  c1_only: those
+// of polynomial 1 of every column alone -- every other pair of K limbs; polynomial 0's stay in the NTT domain
+int rotate_p_to_coef(lumen_ctx *ctx, u64 *u, uint32_t B, KsTables *tb, bool c1_only) {
     const uint32_t N = ctx->N, L = tb->nl, K = ctx->K;
-    u64 *up = u + ks_u_at(0, L, B, L, K) * N; // the limbs modulo P: [2B][K]
-    const size_t pstride = (size_t)K * N;
-    if (int rc = lm_launch_ntt_strided(ctx, up, pstride, up, pstride, B * 2, lm_map_p(ctx), true, "ks_intt_p",
+    u64 *up = u + ks_u_at(c1_only ? 1 : 0, L, B, L, K) * N; // the limbs modulo P: [2B][K]
+    const size_t pstride = (size_t)(c1_only ? 2 : 1) * K * N;
+    const uint32_t npoly = c1_only ? B : B * 2;
+    if (int rc = lm_launch_ntt_strided(ctx, up, pstride, up, pstride, npoly, lm_map_p(ctx), true, "ks_intt_p",
                                        &tb->yscale))
         return rc;
     if (K == 2) {
         lm_prof_scope ps(ctx, "ks_pack_v", (uint64_t)B);
-        if (int rc = lm_launch_pack_v(ctx, up, pstride, B * 2, 1u, K, ctx->L, K)) return rc;
+        if (int rc = lm_launch_pack_v(ctx, up, pstride, npoly, 1u, K, ctx->L, K)) return rc;
     }
     return 0;
 }
@@ -932,6 +934,13 @@ int rotate_add(lumen_ctx *ctx, const u64 *acc, u64 *acc_out, uint32_t B, const l
 // After rotate_product: out = Rot_galEl(in) for every column, canonical, [B][2][L][N] both; `out` is another block than `in`.
 int rotate_store(lumen_ctx *ctx, const u64 *in, u64 *out, uint32_t B, const lm_galois_key &gk, KsTables *tb, const KsScratch &s) {
     return launch_moddown<false>(ctx, in, out, B, gk, tb, s);
+}
+
+// The same for polynomial 1 of every column alone (ModDown's c1_only work list): polynomial 1 of `out` = the ModDown of
+// polynomial 1 of s.u under gk's tables, canonical; `in` is not read (c0 rides on polynomial 0) and polynomial 0 of `out` is
+// not written.  s.u went through rotate_p_to_coef, c1_only or not.
+int rotate_store_c1(lumen_ctx *ctx, const u64 *in, u64 *out, uint32_t B, const lm_galois_key &gk, KsTables *tb, const KsScratch &s) {
+    return launch_moddown<false>(ctx, in, out, B, gk, tb, s, true);
 }
 
 // After rotate_decompose: coef_out = the coefficient form of acc + Rot_galEl(acc), [B][2][L][N]: the last rotation before a

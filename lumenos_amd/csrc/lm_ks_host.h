@@ -40,8 +40,9 @@ int rotate_decompose(lumen_ctx *ctx, const u64 *acc, uint32_t B, KsTables *tb, c
 int rotate_product(lumen_ctx *ctx, const u64 *acc, uint32_t B, const lm_galois_key &gk, KsTables *tb, const KsScratch &s);
 // ... its two halves.  Step 3: the gadget product in s.u, all nl + K limbs in the NTT domain
 int rotate_mac(lumen_ctx *ctx, const u64 *acc, uint32_t B, const lm_galois_key &gk, KsTables *tb, const KsScratch &s);
-// step 4a on any block of s.u's layout (ks_u_at): its limbs modulo P to the coefficient domain, packed
-int rotate_p_to_coef(lumen_ctx *ctx, u64 *u, uint32_t B, KsTables *tb);
+// step 4a on any block of s.u's layout (ks_u_at): its limbs modulo P to the coefficient domain, packed.  c1_only: those of
+// polynomial 1 alone; polynomial 0's stay in the NTT domain (a giant step of the double-hoisted transform, lm_lintrans.hip)
+int rotate_p_to_coef(lumen_ctx *ctx, u64 *u, uint32_t B, KsTables *tb, bool c1_only = false);
 // after rotate_decompose: acc_out = acc + Rot_galEl(acc) for every column, lazy ([0, 2q)); another block than `acc`
 int rotate_add(lumen_ctx *ctx, const u64 *acc, u64 *acc_out, uint32_t B, const lm_galois_key &gk, KsTables *tb, const KsScratch &s);
 // all steps: acc_out = acc + Rot_galEl(acc) for every column, lazy ([0, 2q))
@@ -50,6 +51,9 @@ int rotate_accumulate(lumen_ctx *ctx, const u64 *acc, u64 *acc_out, uint32_t B, 
 // after rotate_product: out = Rot_galEl(in) for every column, canonical; `out` is another block than `in`.  (s.u may be
 // any block of its layout that went through rotate_p_to_coef: InnerSum's lazy accumulator ends so, under the identity)
 int rotate_store(lumen_ctx *ctx, const u64 *in, u64 *out, uint32_t B, const lm_galois_key &gk, KsTables *tb, const KsScratch &s);
+// ... for polynomial 1 alone (ModDown's c1_only work list): polynomial 1 of `out` = ModDown of polynomial 1 of s.u under gk's
+// tables, canonical, after rotate_p_to_coef on that polynomial at least.  `in` is not read, polynomial 0 of `out` not written.
+int rotate_store_c1(lumen_ctx *ctx, const u64 *in, u64 *out, uint32_t B, const lm_galois_key &gk, KsTables *tb, const KsScratch &s);
 // after rotate_decompose, the last rotation before a rescale: coef_out = the coefficient form of acc + Rot_galEl(acc)
 int rotate_close(lumen_ctx *ctx, const u64 *acc, u64 *coef_out, uint32_t B, const lm_galois_key &gk, uint64_t gal_el,
                  KsTables *tb, const KsScratch &s);

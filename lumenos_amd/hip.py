@@ -126,6 +126,8 @@ SYMBOLS = {
     "lumen_rotate_rows": (C.c_int, [_vp, _vp, _vpp]),
     "lumen_rotate_hoisted": (C.c_int, [_vp, _vp, _u64p, C.c_uint32, _vpp]),
     "lumen_lintrans_load": (C.c_int, [_vp, C.POINTER(C.c_int64), _u64p, C.c_uint32, C.c_uint32, _vpp]),
+    "lumen_lintrans_load_bsgs": (C.c_int, [_vp, C.POINTER(C.c_int64), _u64p, C.c_uint32, C.c_uint32, C.c_uint32, _vpp]),
+    "lumen_lintrans_best_baby_steps": (C.c_uint32, [C.c_uint32, C.POINTER(C.c_int64), C.c_uint32]),
     "lumen_lintrans_destroy": (None, [_vp, _vp]),
     "lumen_lintrans_galois_elements": (C.c_uint32, [_vp, _u64p]),
     "lumen_linear_transform": (C.c_int, [_vp, _vp, _vp, _vpp]),
@@ -265,6 +267,13 @@ def pinned_free(arr):
 
 
 _pinned_keep = {}
+
+
+def lintrans_best_baby_steps(log_n, ks):
+    """lumen_lintrans_best_baby_steps: the power of two n1 in [1, N/2] for which the double-hoisted transform of the
+    diagonals `ks` at N = 2^log_n needs the fewest keys; 0 for arguments a load would refuse"""
+    k = np.array([int(x) for x in ks], dtype=np.int64)
+    return int(load().lumen_lintrans_best_baby_steps(int(log_n), k.ctypes.data_as(C.POINTER(C.c_int64)), k.size))
 
 
 def _p64(a):
@@ -748,20 +757,26 @@ class Context:
         self._ck(self.lib.lumen_rotate_hoisted(self.h, s.h, _p64(g) if g.size else _p64(np.zeros(1, dtype=np.uint64)), g.size, hs))
         return [DeviceSet(self, C.c_void_p(hs[i])) for i in range(g.size)]
 
-    def lintrans_load(self, diags, nl=None):
+    def lintrans_load(self, diags, nl=None, baby_steps=None):
         """LinearTransformation: diags {k: pt_k}, pt_k a plaintext over Q and P, [nl + K][N] residues in Encoder.Encode's
-        form (limbs of the level's Q, then of P); |k| < N / 2.  nl=None: the top level"""
+        form (limbs of the level's Q, then of P); |k| < N / 2.  nl=None: the top level.  baby_steps=None: single-hoisted;
+        n1 >= 1: the double-hoisted (baby-step / giant-step) form with n1 baby steps (lintrans_best_baby_steps picks one)"""
         nl = self.L if nl is None else nl
         ks = np.array([int(k) for k in diags], dtype=np.int64)
         pts = np.ascontiguousarray([np.asarray(diags[k], dtype=np.uint64) for k in diags], dtype=np.uint64)
         assert pts.shape == (len(ks), nl + self.K, self.N), pts.shape
         h = C.c_void_p()
-        self._ck(self.lib.lumen_lintrans_load(self.h, ks.ctypes.data_as(C.POINTER(C.c_int64)), _p64(pts), len(ks), nl, C.byref(h)))
+        kp = ks.ctypes.data_as(C.POINTER(C.c_int64))
+        if baby_steps is None:
+            self._ck(self.lib.lumen_lintrans_load(self.h, kp, _p64(pts), len(ks), nl, C.byref(h)))
+        else:
+            self._ck(self.lib.lumen_lintrans_load_bsgs(self.h, kp, _p64(pts), len(ks), nl, int(baby_steps), C.byref(h)))
         return Lintrans(self, h, ks, nl)
 
     def lintrans_galois_elements(self, lt):
-        """the Galois elements of the transform's non-zero diagonals, in the order given: the keys it needs"""
-        g = np.zeros(max(len(lt.ks), 1), dtype=np.uint64)
+        """the keys the transform needs: the Galois elements of its non-zero diagonals in the order given, or, double-hoisted,
+        of its babies and then of its giants (up to two per diagonal)"""
+        g = np.zeros(max(2 * len(lt.ks), 1), dtype=np.uint64)
         cnt = self.lib.lumen_lintrans_galois_elements(lt.h, _p64(g))
         return [int(x) for x in g[:cnt]]
 

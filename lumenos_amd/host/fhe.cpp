@@ -733,14 +733,16 @@ LinearTransformation::~LinearTransformation() {
 }
 
 std::vector<uint64_t> LinearTransformation::GaloisElements() const {
-    std::vector<uint64_t> els(std::max<size_t>(diagonals_, 1));
+    std::vector<uint64_t> els(std::max<size_t>(2 * diagonals_, 1)); // double-hoisted: a baby's and a giant's per diagonal
     els.resize(lumen_lintrans_galois_elements(lt_, els.data()));
     return els;
 }
 
-LinearTransformation ServerBFV::NewLinearTransformation(const std::map<int, std::vector<uint64_t>> &diagonals, int level) {
-    if (diagonals.empty()) throw std::invalid_argument("NewLinearTransformation: no diagonal");
-    if (level < 0 || level >= (int)params_.Q.size()) throw std::invalid_argument("NewLinearTransformation: no such level");
+// both forms: babySteps < 0 single-hoisted, 0 the best count of baby steps, > 0 that count
+LinearTransformation ServerBFV::newLinearTransformation(const std::map<int, std::vector<uint64_t>> &diagonals, int level, int babySteps,
+                                                        const char *what) {
+    if (diagonals.empty()) throw std::invalid_argument(std::string(what) + ": no diagonal");
+    if (level < 0 || level >= (int)params_.Q.size()) throw std::invalid_argument(std::string(what) + ": no such level");
     std::vector<int64_t> ks;
     std::vector<uint64_t> pts;
     for (const auto &kv : diagonals) {
@@ -749,9 +751,28 @@ LinearTransformation ServerBFV::NewLinearTransformation(const std::map<int, std:
         pts.insert(pts.end(), pt.Value.begin(), pt.Value.end());
     }
     LinearTransformation lt;
-    check(lumen_lintrans_load(Context(), ks.data(), pts.data(), (uint32_t)ks.size(), (uint32_t)level + 1, &lt.lt_), "lumen_lintrans_load");
+    if (babySteps < 0) {
+        check(lumen_lintrans_load(Context(), ks.data(), pts.data(), (uint32_t)ks.size(), (uint32_t)level + 1, &lt.lt_), "lumen_lintrans_load");
+    } else {
+        uint32_t n1 = (uint32_t)babySteps;
+        if (!n1) {
+            n1 = lumen_lintrans_best_baby_steps((uint32_t)params_.LogN, ks.data(), (uint32_t)ks.size());
+            if (!n1) throw std::invalid_argument(std::string(what) + ": a diagonal outside (-N/2, N/2)");
+        }
+        check(lumen_lintrans_load_bsgs(Context(), ks.data(), pts.data(), (uint32_t)ks.size(), (uint32_t)level + 1, n1, &lt.lt_),
+              "lumen_lintrans_load_bsgs");
+    }
     lt.ctx_ = Context(), lt.level_ = level, lt.diagonals_ = ks.size();
     return lt;
+}
+
+LinearTransformation ServerBFV::NewLinearTransformation(const std::map<int, std::vector<uint64_t>> &diagonals, int level) {
+    return newLinearTransformation(diagonals, level, -1, "NewLinearTransformation");
+}
+
+LinearTransformation ServerBFV::NewLinearTransformationBSGS(const std::map<int, std::vector<uint64_t>> &diagonals, int level, int babySteps) {
+    if (babySteps < 0) throw std::invalid_argument("NewLinearTransformationBSGS: a negative number of baby steps");
+    return newLinearTransformation(diagonals, level, babySteps, "NewLinearTransformationBSGS");
 }
 
 Ciphertexts ServerBFV::LinearTransformationNew(const Ciphertexts &ct, const LinearTransformation &lt) {

@@ -193,10 +193,11 @@ struct SeededCiphertexts {
     std::vector<uint64_t> C0; // [Count][L][N], NTT domain
 };
 
-// lintrans.LinearTransformation ([LATTIGO-RECALL] NewLinearTransformation + EncodeLinearTransformation, the non-BSGS
-// form): the diagonals of a plaintext matrix, encoded over Q and P at one level and resident on the device as the
-// multipliers of lumen_linear_transform (lumen_lintrans_load).  ServerBFV::NewLinearTransformation makes one; it owns the
-// device object, is move-only and must not outlive the server it was made on (CopyNews of that server may apply it).
+// lintrans.LinearTransformation ([LATTIGO-RECALL] NewLinearTransformation + EncodeLinearTransformation, either form): the
+// diagonals of a plaintext matrix, encoded over Q and P at one level and resident on the device as the multipliers of
+// lumen_linear_transform (lumen_lintrans_load; lumen_lintrans_load_bsgs for the baby-step / giant-step form, pre-rotated
+// there).  ServerBFV::NewLinearTransformation[BSGS] makes one; it owns the device object, is move-only and must not outlive
+// the server it was made on (CopyNews of that server may apply it).
 class LinearTransformation {
   public:
     LinearTransformation() = default;
@@ -205,8 +206,9 @@ class LinearTransformation {
     LinearTransformation(const LinearTransformation &) = delete;
     ~LinearTransformation();
     int Level() const { return level_; }
-    // the Galois elements of the non-zero diagonals, in ascending order of the diagonal's index: the keys the evaluation
-    // needs ([LATTIGO-RECALL] LinearTransformation.GaloisElements(params))
+    // the keys the evaluation needs ([LATTIGO-RECALL] LinearTransformation.GaloisElements(params)): the Galois elements of the
+    // non-zero diagonals, in ascending order of the diagonal's index; of a BSGS transformation, those of its baby steps
+    // and then of its giant steps, each ascending
     std::vector<uint64_t> GaloisElements() const;
     const lumen_lintrans *Handle() const { return lt_; }
 
@@ -334,8 +336,12 @@ class ServerBFV : public LinearEvaluator {
     // ModDown for the sum (lumen_linear_transform).  diagonals: k -> up to N slot values, |k| < N/2; level: the level of the
     // ciphertexts it will meet.  ct at the transform's level; the result keeps ct's MetaData (Encode leaves scale 1) and
     // MulCounter() does not move.  Needs the Galois keys of lt.GaloisElements() (KeyGenerator::GenGaloisKeysNew,
-    // LoadGaloisKeys); diagonal 0 alone needs none.  No BSGS form, column rotations only, at most two special primes.
+    // LoadGaloisKeys); diagonal 0 alone needs none.  Column rotations only, at most two special primes.
+    // NewLinearTransformationBSGS: the double-hoisted form (the BSGS branch, MultiplyByDiagMatrixBSGS) of the same diagonals
+    // with babySteps baby steps, 0 for the count with the fewest keys (lumen_lintrans_best_baby_steps): about
+    // babySteps + D / babySteps keys and gadget products for D diagonals.  The evaluation calls are the same.
     LinearTransformation NewLinearTransformation(const std::map<int, std::vector<uint64_t>> &diagonals, int level);
+    LinearTransformation NewLinearTransformationBSGS(const std::map<int, std::vector<uint64_t>> &diagonals, int level, int babySteps);
     Ciphertexts LinearTransformationNew(const Ciphertexts &ct, const LinearTransformation &lt);
     std::vector<Ciphertexts> LinearTransformationsNew(const Ciphertexts &ct, const std::vector<const LinearTransformation *> &lts);
     // Encoder.Encode(values, pt) at MaxLevel ([LATTIGO-RECALL] m * T^-1 form, slot index matrix)
@@ -372,6 +378,8 @@ class ServerBFV : public LinearEvaluator {
   private:
     ServerBFV(ServerBFV &src, OwnedContext clone);
     Plaintext encode_limbs(const std::vector<uint64_t> &values, int level, bool withP) const;
+    LinearTransformation newLinearTransformation(const std::map<int, std::vector<uint64_t>> &diagonals, int level, int babySteps,
+                                                 const char *what);
     friend class ServerGroup;
     core::PrimeField *ptField_;
     Parameters params_;

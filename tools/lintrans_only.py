@@ -2,7 +2,7 @@
 it -- lumen_rotate_hoisted over the same elements, then lumen_mul_plain / lumen_mul_plain_then_add per diagonal -- at a
 chosen shape, in one process, the two routes alternating.
 
-usage: lintrans_only.py ROWS COLS LOGN [--limbs NL] [--count C] [--rounds R] [--diagonals D[,D...]]
+usage: lintrans_only.py ROWS COLS LOGN [--limbs NL] [--count C] [--rounds R] [--diagonals D[,D...]] [--bsgs N1]
 
 The parameters are the prover's for a ROWS x COLS witness at LogN (ROWS only names the shape).  C (default 64)
 ciphertexts of uniform residues (the kernels are data-independent), random words for the Galois keys and for the
@@ -14,6 +14,9 @@ Per kernel: one more visit of each route under lumen_prof_read, on ONE lane (wit
 neighbour's).  ks_diag_gather moves data and does one Montgomery product per word: its achieved bytes per second -- the
 words it must read and write, from the shapes, over its event time -- are printed against the copy rate of the box,
 measured here as a device-to-device copy of the input set (lumen_automorphism by the identity; read + write).
+--bsgs N1: the double-hoisted (baby-step / giant-step) form of the same diagonals with N1 baby steps (0: the count
+lumen_lintrans_best_baby_steps picks) as a third route, alternating with the other two, its keys counted against the
+single-hoisted transform's and its scopes printed as theirs.
 One box, one run: repeat before quoting a figure.
 """
 import argparse
@@ -24,7 +27,7 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 from lumenos_amd import params as lp
-from lumenos_amd.hip import Context
+from lumenos_amd.hip import Context, lintrans_best_baby_steps
 
 
 def gather_bytes(count, batch, nl, K, N, keyed):
@@ -47,6 +50,7 @@ def main():
     ap.add_argument("--count", type=int, default=64, help="ciphertexts")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--diagonals", default="4,16", help="numbers of diagonals (0 .. D - 1)")
+    ap.add_argument("--bsgs", type=int, default=None, metavar="N1", help="also time the double-hoisted form with N1 baby steps (0: the best)")
     a = ap.parse_args()
     P = lp.generate_bgv_params_for_ntt(a.cols, a.logn)
     L, K, N = len(P.q), len(P.p), P.N
@@ -115,18 +119,32 @@ def main():
         def fused():
             return [ctx.linear_transform(s, lt)]
 
-        timed(fused), timed(composed)
-        tf, tc = [], []
-        for _ in range(a.rounds):  # alternating: what else runs on the box meets both routes alike
-            tf.append(timed(fused))
-            tc.append(timed(composed))
-        mf, txt_f = show(tf)
-        mc, txt_c = show(tc)
+        routes = [("lumen_linear_transform", fused), ("composition", composed)]
+        lb = None
+        if a.bsgs is not None:
+            n1 = a.bsgs or lintrans_best_baby_steps(a.logn, range(d))
+            lb = ctx.lintrans_load({k: diags[k] for k in range(d)}, nl, baby_steps=n1)
+            gb = ctx.lintrans_galois_elements(lb)
+            assert set(gb) <= set(els)
+            print(f"D = {d}: double-hoisted with n1 = {n1}: {len(gb)} keys against {len(g)}", flush=True)
+            routes.append(("double-hoisted", lambda: [ctx.linear_transform(s, lb)]))
+        for _, fn in routes:
+            timed(fn)
+        times = [[] for _ in routes]
+        for _ in range(a.rounds):  # alternating: what else runs on the box meets the routes alike
+            for t, (_, fn) in zip(times, routes):
+                t.append(timed(fn))
+        mf, txt_f = show(times[0])
+        mc, txt_c = show(times[1])
         print(f"D = {d}: lumen_linear_transform {txt_f}", flush=True)
         print(f"D = {d}: rotate_hoisted + mul_plain_then_add {txt_c}", flush=True)
         print(f"D = {d}: linear_transform / composition = {mf / mc:.3f}", flush=True)
+        if lb is not None:
+            mb, txt_b = show(times[2])
+            print(f"D = {d}: double-hoisted {txt_b}", flush=True)
+            print(f"D = {d}: double-hoisted / single-hoisted = {mb / mf:.3f}", flush=True)
         ctx.set_tuning("LUMEN_KS_LANES", 1)
-        for name, fn in (("lumen_linear_transform", fused), ("composition", composed)):
+        for name, fn in routes:
             sc = scopes(fn)
             print(f"# D = {d}, {name}, scopes (ms / launches, one lane): " +
                   " ".join(f"{k}={v[0]:.2f}/{v[1]}" for k, v in sorted(sc.items()) if v[0] > 0), flush=True)
@@ -137,6 +155,8 @@ def main():
                       f"{rate / copy_rate:.2f} of the copy rate", flush=True)
         ctx.set_tuning("LUMEN_KS_LANES", 0)
         lt.close()
+        if lb is not None:
+            lb.close()
     if s is not top:
         s.free()
     top.free()
