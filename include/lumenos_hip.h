@@ -79,6 +79,9 @@ int lumen_ctx_wait(lumen_ctx *ctx, lumen_ctx *other);
 /* The library's tuning switches (A/B tools; every default is the measured best; DESIGN.md "Run-time
  * switches") are read from the environment ONCE, by lumen_ctx_create; clones inherit them.  This setter is
  * the in-process form for tests and tools: name = "LUMEN_KS_BATCH", "LUMEN_KS_LANES",
+ * "LUMEN_KS_PAIR" (1: on one lane lumen_inner_sum / lumen_matrix_inner_sum send two consecutive batches through a rotation
+ * as one pair; 0: single batches; 2: pairs with the second half extended first, for measurements; value < 0: by ring
+ * degree, the default -- 1 at LogN 14; same residues),
  * "LUMEN_KS_FUSED_DIGITS" (value < 0: derived default), "LUMEN_KS_CLOSE_FUSED" (1, the default: the last rotation of
  * lumen_matrix_inner_sum writes the rescale's coefficient-form input itself; 0: ModDown and the whole rescale; same
  * residues), "LUMEN_KS_C0_FOLD" (1, the default: on that route the doublings before the last rotation run ModDown for

@@ -81,6 +81,11 @@ struct lm_shared {
 struct lm_tuning {
     uint32_t ks_batch = 64;      // LUMEN_KS_BATCH: columns per key-switch batch
     uint32_t ks_lanes = 0;       // LUMEN_KS_LANES: 1 / 2 streams for the column batches of a key switch; 0 = by ring degree
+    // LUMEN_KS_PAIR: 1 = on one lane InnerSum / matrixInnerSumEval send two consecutive batches through a rotation as one
+    // pair -- every kernel but the extension once over both, the extension once per half into its own `ext` block
+    // (lm_ks_pair.h, lm_ks_batch.hip); 0 = single batches; 2 = pairs with the second half extended first (measurement
+    // only); negative = by ring degree (ks_pair, lm_ks_batch.hip).  Same residues.
+    int32_t ks_pair = -1;
     int32_t ks_fused_digits = -1; // LUMEN_KS_FUSED_DIGITS: digits packed inside k_intt_pack (-1: derive)
     // LUMEN_KS_CLOSE_FUSED: 1 = the last rotation of matrixInnerSumEval's InnerSum ends in k_ks_close (lm_ks_close.hip), the
     // rescale's inverse transform with the last ModDown folded in; 0 = k_moddown_ntt and the whole rescale.  Same residues.

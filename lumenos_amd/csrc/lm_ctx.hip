@@ -188,6 +188,9 @@ static int tuning_set(lm_tuning &t, const char *name, long v) {
     } else if (n == "LUMEN_KS_LANES") { // 0: the default by ring degree
         if (!in(0, 2)) return 2;
         t.ks_lanes = (uint32_t)v;
+    } else if (n == "LUMEN_KS_PAIR") { // negative: by ring degree
+        if (v > 2) return 2;
+        t.ks_pair = v >= 0 ? (int32_t)v : -1;
     } else if (n == "LUMEN_KS_FUSED_DIGITS") { // negative: the derived default
         if (v > LM_MAX_LIMBS) return 2;
         t.ks_fused_digits = v >= 0 ? (int32_t)v : -1;
@@ -223,7 +226,7 @@ static int tuning_set(lm_tuning &t, const char *name, long v) {
     return 0;
 }
 static void tuning_from_env(lm_tuning &t) {
-    for (const char *n : {"LUMEN_KS_BATCH", "LUMEN_KS_LANES", "LUMEN_KS_FUSED_DIGITS", "LUMEN_KS_CLOSE_FUSED", "LUMEN_KS_C0_FOLD", "LUMEN_DEBUG",
+    for (const char *n : {"LUMEN_KS_BATCH", "LUMEN_KS_LANES", "LUMEN_KS_PAIR", "LUMEN_KS_FUSED_DIGITS", "LUMEN_KS_CLOSE_FUSED", "LUMEN_KS_C0_FOLD", "LUMEN_DEBUG",
                           "LUMEN_MODUP_TGROUP", "LUMEN_MODDOWN_TGROUP", "LUMEN_KS_PLACEMENT", "LUMEN_BATCH_CHUNKS", "LUMEN_DOT_PAIRS", "LUMEN_DOT_PARTS"}) {
         const char *e = getenv(n);
         // an empty override counts as unset; a value out of range is reported and leaves the default

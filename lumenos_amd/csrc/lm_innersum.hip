@@ -145,7 +145,7 @@ int general_check(lumen_ctx *ctx, uint32_t batch, uint32_t n, const char *what) 
 
 // one more block per lane, of the gadget product's size at the top level
 int lazy_blocks(lumen_ctx *ctx, const KsRun &run, u64 **lazy) {
-    const size_t bytes = (size_t)run.Bmax * 2 * (ctx->L + ctx->K) * ctx->N * 8;
+    const size_t bytes = (size_t)run.Bcap() * 2 * (ctx->L + ctx->K) * ctx->N * 8;
     lazy[0] = (u64 *)lm_scratch(ctx, "ks_lazy", bytes);
     lazy[1] = run.lanes > 1 ? (u64 *)lm_scratch(ctx, "ks_lazy_b", bytes) : lazy[0];
     return lazy[0] && lazy[1] ? 0 : 1;
@@ -259,7 +259,7 @@ int inner_sum_run(lumen_ctx *ctx, const lumen_set *in, uint32_t batch, uint32_t 
         LM_CHECK(ctx, is_plain(ctx, batch, n), "InnerSum length %u is not a power of two <= N", n);
     }
     KsRun run;
-    if (int rc = ks_run_open(ctx, in->count, in->nl, is_plain(ctx, batch, n) ? 1 : 2, false, &run)) return rc;
+    if (int rc = ks_run_open(ctx, in->count, in->nl, is_plain(ctx, batch, n) ? 1 : 2, false, &run, true)) return rc;
     SumPlan plan;
     if (in->count)
         if (int rc = sum_plan(ctx, batch, n, &plan)) return rc;
@@ -293,7 +293,7 @@ int matrix_inner_sum_run(lumen_ctx *ctx, const lumen_set *matrix, const uint64_t
         LM_CHECK(ctx, is_plain(ctx, 1, rows), "rows=%u is not a power of two <= N", rows);
     }
     KsRun run;
-    if (int rc = ks_run_open(ctx, matrix->count, matrix->nl, 2, true, &run)) return rc;
+    if (int rc = ks_run_open(ctx, matrix->count, matrix->nl, 2, true, &run, true)) return rc;
     SumPlan plan;
     if (matrix->count)
         if (int rc = sum_plan(ctx, 1, rows, &plan)) return rc;
@@ -328,7 +328,7 @@ int matrix_inner_sum_run(lumen_ctx *ctx, const lumen_set *matrix, const uint64_t
     // blocks of S, one signed three-word integer per coefficient and column.
     u64 *fold_s[2] = {nullptr, nullptr};
     if (close && ctx->tune.ks_c0_fold && ks_fold_serves(ctx, run.tb, plan.cnt)) {
-        const size_t bytes = 2 * ks_fold_words(ctx, run.Bmax) * 8;
+        const size_t bytes = 2 * ks_fold_words(ctx, run.Bcap()) * 8; // (a pair folds in blocks of its own size: S blocks of 2 Bmax columns)
         fold_s[0] = (u64 *)lm_scratch(ctx, "ks_fold_s", bytes);
         fold_s[1] = run.lanes > 1 ? (u64 *)lm_scratch(ctx, "ks_fold_s_b", bytes) : fold_s[0];
         if (!fold_s[0] || !fold_s[1]) return 1;

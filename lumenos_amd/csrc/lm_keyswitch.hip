@@ -36,7 +36,7 @@
 //                                     polynomial 1 alone, polynomial 0 rotated by the gadget product itself (k_ks_mac_fold: the
 //                                     kernel's text, lm_ks_mac_kernel.h, is included twice) and its lifts folded per coefficient
 // with lumen_ks_mac_probe, which times the gadget product alone.  The other subjects of the key switch live beside it:
-// the batching of its callers (batches, lanes, groups) in lm_ks_batch.hip; the callers in lm_innersum.hip (InnerSum with
+// the batching of its callers (batches, lanes, groups, pairs of batches: lm_ks_pair.h) in lm_ks_batch.hip; the callers in lm_innersum.hip (InnerSum with
 // its lazy accumulator, matrixInnerSumEval), lm_rotate.hip (lumen_automorphism, lumen_rotate_columns / _rows / _hoisted)
 // and lm_mulrelin.hip (the relinearisation); where the scratch buffers sit in HBM in lm_ks_scratch.hip (mechanism) and
 // lm_placement.h (policy); Galois- and relinearisation-key loading and lookup in lm_ks_key.hip; the ciphertext x
@@ -805,22 +805,27 @@ static uint32_t ks_fused_digits(lumen_ctx *ctx, uint32_t B, uint32_t L) {
 // 3. the gadget product of a batch of B columns at the level of `tb` under `key`, [ctx L + K][key_beta][2] whatever the
 // level (the RNS gadget does not depend on it): the limbs modulo P sit behind the context's L Q limbs, in the moduli
 // and in the stored key
-static int launch_ks_mac(lumen_ctx *ctx, const u64 *ext, const u64 *acc, const u64 *key, u64 *u, uint32_t B, KsTables *tb) {
+// `ext`: block 0 of the extended digits, in the layout of Bh columns; ext1: the block of the columns from Bh on (a pair,
+// lm_ks_pair.h; a single batch has Bh == B and no second block)
+static int launch_ks_mac(lumen_ctx *ctx, const u64 *ext, const u64 *ext1, uint32_t Bh, const u64 *acc, const u64 *key, u64 *u, uint32_t B,
+                         KsTables *tb) {
     const uint32_t L = tb->nl, K = ctx->K, pshift = ctx->L - L, key_beta = (ctx->L + K - 1) / K;
+    LM_CHECK(ctx, Bh >= 1 && Bh <= B && (Bh == B || (ext1 && B <= 2 * Bh)), "gadget product: %u columns do not fit blocks of %u", B, Bh);
     const dim3 grid(((ctx->N / LM_MAC_VEC + 255) / 256) * (L + K) * ((B + LM_MAC_COLS - 1) / LM_MAC_COLS));
-    hipLaunchKernelGGL(k_ks_mac, grid, dim3(256), 0, ctx->stream, ext, acc, key, u, B, L, K, tb->beta, pshift, key_beta, ctx->logN,
-                       ctx->mods);
+    hipLaunchKernelGGL(k_ks_mac, grid, dim3(256), 0, ctx->stream, ext, ext1 ? ext1 : ext, Bh, acc, key, u, B, L, K, tb->beta, pshift, key_beta,
+                       ctx->logN, ctx->mods);
     LM_HIP(ctx, hipGetLastError());
     return 0;
 }
 // ... of a doubling whose c0 is folded (k_ks_mac_fold): polynomial 0 of acc_out is written here, under gk's tables
-static int launch_ks_mac_fold(lumen_ctx *ctx, const u64 *ext, const u64 *acc, const lm_galois_key &gk, u64 *u, u64 *acc_out, uint32_t B,
-                              KsTables *tb) {
+static int launch_ks_mac_fold(lumen_ctx *ctx, const u64 *ext, const u64 *ext1, uint32_t Bh, const u64 *acc, const lm_galois_key &gk, u64 *u,
+                              u64 *acc_out, uint32_t B, KsTables *tb) {
     const uint32_t L = tb->nl, K = ctx->K, pshift = ctx->L - L, key_beta = (ctx->L + K - 1) / K;
     LM_CHECK(ctx, ctx->N >= 256 && LM_MAC_VEC == 1, "the folded gadget product works on blocks of 256 coefficients");
+    LM_CHECK(ctx, Bh >= 1 && Bh <= B && (Bh == B || (ext1 && B <= 2 * Bh)), "gadget product: %u columns do not fit blocks of %u", B, Bh);
     const dim3 grid((ctx->N / 256) * (L + K) * ((B + LM_MAC_COLS - 1) / LM_MAC_COLS));
-    hipLaunchKernelGGL(k_ks_mac_fold, grid, dim3(256), 0, ctx->stream, ext, acc, gk.d_key.get(), u, B, L, K, tb->beta, pshift, key_beta,
-                       ctx->logN, ctx->mods, acc_out, gk.d_index.get(), gk.d_inv_index.get());
+    hipLaunchKernelGGL(k_ks_mac_fold, grid, dim3(256), 0, ctx->stream, ext, ext1 ? ext1 : ext, Bh, acc, gk.d_key.get(), u, B, L, K, tb->beta, pshift,
+                       key_beta, ctx->logN, ctx->mods, acc_out, gk.d_index.get(), gk.d_inv_index.get());
     LM_HIP(ctx, hipGetLastError());
     return 0;
 }
@@ -871,17 +876,25 @@ int rotate_decompose(lumen_ctx *ctx, const u64 *acc, uint32_t B, KsTables *tb, c
         lm_prof_scope ps(ctx, "ks_pack_v", (uint64_t)B);
         if (int rc = lm_launch_pack_v(ctx, s.coef + (size_t)2 * nf * N, (size_t)L * N, B, beta - nf, K, 2 * nf, L - 2 * nf)) return rc;
     }
-    // 2. digit extension + NTT
+    // 2. digit extension + NTT: one launch for a single batch; for a pair (lm_ks_pair.h) one per half, each with the work list
+    // and the `ext` layout of a batch of s.half columns, on the half's own columns of coef and acc (column-major both: the
+    // column base is an offset) and into the half's own block
     {
-        const uint64_t nb = (uint64_t)B * tb->pairs.size();
-        const uint32_t *work = nullptr;
-        if (int rc = modup_work_list(ctx, tb, B, &work)) return rc;
-        lm_prof_scope ps(ctx, "ks_modup_ntt", nb);
-        if (int rc = lm_for_any_logn(ctx, ctx->logN, [&](auto n) {
-                return lm_launch(ctx, k_modup_ntt<n>, lm_geom_fwd(n), lm_fwd_grid<n>((uint32_t)nb), s.coef, acc, s.ext, tb->d_bx.get(), B, L, K, beta,
-                                 pshift, work, ctx->mods, ctx->sh->tw_fwd.get());
-            }))
-            return rc;
+        const lm_ks_ext_plan plan = lm_ks_ext_launches(B, s.half, s.second_first);
+        for (uint32_t k = 0; k < plan.n; k++) {
+            const lm_ks_ext_launch &h = plan.at[k];
+            const uint64_t nb = (uint64_t)h.count * tb->pairs.size();
+            const uint32_t *work = nullptr;
+            if (int rc = modup_work_list(ctx, tb, h.count, &work)) return rc;
+            const u64 *coef_h = s.coef + (size_t)h.first * L * N, *acc_h = acc + (size_t)h.first * 2 * L * N;
+            u64 *ext_h = h.block ? s.ext1 : s.ext;
+            lm_prof_scope ps(ctx, "ks_modup_ntt", nb);
+            if (int rc = lm_for_any_logn(ctx, ctx->logN, [&](auto n) {
+                    return lm_launch(ctx, k_modup_ntt<n>, lm_geom_fwd(n), lm_fwd_grid<n>((uint32_t)nb), coef_h, acc_h, ext_h, tb->d_bx.get(), plan.layout, L, K,
+                                     beta, pshift, work, ctx->mods, ctx->sh->tw_fwd.get());
+                }))
+                return rc;
+        }
     }
     return 0;
 }
@@ -898,7 +911,7 @@ int rotate_product(lumen_ctx *ctx, const u64 *acc, uint32_t B, const lm_galois_k
 // 3. gadget product: s.u, all nl + K limbs in the NTT domain
 int rotate_mac(lumen_ctx *ctx, const u64 *acc, uint32_t B, const lm_galois_key &gk, KsTables *tb, const KsScratch &s) {
     lm_prof_scope ps(ctx, "ks_mac", (uint64_t)B);
-    return launch_ks_mac(ctx, s.ext, acc, gk.d_key.get(), s.u, B, tb);
+    return launch_ks_mac(ctx, s.ext, s.ext1, lm_ks_ext_launches(B, s.half).layout, acc, gk.d_key.get(), s.u, B, tb);
 }
 
 // 4a. P limbs of u -> coefficient domain (in place) and packed; u: any block of s.u's layout (ks_u_at).  c1_only: those
@@ -974,7 +987,7 @@ int rotate_add_fold(lumen_ctx *ctx, const u64 *acc, u64 *acc_out, uint32_t B, co
                     const KsScratch &s, const u64 *s_in, u64 *s_out) {
     {
         lm_prof_scope ps(ctx, "ks_mac", (uint64_t)B);
-        if (int rc = launch_ks_mac_fold(ctx, s.ext, acc, gk, s.u, acc_out, B, tb)) return rc;
+        if (int rc = launch_ks_mac_fold(ctx, s.ext, s.ext1, lm_ks_ext_launches(B, s.half).layout, acc, gk, s.u, acc_out, B, tb)) return rc;
     }
     if (int rc = rotate_p_to_coef(ctx, s.u, B, tb)) return rc;
     if (int rc = lift_fold_launch(ctx, s.u, s_in, s_out, B, gal_el, tb)) return rc;
@@ -1013,7 +1026,7 @@ extern "C" int lumen_ks_mac_probe(lumen_ctx *ctx, uint32_t batch, const void *ex
     }
     const u64 *pe = ext ? (const u64 *)ext : s.ext;
     u64 *pu = u ? (u64 *)u : s.u;
-    auto launch = [&] { return launch_ks_mac(ctx, pe, (const u64 *)acc, (const u64 *)key, pu, B, tb); }; // the top level's
+    auto launch = [&] { return launch_ks_mac(ctx, pe, nullptr, B, (const u64 *)acc, (const u64 *)key, pu, B, tb); }; // the top level's
     for (int i = 0; i < 3; i++)
         if (int rc = launch()) return rc;
     LM_HIP(ctx, hipEventRecord(ctx->tm0, ctx->stream));

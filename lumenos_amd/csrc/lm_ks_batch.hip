@@ -21,6 +21,20 @@ uint32_t ks_lanes(const lumen_ctx *ctx) {
     return ctx->tune.ks_lanes ? ctx->tune.ks_lanes : (ctx->logN <= 13 ? 2 : 1);
 }
 
+// Pairs (LUMEN_KS_PAIR; lm_ks_pair.h): on ONE lane, two consecutive batches of a group go through a rotation as one pair
+// of 2 x ks_batch columns.  The kernels whose grids have twelve (or two) units per column -- the c1 inverse and its
+// packing, the gadget product, the P-limb leg, the lift fold, ModDown, the close -- run once over the pair, on blocks of
+// the pair's size: at 64 columns their grids are fractions of a round of the device (ModDown for polynomial 1: 768
+// workgroups on 512 slots), two of six digits miss the packing inside the inverse, and the gadget product reads every
+// key slice once per 64 columns.  The extension kernel runs once per half, at its 64-column shape, into the half's own
+// `ext` block: over 128 columns of one block it loses more than the others gain (EXPERIMENTS 6.6, 6.6b, R21).  Two
+// lanes take no pairs: a pair is what the second lane's scratch would hold.  The default is by ring degree, as the
+// lanes': pairs at N = 2^14, where a run has one lane (EXPERIMENTS R21).  LUMEN_KS_PAIR = 0 / 1 overrides; a pair's
+// callers are InnerSum and matrixInnerSumEval, every other caller of the key switch keeps single batches.
+uint32_t ks_pair(const lumen_ctx *ctx) {
+    return ctx->tune.ks_pair >= 0 ? (uint32_t)ctx->tune.ks_pair : (ctx->logN == 14 ? 1 : 0);
+}
+
 // A set at a level of the chain: full width, 1 <= nl <= L (a set of another context may have more).
 int check_level_of_chain(lumen_ctx *ctx, const lumen_set *in, const char *what) {
     LM_FULL_WIDTH(ctx, in, what);
@@ -28,7 +42,7 @@ int check_level_of_chain(lumen_ctx *ctx, const lumen_set *in, const char *what) 
     return 0;
 }
 
-int ks_run_open(lumen_ctx *ctx, uint32_t count, uint32_t nl, uint32_t max_lanes, bool group_acc, KsRun *run) {
+int ks_run_open(lumen_ctx *ctx, uint32_t count, uint32_t nl, uint32_t max_lanes, bool group_acc, KsRun *run, bool may_pair) {
     if (int rc = get_tables(ctx, &run->top)) return rc; // (refuses K > 2)
     if (int rc = get_tables_at(ctx, nl, &run->tb)) return rc;
     run->Bmax = std::min<uint32_t>(ks_batch(ctx), std::max(count, 1u));
@@ -36,6 +50,7 @@ int ks_run_open(lumen_ctx *ctx, uint32_t count, uint32_t nl, uint32_t max_lanes,
     // polynomials) does not fill the 256 CUs in the kernels that take one workgroup per polynomial
     run->group = group_acc ? std::min<uint32_t>(8 * run->Bmax, std::max(count, 1u)) : std::max(count, 1u);
     run->lanes = std::min(ks_lanes(ctx), max_lanes);
+    run->pair = may_pair && ks_pair(ctx) && run->lanes == 1 && count > run->Bmax; // (at most one batch: nothing to pair)
     run->grouped = group_acc;
     run->group_bytes = (size_t)run->group * 2 * ctx->L * ctx->N * 8; // sized for the top level, as the key switch's scratch
     return 0;
@@ -45,8 +60,10 @@ int ks_run_open(lumen_ctx *ctx, uint32_t count, uint32_t nl, uint32_t max_lanes,
 // on small blocks that the first call at the top would regrow.  The group's accumulators are placed together with the
 // first lane's scratch (get_scratch: five buffers drawn instead of four).
 int ks_run_scratch(lumen_ctx *ctx, KsRun *run) {
-    if (get_scratch(ctx, run->Bmax, run->top, &run->s[0], 0, run->grouped ? &run->acc : nullptr, run->grouped ? run->group_bytes : 0) ||
+    if (get_scratch(ctx, run->Bmax, run->top, &run->s[0], 0, run->grouped ? &run->acc : nullptr, run->grouped ? run->group_bytes : 0,
+                    run->pair) ||
         (run->lanes > 1 && get_scratch(ctx, run->Bmax, run->top, &run->s[1], 1)))
         return 1;
+    run->s[0].second_first = run->pair && ks_pair(ctx) == 2;
     return run->grouped && !run->acc ? 1 : 0;
 }

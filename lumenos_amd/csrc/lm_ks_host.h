@@ -6,6 +6,7 @@
 // product that precedes an InnerSum (lm_mulplain.hip).
 #pragma once
 #include "lm_ks_dev.h"
+#include "lm_ks_pair.h"
 
 // per-context constants of the key switch at one level of the modulus chain (nl of the context's L limbs; below, L
 // stands for nl) and its cached work lists (lm_keyswitch.hip)
@@ -27,9 +28,14 @@ int get_tables(lumen_ctx *ctx, KsTables **out); // the top level's
 // the tables of the level with nl limbs, 1 <= nl <= L, built at its first use and cached (nl == L: get_tables)
 int get_tables_at(lumen_ctx *ctx, uint32_t nl, KsTables **out);
 
-// the scratch buffers of one lane
+// the scratch buffers of one lane.  A pair's scratch (lm_ks_pair.h): coef, u and acc2 sized for 2 * half columns, and two
+// `ext` blocks of `half` columns each -- a batch of more than `half` columns is extended half by half (rotate_decompose)
+// and the gadget product reads both blocks.  half == 0: a scratch of single batches, one `ext` block.
 struct KsScratch {
     u64 *coef, *ext, *u, *acc2;
+    u64 *ext1 = nullptr;       // the second half's block
+    uint32_t half = 0;         // columns per `ext` block
+    bool second_first = false; // the second half is extended first (LUMEN_KS_PAIR=2)
 };
 
 // ---- the steps of a rotation of B columns (lm_keyswitch.hip).  acc, in, out: [B][2][nl][N] at the level of `tb`.
@@ -82,8 +88,9 @@ int rotate_close_fold(lumen_ctx *ctx, const u64 *acc, u64 *coef_out, uint32_t B,
 int lift_fold_launch(lumen_ctx *ctx, const u64 *u, const u64 *s_in, u64 *s_out, uint32_t B, uint64_t gal_el, KsTables *tb);
 // the scratch of a batch of B columns on `lane`, placed by measurement at a context's first key switch (lm_ks_scratch.hip).
 // tb: always the TOP level's tables, whatever level asks -- the blocks are sized, and the candidates timed, once.
+// pair: the scratch of a pair of batches of B columns each (lane 0 alone; the second `ext` block is the one lane 1 would have)
 int get_scratch(lumen_ctx *ctx, uint32_t B, KsTables *tb, KsScratch *s, int lane = 0, u64 **group_acc = nullptr,
-                size_t group_acc_bytes = 0);
+                size_t group_acc_bytes = 0, bool pair = false);
 
 // step 0, MulNew(ct, pt) (lm_mulplain.hip): the plaintext as the device multiplier pt * T, and out = ct (.) it
 int upload_ptT(lumen_ctx *ctx, const uint64_t *pt, uint32_t nl, u64 **out);
@@ -109,9 +116,10 @@ std::shared_ptr<lm_galois_key> lm_relin_key(lumen_ctx *ctx);
 int ks_find_key(lumen_ctx *ctx, uint64_t gal_el, const lm_galois_key **gk);
 // a set at a level of the chain: full width, 1 <= nl <= L (lm_ks_batch.hip)
 int check_level_of_chain(lumen_ctx *ctx, const lumen_set *in, const char *what);
-// the batching of a key switch: columns per batch and lanes of the context (lm_ks_batch.hip)
+// the batching of a key switch: columns per batch, lanes of the context, pairs of batches (lm_ks_batch.hip)
 uint32_t ks_batch(const lumen_ctx *ctx);
 uint32_t ks_lanes(const lumen_ctx *ctx);
+uint32_t ks_pair(const lumen_ctx *ctx); // 0: none; 1: pairs; 2: pairs, the second half extended first
 // enqueue on the context's second stream for the lifetime of the guard
 struct LaneGuard {
     lumen_ctx *ctx;
@@ -125,11 +133,14 @@ struct LaneGuard {
 // ---- the batch driver of the key switch's callers (lm_ks_batch.hip): `count` ciphertexts at the level of nl limbs go
 // through the key switch in BATCHES of at most Bmax columns, which alternate between the LANES; a caller with an
 // accumulator for a GROUP of batches (matrixInnerSumEval, lumen_mul_relin: every batch works in its own slice of it)
-// takes groups of 8 batches, the others one group of everything.
+// takes groups of 8 batches, the others one group of everything.  With `pair` (one lane, a caller that asked for it:
+// InnerSum and matrixInnerSumEval) two consecutive batches of a group go as one pair of up to Bcap = 2 Bmax columns
+// (lm_ks_take).
 struct KsRun {
     KsTables *top = nullptr, *tb = nullptr; // the top level's tables (they size the scratch) and the level's
     uint32_t Bmax = 0, group = 0, lanes = 1;
-    bool grouped = false;
+    bool grouped = false, pair = false;
+    uint32_t Bcap() const { return pair ? 2 * Bmax : Bmax; } // the most columns a batch has: a caller's per-lane blocks are sized for it
     size_t group_bytes = 0; // a group's accumulators at the TOP level
     KsScratch s[2] = {};    // per lane
     u64 *acc = nullptr;     // the group's accumulators (grouped runs)
@@ -137,7 +148,8 @@ struct KsRun {
 // Opens a run in two steps, because a caller's own refusals and allocations stand between them.  ks_run_open: both table
 // sets (it refuses what the key switch cannot serve) and the batching; allocates no scratch.  max_lanes: 1 keeps the run
 // on the main stream, 2 gives it the context's lanes.  ks_run_scratch: the lanes' scratch and the group's accumulators.
-int ks_run_open(lumen_ctx *ctx, uint32_t count, uint32_t nl, uint32_t max_lanes, bool group_acc, KsRun *run);
+// may_pair: the caller's per-batch work takes a pair's scratch (every rotate_* step does).
+int ks_run_open(lumen_ctx *ctx, uint32_t count, uint32_t nl, uint32_t max_lanes, bool group_acc, KsRun *run, bool may_pair = false);
 int ks_run_scratch(lumen_ctx *ctx, KsRun *run);
 // The loop: per group fork, batch(g0, first, B, s, acc) for every batch -- ciphertexts [g0 + first, g0 + first + B) of the
 // caller's, on the batch's lane, s that lane's scratch, acc the batch's slice of the group's accumulators (words of ctw per
@@ -151,8 +163,8 @@ int ks_run(lumen_ctx *ctx, const KsRun &run, uint32_t count, size_t ctw, Batch &
             LM_HIP(ctx, hipStreamWaitEvent(ctx->stream2, ctx->ev_fork, 0));
         }
         uint32_t lane = 0;
-        for (uint32_t first = 0; first < gn; first += run.Bmax, lane = (lane + 1) % run.lanes) {
-            const uint32_t B = std::min(run.Bmax, gn - first);
+        for (uint32_t first = 0, B = 0; first < gn; first += B, lane = (lane + 1) % run.lanes) {
+            B = lm_ks_take(run.Bmax, run.pair, gn - first);
             LaneGuard guard(ctx, (int)lane);
             if (int rc = batch(g0, first, B, run.s[lane], run.acc ? run.acc + (size_t)first * ctw : nullptr)) return rc;
         }

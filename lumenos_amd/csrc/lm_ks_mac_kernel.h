@@ -4,14 +4,16 @@
 // the kernel it was before the fold existed (tools/kernel_asm_diff.py), whoever calls it.
 #if LM_KS_MAC_FOLD
 // acc_out: the other block of the accumulator's ping-pong; index, inv_index: the rotation's gather tables
-__global__ __launch_bounds__(256) void k_ks_mac_fold(const u64 *__restrict__ ext, const u64 *__restrict__ acc,
+__global__ __launch_bounds__(256) void k_ks_mac_fold(const u64 *__restrict__ ext, const u64 *__restrict__ ext1, uint32_t Bh,
+                                                     const u64 *__restrict__ acc,
                                                      const u64 *__restrict__ key, u64 *__restrict__ u, uint32_t B,
                                                      uint32_t L, uint32_t K, uint32_t beta, uint32_t pshift,
                                                      uint32_t key_beta, uint32_t logN, lm_mods mods,
                                                      u64 *__restrict__ acc_out, const uint32_t *__restrict__ index,
                                                      const uint32_t *__restrict__ inv_index) {
 #else
-__global__ __launch_bounds__(256) void k_ks_mac(const u64 *__restrict__ ext, const u64 *__restrict__ acc,
+__global__ __launch_bounds__(256) void k_ks_mac(const u64 *__restrict__ ext, const u64 *__restrict__ ext1, uint32_t Bh,
+                                                const u64 *__restrict__ acc,
                                                 const u64 *__restrict__ key, u64 *__restrict__ u, uint32_t B,
                                                 uint32_t L, uint32_t K, uint32_t beta, uint32_t pshift,
                                                 uint32_t key_beta, uint32_t logN, lm_mods mods) {
@@ -61,8 +63,11 @@ __global__ __launch_bounds__(256) void k_ks_mac(const u64 *__restrict__ ext, con
 #pragma unroll
         for (int c = 0; c < LM_MAC_COLS; c++) {
             const uint32_t bc = b0 + c < B ? b0 + c : B - 1;
+            // the extended digits sit in blocks of Bh columns (a pair of batches, lm_ks_pair.h: two; a single batch has Bh == B):
+            // column bc is local column bc % Bh of block bc / Bh -- workgroup-uniform, as bc is
+            const u64 *xb = bc < Bh ? ext : ext1;
             g.x[c] = d == own ? vec::load(acc + ((size_t)(bc * 2 + 1) * L + t) * N + i)
-                              : vec::load_once(ext + ks_ext_at(bc, d, t, B, beta) * N + i);
+                              : vec::load_once(xb + ks_ext_at(bc < Bh ? bc : bc - Bh, d, t, Bh, beta) * N + i);
         }
         return g;
     };

@@ -39,23 +39,34 @@ struct EventPair { // two pooled events
 // its own slice of it) is placed by the same measurement -- in situ the rotations alternate between reading a slice of it
 // and reading the twin, and with only the four buffers above chosen the gadget product still came out in two modes from
 // process to process (331 / 349 ms per step).
-int get_scratch(lumen_ctx *ctx, uint32_t B, KsTables *tb, KsScratch *s, int lane, u64 **group_acc, size_t group_acc_bytes) {
+// pair (lm_ks_pair.h; lane 0): coef, u and the twin hold 2 B columns, and a SECOND `ext` block of B columns -- the one lane 1
+// would have, under lane 1's name -- is drawn and chosen like the first, right after it; the timed rotations are a pair's.
+// The selection's transient memory and time roughly double.
+int get_scratch(lumen_ctx *ctx, uint32_t B, KsTables *tb, KsScratch *s, int lane, u64 **group_acc, size_t group_acc_bytes, bool pair) {
     const size_t N = ctx->N, L = ctx->L, LK = ctx->L + ctx->K, beta = tb->beta;
-    const char *names[2][5] = {{"ks_coef", "ks_ext", "ks_u", "ks_acc2", "ks_acc"}, {"ks_coef_b", "ks_ext_b", "ks_u_b", "ks_acc2_b", "ks_acc"}};
-    const int NB = group_acc ? 5 : 4;
-    const size_t bytes[5] = {(size_t)B * L * N * 8, (size_t)B * beta * LK * N * 8, (size_t)B * 2 * LK * N * 8, (size_t)B * 2 * L * N * 8,
-                             std::max(group_acc_bytes, (size_t)B * 2 * L * N * 8)};
+    LM_CHECK(ctx, !pair || lane == 0, "a pair of key-switch batches runs on the first lane");
+    enum { COEF, EXT, U, ACC2, ACC, EXT1, NBUF };
+    const char *names[2][NBUF] = {{"ks_coef", "ks_ext", "ks_u", "ks_acc2", "ks_acc", "ks_ext_b"}, {"ks_coef_b", "ks_ext_b", "ks_u_b", "ks_acc2_b", "ks_acc", ""}};
+    const uint32_t Bt = pair ? 2 * B : B; // columns of the blocks every kernel but the extension works on
+    const size_t bytes[NBUF] = {(size_t)Bt * L * N * 8, (size_t)B * beta * LK * N * 8, (size_t)Bt * 2 * LK * N * 8, (size_t)Bt * 2 * L * N * 8,
+                                std::max(group_acc_bytes, (size_t)Bt * 2 * L * N * 8), (size_t)B * beta * LK * N * 8};
     u64 *dummy = nullptr;
-    u64 **slot[5] = {&s->coef, &s->ext, &s->u, &s->acc2, group_acc ? group_acc : &dummy};
+    u64 **slot[NBUF] = {&s->coef, &s->ext, &s->u, &s->acc2, group_acc ? group_acc : &dummy, &s->ext1};
+    std::vector<int> ids = {COEF, EXT, U, ACC2}; // the buffers of this call; at[c]: buffer c's place among them
+    if (group_acc) ids.push_back(ACC);
+    if (pair) ids.push_back(EXT1);
+    int at[NBUF] = {-1, -1, -1, -1, -1, -1};
+    for (size_t k = 0; k < ids.size(); k++) at[ids[k]] = (int)k;
+    s->ext1 = nullptr, s->half = pair ? B : 0, s->second_first = false;
     const uint32_t Kc = ctx->tune.ks_placement;
     // what is already there and large enough stays (a buffer shared with the other lane, a context whose batch size grew):
     // only the missing buffers are drawn
     std::vector<lm_place_buf> bufs;
     bool have = true;
-    for (int c = 0; c < NB; c++) {
+    for (int c : ids) {
         auto it = ctx->scratch.find(names[lane][c]);
         const bool there = it != ctx->scratch.end() && it->second && it->second.count() >= bytes[c];
-        bufs.push_back({bytes[c], there ? it->second.get() : nullptr, c == 4 ? 4u : Kc}); // (the group accumulator is the big one: four draws)
+        bufs.push_back({bytes[c], there ? it->second.get() : nullptr, c == ACC ? 4u : Kc}); // (the group accumulator is the big one: four draws)
         have = have && there;
     }
     // the key the timed rotations run under: any Galois key, or the relinearisation key where a context's first key
@@ -69,20 +80,20 @@ int get_scratch(lumen_ctx *ctx, uint32_t B, KsTables *tb, KsScratch *s, int lane
     if (!gk) gk = rlk.get();
     auto plain = [&]() -> int {
         bool ok = true;
-        for (int c = 0; c < NB; c++) ok = (*slot[c] = (u64 *)lm_scratch(ctx, names[lane][c], bytes[c])) != nullptr && ok;
+        for (int c : ids) ok = (*slot[c] = (u64 *)lm_scratch(ctx, names[lane][c], bytes[c])) != nullptr && ok;
         return ok ? 0 : 1;
     };
     // small buffers live in the caches, and without a key no rotation can be timed: plain allocation
-    if (have || Kc < 2 || bytes[1] < ((size_t)64 << 20) || !gk || !gk->d_key) return plain();
+    if (have || Kc < 2 || bytes[EXT] < ((size_t)64 << 20) || !gk || !gk->d_key) return plain();
     { // the selection: whatever it drew and did not hand out is freed when this scope ends, on every path
         size_t free_b = 0, total_b = 0;
         (void)hipMemGetInfo(&free_b, &total_b);
         lm_dev<u64> probe_acc;
-        if (!group_acc) (void)probe_acc.alloc(ctx, bytes[3] / 8, "the placement's probe accumulator");
+        if (!group_acc) (void)probe_acc.alloc(ctx, bytes[ACC2] / 8, "the placement's probe accumulator");
         lm_placement place(bufs, [](void *p) { hipFree(p); });
-        const bool drew = place.draw(Kc, free_b, [&](size_t c) {
+        const bool drew = place.draw(Kc, free_b, [&](size_t k) {
             void *p = nullptr;
-            return hipMalloc(&p, bytes[c]) == hipSuccess ? p : nullptr;
+            return hipMalloc(&p, bytes[ids[k]]) == hipSuccess ? p : nullptr;
         });
         (void)hipGetLastError();
         if (drew && (group_acc || probe_acc)) { // otherwise memory is short: no choice to make
@@ -93,37 +104,42 @@ int get_scratch(lumen_ctx *ctx, uint32_t B, KsTables *tb, KsScratch *s, int lane
                 // two rotations of a batch (the accumulator ping-pongs with its twin): one pair untimed, two timed -- in the first
                 // and in the last batch slice of the group accumulator
                 auto eval = [&](const size_t *pick, float *ms) -> int {
+                    auto blk = [&](int c) { return (u64 *)place.block((size_t)at[c], pick[at[c]]); };
                     KsScratch t;
-                    t.coef = (u64 *)place.block(0, pick[0]), t.ext = (u64 *)place.block(1, pick[1]), t.u = (u64 *)place.block(2, pick[2]),
-                    t.acc2 = (u64 *)place.block(3, pick[3]);
-                    u64 *a0 = group_acc ? (u64 *)place.block(4, pick[4]) : probe_acc.get();
-                    u64 *a1 = group_acc ? a0 + (bytes[4] - bytes[3]) / 8 : a0;
+                    t.coef = blk(COEF), t.ext = blk(EXT), t.u = blk(U), t.acc2 = blk(ACC2);
+                    if (pair) t.ext1 = blk(EXT1), t.half = B;
+                    u64 *a0 = group_acc ? blk(ACC) : probe_acc.get();
+                    u64 *a1 = group_acc ? a0 + (bytes[ACC] - bytes[ACC2]) / 8 : a0;
                     for (int r = 0; r < 3; r++) {
                         if (r == 1) LM_HIP(ctx, hipEventRecord(ev.e0, ctx->stream));
                         u64 *a = r == 2 ? a1 : a0;
-                        if (int e = rotate_accumulate(ctx, a, t.acc2, B, *gk, tb, t)) return e;
-                        if (int e = rotate_accumulate(ctx, t.acc2, a, B, *gk, tb, t)) return e;
+                        if (int e = rotate_accumulate(ctx, a, t.acc2, Bt, *gk, tb, t)) return e;
+                        if (int e = rotate_accumulate(ctx, t.acc2, a, Bt, *gk, tb, t)) return e;
                     }
                     LM_HIP(ctx, hipEventRecord(ev.e1, ctx->stream));
                     LM_HIP(ctx, hipEventSynchronize(ev.e1));
                     LM_HIP(ctx, hipEventElapsedTime(ms, ev.e0, ev.e1));
                     return 0;
                 };
-                // u, ext, the group accumulator, its twin, coef: the order the sensitivities were measured in
-                rc = place.descend(group_acc ? std::vector<int>{2, 1, 4, 3, 0} : std::vector<int>{2, 1, 3, 0}, eval);
+                // u, ext (both blocks of a pair), the group accumulator, its twin, coef: the order the sensitivities were measured in
+                std::vector<int> order;
+                for (int c : {U, EXT, EXT1, ACC, ACC2, COEF})
+                    if (at[c] >= 0) order.push_back(at[c]);
+                rc = place.descend(order, eval);
             }
             if (rc) {
                 lm_sync_all(ctx);
                 return rc;
             }
             if (ctx->tune.debug)
-                fprintf(stderr, "[lumenos_hip] key-switch scratch placement (lane %d, %u columns): %zu / %zu / %zu candidates for u / ext / the group "
-                                "accumulator, 4 rotations of the first draw %.3f ms, of the chosen blocks %.3f ms\n", lane, B, place.count(2),
-                        place.count(1), NB == 5 ? place.count(4) : (size_t)0, place.first, place.best_all);
+                fprintf(stderr, "[lumenos_hip] key-switch scratch placement (lane %d, %u columns%s): %zu / %zu / %zu candidates for u / ext / the group "
+                                "accumulator, 4 rotations of the first draw %.3f ms, of the chosen blocks %.3f ms\n", lane, Bt, pair ? ", a pair" : "",
+                        place.count((size_t)at[U]), place.count((size_t)at[EXT]), group_acc ? place.count((size_t)at[ACC]) : (size_t)0, place.first,
+                        place.best_all);
             LM_HIP(ctx, hipStreamSynchronize(ctx->stream)); // nothing may still run on a block that is about to be freed
-            for (int c = 0; c < NB; c++) {
-                void *chosen = place.take(c);
-                if (!bufs[c].fixed) lm_scratch_adopt(ctx, names[lane][c], chosen, bytes[c]);
+            for (int c : ids) {
+                void *chosen = place.take((size_t)at[c]);
+                if (!bufs[(size_t)at[c]].fixed) lm_scratch_adopt(ctx, names[lane][c], chosen, bytes[c]);
                 *slot[c] = (u64 *)chosen;
             }
             return 0;
