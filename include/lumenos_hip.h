@@ -93,7 +93,12 @@ int lumen_ctx_wait(lumen_ctx *ctx, lumen_ctx *other);
  * per limb in lumen_batch_ciphertexts, 0 .. 4096, 0 = derived from the CU count; the residues do not depend on it),
  * "LUMEN_DOT_PAIRS" (coefficient pairs per block of the dot product's tensor kernel, 256 or 512, 0 = by the size of the
  * launch; same residues), "LUMEN_DOT_PARTS" (blocks the terms of one sum are split over there, 1 .. 256, 0 = by the size
- * of the launch; same residues).  An
+ * of the launch; same residues), "LUMEN_ALLOC_FILL" (a testing mode; 0, the default: off, nothing changes; 1 .. 255:
+ * every device block the library draws from then on -- tables, keys, temporaries, scratch, set storage, fresh or out of
+ * the pool -- is filled with this byte before its first use and, when freshly drawn, has a 4 KiB guard band of another
+ * byte behind it; setting a non-zero value on a live context, the current one as well, waits for the context's
+ * streams and fills every scratch buffer and pooled block again, and is refused while a lumen_leaf_digests_begin job
+ * is in flight; results must not depend on it; see lumen_ctx_alloc_check).  An
  * unknown name or a value out of a switch's range is an error and changes nothing. */
 int lumen_ctx_set_tuning(lumen_ctx *ctx, const char *name, long value);
 /* TEST HOOK (not a tuning switch, never read from the environment): lumen_group_create then lets LUMEN_TRANSPORT_RCCL
@@ -887,6 +892,12 @@ int lumen_group_stats_reset(lumen_group *g);
  * block the library itself uses (batch 0 = the library's batch size).  Contents are irrelevant (data-independent
  * kernel). */
 int lumen_ctx_scratch_info(lumen_ctx *ctx, const char *name, void **ptr, size_t *bytes);
+/* The fill-and-fence mode of the tests ("LUMEN_ALLOC_FILL", see lumen_ctx_set_tuning): waits for the context's streams
+ * and reads back the guard band behind every live guarded block of the context -- its scratch buffers, the sets in its
+ * pool and the sets the caller holds.  Fails naming the first damaged block, its size and the offset of the first
+ * changed byte behind its end.  With the mode off it returns 0 and touches nothing.  The same check runs, reporting on
+ * stderr, whenever a guarded block is released and at lumen_ctx_destroy. */
+int lumen_ctx_alloc_check(lumen_ctx *ctx);
 int lumen_ks_mac_probe(lumen_ctx *ctx, uint32_t batch, const void *ext, const void *acc, const void *key, void *u,
                        uint32_t reps, float *ms_per_launch);
 

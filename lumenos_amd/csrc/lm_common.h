@@ -53,6 +53,7 @@ struct lumen_set {
     size_t words = 0;
     bool owner = true;
     lumen_ctx *home = nullptr; // context whose pool the storage returns to
+    unsigned char canary = 0;  // of the guard band behind the storage (LUMEN_ALLOC_FILL); 0: none
 };
 
 // Device tables that never change once loaded: shared by a context and its clones
@@ -107,6 +108,9 @@ struct lm_tuning {
     uint32_t dot_pairs = 0;
     // LUMEN_DOT_PARTS: blocks a group's terms are split over in k_tensor_dot, 1 .. 256 (at most the terms); 0 = by the size of the launch
     uint32_t dot_parts = 0;
+    // LUMEN_ALLOC_FILL: 0 = off; 1 .. 255 = every block the library draws is filled with this byte before its first use and
+    // fenced with a guard band (lm_dev.h, lm_ctx.hip; DESIGN.md, "Who owns device memory").  A testing mode: fills wait.
+    uint32_t alloc_fill = 0;
     // lumen_test_allow_shared_device_rccl (tests only; not reachable through lumen_ctx_set_tuning or the environment):
     // LUMEN_TRANSPORT_RCCL accepts ranks that share a device, for the test double tests/cpp/fake_rccl.cpp
     uint32_t rccl_shared_device = 0;
@@ -159,6 +163,7 @@ struct lumen_ctx {
     struct pool_block {
         void *p;
         hipEvent_t ready;
+        unsigned char canary = 0; // of the guard band the block was drawn with; 0: none
     };
     std::multimap<size_t, pool_block> pool;
     size_t pool_bytes = 0;

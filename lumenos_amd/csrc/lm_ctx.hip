@@ -4,6 +4,7 @@
 // tables (Lattigo SubRing.RootsForward/RootsBackward -- rebuilt here from the
 // primitive 2N-th root the host passes, with Shoup companions instead of
 // Montgomery form).
+#include <atomic>
 #include <cstring>
 #include <thread>
 
@@ -21,6 +22,101 @@ int lm_fail(lumen_ctx *ctx, const char *fmt, ...) {
     lm_global_err = buf;
     fprintf(stderr, "[lumenos_hip] error: %s\n", buf); // vdec_wrapper.c:19-22 convention
     return 1;
+}
+
+// ---- the fill-and-fence mode (LUMEN_ALLOC_FILL; lm_dev.h; DESIGN.md, "Who owns device memory")
+// What tuning_from_env last read, for a block drawn without a context.  Process-wide and written by every lumen_ctx_create: it
+// follows the environment as the LAST created context saw it, and lumen_ctx_set_tuning does not reach it.  No caller passes a
+// NULL context to lm_dev::alloc today; one that does gets the mode of the environment, never that of a live context.
+static std::atomic<unsigned> lm_env_alloc_fill{0};
+static inline unsigned char canary_for(unsigned fill) { return fill == 0xC3 ? 0x3C : 0xC3; }
+
+unsigned lm_alloc_fill_byte(const lumen_ctx *ctx) { return ctx ? ctx->tune.alloc_fill : lm_env_alloc_fill.load(); }
+
+unsigned char lm_alloc_fill(lumen_ctx *ctx, void *p, size_t bytes, unsigned fill, bool band, const char *what) {
+    const unsigned char canary = canary_for(fill);
+    char *b = (char *)p;
+    hipStream_t s = ctx ? ctx->stream : nullptr;
+    // the block's first user may sit on any of the context's streams: the fill is waited for
+    hipError_t e = s ? hipMemsetAsync(b, (int)fill, bytes, s) : hipMemset(b, (int)fill, bytes);
+    if (e == hipSuccess && band) e = s ? hipMemsetAsync(b + bytes, canary, LM_GUARD_BYTES, s) : hipMemset(b + bytes, canary, LM_GUARD_BYTES);
+    if (e == hipSuccess && s) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        lm_fail(ctx, "LUMEN_ALLOC_FILL: filling %s (%zu bytes) failed: %s", what, bytes, hipGetErrorString(e));
+        return 0;
+    }
+    return canary;
+}
+
+int lm_alloc_band_check(lumen_ctx *ctx, const void *p, size_t bytes, unsigned char canary, const char *what) {
+    unsigned char host[LM_GUARD_BYTES];
+    if (hipMemcpy(host, (const char *)p + bytes, LM_GUARD_BYTES, hipMemcpyDeviceToHost) != hipSuccess) {
+        (void)hipGetLastError();
+        return lm_fail(ctx, "reading the guard band of %s (%zu bytes) back failed", what, bytes);
+    }
+    for (size_t i = 0; i < LM_GUARD_BYTES; i++)
+        if (host[i] != canary)
+            return lm_fail(ctx, "the guard band of %s (%zu bytes) is damaged: a write past the block's end, the first changed byte at offset %zu "
+                                "behind it (0x%02x where the canary is 0x%02x)", what, bytes, i, host[i], canary);
+    return 0;
+}
+
+// the sets callers hold whose storage has a guard band, with the context that drew it: a set may be destroyed through
+// another context than its home, hence one table for the process
+static std::mutex guarded_mu;
+static std::map<lumen_set *, lumen_ctx *> guarded_sets;
+static void guarded_add(lumen_ctx *ctx, lumen_set *s) {
+    std::lock_guard<std::mutex> lk(guarded_mu);
+    guarded_sets[s] = ctx;
+}
+static void guarded_drop(lumen_set *s) {
+    std::lock_guard<std::mutex> lk(guarded_mu);
+    guarded_sets.erase(s);
+}
+// a context that goes: the sets it drew and the caller still holds stay what they are, but no later context at the same
+// address may take them for its own
+static void guarded_forget(lumen_ctx *ctx) {
+    std::lock_guard<std::mutex> lk(guarded_mu);
+    for (auto it = guarded_sets.begin(); it != guarded_sets.end();) it = it->second == ctx ? guarded_sets.erase(it) : std::next(it);
+}
+static std::string set_name(const lumen_set *s) {
+    char buf[64];
+    snprintf(buf, sizeof(buf), "a %u x %u-limb set", s->count, s->nl);
+    return buf;
+}
+
+// the digest buffers are handed out by pointer (lumen_leaf_digests_end_device, the group's gathered leaves): state, not
+// scratch -- lumen_ctx_trim keeps them and the refill of LUMEN_ALLOC_FILL leaves them alone
+static bool scratch_is_state(const std::string &name) { return name == "digests_async" || name == "group_digests"; }
+
+// LUMEN_ALLOC_FILL set on a live context: every scratch block and every pooled block is filled again (the streams drained)
+static int alloc_refill(lumen_ctx *ctx) {
+    const unsigned fill = ctx->tune.alloc_fill;
+    lm_sync_all(ctx);
+    for (auto &kv : ctx->scratch)
+        if (kv.second && !scratch_is_state(kv.first)) LM_HIP(ctx, hipMemsetAsync(kv.second.get(), (int)fill, std::max<size_t>(kv.second.count(), 1), ctx->stream));
+    for (auto &kv : ctx->pool) LM_HIP(ctx, hipMemsetAsync(kv.second.p, (int)fill, kv.first, ctx->stream));
+    LM_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+extern "C" int lumen_ctx_alloc_check(lumen_ctx *ctx) {
+    LM_CHECK(nullptr, ctx, "lumen_ctx_alloc_check: NULL ctx");
+    LM_ENTER(ctx);
+    if (!ctx->tune.alloc_fill) return 0;
+    lm_sync_all(ctx);
+    for (auto &kv : ctx->scratch)
+        if (kv.second.canary())
+            if (int rc = lm_alloc_band_check(ctx, kv.second.get(), std::max<size_t>(kv.second.count(), 1), kv.second.canary(), kv.first.c_str())) return rc;
+    for (auto &kv : ctx->pool)
+        if (kv.second.canary)
+            if (int rc = lm_alloc_band_check(ctx, kv.second.p, kv.first, kv.second.canary, "a pooled set")) return rc;
+    std::lock_guard<std::mutex> lk(guarded_mu);
+    for (auto &kv : guarded_sets)
+        if (kv.second == ctx)
+            if (int rc = lm_alloc_band_check(ctx, kv.first->d, kv.first->words * sizeof(u64), kv.first->canary, set_name(kv.first).c_str())) return rc;
+    return 0;
 }
 
 void *lm_scratch(lumen_ctx *ctx, const char *name, size_t bytes) {
@@ -155,6 +251,7 @@ void lm_build_tw(uint64_t q, uint64_t psi, uint32_t logN, std::vector<tw_t> &fwd
 // frees the pooled storage (the caller has waited for the context's streams)
 static void pool_drain(lumen_ctx *ctx) {
     for (auto &kv : ctx->pool) {
+        if (kv.second.canary) (void)lm_alloc_band_check(nullptr, kv.second.p, kv.first, kv.second.canary, "a pooled set");
         hipFree(kv.second.p);
         if (kv.second.ready) ctx->ev_pool.push_back(kv.second.ready);
     }
@@ -220,6 +317,9 @@ static int tuning_set(lm_tuning &t, const char *name, long v) {
     } else if (n == "LUMEN_DOT_PARTS") { // 0: by the size of the launch
         if (!in(0, 256)) return 2;
         t.dot_parts = (uint32_t)v;
+    } else if (n == "LUMEN_ALLOC_FILL") { // 0: off; otherwise the fill byte
+        if (!in(0, 255)) return 2;
+        t.alloc_fill = (uint32_t)v;
     } else {
         return 1;
     }
@@ -227,12 +327,14 @@ static int tuning_set(lm_tuning &t, const char *name, long v) {
 }
 static void tuning_from_env(lm_tuning &t) {
     for (const char *n : {"LUMEN_KS_BATCH", "LUMEN_KS_LANES", "LUMEN_KS_PAIR", "LUMEN_KS_FUSED_DIGITS", "LUMEN_KS_CLOSE_FUSED", "LUMEN_KS_C0_FOLD", "LUMEN_DEBUG",
-                          "LUMEN_MODUP_TGROUP", "LUMEN_MODDOWN_TGROUP", "LUMEN_KS_PLACEMENT", "LUMEN_BATCH_CHUNKS", "LUMEN_DOT_PAIRS", "LUMEN_DOT_PARTS"}) {
+                          "LUMEN_MODUP_TGROUP", "LUMEN_MODDOWN_TGROUP", "LUMEN_KS_PLACEMENT", "LUMEN_BATCH_CHUNKS", "LUMEN_DOT_PAIRS", "LUMEN_DOT_PARTS",
+                          "LUMEN_ALLOC_FILL"}) {
         const char *e = getenv(n);
         // an empty override counts as unset; a value out of range is reported and leaves the default
         if (e && *e && tuning_set(t, n, atol(e)))
             fprintf(stderr, "[lumenos_hip] %s=%s is out of range: ignored\n", n, e);
     }
+    lm_env_alloc_fill = t.alloc_fill; // blocks drawn without a context follow the environment (lm_alloc_fill_byte)
 }
 
 // A/B tools and tests: the same switches the environment sets at lumen_ctx_create, on a live context
@@ -240,9 +342,13 @@ static void tuning_from_env(lm_tuning &t) {
 extern "C" int lumen_ctx_set_tuning(lumen_ctx *ctx, const char *name, long value) {
     LM_CHECK(nullptr, ctx && name, "lumen_ctx_set_tuning: NULL argument");
     LM_ENTER(ctx);
+    const bool fill = std::string(name) == "LUMEN_ALLOC_FILL";
+    LM_CHECK(ctx, !fill || !ctx->aux_digests, "lumen_ctx_set_tuning(LUMEN_ALLOC_FILL): a lumen_leaf_digests_begin job is in flight");
     const int rc = tuning_set(ctx->tune, name, value);
     LM_CHECK(ctx, rc != 1, "unknown tuning switch %s", name);
     LM_CHECK(ctx, rc == 0, "tuning switch %s: value %ld is out of range (nothing changed)", name, value);
+    // a fill byte, the one already set as well: what the context holds in scratch and in its pool is filled again
+    if (fill && value) return alloc_refill(ctx);
     return 0;
 }
 
@@ -385,6 +491,7 @@ extern "C" void lumen_ctx_destroy(lumen_ctx *ctx) {
         if (ctx->stream) hipStreamDestroy(ctx->stream);
         ctx->sh.reset(); // the shared tables go with their last user
     }
+    guarded_forget(ctx);
     delete ctx;
 }
 
@@ -399,7 +506,7 @@ extern "C" int lumen_ctx_trim(lumen_ctx *ctx) {
     for (auto it = ctx->scratch.begin(); it != ctx->scratch.end();) {
         // the digest buffers are handed out by pointer (lumen_leaf_digests_end_device, the group's gathered
         // leaves) and are a few hundred KB: they stay
-        if (it->first == "digests_async" || it->first == "group_digests") {
+        if (scratch_is_state(it->first)) {
             ++it;
             continue;
         }
@@ -453,9 +560,12 @@ extern "C" int lumen_set_create_lanes(lumen_ctx *ctx, uint32_t count, uint32_t n
     s->home = ctx;
     if (s->words) {
         const size_t bytes = s->words * sizeof(u64);
+        const unsigned fill = ctx->tune.alloc_fill; // (the pool keys on the caller's bytes, band or none)
+        bool band = false;
         auto it = ctx->pool.find(bytes);
         if (it != ctx->pool.end()) { // reuse a block of exactly this size
             s->d = (u64 *)it->second.p;
+            s->canary = it->second.canary;
             if (hipEvent_t ready = it->second.ready) { // returned in stream order: whatever runs next waits on the device
                 (void)hipStreamWaitEvent(ctx->stream, ready, 0);
                 (void)hipStreamWaitEvent(ctx->stream2, ready, 0);
@@ -465,12 +575,14 @@ extern "C" int lumen_set_create_lanes(lumen_ctx *ctx, uint32_t count, uint32_t n
             ctx->pool.erase(it);
             ctx->pool_bytes -= bytes;
         } else {
-            hipError_t e = hipMalloc((void **)&s->d, bytes);
+            band = fill != 0;
+            const size_t draw = bytes + (band ? LM_GUARD_BYTES : 0);
+            hipError_t e = hipMalloc((void **)&s->d, draw);
             if (e != hipSuccess && !ctx->pool.empty()) { // give the pool back and retry once
                 (void)hipGetLastError();
                 lm_sync_all(ctx);
                 pool_drain(ctx);
-                e = hipMalloc((void **)&s->d, bytes);
+                e = hipMalloc((void **)&s->d, draw);
             }
             if (e != hipSuccess) {
                 (void)hipGetLastError();
@@ -479,6 +591,16 @@ extern "C" int lumen_set_create_lanes(lumen_ctx *ctx, uint32_t count, uint32_t n
                                num_limbs, hipGetErrorString(e));
             }
         }
+        if (fill) { // behind the pooled block's `ready` event: the streams wait for it above
+            const unsigned char c = lm_alloc_fill(ctx, s->d, bytes, fill, band, set_name(s).c_str());
+            if (band) s->canary = c;
+            if (!c) {
+                hipFree(s->d);
+                delete s;
+                return 1;
+            }
+        }
+        if (s->canary) guarded_add(ctx, s);
     }
     *out = s;
     return 0;
@@ -486,6 +608,8 @@ extern "C" int lumen_set_create_lanes(lumen_ctx *ctx, uint32_t count, uint32_t n
 
 extern "C" void lumen_set_destroy(lumen_ctx *ctx, lumen_set *set) {
     if (!set) return;
+    const bool guarded = set->canary && set->owner && set->d;
+    if (set->canary) guarded_drop(set);
     if (ctx) {
         LM_ENTER(ctx);
         // nothing enqueued may still touch the storage once it is back in the pool: the main stream and
@@ -495,16 +619,18 @@ extern "C" void lumen_set_destroy(lumen_ctx *ctx, lumen_set *set) {
         hipStreamSynchronize(ctx->stream2);
         if (ctx->aux_digests && set->d && set->d < ctx->aux_hi && set->d + set->words > ctx->aux_lo)
             hipStreamSynchronize(ctx->stream_aux);
+        if (guarded) (void)lm_alloc_band_check(nullptr, set->d, set->words * sizeof(u64), set->canary, set_name(set).c_str());
         if (set->owner && set->d) {
             const size_t bytes = set->words * sizeof(u64);
             if (ctx == set->home && ctx->pool_bytes + bytes <= ((size_t)96 << 30)) {
-                ctx->pool.emplace(bytes, lumen_ctx::pool_block{set->d, nullptr});
+                ctx->pool.emplace(bytes, lumen_ctx::pool_block{set->d, nullptr, set->canary});
                 ctx->pool_bytes += bytes;
             } else {
                 hipFree(set->d); // never touch a context the caller did not pass
             }
         }
     } else if (set->owner && set->d) {
+        if (guarded) (void)lm_alloc_band_check(nullptr, set->d, set->words * sizeof(u64), set->canary, set_name(set).c_str());
         hipFree(set->d); // hipFree waits for the device
     }
     delete set;
@@ -531,7 +657,9 @@ void lm_set_release_async(lumen_ctx *ctx, lumen_set *set) {
         lumen_set_destroy(ctx, set);
         return;
     }
-    ctx->pool.emplace(bytes, lumen_ctx::pool_block{set->d, ready});
+    // (a guarded block stays guarded in the pool: lumen_ctx_alloc_check and the pool's drain read its band)
+    if (set->canary) guarded_drop(set);
+    ctx->pool.emplace(bytes, lumen_ctx::pool_block{set->d, ready, set->canary});
     ctx->pool_bytes += bytes;
     delete set;
 }

@@ -4,11 +4,26 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstdio>
+#include <cstring>
 #include <vector>
 
 #include "../../include/lumenos_hip.h"
 
 int lm_fail(lumen_ctx *ctx, const char *fmt, ...);
+
+// The fill-and-fence mode (LUMEN_ALLOC_FILL; lm_ctx.hip; DESIGN.md, "Who owns device memory").  Off, a block is drawn and
+// freed exactly as without it.  On, a block is drawn with LM_GUARD_BYTES behind it, filled with the byte before its first
+// use, the band with a canary; the band is read back when the block goes (and by lumen_ctx_alloc_check).
+#define LM_GUARD_BYTES ((size_t)4096)
+// the fill byte `ctx` draws under (NULL: what lumen_ctx_create last read from the environment); 0 = the mode is off
+unsigned lm_alloc_fill_byte(const lumen_ctx *ctx);
+// fills [p, p + bytes) with the byte and -- band -- the LM_GUARD_BYTES behind it with the canary, on the context's
+// stream (NULL: blocking), and waits; returns the canary, 0 after an error (reported through lm_fail)
+unsigned char lm_alloc_fill(lumen_ctx *ctx, void *p, size_t bytes, unsigned fill, bool band, const char *what);
+// reads the band behind [p, p + bytes) back (a blocking copy): 0, or 1 with the first changed byte reported -- through
+// lm_fail(ctx, ...), which prints it on stderr
+int lm_alloc_band_check(lumen_ctx *ctx, const void *p, size_t bytes, unsigned char canary, const char *what);
 
 template <class T>
 class lm_dev {
@@ -16,15 +31,24 @@ class lm_dev {
     size_t n_ = 0;
     hipStream_t stream_ = nullptr; // release_on
     bool wipe_ = false;
+    unsigned char canary_ = 0; // of the guard band behind the block; 0: none (the mode was off, or a block drawn elsewhere)
+    char what_[40] = {0};      // a guarded block's name, for the report
+
+    size_t bytes_() const { return (n_ ? n_ : 1) * sizeof(T); }
+    void take_guard(const lm_dev &o) {
+        canary_ = o.canary_;
+        memcpy(what_, o.what_, sizeof(what_));
+    }
 
   public:
     lm_dev() = default;
     lm_dev(T *block, size_t count) : p_(block), n_(count) {} // takes over a block drawn elsewhere (a placement's choice)
-    lm_dev(lm_dev &&o) noexcept : p_(o.release()), n_(o.n_), stream_(o.stream_), wipe_(o.wipe_) {}
+    lm_dev(lm_dev &&o) noexcept : p_(o.release()), n_(o.n_), stream_(o.stream_), wipe_(o.wipe_) { take_guard(o); }
     lm_dev &operator=(lm_dev &&o) noexcept {
         if (this != &o) {
             reset();
             n_ = o.n_, stream_ = o.stream_, wipe_ = o.wipe_;
+            take_guard(o);
             p_ = o.release();
         }
         return *this;
@@ -43,12 +67,20 @@ class lm_dev {
     int alloc(lumen_ctx *ctx, size_t count, const char *what) {
         reset();
         const size_t bytes = (count ? count : 1) * sizeof(T);
-        if (hipMalloc((void **)&p_, bytes) != hipSuccess) {
+        const unsigned fill = lm_alloc_fill_byte(ctx);
+        if (hipMalloc((void **)&p_, bytes + (fill ? LM_GUARD_BYTES : 0)) != hipSuccess) {
             (void)hipGetLastError();
             p_ = nullptr;
             return lm_fail(ctx, "hipMalloc(%zu bytes) for %s failed", bytes, what);
         }
-        n_ = count;
+        n_ = count, canary_ = 0;
+        if (fill) {
+            snprintf(what_, sizeof(what_), "%s", what);
+            if (!(canary_ = lm_alloc_fill(ctx, p_, bytes, fill, true, what))) {
+                reset();
+                return 1;
+            }
+        }
         return 0;
     }
     // alloc + a blocking copy: one-off table loads out of pageable memory
@@ -65,6 +97,9 @@ class lm_dev {
 
     T *get() const { return p_; }
     size_t count() const { return n_; }
+    // the guard band's canary (0: the block has none) and the name the block was drawn under
+    unsigned char canary() const { return canary_; }
+    const char *what() const { return what_; }
     explicit operator bool() const { return p_ != nullptr; }
     T *release() {
         T *r = p_;
@@ -75,6 +110,8 @@ class lm_dev {
         if (!p_) return;
         if (wipe_) (void)(stream_ ? hipMemsetAsync(p_, 0, n_ * sizeof(T), stream_) : hipMemset(p_, 0, n_ * sizeof(T)));
         if (stream_) (void)hipStreamSynchronize(stream_);
+        if (canary_) (void)lm_alloc_band_check(nullptr, p_, bytes_(), canary_, what_);
+        canary_ = 0;
         (void)hipFree(release());
         (void)hipGetLastError();
     }

@@ -188,6 +188,7 @@ SYMBOLS = {
     "lumen_group_stats": (C.c_int, [_vp, C.c_char_p, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "lumen_group_stats_reset": (C.c_int, [_vp]),
     "lumen_ctx_scratch_info": (C.c_int, [_vp, C.c_char_p, _vpp, C.POINTER(C.c_size_t)]),
+    "lumen_ctx_alloc_check": (C.c_int, [_vp]),
     "lumen_ks_mac_probe": (C.c_int, [_vp, C.c_uint32, _vp, _vp, _vp, _vp, C.c_uint32, C.POINTER(C.c_float)]),
     "lumen_timer_start": (C.c_int, [_vp]),
     "lumen_timer_stop": (C.c_int, [_vp, C.POINTER(C.c_float)]),
@@ -442,6 +443,11 @@ class Context:
         p, n = C.c_void_p(), C.c_size_t()
         self._ck(self.lib.lumen_ctx_scratch_info(self.h, name.encode(), C.byref(p), C.byref(n)))
         return p.value, n.value
+
+    def alloc_check(self):
+        """LUMEN_ALLOC_FILL: read back the guard band behind every live block of the context; raises on the first damaged
+        one, with its name, its size and the offset of the first changed byte (nothing to do with the mode off)"""
+        self._ck(self.lib.lumen_ctx_alloc_check(self.h))
 
     def ks_mac_probe(self, batch=0, ext=None, acc=None, key=None, u=None, reps=100):
         """ms per launch of the key switch's gadget product alone on the given device addresses (None = the

@@ -10,7 +10,10 @@ out), L = 5, K = 2, on a reference-style chain and on one right under the modulu
 primes from every degree >= 2^10 into 2^8 and into itself at the bound.  Still only here: random limb counts (1 ... 6) with K = 1 for the
 key switch (the suite has L = 1 and 3 with one special prime at every degree), random InnerSum lengths and ciphertext counts, random serialisation formats, and the lumen_group runs.
 
-usage: [FUZZ_LOGN=13,14] [FUZZ_GROUP_TRANSPORT=rccl LD_LIBRARY_PATH=tests/cpp/fake_rccl:...] python tests/dev/fuzz_gpu.py [cases] [seed]
+--alloc-fill BYTE runs every case under the fill-and-fence mode (LUMEN_ALLOC_FILL, tests/test_stale_memory.py): the contexts are
+created under the byte, and their fences are read back (lumen_ctx_alloc_check) before a case's context closes.
+
+usage: [FUZZ_LOGN=13,14] [FUZZ_GROUP_TRANSPORT=rccl LD_LIBRARY_PATH=tests/cpp/fake_rccl:...] python tests/dev/fuzz_gpu.py [--alloc-fill BYTE] [cases] [seed]
 """
 import os
 import sys
@@ -145,6 +148,7 @@ def one_case(o, rng, case):
             for cx in ctxs[1:]:
                 cx.close()
             what.append(f"group(W={W},cols={cols},rho={rho},nl={nlg})")
+    ctx.alloc_check()  # (--alloc-fill: no fence is damaged; nothing to do otherwise)
     ctx.close()
     # ring switch on the gadget path the number of special primes selects (a context of its own: K = 0 too)
     kp = int(rng.choice([0, 1, 2]))
@@ -165,13 +169,23 @@ def one_case(o, rng, case):
         assert np.array_equal(P2.decrypt_small_coeffs(sks, small, got[c]),
                               P2.decrypt_big_coeffs_l0(sk2, ctr[c])[::P2.N >> small]), (tag, "ring switch decrypt", kp, small)
     what.append(f"ringswitch(K={kp}->2^{small})")
+    ctx2.alloc_check()
     ctx2.close()
     print(tag, "ok:", " ".join(what), flush=True)
 
 
 def main():
-    cases = int(sys.argv[1]) if len(sys.argv) > 1 else 20
-    seed = int(sys.argv[2]) if len(sys.argv) > 2 else 1
+    import argparse
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--alloc-fill", type=lambda x: int(x, 0), default=0, metavar="BYTE", help="LUMEN_ALLOC_FILL for every context (1 .. 255; 0: off)")
+    ap.add_argument("cases", type=int, nargs="?", default=20)
+    ap.add_argument("seed", type=int, nargs="?", default=1)
+    args = ap.parse_args()
+    if not 0 <= args.alloc_fill <= 255:
+        ap.error("--alloc-fill takes a byte")
+    if args.alloc_fill:
+        os.environ["LUMEN_ALLOC_FILL"] = str(args.alloc_fill)  # read by lumen_ctx_create
+    cases, seed = args.cases, args.seed
     o = Oracle()
     rng = np.random.default_rng(seed)
     t0 = time.time()

@@ -19,7 +19,7 @@ def test_header_symbols_all_exported_and_bound():
     from lumenos_amd import hip
     lib = hip.load()
     names = declared_symbols()
-    assert len(names) >= 30
+    assert len(names) >= 30 and "lumen_ctx_alloc_check" in names
     for n in names:
         assert hasattr(lib, n), f"{n} declared in include/lumenos_hip.h but not exported"
     assert set(names) == set(hip.SYMBOLS), set(names) ^ set(hip.SYMBOLS)
@@ -142,6 +142,11 @@ def test_environment_is_read_once_at_context_creation():
     body = body[:body.index("\n}\n")]
     assert "getenv(" in body
     assert src.count("tuning_from_env(") == 2  # the definition and the call in lumen_ctx_create
+    # the fill-and-fence mode comes in with the other switches: lm_dev::alloc (lm_dev.h), which may have no context, asks
+    # lm_ctx.hip for the byte -- the value this helper last read -- and never the environment
+    assert '"LUMEN_ALLOC_FILL"' in body and "lm_env_alloc_fill = t.alloc_fill" in body
+    dev = open(os.path.join(csrc, "lm_dev.h")).read()
+    assert "lm_alloc_fill_byte(ctx)" in dev and "getenv" not in dev
 
 
 def test_host_gather_scatter_round_trip():
